@@ -20,7 +20,10 @@ with ONE all-gather of [score | tokens] records and the same grouped arg-max on 
   --scaling strong the headline N = 32 itself sharded: rank r takes prompts r, r+W, ... (8/W prompts x 4 samples). Every rank
                    still streams all the decoder weights per decode pass (M = 32/W rows), so the expected gain is small.
 
-Prints ONE JSON line (rank 0). Extra objects:
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps decisions and prints the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed decision, config); --dump-outputs DIR also writes what the last timed
+decision returned as DIR/<name>.npy (float32 / float64; the inputs and weights are seeded, so two builds compare output for output).
+Everything else runs only with --full, which adds these objects (and, with --dtype fp8, "fp8_vs_bf16"):
   "roofline"       dominant kernel = the weight-streaming GEMM of the decode passes (HBM-bound), timed live per launch
                    with the kernels' own start/stop stamps (hipExtLaunchKernelGGL event pairs on their stream);
   "roofline_mfma"  every LDS-tiled MFMA GEMM of the decision (LLM prefill + all ViT towers + projector):
@@ -425,6 +428,8 @@ def main_pi0(a):
         idx, x = pipe.decision()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"actions": x, "scores": pipe.last_scores, "winner_index": [idx]})
     assert torch.isfinite(x).all()
     ms_per_step = 1e3 * dt / a.steps
     B, c = pipe.B, pipe.c
@@ -436,7 +441,7 @@ def main_pi0(a):
                                   f"tokenizer max_length {pipe.L}, one 224x224 RGB frame; CoVer verifier SigLIP2-L/16-384 + 3-member ensemble; random-init weights",
                       "candidates_total": B, "parallelism": "one GPU", "lib_sha16": lib_hash(), "selected": idx,
                       "denoise_chains": pipe.model.n_chains, "denoise_graph": pipe.model.denoise_graph}}
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         ph = _profile_phases(pipe)
         M_exp = B * (1 + c["chunk"])
         ms_d, cnt_d, work_d = ph["denoise"]
@@ -474,7 +479,7 @@ def main_pi0(a):
         for k in ("roofline", "roofline_mfma"):
             if k in out and out[k]["frac"] > 1.0:
                 out[k] = {"invalid": f"frac {out[k]['frac']} > 1: refused"}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = pi0_cpu_baseline(pipe, a.cpu_batch)
     print(json.dumps(out), flush=True)
 
@@ -757,6 +762,19 @@ def fp8_agreement(pipe, dev, a, n_prompts_global, prompt_ids):
     return res
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the last timed decision returned, one DIR/<name>.npy per array (float32 scores / actions, float64 indices and
+    tokens: exact as integers). The arrays are small (a decision returns N scores and N x 7 x horizon tokens or N x chunk x 32 actions)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu()
+            x = (x.double() if x.dtype == torch.float64 or not x.is_floating_point() else x.float()).numpy()
+        else:
+            x = np.asarray(x, dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(x))
+
+
 def lib_hash():
     from cover_vla_amd import _lib as L
     h = hashlib.sha256()
@@ -891,7 +909,14 @@ def main():
     ap.add_argument("--profile", choices=["openvla", "pi0"], default="openvla",
                     help="pi0 = profile P1 (what the reference ships: pi0 sampler B = 40 + verifier), one GPU; the default is the BASELINE.json metric (OpenVLA-7B shapes)")
     ap.add_argument("--cpu-batch", type=int, default=40, help="--profile pi0: rows of the CPU-baseline decision (40 = as the reference executes it)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the profiled decision (roofline objects), the fp8-vs-bf16 comparison and the CPU baseline "
+                         "with its agreement check (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed decision returned as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.profile == "pi0":
         if a.gpus != 1:
             raise SystemExit("--profile pi0 is a one-GPU line")
@@ -958,6 +983,12 @@ def main():
         t = torch.tensor([dt], device=dev if a.backend == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t[0])
+    if a.dump_outputs and rank == 0:
+        gi, toks, sel = last
+        arrays = {"winner_index": [gi], "tokens": toks, "scores": pipe.last_scores}
+        if sel is not None:   # world > 1: what every rank receives from the all-gather (rank 0's own tokens above)
+            arrays.update(scores=sel["scores"], winner_tokens=sel["winner_payload"], group_tokens=sel["group_payload"])
+        dump_outputs(a.dump_outputs, arrays)
     if a.check_out:
         gi, toks, sel = last
         rec = {"rank": rank, "global_idx": int(gi), "local_tokens": toks.cpu().tolist(), "prompt_ids": pipe.prompt_ids}
@@ -992,7 +1023,7 @@ def main():
                    "candidates_total": n_total, "candidates_per_gpu": n_local, "prompts_per_gpu": len(pipe.prompt_ids),
                    "parallelism": f"candidate-sharded x{world} ({'strong' if strong else 'weak'})", "own_kv": pipe.own_kv or "legacy", "lib_sha16": lib_hash()},
     }
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         # ---- rooflines: kernel start/stop stamps of every GEMM / attention launch of one extra (serialised) decision
         ms, cnt, work = profile_decision(pipe, world, rank, cpu_gather)
         out.update(roofline_objects(ms, cnt, work, ms_per_step, out["config"]["lib_sha16"]))
@@ -1008,9 +1039,9 @@ def main():
                             "sustains the clock reported here (power limit), so the same kernel time is a larger share of the peak actually available"}
         except Exception as e:   # noqa: BLE001 -- a measurement hook must never take the bench line down
             out.setdefault("notes", []).append(f"in-kernel clock probe unavailable: {e}")
-    if a.dtype == "fp8" and world == 1 and not a.no_agreement:
+    if a.full and a.dtype == "fp8" and world == 1 and not a.no_agreement:
         out["fp8_vs_bf16"] = fp8_agreement(pipe, dev, a, n_prompts_global, prompt_ids)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.small:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.small:
         out["cpu_baseline"] = cpu_baseline(pipe, batched=not a.no_cpu_batched, free=(last[0], last[1]))
         ag = out["cpu_baseline"].get("agreement")
         if ag is not None and ag["decided"] > 0 and ag["agree_on_decided"] < 1.0:

@@ -16,6 +16,22 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 from cover_ref import verifier as V  # noqa: E402
 from cover_vla_amd import synth  # noqa: E402
 
+# The goldens were written on one CPU with one thread count. The same eager graph on another CPU (another ISA: AMX vs AVX-512 BF16
+# vs AVX2 kernels) or another thread split sums its GEMMs in another order: fp32 results move by about an ulp, a few bf16 results
+# land one bf16 ulp away and a layer carries those on. Measured for one eager bf16 layer of the SAME graph on other kernel paths:
+# <= 4.3e-3 rel-L2 from its golden; the nearest DIFFERENT graph (G3 (b): fp32 attention scores) sits >= 7.1e-3 from the same golden.
+# XCPU_REL lies between the two: it accepts the rounding of other kernels and still rejects a different graph.
+XCPU_REL = 5e-3
+
+
+def _kernel_rounding_equal(a, b, rel_l2, max_frac=1.0):
+    """a equals the golden b up to the summation order of the CPU's kernels: same shape, rel-L2 <= rel_l2 (orders of magnitude below
+    what a structural difference produces) and at most max_frac of the elements different at all."""
+    a, b = (x.double() if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, dtype=np.float64)) for x in (a, b))
+    if a.shape != b.shape:
+        return False
+    return ((a - b).norm() / b.norm()).item() <= rel_l2 and (a != b).double().mean().item() <= max_frac
+
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "verifier_m*.npz"))))
 def test_verifier_oracle_matches_reference(path):
@@ -108,18 +124,23 @@ def test_pi0_oracle_matches_reference(name):
                                  prefix_embs=torch.from_numpy(z["prefix_embs"]).to(torch.bfloat16))
     nimg = cfg.n_img_tokens
     a, b = pe.float().numpy(), z["prefix_embs"]
-    # language tokens, suffix embedding: same eager op sequence -> bit-identical
+    # language tokens: same eager op sequence -> bit-identical; suffix embedding (fp32 projections): bit-identical on the CPU that
+    # wrote the golden, elsewhere equal up to the summation order of the CPU's GEMM kernels
     assert np.array_equal(a[:, nimg:], b[:, nimg:])
-    assert np.array_equal(se.float().numpy(), z["suffix_embs_t1"])
+    assert _kernel_rounding_equal(se.float(), z["suffix_embs_t1"], rel_l2=1e-6)
     # image tokens go through the un-vendored HF SigLIP tower whose attention rounds differently (sdpa, bf16 scores):
     # bf16-ulp level agreement only
     assert np.linalg.norm(a[:, :nimg] - b[:, :nimg]) / np.linalg.norm(b[:, :nimg]) < 1e-2
-    # decoder + flow matching, isolated from the tower by feeding the reference's own prefix embeddings
-    assert np.allclose(x_iso.numpy(), z["actions"], atol=2e-5), np.abs(x_iso.numpy() - z["actions"]).max()
+    # decoder + flow matching, isolated from the tower by feeding the reference's own prefix embeddings: bit-identical on the CPU
+    # that wrote the golden; on another CPU the bf16 GEMM kernels' rounding runs through 10 Euler steps (measured on other kernel
+    # paths: rel-L2 <= 5.2e-3 of the update, max-abs <= 1.5e-2), judged on the UPDATE like the end-to-end check below but half as
+    # wide in both measures (that one also carries the tower's rounding)
+    upd = z["actions"] - noise.numpy()
+    d_iso = x_iso.numpy() - z["actions"]
+    assert np.linalg.norm(d_iso) / np.linalg.norm(upd) < 1e-2 and np.abs(d_iso).max() < 2e-2, np.abs(d_iso).max()
     # end to end (tower included): bf16-ulp differences of the tower propagate through randomly initialised layers;
     # judged on the flow-matching UPDATE (actions - noise): relative L2 <= 2e-2, and max-abs within 2x the loosest
     # rung the reference itself accepted against JAX (atol 3e-2, compare_with_jax.py:131-133)
-    upd = z["actions"] - noise.numpy()
     assert np.linalg.norm(x.numpy() - z["actions"]) / np.linalg.norm(upd) < 2e-2
     assert np.abs(x.numpy() - z["actions"]).max() < 6e-2
 
@@ -209,10 +230,10 @@ def test_oracle_full_width_gemma_layers_match_reference_g2():
         suf, _ = Bk.decoder_forward(ex, P.sub(sd, "expert."), suffix, spos, full, past=kv, keep_kv=False, final_norm=True)
     n0, n1 = int(pad[0].sum()), int(pad[1].sum())
     rel = lambda a, b: ((a.float() - b).norm() / b.norm()).item()
-    assert rel(pre[0, :n0], gold["pre_b0"][:n0]) < 2e-3                       # two eager bf16 evaluations of the same graph
-    assert rel(pre[1, ::4][: (n1 + 3) // 4], gold["pre_b1"][: (n1 + 3) // 4]) < 2e-3
-    assert rel(kv[0][0][0, :n0, 0], gold["k_b0"][:n0]) < 2e-3 and rel(kv[0][1][0, :n0, 0], gold["v_b0"][:n0]) < 2e-3
-    assert rel(suf, gold["suffix"]) < 2e-3
+    assert rel(pre[0, :n0], gold["pre_b0"][:n0]) < XCPU_REL                   # two eager bf16 evaluations of the same graph
+    assert rel(pre[1, ::4][: (n1 + 3) // 4], gold["pre_b1"][: (n1 + 3) // 4]) < XCPU_REL
+    assert rel(kv[0][0][0, :n0, 0], gold["k_b0"][:n0]) < XCPU_REL and rel(kv[0][1][0, :n0, 0], gold["v_b0"][:n0]) < XCPU_REL
+    assert rel(suf, gold["suffix"]) < XCPU_REL
 
 
 def _g3_case():
@@ -231,7 +252,8 @@ def _g3_case():
 def test_oracle_full_width_llama7b_layer_matches_hf_g3():
     """G3: one full-width Llama-2-7B layer (4096 wide, 32 x 128 MHA, MLP 11008) on [BOS | 256 patches | text] and one decode row per
     sample over the cache -- HF LlamaModel (bf16, eager) vs the oracle's decoder_forward. Prompts 0 and 5 (CPU time).
-    (a) with HF's bf16 attention scores restated (scores_bf16) the oracle IS HF's graph: rel-L2 < 2e-3, post-RoPE K / V bit-exact;
+    (a) with HF's bf16 attention scores restated (scores_bf16) the oracle IS HF's graph: rel-L2 < XCPU_REL, post-RoPE K / V bit-exact
+        up to the rounding of the CPU's GEMM kernels;
     (b) in its default form (fp32 scores, what the HIP kernels compute) it sits no further from HF's fp32 evaluation of the same
         bf16 parameters than HF's own bf16 path does (HF-bf16: ~0.8e-2)."""
     from cover_ref import blocks as Bk
@@ -240,6 +262,8 @@ def test_oracle_full_width_llama7b_layer_matches_hf_g3():
     sdb = Bk.to_bf16(sd)
     T0 = 1 + N_PATCH
     rel = lambda a, b: ((a.float() - b).norm() / b.norm()).item()
+    # one projection + RoPE: bit-exact but for the odd element whose fp32 sum sits on a bf16 rounding boundary (another CPU's kernel)
+    kv_equal = lambda a, b: _kernel_rounding_equal(a, b, rel_l2=1e-4, max_frac=1e-3)
     hf_own = {"text": rel(gold["text_p5"], gold["f32_text_p5"]), "dec": rel(gold["decode_rows"], gold["f32_decode_rows"]),
               "last": rel(gold["last_text_rows"], gold["f32_last_text_rows"]), "prefix": rel(gold["prefix_every4"][::4], gold["f32_prefix_every16"])}
     assert all(5e-3 < v < 1.2e-2 for v in hf_own.values()), hf_own
@@ -262,14 +286,14 @@ def test_oracle_full_width_llama7b_layer_matches_hf_g3():
                 dec = torch.stack(dec)
                 if hf_scores:
                     if p == 0:
-                        assert rel(h[0, 1:T0][::4], gold["prefix_every4"]) < 2e-3
-                        assert torch.equal(kv[0][0][0, 1:T0][::4][:, list(HEADS)].transpose(0, 1).float(), gold["k_prefix_every4"])
-                        assert torch.equal(kv[0][1][0, 1:T0][::4][:, list(HEADS)].transpose(0, 1).float(), gold["v_prefix_every4"])
+                        assert rel(h[0, 1:T0][::4], gold["prefix_every4"]) < XCPU_REL
+                        assert kv_equal(kv[0][0][0, 1:T0][::4][:, list(HEADS)].transpose(0, 1).float(), gold["k_prefix_every4"])
+                        assert kv_equal(kv[0][1][0, 1:T0][::4][:, list(HEADS)].transpose(0, 1).float(), gold["v_prefix_every4"])
                     else:
-                        assert torch.equal(kv[0][0][0, T0:][:, list(HEADS)].transpose(0, 1).float(), gold["k_text_p5"])
-                    assert rel(h[0, T0:], gold["text_p0" if p == 0 else "text_p5"]) < 2e-3
-                    assert rel(h[0, -1], gold["last_text_rows"][p]) < 2e-3
-                    assert rel(dec, gold["decode_rows"][p * S:(p + 1) * S]) < 2e-3
+                        assert kv_equal(kv[0][0][0, T0:][:, list(HEADS)].transpose(0, 1).float(), gold["k_text_p5"])
+                    assert rel(h[0, T0:], gold["text_p0" if p == 0 else "text_p5"]) < XCPU_REL
+                    assert rel(h[0, -1], gold["last_text_rows"][p]) < XCPU_REL
+                    assert rel(dec, gold["decode_rows"][p * S:(p + 1) * S]) < XCPU_REL
                 else:
                     if p == 0:
                         assert rel(h[0, 1:T0][::16], gold["f32_prefix_every16"]) <= 1.1 * hf_own["prefix"]
