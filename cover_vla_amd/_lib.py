@@ -185,6 +185,7 @@ SYMBOLS = {
     "cover_gemm_workspace_bytes": (C.c_size_t, [c_i, c_i, c_i]),
     "cover_gemm_bf16": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, _P(GemmEpi), c_p, C.c_size_t, c_i, c_p]),
     "cover_gemm_plan_counts": (c_i, [C.POINTER(C.c_longlong), c_i, c_i]),
+    "cover_gemm_plan": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, _P(GemmEpi), c_p, C.c_size_t, c_i, C.POINTER(c_i)]),
     "cover_gemm_probe": (c_i, [C.POINTER(C.c_ulonglong)]),
     "cover_attention_bf16": (c_i, [_P(AttnArgs), c_p]),
     "cover_decode_attention_fused": (c_i, [_P(DecodeAttnArgs), c_p]),

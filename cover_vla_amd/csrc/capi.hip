@@ -93,12 +93,24 @@ int cover_gemm_plan_counts(long long* counts, int n, int reset) {
     gemm_plan_counts(counts, n, reset);
     return COVER_GEMM_PLANS;
 }
+// cover_gemm_bf16's own argument checks (shared with cover_gemm_plan); nullptr when they pass
+static const char* gemm_args_error(const void* A, int lda, const void* Wp, const void* C, int N, int K, const cover_gemm_epi* epi) {
+    if (!A || !Wp || !C) return "cover_gemm_bf16: null pointer";
+    if (lda % 8) return "cover_gemm_bf16: lda must be a multiple of 8 elements";
+    if (lda < cover_packed_k(K)) return "cover_gemm_bf16: lda < padded K";
+    if (epi && epi->glu && (N % 32)) return "cover_gemm_bf16: glu needs N % 32 == 0";
+    return nullptr;
+}
+int cover_gemm_plan(const void* A, int lda, const void* Wp, void* C, int ldc, int M, int N, int K,
+                    const cover_gemm_epi* epi, void* ws, size_t ws_bytes, int variant, int plan[6]) {
+    if (!plan) return fail(COVER_EINVAL, "cover_gemm_plan: null plan");
+    if (const char* why = gemm_args_error(A, lda, Wp, C, N, K, epi)) return fail(COVER_EINVAL, why);
+    HIPCHK(gemm_plan_query((const bf16_t*)A, lda, (const bf16_t*)Wp, C, ldc, M, N, K, epi, (const float*)ws, ws_bytes, variant, plan), "gemm_plan");
+    return COVER_OK;
+}
 int cover_gemm_bf16(const void* A, int lda, const void* Wp, void* C, int ldc, int M, int N, int K,
                     const cover_gemm_epi* epi, void* ws, size_t ws_bytes, int variant, void* stream) {
-    if (!A || !Wp || !C) return fail(COVER_EINVAL, "cover_gemm_bf16: null pointer");
-    if (lda % 8) return fail(COVER_EINVAL, "cover_gemm_bf16: lda must be a multiple of 8 elements");
-    if (lda < cover_packed_k(K)) return fail(COVER_EINVAL, "cover_gemm_bf16: lda < padded K");
-    if (epi && epi->glu && (N % 32)) return fail(COVER_EINVAL, "cover_gemm_bf16: glu needs N % 32 == 0");
+    if (const char* why = gemm_args_error(A, lda, Wp, C, N, K, epi)) return fail(COVER_EINVAL, why);
     HIPCHK(launch_gemm_bf16((const bf16_t*)A, lda, (const bf16_t*)Wp, C, ldc, M, N, K, epi, (float*)ws, ws_bytes, variant,
                             ST(stream)),
            "gemm_bf16");
@@ -489,7 +501,7 @@ int cover_decoder_forward(const cover_dec_desc* d, const cover_dec_pass* p, void
     // on it (same bytes, one launch more: the A/B of the fusion). Sizes below the fp8 tiles' (tests on small geometries) stay on the bf16 kernels.
     const int mlp_p = (d->mlp + 127) / 128 * 128;
     const bool down_kl = d->layers_host[0].down_klinear != 0;
-    const bool mx = f8 && down_kl && rows >= 400 && dim >= 2048 && d->mlp >= 2048 && (d->mlp % 32) == 0 &&
+    const bool mx = f8 && down_kl && rows >= 400 && dim >= 2048 && d->mlp >= 2048 && (d->mlp % 128) == 0 &&
                     (d->act == COVER_ACT_SILU || d->act == COVER_ACT_GELU_TANH);
     const char* mxf_env = getenv("COVER_FP8_MX_FUSE");
     const bool mx_fused = mx && !(mxf_env && mxf_env[0] == '0');

@@ -1382,14 +1382,11 @@ static EpiDev make_epi(const cover_gemm_epi* e) {
 
 // profiling class of a weight-streaming launch: 0 = the large (>= 16 MB of weights) GEMMs of an LLM decode pass, i.e. the
 // kernel bench.py's roofline object is about; 3 = small ones (verifier / pi0-expert sized) that are latency-, not HBM-bound
+static inline int sk_class(int N, int K) { return 2.0 * (double)N * (double)K >= 16.0e6 ? 0 : 3; }
+
 // Third-generation plan: NBW n-blocks per wave (x NG = 2 n-groups) and S grid-level K slices such that the grid is as close
 // to ONE block per CU (128 KiB of LDS) as possible; every block must see at least two 1024-wide chunks (otherwise the
 // second generation does the same work with two blocks per CU).
-struct Skinny3Plan {
-    bool ok;
-    int MF, NBW, S, kper, gx;
-    size_t lds, ws_bytes;
-};
 static Skinny3Plan plan_skinny3(int M, int N, int Kp) {
     Skinny3Plan best;
     best.ok = false;
@@ -1424,22 +1421,6 @@ static Skinny3Plan plan_skinny3(int M, int N, int Kp) {
     return best;
 }
 
-// weight-streaming launches: with profiling on, the kernel's own start / stop timestamps go into a reserved event pair
-template <typename F, typename... Args>
-static inline void launch_streaming(int cls, double work, F kfn, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
-    hipEvent_t ea, eb;
-    if (prof_enabled() && prof_reserve(cls, work, &ea, &eb) >= 0)
-        hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds, st, ea, eb, 0, args...);
-    else
-        hipLaunchKernelGGL(kfn, grid, block, lds, st, args...);
-}
-
-static inline int sk_class(int N, int K) { return 2.0 * (double)N * (double)K >= 16.0e6 ? 0 : 3; }
-
-struct SkinnyPlan {
-    int MF, KC, S, nbpb, gx;
-    size_t lds, ws_bytes;
-};
 static SkinnyPlan plan_skinny(int M, int N, int Kp) {
     SkinnyPlan p;
     p.MF = (M + 15) / 16;
@@ -1460,10 +1441,6 @@ static SkinnyPlan plan_skinny(int M, int N, int Kp) {
     return p;
 }
 
-struct Skinny2Plan {
-    int MF, KS, NBW, gx, S;
-    size_t lds, ws_bytes;
-};
 static Skinny2Plan plan_skinny2(int M, int N, int Kp) {
     Skinny2Plan p;
     p.MF = (M + 15) / 16;
@@ -1510,9 +1487,7 @@ size_t gemm_workspace_bytes(int M, int N, int K) {
     return ab > c ? ab : c;
 }
 
-// second-generation weight streaming; e4m3 weights for M <= 32 when a twin is given
-// which plan every GEMM launch took since the last reset (cover_gemm_plan_counts: tests assert the tile a shape really ran on):
-// [0..18] LDS-tiled picks (index into cands below), [19] gemm_skinny2, [20] gemm_skinny3, [21] fp8 tiled (any pick), [22] gemm_skinny (gen 1)
+// which plan every GEMM launch took since the last reset (cover_gemm_plan_counts: tests assert the tile a shape really ran on): GemmPlan.slot
 static std::atomic<long long> g_plan_counts[COVER_GEMM_PLANS];
 static inline void plan_hit(int i) { g_plan_counts[i].fetch_add(1, std::memory_order_relaxed); }
 void gemm_plan_counts(long long* out, int n, int reset) {
@@ -1522,210 +1497,88 @@ void gemm_plan_counts(long long* out, int n, int reset) {
     }
 }
 
-static void launch_skinny2(const Skinny2Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, float* ws, int M, int N, int K, int Kp,
-                           const uint8_t* w8, const float* w8s, int kl, hipStream_t st) {
-    dim3 grid(p.gx, p.S), block(512);
-    plan_hit(19);
-#define SK2(MF_, KS_, NBW_, W8_) launch_streaming(sk_class(N, K), (W8_ ? 1.0 : 2.0) * (double)N * (double)K, gemm_skinny2<MF_, KS_, NBW_, W8_>, grid, block, p.lds, st, A, lda, W8_ ? (const bf16_t*)w8 : Wp, ws, M, N, Kp, w8s, kl)
-    if (w8 && w8s && p.MF <= 2) {
-        if (p.MF == 1) { if (p.NBW == 6) SK2(1, 4, 6, true); else if (p.NBW == 4) SK2(1, 4, 4, true); else if (p.NBW == 3) SK2(1, 4, 3, true); else SK2(1, 4, 2, true); }
-        else { if (p.NBW == 6) SK2(2, 4, 6, true); else if (p.NBW == 4) SK2(2, 4, 4, true); else if (p.NBW == 3) SK2(2, 4, 3, true); else SK2(2, 4, 2, true); }
-    } else {
-        if (p.MF == 1) { if (p.NBW == 6) SK2(1, 4, 6, false); else if (p.NBW == 4) SK2(1, 4, 4, false); else if (p.NBW == 3) SK2(1, 4, 3, false); else SK2(1, 4, 2, false); }
-        else if (p.MF == 2) { if (p.NBW == 6) SK2(2, 4, 6, false); else if (p.NBW == 4) SK2(2, 4, 4, false); else if (p.NBW == 3) SK2(2, 4, 3, false); else SK2(2, 4, 2, false); }
-        else if (p.MF == 3) SK2(3, 2, 2, false);
-        else SK2(4, 2, 2, false);
+// The weight-streaming plan of variants 3 / 6 and of launch_gemm_skinny_partial (all_slabs: even an unsplit third-generation launch writes its
+// sums as one slab): the third generation (full-K chunk loop per block, one block per CU) whenever its plan fills the chip and its slabs fit,
+// else the second generation (in-block k-slices). forced3 (variant 6, tests): the third generation on any legal problem, unsplit.
+static hipError_t plan_streaming(GemmPlan& p, int M, int N, int Kp, const float* ws, size_t ws_bytes, bool forced3, bool all_slabs) {
+    static const char* g3 = getenv("COVER_SKINNY3");   // experiment knob: 0 disables the automatic choice
+    p.pick = -1;
+    Skinny3Plan p3 = plan_skinny3(M, N, Kp);
+    const int N16 = (N + 15) / 16;
+    if (forced3 && !p3.ok) {
+        if (M > 32 || (N16 & 1) || Kp < 2048) return hipErrorInvalidValue;
+        p3.ok = true; p3.NBW = 3; p3.S = 1; p3.kper = Kp; p3.gx = (N16 + 5) / 6;
+        p3.lds = (size_t)2 * p3.MF * 16 * 1024 * 2; p3.ws_bytes = 0;
     }
-#undef SK2
+    const size_t need3 = all_slabs ? (size_t)p3.S * M * N * sizeof(float) : p3.ws_bytes;
+    if (p3.ok && need3 > 0 && (ws == nullptr || ws_bytes < need3)) p3.ok = false;
+    if (p3.ok && (forced3 || !(g3 && g3[0] == '0'))) {
+        p.kind = GK_SKINNY3; p.slot = PLAN_SKINNY3; p.p3 = p3; p.S = p3.S; p.lds = p3.lds;
+        return hipSuccess;
+    }
+    if (forced3 || M > 64) return hipErrorInvalidValue;
+    const Skinny2Plan p2 = plan_skinny2(M, N, Kp);
+    if (ws == nullptr || ws_bytes < p2.ws_bytes) return hipErrorInvalidValue;
+    p.kind = GK_SKINNY2; p.slot = PLAN_SKINNY2; p.p2 = p2; p.S = p2.S; p.lds = p2.lds;
+    return hipSuccess;
 }
 
-static hipError_t launch_skinny3(const Skinny3Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N,
-                                 int Kp, const EpiDev& epi, float* partial, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    dim3 grid(p.gx, p.S), block(512);
-    plan_hit(20);
-#define SK3(MF_, NBW_, W8_)                                                                                                  \
-    do {                                                                                                                    \
-        auto kfn = gemm_skinny3<MF_, 4, NBW_, NBW_, W8_>;                                                                   \
-        if (p.lds > 64 * 1024) e = LDS_ATTR_160K(kfn);                                                         \
-        if (e == hipSuccess)                                                                                                \
-            launch_streaming(sk_class(N, Kp), (W8_ ? 1.0 : 2.0) * (double)N * (double)Kp, kfn, grid, block, p.lds, st, A, lda,  \
-                             W8_ ? (const bf16_t*)epi.w8 : Wp, C, ldc, M, N, Kp, epi, partial, p.kper, epi.w8s, epi.w8_kl);             \
-    } while (0)
-    if (epi.w8) {   // e4m3 weight stream
-        if (p.MF == 1) { if (p.NBW == 4) SK3(1, 4, true); else if (p.NBW == 3) SK3(1, 3, true); else SK3(1, 2, true); }
-        else { if (p.NBW == 4) SK3(2, 4, true); else if (p.NBW == 3) SK3(2, 3, true); else SK3(2, 2, true); }
-    } else {
-        if (p.MF == 1) { if (p.NBW == 4) SK3(1, 4, false); else if (p.NBW == 3) SK3(1, 3, false); else SK3(1, 2, false); }
-        else { if (p.NBW == 4) SK3(2, 4, false); else if (p.NBW == 3) SK3(2, 3, false); else SK3(2, 2, false); }
-    }
-#undef SK3
-    if (e == hipSuccess) e = hipGetLastError();
-    return e;
-}
+// ---- the LDS-tiled kernels: tile configurations {wave tile (WM, WN) in 16-row units, wave grid, stages}, indexed by TilePick
+struct TileCfg { int wm, wn, wgm, wgn, nst; };
+static const TileCfg k_tiles[32] = {
+    {4, 4, 2, 2, 2},   // TP_128x128:     4 waves of 64x64, 2 stages (64 KiB)
+    {2, 4, 2, 2, 2},   // TP_64x128:      4 waves of 32x64, 2 stages (48 KiB)
+    {2, 2, 2, 2, 3},   // TP_64x64:       4 waves of 32x32, 3 stages (48 KiB)
+    {4, 4, 2, 2, 4},   // TP_128x128_S4:  4 waves, 4 stages (128 KiB, one block per CU, three k-tiles in flight)
+    {4, 4, 4, 2, 3},   // TP_256x128:     8 waves of 64x64, 3 stages (144 KiB)
+    {4, 4, 2, 4, 3},   // TP_128x256:     8 waves of 64x64, 3 stages (144 KiB)
+    {2, 4, 4, 2, 4},   // TP_128x128_W8:  8 waves of 32x64, 4 stages (128 KiB)
+    {2, 4, 2, 2, 3},   // TP_64x128_S3:   4 waves, 3 stages (72 KiB, two blocks per CU, two k-tiles in flight each)
+    {4, 4, 2, 2, 3},   // TP_128x128_S3:  4 waves, 3 stages (96 KiB, one block per CU)
+    {2, 4, 2, 2, 3},   // TP_PC_64x128_S3:  loader wave + 4 MFMA waves, 3 stages (72 KiB)
+    {2, 4, 2, 2, 4},   // TP_PC_64x128:     loader wave + 4 MFMA waves, 4 stages (96 KiB)
+    {4, 4, 2, 2, 3},   // TP_PC_128x128:    loader wave + 4 MFMA waves, 3 stages (96 KiB)
+    {4, 4, 4, 2, 3},   // TP_PC_256x128:    4 loader waves + 8 MFMA waves of 64x64, 3 stages (144 KiB)
+    {4, 4, 2, 4, 3},   // TP_PC_128x256:    4 loader waves + 8 MFMA waves of 64x64, 3 stages (144 KiB)
+    // 224-row tiles (M = 448 = 2 x 224: no row padding, and the column width is chosen per GEMM so that the whole tile
+    // grid is ONE round of <= 256 blocks): 4 loader waves + MFMA waves of 112 x 48 / 112 x 32
+    {7, 3, 2, 2, 4},   // TP_PC_224x96_W4:  4 MFMA waves of 112x48 + 4 loaders, 4 stages (160 KiB)
+    {7, 2, 2, 4, 3},   // TP_PC_224x128:    8 MFMA waves of 112x32 + 4 loaders, 3 stages (132 KiB)
+    {7, 3, 2, 4, 3},   // TP_PC_224x192:    8 MFMA waves of 112x48 + 4 loaders, 3 stages (156 KiB)
+    {7, 2, 2, 3, 4},   // TP_PC_224x96:     6 MFMA waves of 112x32 + 4 loaders, 4 stages (160 KiB)
+    {4, 3, 2, 4, 3},   // TP_PC_128x192:    8 MFMA waves of 64x48 + 4 loaders, 3 stages (120 KiB) -- fp8 instantiation only (gemm_fp8.hip)
+    {}, {}, {}, {},    // (19..22: plan-counter slots of the weight-streaming / fp8 kernels)
+    // self-loading 8-wave tiles (gemm_v3.hip): no loader waves, fragment reads and LDS-DMA pieces interleaved with the MFMAs
+    {7, 3, 2, 4, 3},   // TP_V3_224x192: 8 waves of 112x48, 3 stages (156 KiB)
+    {7, 2, 2, 4, 3},   // TP_V3_224x128: 8 waves of 112x32, 3 stages (132 KiB)
+    {8, 2, 2, 4, 3},   // TP_V3_256x128: 8 waves of 128x32, 3 stages (144 KiB)
+    {4, 4, 2, 4, 3},   // TP_V3_128x256: 8 waves of 64x64,  3 stages (144 KiB)
+    {7, 3, 2, 2, 4},   // TP_V3_224x96:  4 waves of 112x48 (one per SIMD), 4 stages (160 KiB)
+    {}, {},            // (28, 29: 112x128 and 224x128 on four waves -- measured slower in round 5, removed in round 6)
+    // k-split wave pairs (gemm_v3.hip gemm_tiled_v3k): 2 x 2 wave tiles, each owned by the two waves of a SIMD, which split every k-tile
+    {7, 3, 2, 2, 4},   // TP_V3K_224x96: 4 wave pairs of 112x48, 4 stages (160 KiB)
+    {},                // (31: 224x128 on wave pairs of 112x64 and 224x64 on pairs of 112x32 were built and not kept; gemm_v3.hip)
+};
+static inline bool f8_self_loading(int pick) { return pick == TP_PC_256x128 || pick == TP_PC_128x256 || pick == TP_PC_224x128 || pick == TP_PC_128x192; }
 
-// the norm requested through the epilogue, as its own launch (paths that cannot fold it into a split-K reduction)
-static hipError_t run_norm(const EpiDev& epi, void* C, int ldc, int M, int Nout, hipStream_t st) {
-    if (epi.norm_style == 2)
-        return launch_layernorm_bf16((const bf16_t*)C, ldc, epi.norm_w, epi.norm_b, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st);
-    return launch_rmsnorm(C, 0, ldc, epi.norm_w, epi.norm_w_offset, epi.norm_style, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st,
-                          epi.nq8, epi.ldnq8, epi.nq8s);
-}
-
-hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K,
-                            const cover_gemm_epi* epi_in, float* ws, size_t ws_bytes, int variant, hipStream_t st, int* splits_out) {
-    if (splits_out) *splits_out = 0;
-    if (M <= 0 || N <= 0) return hipSuccess;
-    const int Kp = (K + 127) / 128 * 128;
-    EpiDev epi = make_epi(epi_in);
-    if (variant == 0) variant = (M <= 64 && ws != nullptr) ? 3 : 1;
-    // MX block scales (cover_gemm_epi.a8_mx / out8): the self-loading fp8 tiles only
-    const bool mx_any = epi.a8mx != nullptr || epi.o8 != nullptr;
-    if (mx_any) {
-        if (variant != 1 || !epi.a8 || !epi.w8 || M <= 64 || (size_t)M * epi.lda8 + 4096 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-        if (epi.a8mx && (!epi.w8_kl || epi.glu)) return hipErrorInvalidValue;
-        if (epi.o8 && (!epi.glu || (epi.act != ACT_SILU && epi.act != ACT_GELU_TANH) || ((N / 2) % 32) != 0 || epi.ldo8 < N / 2 || (epi.ldo8 & 15) || epi.out_f32))
-            return hipErrorInvalidValue;
-    }
-    // the reduction launch that can carry the norm (splitk_reduce_norm)
-    const bool norm_fusable = epi.norm_w != nullptr && epi.norm_out != nullptr && !epi.glu && !epi.out_f32 && (N % 8) == 0 && N <= 8192 && (ldc % 8) == 0 &&
-                              (epi.ld_norm_out % 8) == 0 && (((uintptr_t)epi.norm_w) & 15) == 0;
-    // Third generation (full-K chunk loop per block, one block per CU): used whenever its plan fills the chip -- with the
-    // epilogue fused when no grid split is needed (wide outputs), else leaving S (< the second generation's) partial slabs.
-    int S3 = 0;   // > 0: the third generation has left S3 slabs in ws, fall through to the shared reduction
-    if (variant == 3 || variant == 6) {
-        static const char* g3 = getenv("COVER_SKINNY3");   // experiment knob: 0 disables the automatic choice
-        Skinny3Plan p3 = plan_skinny3(M, N, Kp);
-        const int N16 = (N + 15) / 16;
-        if (variant == 6 && !p3.ok) {   // forced (tests): any legal problem, unsplit
-            if (M > 32 || (N16 & 1) || Kp < 2048) return hipErrorInvalidValue;
-            p3.ok = true; p3.NBW = 3; p3.S = 1; p3.kper = Kp; p3.gx = (N16 + 5) / 6;
-            p3.lds = (size_t)2 * p3.MF * 16 * 1024 * 2; p3.ws_bytes = 0;
-        }
-        if (p3.ok && p3.S > 1 && (ws == nullptr || ws_bytes < p3.ws_bytes)) p3.ok = false;
-        if (p3.ok && (variant == 6 || !(g3 && g3[0] == '0'))) {
-            hipError_t e = launch_skinny3(p3, A, lda, Wp, C, ldc, M, N, Kp, epi, p3.S > 1 ? ws : nullptr, st);
-            if (e != hipSuccess) return e;
-            if (p3.S == 1) {
-                if (epi.norm_w != nullptr && epi.norm_out != nullptr) e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
-                return e;
-            }
-            S3 = p3.S;
-        } else if (variant == 6) {
-            return hipErrorInvalidValue;
-        }
-        variant = 3;
-    }
-    if (variant == 3) {  // second-generation weight streaming (in-block k-slices), or the reduction of either generation
-        if (M > 64) return hipErrorInvalidValue;
-        int S = S3;
-        if (S == 0) {
-            Skinny2Plan p = plan_skinny2(M, N, Kp);
-            if (ws == nullptr || ws_bytes < p.ws_bytes) return hipErrorInvalidValue;
-            dim3 grid(p.gx, p.S), block(512);
-            launch_skinny2(p, A, lda, Wp, ws, M, N, K, Kp, epi.w8, epi.w8s, epi.w8_kl, st);
-            S = p.S;
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const bool want_norm = epi.norm_w != nullptr && epi.norm_out != nullptr;
-        if (norm_fusable) {
-            launch_streaming(5, 0.0, splitk_reduce_norm, dim3(M), dim3(512), 0, st, (const float*)ws, S, (bf16_t*)C, ldc, M, N, epi);
-            return hipGetLastError();
-        }
-        const int Nout = epi.glu ? N / 2 : N;
-        const long long total = (long long)M * ((Nout + 3) / 4);
-        int rb = (int)((total + 255) / 256);
-        if (rb > 2048) rb = 2048;
-        launch_streaming(5, 0.0, splitk_reduce, dim3(rb), dim3(256), 0, st, (const float*)ws, S, C, ldc, M, N, epi);
-        e = hipGetLastError();
-        if (e == hipSuccess && want_norm) e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
-        return e;
-    }
-    if (variant == 5) {  // first-generation weight streaming (grid-level split-K only), kept for A/B measurements
-        if (M > 64) return hipErrorInvalidValue;
-        SkinnyPlan p = plan_skinny(M, N, Kp);
-        if (ws == nullptr || ws_bytes < p.ws_bytes) return hipErrorInvalidValue;
-        dim3 grid(p.gx, p.S), block(512);
-        const int pid = prof_enabled() ? prof_open(st, sk_class(N, K), 2.0 * (double)N * (double)K) : -1;
-        plan_hit(22);
-        switch (p.MF) {
-            case 1: hipLaunchKernelGGL(gemm_skinny<1>, grid, block, p.lds, st, A, lda, Wp, ws, M, N, Kp, p.KC, p.nbpb); break;
-            case 2: hipLaunchKernelGGL(gemm_skinny<2>, grid, block, p.lds, st, A, lda, Wp, ws, M, N, Kp, p.KC, p.nbpb); break;
-            case 3: hipLaunchKernelGGL(gemm_skinny<3>, grid, block, p.lds, st, A, lda, Wp, ws, M, N, Kp, p.KC, p.nbpb); break;
-            default: hipLaunchKernelGGL(gemm_skinny<4>, grid, block, p.lds, st, A, lda, Wp, ws, M, N, Kp, p.KC, p.nbpb); break;
-        }
-        prof_close(st, pid);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const bool want_norm = epi.norm_w != nullptr && epi.norm_out != nullptr;
-        if (want_norm && !epi.glu && !epi.out_f32 && (N % 8) == 0 && N <= 8192 && (ldc % 8) == 0 && (epi.ld_norm_out % 8) == 0 && (((uintptr_t)epi.norm_w) & 15) == 0) {
-            hipLaunchKernelGGL(splitk_reduce_norm, dim3(M), dim3(512), 0, st, (const float*)ws, p.S, (bf16_t*)C, ldc, M, N, epi);
-            return hipGetLastError();
-        }
-        const int Nout = epi.glu ? N / 2 : N;
-        const long long total = (long long)M * ((Nout + 3) / 4);
-        int rb = (int)((total + 255) / 256);
-        if (rb > 2048) rb = 2048;
-        hipLaunchKernelGGL(splitk_reduce, dim3(rb), dim3(256), 0, st, (const float*)ws, p.S, C, ldc, M, N, epi);
-        e = hipGetLastError();
-        if (e == hipSuccess && want_norm)
-            e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
-        return e;
-    }
-    // ---- tile / split-K selection: fill >= ~1 block per CU when the problem allows it
-    // tile configurations: {wave tile (WM, WN) in 16-row units, wave grid, stages}
-    struct Cand { int wm, wn, wgm, wgn, nst; };
-    const Cand cands[32] = {
-        {4, 4, 2, 2, 2},   // 0: 128x128, 4 waves of 64x64, 2 stages (64 KiB)
-        {2, 4, 2, 2, 2},   // 1:  64x128, 4 waves of 32x64, 2 stages (48 KiB)
-        {2, 2, 2, 2, 3},   // 2:  64x64,  4 waves of 32x32, 3 stages (48 KiB)
-        {4, 4, 2, 2, 4},   // 3: 128x128, 4 waves, 4 stages (128 KiB, one block per CU, three k-tiles in flight)
-        {4, 4, 4, 2, 3},   // 4: 256x128, 8 waves of 64x64, 3 stages (144 KiB)
-        {4, 4, 2, 4, 3},   // 5: 128x256, 8 waves of 64x64, 3 stages (144 KiB)
-        {2, 4, 4, 2, 4},   // 6: 128x128, 8 waves of 32x64, 4 stages (128 KiB)
-        {2, 4, 2, 2, 3},   // 7:  64x128, 4 waves, 3 stages (72 KiB, two blocks per CU, two k-tiles in flight each)
-        {4, 4, 2, 2, 3},   // 8: 128x128, 4 waves, 3 stages (96 KiB, one block per CU)
-        {2, 4, 2, 2, 3},   // 9:  64x128, loader wave + 4 MFMA waves, 3 stages (72 KiB)
-        {2, 4, 2, 2, 4},   // a:  64x128, loader wave + 4 MFMA waves, 4 stages (96 KiB)
-        {4, 4, 2, 2, 3},   // b: 128x128, loader wave + 4 MFMA waves, 3 stages (96 KiB)
-        {4, 4, 4, 2, 3},   // c: 256x128, 4 loader waves + 8 MFMA waves of 64x64, 3 stages (144 KiB)
-        {4, 4, 2, 4, 3},   // d: 128x256, 4 loader waves + 8 MFMA waves of 64x64, 3 stages (144 KiB)
-        // 224-row tiles (M = 448 = 2 x 224: no row padding, and the column width is chosen per GEMM so that the whole tile
-        // grid is ONE round of <= 256 blocks): 4 loader waves + MFMA waves of 112 x 48 / 112 x 32
-        {7, 3, 2, 2, 4},   // e: 224x96,  4 MFMA waves of 112x48 + 4 loaders, 4 stages (160 KiB)
-        {7, 2, 2, 4, 3},   // f: 224x128, 8 MFMA waves of 112x32 + 4 loaders, 3 stages (132 KiB)
-        {7, 3, 2, 4, 3},   // g: 224x192, 8 MFMA waves of 112x48 + 4 loaders, 3 stages (156 KiB)
-        {7, 2, 2, 3, 4},   // h: 224x96,  6 MFMA waves of 112x32 + 4 loaders, 4 stages (160 KiB)
-        {4, 3, 2, 4, 3},   // i: 128x192, 8 MFMA waves of 64x48 + 4 loaders, 3 stages (120 KiB) -- fp8 instantiation only (gemm_fp8.hip)
-        {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0},   // (19..22: plan-counter slots of the weight-streaming / fp8 kernels)
-        // self-loading 8-wave tiles (gemm_v3.hip): no loader waves, fragment reads and LDS-DMA pieces interleaved with the MFMAs
-        {7, 3, 2, 4, 3},   // n (23): 224x192, 8 waves of 112x48, 3 stages (156 KiB)
-        {7, 2, 2, 4, 3},   // o (24): 224x128, 8 waves of 112x32, 3 stages (132 KiB)
-        {8, 2, 2, 4, 3},   // p (25): 256x128, 8 waves of 128x32, 3 stages (144 KiB)
-        {4, 4, 2, 4, 3},   // q (26): 128x256, 8 waves of 64x64,  3 stages (144 KiB)
-        {7, 3, 2, 2, 4},   // r (27): 224x96,  4 waves of 112x48 (one per SIMD), 4 stages (160 KiB)
-        {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0},   // (28, 29: 112x128 and 224x128 on four waves -- measured slower in round 5, removed in round 6)
-        // k-split wave pairs (gemm_v3.hip gemm_tiled_v3k): 2 x 2 wave tiles, each owned by the two waves of a SIMD, which split every k-tile
-        {7, 3, 2, 2, 4},   // u (30): 224x96,  4 wave pairs of 112x48, 4 stages (160 KiB)
-        {0, 0, 0, 0, 0},   // (31: 224x128 on wave pairs of 112x64 and 224x64 on pairs of 112x32 were built and not kept; gemm_v3.hip)
-    };
+// The tile, the K split and the kernel family of an LDS-tiled GEMM (variants 1 / 2).
+static hipError_t plan_tiles(GemmPlan& p, int lda, int M, int N, int Kp, const EpiDev& epi, const float* ws, size_t ws_bytes, int variant, bool mx_any) {
     // Measured on MI355X (tools/bench_kernels.py, M = 441): this single-barrier-per-k-tile structure is latency-bound per
     // block, so residency beats tile size until the tile grid oversubscribes the chip several times over, while 64x64
     // tiles on a wide N become L2-traffic-bound (the activation panel is re-read N/64 times).
     auto nblocks = [&](int c) {
-        const int bm_ = cands[c].wm * cands[c].wgm * 16, bn_ = cands[c].wn * cands[c].wgn * 16;
+        const int bm_ = k_tiles[c].wm * k_tiles[c].wgm * 16, bn_ = k_tiles[c].wn * k_tiles[c].wgn * 16;
         return (long long)((M + bm_ - 1) / bm_) * ((N + bn_ - 1) / bn_);
     };
-    int pick = 0;
+    int pick = TP_128x128;
     // (tools/exp_tiles.py re-reads one weight matrix, i.e. measures Infinity-Cache-warm: there 128x128 wins already at 688
     // tiles (N = 22016, M = 449); inside the decision, with cold weights, it does not -- 137 vs ~130 us -- so 1024 stays)
-    if (nblocks(0) < 1024) pick = (nblocks(1) >= 384) ? 1 : 2;
+    if (nblocks(TP_128x128) < 1024) pick = (nblocks(TP_64x128) >= 384) ? TP_64x128 : TP_64x64;
     // a 64x128 grid of about one block per CU on a long K (M = 448: o_proj / down of a 7B decoder) is latency-bound per block:
     // deeper rings beat the 64x64 tile there (cold weights, down / o_proj: 64x64 90.9 / 35.7 us, 64x128 3-stage 81.9 / 35.6,
     // 64x128 with a loader wave and 4 stages 78.2 / 34.6). For the multi-round grids (qkv, gate_up) neither the deeper ring
     // nor the loader wave helps (they cost a resident block per CU): 2 stages x 3 blocks stays.
-    if (pick == 2 && nblocks(1) >= 192 && Kp >= 4096) pick = 10;   // loader-wave variant, 4 stages: 83.4 -> 78.2 us (down), 35.9 -> 34.6 (o_proj)
+    if (pick == TP_64x64 && nblocks(TP_64x128) >= 192 && Kp >= 4096) pick = TP_PC_64x128;   // 4 stages: 83.4 -> 78.2 us (down), 35.9 -> 34.6 (o_proj)
     // 8 MFMA waves of 64x64 + 4 loader waves on 256x128 / 128x256 tiles (3 stages, one block per CU): per k-tile a SIMD has 1024
     // cycles of MFMA against 768 cycles of LDS-DMA on the CU's address path, and none of the DMA issue sits in an MFMA wave.
     // Cold weights: M = 2624 qkv 715 -> 867 TF, gate_up 792 -> 1026 TF, down 660 -> 833 TF (M = 448 in isolation: qkv 80.5 ->
@@ -1734,8 +1587,8 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
     // M = 512 (decode rows of BASELINE config 5: N = 512 candidates) is two 256-row tiles: qkv 75.4 -> 60.2 us, gate_up 135.9 -> 116.9,
     // down 73.1 -> 48.4 + 13.5 (four K slices + reduction); o_proj stays on the 64 x 128 tiles (29.0 vs 25.4 + 13.5).
     if (variant != 2 && Kp >= 2048 && M >= 512) {
-        if (N > 4096 && nblocks(13) >= 176) pick = N >= 16384 ? 12 : 13;
-        else if (N <= 4096 && Kp >= 8192 && (nblocks(12) >= 256 || (M < 1024 && ws != nullptr))) pick = 12;
+        if (N > 4096 && nblocks(TP_PC_128x256) >= 176) pick = N >= 16384 ? TP_PC_256x128 : TP_PC_128x256;
+        else if (N <= 4096 && Kp >= 8192 && (nblocks(TP_PC_256x128) >= 256 || (M < 1024 && ws != nullptr))) pick = TP_PC_256x128;
     }
     // fp8 operands (config 5, M = 512 decode rows): with half the bytes per FLOP the 12-wave tiles are bound by how evenly the tile grid
     // covers the 256 CUs, not by the fill: qkv (N = 12288) is 192 tiles of 256 x 128 / 128 x 256 -- a quarter of the chip idle -- but
@@ -1744,18 +1597,18 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
     // M = 512: qkv 35 -> 28 us, gate_up 70 -> 54 us.
     const char* f8_env = epi.a8 ? getenv("COVER_FP8_MFMA") : nullptr;   // experiment knob, read per call: 0 keeps the bf16 MFMA path on fp8 operands
     const bool f8_on = epi.a8 && !(f8_env && f8_env[0] == '0');
-    if (f8_on && variant != 2 && Kp >= 2048 && M >= 512 && N > 4096 && gemm_fp8_tiled_supported(18)) {
-        const int idx[3] = {12, 13, 18};
+    if (f8_on && variant != 2 && Kp >= 2048 && M >= 512 && N > 4096) {
+        const int idx[3] = {TP_PC_256x128, TP_PC_128x256, TP_PC_128x192};
         double best = 1e30;
         for (int c = 0; c < 3; ++c) {
-            const int bm_ = cands[idx[c]].wm * cands[idx[c]].wgm * 16, bn_ = cands[idx[c]].wn * cands[idx[c]].wgn * 16;
+            const int bm_ = k_tiles[idx[c]].wm * k_tiles[idx[c]].wgm * 16, bn_ = k_tiles[idx[c]].wn * k_tiles[idx[c]].wgn * 16;
             if (epi.glu && (bn_ % 32)) continue;
             const long long rounds = (nblocks(idx[c]) + 255) / 256;
             const double cost = rounds * (0.55 * (double)bm_ * bn_ / 32768.0 + 0.45 * (double)(bm_ + bn_) / 384.0);
             if (cost < best) { best = cost; pick = idx[c]; }
         }
     }
-    // 224-row tiles (picks 15-17): M = 448 -- the OpenVLA prefill pass: 256 patch rows + 8 prompts x 24 text rows -- is exactly two
+    // 224-row tiles: M = 448 -- the OpenVLA prefill pass: 256 patch rows + 8 prompts x 24 text rows -- is exactly two
     // of them, where 128-row tiles pad 12.5 % and 64 x 128 tiles need 1.3-2.7 rounds of blocks. The column width and the number of
     // K slices are chosen per GEMM so that the grid is ONE round of <= 256 blocks, with a cost model fitted to per-block timelines
     // (tools/dbg/pc_timeline.py; us per 64-deep k-tile: 224x96 0.67, 224x128 0.70, 224x192 1.05; ~5 us of prologue + epilogue
@@ -1771,8 +1624,8 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
             // loader-wave kernels (gemm_tiled_pc): 224x96 (6 MFMA waves) / 224x128 / 224x192; self-loading kernels (gemm_v3.hip, round 5,
             // in-kernel probe of workgroup 0 at M = 448 / 2232): 224x96 with one wave of 112x48 per SIMD 0.62 us per k-tile, 224x128
             // 0.69-0.78, 224x192 0.91-1.02; prologue + epilogue 6 / 7 / 10 us
-            // (round 6: 224x96 on k-split wave pairs, pick 30, instead of one wave per SIMD, pick 27)
-            const int bns[3] = {96, 128, 192}, idx_pc[3] = {17, 15, 16}, idx_v3[3] = {30, 24, 23};
+            // (round 6: 224x96 on k-split wave pairs instead of one wave per SIMD)
+            const int bns[3] = {96, 128, 192}, idx_pc[3] = {TP_PC_224x96, TP_PC_224x128, TP_PC_224x192}, idx_v3[3] = {TP_V3K_224x96, TP_V3_224x128, TP_V3_224x192};
             const double kt_pc[3] = {0.67, 0.70, 1.05}, kt_v3[3] = {0.60, 0.72, 0.93}, fix_v3[3] = {6.0, 7.0, 10.0};
             double best = 1e30;
             for (int c = 0; c < 3; ++c) {
@@ -1791,139 +1644,277 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
             }
         }
     }
-    {
-        static const char* force = getenv("COVER_TILE_PICK");  // experiment knob: index into cands
-        if (force && force[0] >= '0' && force[0] <= '9') pick = force[0] - '0';
-        if (force && force[0] >= 'a' && force[0] <= 'i') pick = 10 + (force[0] - 'a');   // (b .. i: fp8 operands only)
-        if (force && force[0] >= 'n' && force[0] <= 'u' && force[0] != 's' && force[0] != 't') pick = 10 + (force[0] - 'a');
-    }
+    // experiment knob: a row of the tile table, by its digit / letter ('a' = 10 ... 'i' = 18, 'n' = 23 ... 'u' = 30; b .. i: fp8 operands only)
+    static const char* force = getenv("COVER_TILE_PICK");
+    if (force && force[0] >= '0' && force[0] <= '9') pick = force[0] - '0';
+    if (force && force[0] >= 'a' && force[0] <= 'i') pick = 10 + (force[0] - 'a');
+    if (force && force[0] >= 'n' && force[0] <= 'u' && force[0] != 's' && force[0] != 't') pick = 10 + (force[0] - 'a');
     // the 256 x 128 / 128 x 256 tiles (M >= 512 with more than 10 % of 224-row padding: config 4's 704-row prefill) run on the self-loading kernel
-    if (v3_on) pick = pick == 12 ? 25 : pick == 13 ? 26 : pick;
-    if (!v3_on && pick >= 23) pick = f8_on ? (pick == 24 ? 15 : pick == 25 ? 12 : pick == 26 ? 13 : pick == 27 ? 17 : 10) : 0;
+    if (v3_on) pick = pick == TP_PC_256x128 ? TP_V3_256x128 : pick == TP_PC_128x256 ? TP_V3_128x256 : pick;
+    if (!v3_on && pick >= TP_V3_224x192)
+        pick = f8_on ? (pick == TP_V3_224x128 ? TP_PC_224x128 : pick == TP_V3_256x128 ? TP_PC_256x128 : pick == TP_V3_128x256 ? TP_PC_128x256
+                        : pick == TP_V3_224x96 ? TP_PC_224x96 : TP_PC_64x128)
+                     : TP_128x128;
     if (mx_any) {
-        if (!f8_on) return hipErrorInvalidValue;                                   // (COVER_FP8_MFMA=0 with block-scaled operands)
-        if (pick != 12 && pick != 13 && pick != 15 && pick != 18 && !(pick == 10 && epi.a8mx && !epi.o8)) pick = 13;   // any M on the 128 x 256 self-loading tile (the 64 x 128 loader-wave tile reads block scales too)
+        if (!f8_on) return hipErrorInvalidValue;   // (COVER_FP8_MFMA=0 with block-scaled operands)
+        // any M on the 128 x 256 self-loading tile (the 64 x 128 loader-wave tile reads block scales too)
+        if (pick != TP_PC_256x128 && pick != TP_PC_128x256 && pick != TP_PC_224x128 && pick != TP_PC_128x192 && !(pick == TP_PC_64x128 && epi.a8mx && !epi.o8))
+            pick = TP_PC_128x256;
     }
-    // bf16 operands: of the loader-wave tiles only the 64 x 128 four-stage one (pick 10) is still a default; the others exist as fp8 kernels
-    if (!(f8_on && gemm_fp8_tiled_supported(pick)) && ((pick >= 11 && pick <= 18) || pick == 9)) pick = (variant == 2 || pick == 9) ? 1 : 0;
-    if (variant == 2 && pick > 2) pick = 0;
-    const Cand cd = cands[pick];
+    // bf16 operands: of the loader-wave tiles only the 64 x 128 four-stage one is still a default; the others exist as fp8 kernels
+    if (!(f8_on && gemm_fp8_tiled_supported(pick)) && ((pick >= TP_PC_128x128 && pick <= TP_PC_128x192) || pick == TP_PC_64x128_S3)) pick = (variant == 2 || pick == TP_PC_64x128_S3) ? TP_64x128 : TP_128x128;
+    if (variant == 2 && pick > TP_64x64) pick = TP_128x128;
+    const bool f8 = f8_on && gemm_fp8_tiled_supported(pick);
+    const TileCfg cd = k_tiles[pick];
     const int bm = cd.wm * cd.wgm * 16, bn = cd.wn * cd.wgn * 16;
-    const int tiles_m = (M + bm - 1) / bm, tiles_n = (N + bn - 1) / bn;
+    p.pick = pick;
+    p.tiles_m = (M + bm - 1) / bm;
+    p.tiles_n = (N + bn - 1) / bn;
     const int nk_total = Kp / BK;
     int S = 1;
-    static const char* force_pick = getenv("COVER_TILE_PICK");
-    if (S_forced > 0 && !force_pick) {
+    if (S_forced > 0 && !force) {
         S = S_forced;
     } else if (ws != nullptr) {
-        while ((long long)tiles_m * tiles_n * S < 192 && S < 8 && nk_total / (S * 2) >= 8 &&
-               (size_t)(S * 2) * M * N * sizeof(float) <= ws_bytes)
+        while ((long long)p.tiles_m * p.tiles_n * S < 192 && S < 8 && nk_total / (S * 2) >= 8 && (size_t)(S * 2) * M * N * sizeof(float) <= ws_bytes)
             S *= 2;
         static const char* split_env = getenv("COVER_TILE_SPLIT");   // experiment knob: force the number of K slices
         if (split_env && atoi(split_env) >= 1 && (size_t)atoi(split_env) * M * N * sizeof(float) <= ws_bytes) S = atoi(split_env);
     }
     if (epi.o8) S = 1;   // (the block-scaled GLU output is written by the GEMM's own epilogue, not by a split-K reduction)
-    const int kt_per = (nk_total + S - 1) / S;
-    S = (nk_total + kt_per - 1) / kt_per;
-    float* partial = S > 1 ? ws : nullptr;
     // stages: measured at M = 441 (tools/bench_kernels.py): the 64x64 tile gains 40-55 % from a third stage (48 KiB, still
     // 3 blocks/CU); 64x128 and 128x128 are bound by the bytes a CU keeps in flight (LDS capacity x resident blocks) over
     // the load latency (~12.8 TB/s chip-wide at 2 stages => 42.7 / 64 FLOP per byte).
     const int nst = variant == 2 ? 2 : cd.nst;
-    const size_t lds = (size_t)nst * (bm + bn) * BK * 2;
-    const bool pc = pick == 10;
-    dim3 grid(tiles_m * tiles_n, S), block(pc ? 64 * cd.wgm * cd.wgn + 256 : 64 * cd.wgm * cd.wgn);
-    // profiling: the GEMM kernel's own start / stop stamps; class 4 = LLM-sized weight matrix (prefill), 1 = ViT-sized
+    p.lds = (size_t)nst * (bm + bn) * BK * 2;
+    p.block = 64 * cd.wgm * cd.wgn;
+    p.slot = pick;
+    if (f8) {
+        // both operands e4m3: the MX-scaled matrix instruction, 128 k per k-tile (same LDS bytes per tile as 64 k of bf16), K slices of whole 128-deep tiles
+        if (epi.lda8 < Kp || (epi.lda8 & 15)) return hipErrorInvalidValue;
+        static const char* v3f8_env = getenv("COVER_V3_F8");   // experiment knob: 0 keeps the loader-wave form of the self-loading fp8 tiles
+        const bool v3f8 = !(v3f8_env && v3f8_env[0] == '0') && (size_t)M * epi.lda8 + 4096 < ((size_t)1 << 31);
+        p.kind = v3f8 && f8_self_loading(pick) ? GK_F8_V3 : GK_F8_PC;
+        // MX block scales (operand or output) exist on the self-loading kernels and, for a8_mx, on the 64 x 128 loader-wave tile
+        if (mx_any && p.kind != GK_F8_V3 && !(pick == TP_PC_64x128 && epi.a8mx && !epi.o8)) return hipErrorInvalidValue;
+        if (epi.a8mx) p.lds += p.kind == GK_F8_V3 ? 3 * 1024 : 4 * 256;   // (+ the block-scale ring)
+        if (p.kind == GK_F8_PC) p.block += 256;
+        p.slot = PLAN_FP8;
+        const int nk8 = Kp / 128;
+        p.kt_per = (nk8 + S - 1) / S;
+        p.S = (nk8 + p.kt_per - 1) / p.kt_per;
+        return hipSuccess;
+    }
+    p.kt_per = (nk_total + S - 1) / S;
+    p.S = (nk_total + p.kt_per - 1) / p.kt_per;
+    if (pick >= TP_V3_224x192) {
+        if ((size_t)M * lda * 2 + 4096 >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // 32-bit lane offsets of the activation pieces
+        p.kind = GK_V3;
+        if (pick == TP_V3K_224x96) p.block *= 2;   // two waves per wave tile
+    } else if (pick == TP_PC_64x128) {
+        p.kind = GK_TILED_PC;
+        p.block += 256;   // four loader waves
+    } else {
+        p.kind = GK_TILED;
+    }
+    return hipSuccess;
+}
+
+// The whole plan of one GEMM: validation, kernel family, grid, and how the K slices are completed. No HIP call.
+// want_slabs: the caller can fold the slabs of a split-K tiled launch itself (launch_gemm_bf16's splits_out).
+static hipError_t plan_gemm(GemmPlan& p, int lda, const void* C, int ldc, int M, int N, int K, const EpiDev& epi, const float* ws, size_t ws_bytes,
+                            int variant, bool want_slabs) {
+    p = GemmPlan{};
+    p.kind = GK_NONE; p.slot = -1; p.pick = -1;
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const int Kp = (K + 127) / 128 * 128;
+    if (variant == 0) variant = (M <= 64 && ws != nullptr) ? 3 : 1;
+    // MX block scales (cover_gemm_epi.a8_mx / out8): the self-loading fp8 tiles only
+    const bool mx_any = epi.a8mx != nullptr || epi.o8 != nullptr;
+    if (mx_any) {
+        if (variant != 1 || !epi.a8 || !epi.w8 || M <= 64 || (size_t)M * epi.lda8 + 4096 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+        if (epi.a8mx && (!epi.w8_kl || epi.glu)) return hipErrorInvalidValue;
+        if (epi.o8 && (!epi.glu || (epi.act != ACT_SILU && epi.act != ACT_GELU_TANH) || ((N / 2) % 32) != 0 || epi.ldo8 < N / 2 || (epi.ldo8 & 15) || epi.out_f32))
+            return hipErrorInvalidValue;
+        if (epi.o8 && ((((uintptr_t)C) & 15) || (ldc % 8))) return hipErrorInvalidValue;   // (the bf16 tile stores the out8 epilogue stages)
+    }
+    // a k-linear e4m3 twin needs block-scaled activations on the fp8 tiles: per-row a8 would be read in the default image's k order
+    if (epi.w8_kl && epi.a8 && !epi.a8mx && M > 64) return hipErrorInvalidValue;
+    hipError_t e;
+    if (variant == 3 || variant == 6) e = plan_streaming(p, M, N, Kp, ws, ws_bytes, variant == 6, false);
+    else if (variant == 5) {   // first-generation weight streaming (grid-level split-K only), kept for A/B measurements
+        if (M > 64) return hipErrorInvalidValue;
+        p.p1 = plan_skinny(M, N, Kp);
+        if (ws == nullptr || ws_bytes < p.p1.ws_bytes) return hipErrorInvalidValue;
+        p.kind = GK_SKINNY; p.slot = PLAN_SKINNY; p.S = p.p1.S; p.lds = p.p1.lds;
+        e = hipSuccess;
+    } else e = plan_tiles(p, lda, M, N, Kp, epi, ws, ws_bytes, variant, mx_any);
+    if (e != hipSuccess) return e;
+    // completion: weight streaming always reduces its slabs (but an unsplit third-generation launch, which runs the fused epilogue);
+    // a tiled launch reduces them when it splits K, unless the caller folds them itself
+    const bool want_norm = epi.norm_w != nullptr && epi.norm_out != nullptr;
+    const bool streaming = p.kind == GK_SKINNY || p.kind == GK_SKINNY2 || p.kind == GK_SKINNY3;
+    const bool split = streaming ? !(p.kind == GK_SKINNY3 && p.S == 1) : p.S > 1;
+    const bool norm_fusable = want_norm && !epi.glu && !epi.out_f32 && (N % 8) == 0 && N <= 8192 && (ldc % 8) == 0 && (epi.ld_norm_out % 8) == 0 &&
+                              (((uintptr_t)epi.norm_w) & 15) == 0;   // the reduction launch that can carry the norm (splitk_reduce_norm)
+    p.rcls = streaming ? 5 : p.kind == GK_F8_PC || p.kind == GK_F8_V3 ? 9 : (double)N * (double)Kp >= 16.0e6 ? 8 : 6;
+    if (!split) p.done = GD_NONE;
+    else if (!streaming && want_slabs && !epi.residual && !epi.lscale && epi.act == ACT_NONE && epi.out_scale == 1.0f && !epi.glu && !epi.norm_out)
+        p.done = GD_SLABS;   // the caller folds the slabs (+ bias, bf16 rounding) itself
+    else p.done = norm_fusable ? GD_REDUCE_NORM : GD_REDUCE;
+    p.norm_launch = want_norm && p.done != GD_REDUCE_NORM;
+    return hipSuccess;
+}
+
+hipError_t gemm_plan_query(const bf16_t* A, int lda, const bf16_t* Wp, const void* C, int ldc, int M, int N, int K, const cover_gemm_epi* epi_in,
+                           const float* ws, size_t ws_bytes, int variant, int* plan) {
+    GemmPlan p;
+    const hipError_t e = plan_gemm(p, lda, C, ldc, M, N, K, make_epi(epi_in), ws, ws_bytes, variant, false);
+    if (e != hipSuccess) return e;
+    const int out[6] = {p.slot, p.pick, p.kind == GK_F8_V3 ? 1 : 0, p.S, p.done == GD_NONE ? 0 : p.done == GD_REDUCE ? 1 : 2, p.norm_launch ? 1 : 0};
+    for (int i = 0; i < 6; ++i) plan[i] = out[i];
+    return hipSuccess;
+}
+
+// the norm requested through the epilogue, as its own launch (paths that cannot fold it into a split-K reduction)
+static hipError_t run_norm(const EpiDev& epi, void* C, int ldc, int M, int Nout, hipStream_t st) {
+    if (epi.norm_style == 2)
+        return launch_layernorm_bf16((const bf16_t*)C, ldc, epi.norm_w, epi.norm_b, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st);
+    return launch_rmsnorm(C, 0, ldc, epi.norm_w, epi.norm_w_offset, epi.norm_style, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st,
+                          epi.nq8, epi.ldnq8, epi.nq8s);
+}
+
+// the completion of a planned launch: the split-K reduction (with the norm folded in, or followed by its own norm launch)
+static hipError_t complete_splitk(const GemmPlan& p, const EpiDev& epi, const float* ws, void* C, int ldc, int M, int N, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (p.done == GD_REDUCE_NORM) {
+        e = launch_kernel<splitk_reduce_norm>(p.rcls, 0.0, dim3(M), dim3(512), 0, st, ws, p.S, (bf16_t*)C, ldc, M, N, epi);
+    } else if (p.done == GD_REDUCE) {
+        const int Nout = epi.glu ? N / 2 : N;
+        const long long total = (long long)M * ((Nout + 3) / 4);
+        int rb = (int)((total + 255) / 256);
+        if (rb > 2048) rb = 2048;
+        e = launch_kernel<splitk_reduce>(p.rcls, 0.0, dim3(rb), dim3(256), 0, st, ws, p.S, C, ldc, M, N, epi);
+    }
+    if (e == hipSuccess && p.done != GD_NONE) e = hipGetLastError();
+    if (e == hipSuccess && p.norm_launch) e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
+    return e;
+}
+
+// second-generation weight streaming; e4m3 weights for M <= 32 when a twin is given
+static hipError_t launch_skinny2(const Skinny2Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, float* ws, int M, int N, int K, int Kp,
+                                 const uint8_t* w8, const float* w8s, int kl, hipStream_t st) {
+    const dim3 grid(p.gx, p.S), block(512);
+    plan_hit(PLAN_SKINNY2);
+#define SK2(MF_, KS_, NBW_, W8_) launch_kernel<gemm_skinny2<MF_, KS_, NBW_, W8_>>(sk_class(N, K), (W8_ ? 1.0 : 2.0) * (double)N * (double)K, grid, block, p.lds, st, \
+                                                                                   A, lda, W8_ ? (const bf16_t*)w8 : Wp, ws, M, N, Kp, w8s, kl)
+    hipError_t e;
+    if (w8 && w8s && p.MF <= 2) {
+        if (p.MF == 1) e = p.NBW == 6 ? SK2(1, 4, 6, true) : p.NBW == 4 ? SK2(1, 4, 4, true) : p.NBW == 3 ? SK2(1, 4, 3, true) : SK2(1, 4, 2, true);
+        else e = p.NBW == 6 ? SK2(2, 4, 6, true) : p.NBW == 4 ? SK2(2, 4, 4, true) : p.NBW == 3 ? SK2(2, 4, 3, true) : SK2(2, 4, 2, true);
+    } else {
+        if (p.MF == 1) e = p.NBW == 6 ? SK2(1, 4, 6, false) : p.NBW == 4 ? SK2(1, 4, 4, false) : p.NBW == 3 ? SK2(1, 4, 3, false) : SK2(1, 4, 2, false);
+        else if (p.MF == 2) e = p.NBW == 6 ? SK2(2, 4, 6, false) : p.NBW == 4 ? SK2(2, 4, 4, false) : p.NBW == 3 ? SK2(2, 4, 3, false) : SK2(2, 4, 2, false);
+        else if (p.MF == 3) e = SK2(3, 2, 2, false);
+        else e = SK2(4, 2, 2, false);
+    }
+#undef SK2
+    if (e == hipSuccess) e = hipGetLastError();
+    return e;
+}
+
+static hipError_t launch_skinny3(const Skinny3Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N,
+                                 int Kp, const EpiDev& epi, float* partial, hipStream_t st) {
+    const dim3 grid(p.gx, p.S), block(512);
+    plan_hit(PLAN_SKINNY3);
+#define SK3(MF_, NBW_, W8_) launch_kernel<gemm_skinny3<MF_, 4, NBW_, NBW_, W8_>>(sk_class(N, Kp), (W8_ ? 1.0 : 2.0) * (double)N * (double)Kp, grid, block, p.lds, st, \
+                                                                                  A, lda, W8_ ? (const bf16_t*)epi.w8 : Wp, C, ldc, M, N, Kp, epi, partial, p.kper, epi.w8s, epi.w8_kl)
+    hipError_t e;
+    if (epi.w8) {   // e4m3 weight stream
+        if (p.MF == 1) e = p.NBW == 4 ? SK3(1, 4, true) : p.NBW == 3 ? SK3(1, 3, true) : SK3(1, 2, true);
+        else e = p.NBW == 4 ? SK3(2, 4, true) : p.NBW == 3 ? SK3(2, 3, true) : SK3(2, 2, true);
+    } else {
+        if (p.MF == 1) e = p.NBW == 4 ? SK3(1, 4, false) : p.NBW == 3 ? SK3(1, 3, false) : SK3(1, 2, false);
+        else e = p.NBW == 4 ? SK3(2, 4, false) : p.NBW == 3 ? SK3(2, 3, false) : SK3(2, 2, false);
+    }
+#undef SK3
+    if (e == hipSuccess) e = hipGetLastError();
+    return e;
+}
+
+// the LDS-tiled kernels of a GK_TILED / GK_TILED_PC / GK_V3 / GK_F8_* plan
+static hipError_t launch_tiles(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K, int Kp,
+                               const EpiDev& epi, float* partial, int variant, hipStream_t st) {
+    // profiling: the GEMM kernel's own start / stop stamps; class 4 = LLM-sized weight matrix (prefill), 1 = ViT-sized, 7 = fp8 tiles
     const int tcls = (double)N * (double)Kp >= 16.0e6 ? 4 : 1;
     const double twork = 2.0 * (double)M * (double)N * (double)K;
-    hipError_t e = hipSuccess;
-#define LAUNCH_T(WM_, WN_, G_, NST_, WGM_, WGN_)                                                                            \
-    do {                                                                                                                    \
-        auto kfn = gemm_tiled<WM_, WN_, G_, NST_, WGM_, WGN_>;                                                              \
-        if (lds > 64 * 1024) {                                                                                              \
-            e = LDS_ATTR_160K(kfn);                                                                                                       \
-        }                                                                                                                   \
-        if (e == hipSuccess)                                                                                                \
-            launch_streaming(tcls, twork, kfn, grid, block, lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-    } while (0)
-#define LAUNCH_PC(WM_, WN_, NST_, NL_)                                                                                      \
-    do {                                                                                                                    \
-        auto kfn = gemm_tiled_pc<WM_, WN_, NST_, NL_>;                                                                      \
-        if (lds > 64 * 1024) {                                                                                              \
-            e = LDS_ATTR_160K(kfn);                                                                                                       \
-        }                                                                                                                   \
-        if (e == hipSuccess)                                                                                                \
-            launch_streaming(tcls, twork, kfn, grid, block, lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-    } while (0)
-    if (f8_on && gemm_fp8_tiled_supported(pick)) {
-        plan_hit(21);
-        // both operands e4m3: the MX-scaled matrix instruction, 128 k per k-tile (same LDS bytes per tile as 64 k of bf16)
-        if (epi.lda8 < Kp || (epi.lda8 & 15)) return hipErrorInvalidValue;
-        const int nk8 = Kp / 128;
-        const int kt8 = (nk8 + S - 1) / S;
-        S = (nk8 + kt8 - 1) / kt8;                                      // K slices of whole 128-deep tiles
-        partial = S > 1 ? ws : nullptr;
-        e = launch_gemm_fp8_tiled(pick, epi.a8, epi.lda8, epi.a8s, epi.w8, epi.w8s, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt8, S, partial, lds,
-                                  7, 2.0 * (double)M * (double)N * (double)K, st);
-    } else if (pick >= 23) {
-        plan_hit(pick);
+    plan_hit(p.slot);
+    if (p.kind == GK_F8_PC || p.kind == GK_F8_V3) return launch_gemm_fp8_tiled(p, epi, C, ldc, M, N, Kp, partial, twork, st);
+    if (p.kind == GK_V3) {
         // an unsplit launch with a plain fp32 output IS one split-K slab: take the raw-slab epilogue (LDS-staged 16-byte stores of the fp32 sums;
         // the consumer -- the qkv fold of the attention launch -- rounds them exactly as it rounds a sum of slabs)
-        float* part3 = partial;
-        if (S == 1 && epi.out_f32 && !epi.bias && !epi.residual && !epi.lscale && epi.act == ACT_NONE && epi.out_scale == 1.0f && !epi.glu && !epi.norm_out &&
-            ldc == N)
-            part3 = (float*)C;
-        e = launch_gemm_v3(pick, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, S, part3, tcls, twork, st);
-    } else if (pc) {
-        plan_hit(pick);
-        // 64 x 128 tile, four loader waves + four MFMA waves, four stages (narrow outputs on a long K at a few hundred rows)
-        LAUNCH_PC(2, 4, 4, 4);
+        if (p.S == 1 && epi.out_f32 && !epi.bias && !epi.residual && !epi.lscale && epi.act == ACT_NONE && epi.out_scale == 1.0f && !epi.glu &&
+            !epi.norm_out && ldc == N)
+            partial = (float*)C;
+        return launch_gemm_v3(p, A, lda, Wp, C, ldc, M, N, Kp, epi, partial, tcls, twork, st);
+    }
+    const dim3 grid(p.tiles_m * p.tiles_n, p.S), block(p.block);
+#define T(KFN) launch_kernel<KFN>(tcls, twork, grid, block, p.lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, p.tiles_m, p.tiles_n, p.kt_per, partial)
+    hipError_t e;
+    if (p.kind == GK_TILED_PC) {
+        e = T((gemm_tiled_pc<2, 4, 4, 4>));   // 64 x 128 tile, four loader waves + four MFMA waves, four stages (narrow outputs on a long K at a few hundred rows)
     } else if (variant == 2) {
-        plan_hit(pick);
-        if (pick == 0) LAUNCH_T(4, 4, false, 2, 2, 2);
-        else if (pick == 1) LAUNCH_T(2, 4, false, 2, 2, 2);
-        else LAUNCH_T(2, 2, false, 2, 2, 2);
+        e = p.pick == TP_128x128 ? T((gemm_tiled<4, 4, false, 2, 2, 2>)) : p.pick == TP_64x128 ? T((gemm_tiled<2, 4, false, 2, 2, 2>)) : T((gemm_tiled<2, 2, false, 2, 2, 2>));
     } else {
-        plan_hit(pick);
-        switch (pick) {
-            case 0: LAUNCH_T(4, 4, true, 2, 2, 2); break;
-            case 1: LAUNCH_T(2, 4, true, 2, 2, 2); break;
-            case 2: LAUNCH_T(2, 2, true, 3, 2, 2); break;
-            case 3: LAUNCH_T(4, 4, true, 4, 2, 2); break;
-            case 4: LAUNCH_T(4, 4, true, 3, 4, 2); break;
-            case 5: LAUNCH_T(4, 4, true, 3, 2, 4); break;
-            case 7: LAUNCH_T(2, 4, true, 3, 2, 2); break;
-            case 8: LAUNCH_T(4, 4, true, 3, 2, 2); break;
-            default: LAUNCH_T(2, 4, true, 4, 4, 2); break;
+        switch (p.pick) {
+            case TP_128x128: e = T((gemm_tiled<4, 4, true, 2, 2, 2>)); break;
+            case TP_64x128: e = T((gemm_tiled<2, 4, true, 2, 2, 2>)); break;
+            case TP_64x64: e = T((gemm_tiled<2, 2, true, 3, 2, 2>)); break;
+            case TP_128x128_S4: e = T((gemm_tiled<4, 4, true, 4, 2, 2>)); break;
+            case TP_256x128: e = T((gemm_tiled<4, 4, true, 3, 4, 2>)); break;
+            case TP_128x256: e = T((gemm_tiled<4, 4, true, 3, 2, 4>)); break;
+            case TP_64x128_S3: e = T((gemm_tiled<2, 4, true, 3, 2, 2>)); break;
+            case TP_128x128_S3: e = T((gemm_tiled<4, 4, true, 3, 2, 2>)); break;
+            default: e = T((gemm_tiled<2, 4, true, 4, 4, 2>)); break;   // TP_128x128_W8
         }
     }
-#undef LAUNCH_T
+#undef T
     if (e == hipSuccess) e = hipGetLastError();
-    bool norm_done = false;
-    if (e == hipSuccess && S > 1 && splits_out && !epi.residual && !epi.lscale && epi.act == ACT_NONE && epi.out_scale == 1.0f && !epi.glu &&
-        !epi.norm_out) {
-        *splits_out = S;   // the caller folds the slabs (+ bias, bf16 rounding) itself
+    return e;
+}
+
+hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K,
+                            const cover_gemm_epi* epi_in, float* ws, size_t ws_bytes, int variant, hipStream_t st, int* splits_out) {
+    if (splits_out) *splits_out = 0;
+    const EpiDev epi = make_epi(epi_in);
+    GemmPlan p;
+    hipError_t e = plan_gemm(p, lda, C, ldc, M, N, K, epi, ws, ws_bytes, variant, splits_out != nullptr);
+    if (e != hipSuccess || p.kind == GK_NONE) return e;
+    const int Kp = (K + 127) / 128 * 128;
+    float* partial = p.S > 1 ? ws : nullptr;
+    switch (p.kind) {
+        case GK_SKINNY3: e = launch_skinny3(p.p3, A, lda, Wp, C, ldc, M, N, Kp, epi, partial, st); break;
+        case GK_SKINNY2: e = launch_skinny2(p.p2, A, lda, Wp, ws, M, N, K, Kp, epi.w8, epi.w8s, epi.w8_kl, st); break;
+        case GK_SKINNY:
+            plan_hit(PLAN_SKINNY);
+            switch (p.p1.MF) {
+#define SK1(MF_) launch_kernel<gemm_skinny<MF_>>(sk_class(N, K), 2.0 * (double)N * (double)K, dim3(p.p1.gx, p.S), dim3(512), p.lds, st, A, lda, Wp, ws, M, N, Kp, \
+                                                 p.p1.KC, p.p1.nbpb)
+                case 1: e = SK1(1); break;
+                case 2: e = SK1(2); break;
+                case 3: e = SK1(3); break;
+                default: e = SK1(4); break;
+#undef SK1
+            }
+            if (e == hipSuccess) e = hipGetLastError();
+            break;
+        default: e = launch_tiles(p, A, lda, Wp, C, ldc, M, N, K, Kp, epi, partial, variant, st); break;
+    }
+    if (e != hipSuccess) return e;
+    if (p.done == GD_SLABS) {
+        *splits_out = p.S;
         return e;
     }
-    if (e == hipSuccess && S > 1) {
-        // the reduction is charged to the class of the GEMM it completes: 6 behind a ViT-sized tiled GEMM, 8 behind an LLM-sized one, 9 behind an fp8 one
-        const int rcls = (f8_on && gemm_fp8_tiled_supported(pick)) ? 9 : (tcls == 4 ? 8 : 6);
-        const bool want_norm = epi.norm_w != nullptr && epi.norm_out != nullptr;
-        if (want_norm && !epi.glu && !epi.out_f32 && (N % 8) == 0 && N <= 8192 && (ldc % 8) == 0 && (epi.ld_norm_out % 8) == 0 && (((uintptr_t)epi.norm_w) & 15) == 0) {
-            launch_streaming(rcls, 0.0, splitk_reduce_norm, dim3(M), dim3(512), 0, st, (const float*)ws, S, (bf16_t*)C, ldc, M, N, epi);
-            norm_done = true;
-        } else {
-            const int Nout = epi.glu ? N / 2 : N;
-            const long long total = (long long)M * ((Nout + 3) / 4);
-            int rb = (int)((total + 255) / 256);
-            if (rb > 2048) rb = 2048;
-            launch_streaming(rcls, 0.0, splitk_reduce, dim3(rb), dim3(256), 0, st, (const float*)ws, S, C, ldc, M, N, epi);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !norm_done && epi.norm_w != nullptr && epi.norm_out != nullptr)
-        e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
-    return e;
+    return complete_splitk(p, epi, ws, C, ldc, M, N, st);
 }
 
 // Weight-streaming GEMM WITHOUT its reduction: leaves fp32 partials [S][M][N] in ws for a consumer that folds them
@@ -1932,24 +1923,18 @@ hipError_t launch_gemm_skinny_partial(const bf16_t* A, int lda, const bf16_t* Wp
                                       int K, int* S_out, hipStream_t st, const void* w8, const float* w8s) {
     if (M <= 0 || M > 64 || N <= 0) return hipErrorInvalidValue;
     const int Kp = (K + 127) / 128 * 128;
-    {
-        static const char* g3 = getenv("COVER_SKINNY3");
-        Skinny3Plan p3 = plan_skinny3(M, N, Kp);
-        const size_t need = (size_t)p3.S * M * N * sizeof(float);
-        if (p3.ok && !(g3 && g3[0] == '0') && ws != nullptr && ws_bytes >= need) {
-            EpiDev none = make_epi(nullptr);
-            if (w8 && w8s) { none.w8 = (const uint8_t*)w8; none.w8s = w8s; }
-            hipError_t e = launch_skinny3(p3, A, lda, Wp, nullptr, 0, M, N, Kp, none, ws, st);
-            *S_out = p3.S;
-            return e;
-        }
+    GemmPlan p = GemmPlan{};
+    hipError_t e = plan_streaming(p, M, N, Kp, ws, ws_bytes, false, true);
+    if (e != hipSuccess) return e;
+    if (p.kind == GK_SKINNY3) {
+        EpiDev none = make_epi(nullptr);
+        if (w8 && w8s) { none.w8 = (const uint8_t*)w8; none.w8s = w8s; }
+        e = launch_skinny3(p.p3, A, lda, Wp, nullptr, 0, M, N, Kp, none, ws, st);
+    } else {
+        e = launch_skinny2(p.p2, A, lda, Wp, ws, M, N, K, Kp, (const uint8_t*)w8, w8s, 0, st);
     }
-    Skinny2Plan p = plan_skinny2(M, N, Kp);
-    if (ws == nullptr || ws_bytes < p.ws_bytes) return hipErrorInvalidValue;
-    dim3 grid(p.gx, p.S), block(512);
-    launch_skinny2(p, A, lda, Wp, ws, M, N, K, Kp, (const uint8_t*)w8, w8s, 0, st);
     *S_out = p.S;
-    return hipGetLastError();
+    return e;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -586,12 +586,76 @@ __device__ __forceinline__ void glds4_s(uint32_t voff, const void* sbase, uint32
         : "memory");
 }
 
-// gemm_fp8.hip: the LDS-tiled GEMM on the MX-scaled fp8 matrix instruction, for the tile configurations listed there
-bool gemm_fp8_tiled_supported(int pick);
-hipError_t launch_gemm_fp8_tiled(int pick, const uint8_t* A8, int lda8, const float* a_scale, const uint8_t* W8, const float* w_scale, void* C, int ldc,
-                                 int M, int N, int Kp, const EpiDev& epi, int tiles_m, int tiles_n, int kt_per, int S, float* partial, size_t lds,
-                                 int prof_cls, double prof_work, hipStream_t st);
+// ---- host side: the GEMM plan (gemm_bf16.hip: plan_gemm) and the launches that carry it out
 
-// gemm_v3.hip: the self-loading 8-wave tiled bf16 GEMM (picks 23..26 of launch_gemm_bf16's tile table)
-hipError_t launch_gemm_v3(int pick, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp, const EpiDev& epi, int tiles_m,
-                          int tiles_n, int kt_per, int S, float* partial, int prof_cls, double prof_work, hipStream_t st);
+// tile picks = rows of the tile table in gemm_bf16.hip = the public plan-counter slots (include/cover_hip.h): never renumbered
+enum TilePick {
+    TP_128x128 = 0, TP_64x128 = 1, TP_64x64 = 2, TP_128x128_S4 = 3, TP_256x128 = 4, TP_128x256 = 5, TP_128x128_W8 = 6, TP_64x128_S3 = 7,
+    TP_128x128_S3 = 8,                                                    // gemm_tiled (0..8; 3..8: COVER_TILE_PICK only)
+    TP_PC_64x128_S3 = 9, TP_PC_64x128 = 10, TP_PC_128x128 = 11, TP_PC_256x128 = 12, TP_PC_128x256 = 13, TP_PC_224x96_W4 = 14,
+    TP_PC_224x128 = 15, TP_PC_224x192 = 16, TP_PC_224x96 = 17, TP_PC_128x192 = 18,   // loader-wave tiles (bf16: 10 only; the rest fp8 or gone)
+    PLAN_SKINNY2 = 19, PLAN_SKINNY3 = 20, PLAN_FP8 = 21, PLAN_SKINNY = 22,             // counter slots of the weight-streaming / fp8 kernels
+    TP_V3_224x192 = 23, TP_V3_224x128 = 24, TP_V3_256x128 = 25, TP_V3_128x256 = 26, TP_V3_224x96 = 27,   // self-loading (gemm_v3.hip)
+    TP_V3K_224x96 = 30,                                                                 // k-split wave pairs (gemm_tiled_v3k); 28, 29, 31: gaps
+};
+
+// weight-streaming plans (gemm_bf16.hip: plan_skinny / plan_skinny2 / plan_skinny3)
+struct SkinnyPlan {
+    int MF, KC, S, nbpb, gx;
+    size_t lds, ws_bytes;
+};
+struct Skinny2Plan {
+    int MF, KS, NBW, gx, S;
+    size_t lds, ws_bytes;
+};
+struct Skinny3Plan {
+    bool ok;
+    int MF, NBW, S, kper, gx;
+    size_t lds, ws_bytes;
+};
+
+enum GemmKind { GK_NONE, GK_SKINNY, GK_SKINNY2, GK_SKINNY3, GK_TILED, GK_TILED_PC, GK_F8_PC, GK_F8_V3, GK_V3 };
+enum GemmDone { GD_NONE = 0, GD_REDUCE = 1, GD_REDUCE_NORM = 2, GD_SLABS = 3 };   // how the K slices are completed
+
+// Everything launch_gemm_bf16 decides before it launches: which kernel, on which grid, and what completes it. plan_gemm makes no HIP call.
+struct GemmPlan {
+    GemmKind kind;
+    int slot;            // plan-counter slot (PLAN_FP8 for every fp8 tile)
+    int pick;            // TilePick, -1 for weight streaming
+    int S, kt_per;       // K slices, k-tiles per slice (128-deep k-tiles on the fp8 kernels)
+    int tiles_m, tiles_n, block;
+    size_t lds;
+    SkinnyPlan p1;
+    Skinny2Plan p2;
+    Skinny3Plan p3;
+    GemmDone done;       // GD_SLABS: the caller folds the S slabs itself (launch_gemm_bf16's splits_out)
+    bool norm_launch;    // the epilogue's norm runs as its own launch after the GEMM (or its reduction)
+    int rcls;            // profiling class of the reduction: 5 behind weight streaming, 6 / 8 / 9 behind ViT-sized / LLM-sized / fp8 tiles
+};
+
+// Every GEMM kernel launch: the 160 KiB dynamic-LDS attribute once per kernel and device when the launch needs more than 64 KiB and, with
+// profiling on, the kernel's own start / stop timestamps in a reserved event pair of class cls. Returns the attribute's error, if any
+// (the launch itself is checked by the caller's hipGetLastError).
+template <auto kfn, typename... Args>
+static inline hipError_t launch_kernel(int cls, double work, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if (lds > 64 * 1024) {
+        static LdsAttrCache c;
+        const hipError_t e = lds_attr_160k_cached((const void*)kfn, c);
+        if (e != hipSuccess) return e;
+    }
+    hipEvent_t ea, eb;
+    if (prof_enabled() && prof_reserve(cls, work, &ea, &eb) >= 0)
+        hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds, st, ea, eb, 0, args...);
+    else
+        hipLaunchKernelGGL(kfn, grid, block, lds, st, args...);
+    return hipSuccess;
+}
+
+// gemm_fp8.hip: the LDS-tiled GEMM on the MX-scaled fp8 matrix instruction (GK_F8_PC / GK_F8_V3 plans)
+bool gemm_fp8_tiled_supported(int pick);
+hipError_t launch_gemm_fp8_tiled(const GemmPlan& p, const EpiDev& epi, void* C, int ldc, int M, int N, int Kp, float* partial, double prof_work,
+                                 hipStream_t st);
+
+// gemm_v3.hip: the self-loading tiled bf16 GEMM (GK_V3 plans: picks 23..27, 30)
+hipError_t launch_gemm_v3(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp, const EpiDev& epi,
+                          float* partial, int prof_cls, double prof_work, hipStream_t st);

@@ -651,76 +651,41 @@ hipError_t launch_quantize_act_fp8(const bf16_t* X, int ldx, int M, int K, uint8
     return hipGetLastError();
 }
 
-// pick: the tile configuration index of launch_gemm_bf16's table (10: 64x128, 12: 256x128, 13: 128x256, 15: 224x128, 17: 224x96, 18: 128x192; the 224x192 tile needs 84 accumulator + 80 fragment registers and spills at 3 waves per SIMD)
-bool gemm_fp8_tiled_supported(int pick) { return pick == 10 || pick == 12 || pick == 13 || pick == 15 || pick == 17 || pick == 18; }
+// the tiles with an fp8 instantiation (TilePick): 64x128, 256x128, 128x256, 224x128, 224x96, 128x192; the 224x192 tile needs 84 accumulator + 80 fragment
+// registers and spills at 3 waves per SIMD
+bool gemm_fp8_tiled_supported(int pick) {
+    return pick == TP_PC_64x128 || pick == TP_PC_256x128 || pick == TP_PC_128x256 || pick == TP_PC_224x128 || pick == TP_PC_224x96 || pick == TP_PC_128x192;
+}
 
-hipError_t launch_gemm_fp8_tiled(int pick, const uint8_t* A8, int lda8, const float* a_scale, const uint8_t* W8, const float* w_scale, void* C, int ldc,
-                                 int M, int N, int Kp, const EpiDev& epi, int tiles_m, int tiles_n, int kt_per, int S, float* partial, size_t lds,
-                                 int prof_cls, double prof_work, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    dim3 grid(tiles_m * tiles_n, S);
-#define LAUNCH_F8(WM_, WN_, NST_, NL_, CGM_, CGN_) LAUNCH_F8X(WM_, WN_, NST_, NL_, CGM_, CGN_, false, lds)
-#define LAUNCH_F8X(WM_, WN_, NST_, NL_, CGM_, CGN_, MX_, lds)                                                                \
-    do {                                                                                                                     \
-        auto kfn = gemm_tiled_pc_f8<WM_, WN_, NST_, NL_, CGM_, CGN_, MX_>;                                                   \
-        if (lds > 64 * 1024) {                                                                                               \
-            e = LDS_ATTR_160K(kfn);                                                                                                        \
-        }                                                                                                                    \
-        if (e == hipSuccess) {                                                                                               \
-            dim3 block(64 * (CGM_ * CGN_ + NL_));                                                                            \
-            hipEvent_t ea, eb;                                                                                               \
-            if (prof_enabled() && prof_reserve(prof_cls, prof_work, &ea, &eb) >= 0)                                          \
-                hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds, st, ea, eb, 0, A8, lda8, W8, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial, a_scale, w_scale); \
-            else                                                                                                             \
-                hipLaunchKernelGGL(kfn, grid, block, lds, st, A8, lda8, W8, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial, a_scale, w_scale); \
-        }                                                                                                                    \
-    } while (0)
-#define LAUNCH_F8V3(WM_, WN_, CGM_, CGN_, NA_, NB_) \
-    do { if (epi.a8mx) LAUNCH_F8V3X(WM_, WN_, CGM_, CGN_, NA_, NB_, 1); else if (epi.o8) LAUNCH_F8V3X(WM_, WN_, CGM_, CGN_, NA_, NB_, 2); else LAUNCH_F8V3X(WM_, WN_, CGM_, CGN_, NA_, NB_, 0); } while (0)
-#define LAUNCH_F8V3X(WM_, WN_, CGM_, CGN_, NA_, NB_, MX_)                                                                    \
-    do {                                                                                                                     \
-        auto kfn = gemm_tiled_v3_f8<WM_, WN_, CGM_, CGN_, NA_, NB_, MX_>;                                                    \
-        const size_t lds3 = ((size_t)NA_ * CGM_ * WM_ * 16 + (size_t)NB_ * CGN_ * WN_ * 16) * 128 + (MX_ == 1 ? (size_t)NA_ * 1024 : 0); \
-        e = LDS_ATTR_160K(kfn);                                                                                                            \
-        if (e == hipSuccess) {                                                                                               \
-            dim3 block(64 * CGM_ * CGN_);                                                                                    \
-            hipEvent_t ea, eb;                                                                                               \
-            if (prof_enabled() && prof_reserve(prof_cls, prof_work, &ea, &eb) >= 0)                                          \
-                hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds3, st, ea, eb, 0, A8, lda8, W8, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial, a_scale, w_scale); \
-            else                                                                                                             \
-                hipLaunchKernelGGL(kfn, grid, block, lds3, st, A8, lda8, W8, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial, a_scale, w_scale); \
-        }                                                                                                                    \
-    } while (0)
-    // the self-loading form (gemm_tiled_v3_f8) for the tiles whose eight MFMA waves split into two DMA roles; COVER_V3_F8=0 keeps the loader-wave form
-    static const char* v3f8_env = getenv("COVER_V3_F8");
-    const bool v3f8 = !(v3f8_env && v3f8_env[0] == '0') && (size_t)M * lda8 + 4096 < ((size_t)1 << 31);
-    // MX block scales (operand or output) exist on the self-loading kernels only: launch_gemm_bf16 keeps such a GEMM on their tiles
-    if ((epi.a8mx || epi.o8) && !(v3f8 && (pick == 12 || pick == 13 || pick == 15 || pick == 18)) && !(pick == 10 && epi.a8mx && !epi.o8)) return hipErrorInvalidValue;
-    if (epi.a8mx && !epi.w8_kl) return hipErrorInvalidValue;
-    if (v3f8 && (pick == 12 || pick == 13 || pick == 15 || pick == 18)) {
-        switch (pick) {
-            case 12: LAUNCH_F8V3(4, 4, 4, 2, 3, 3); break;
-            case 13: LAUNCH_F8V3(4, 4, 2, 4, 3, 3); break;
-            case 15: LAUNCH_F8V3(7, 2, 2, 4, 3, 3); break;
-            default: LAUNCH_F8V3(4, 3, 2, 4, 3, 3); break;
+// GK_F8_V3: the self-loading form (gemm_tiled_v3_f8, MX forms 0 / 1 = a8_mx / 2 = out8); GK_F8_PC: the loader-wave form (gemm_tiled_pc_f8). plan_gemm chose
+// the form and validated the operands.
+hipError_t launch_gemm_fp8_tiled(const GemmPlan& p, const EpiDev& epi, void* C, int ldc, int M, int N, int Kp, float* partial, double prof_work,
+                                 hipStream_t st) {
+    const dim3 grid(p.tiles_m * p.tiles_n, p.S), block(p.block);
+#define F8(KFN) launch_kernel<KFN>(7, prof_work, grid, block, p.lds, st, epi.a8, epi.lda8, epi.w8, C, ldc, M, N, Kp, epi, p.tiles_m, p.tiles_n, p.kt_per, \
+                                   partial, epi.a8s, epi.w8s)
+#define F8V3(WM_, WN_, CGM_, CGN_) (epi.a8mx ? F8((gemm_tiled_v3_f8<WM_, WN_, CGM_, CGN_, 3, 3, 1>)) : epi.o8 ? F8((gemm_tiled_v3_f8<WM_, WN_, CGM_, CGN_, 3, 3, 2>)) \
+                                                                     : F8((gemm_tiled_v3_f8<WM_, WN_, CGM_, CGN_, 3, 3, 0>)))
+    hipError_t e = hipErrorInvalidValue;
+    if (p.kind == GK_F8_V3) {
+        switch (p.pick) {
+            case TP_PC_256x128: e = F8V3(4, 4, 4, 2); break;
+            case TP_PC_128x256: e = F8V3(4, 4, 2, 4); break;
+            case TP_PC_224x128: e = F8V3(7, 2, 2, 4); break;
+            case TP_PC_128x192: e = F8V3(4, 3, 2, 4); break;
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        return e;
+    } else {
+        switch (p.pick) {
+            case TP_PC_64x128: e = epi.a8mx ? F8((gemm_tiled_pc_f8<2, 4, 4, 4, 2, 2, true>)) : F8((gemm_tiled_pc_f8<2, 4, 4, 4, 2, 2, false>)); break;
+            case TP_PC_256x128: e = F8((gemm_tiled_pc_f8<4, 4, 3, 4, 4, 2, false>)); break;
+            case TP_PC_128x256: e = F8((gemm_tiled_pc_f8<4, 4, 3, 4, 2, 4, false>)); break;
+            case TP_PC_224x128: e = F8((gemm_tiled_pc_f8<7, 2, 3, 4, 2, 4, false>)); break;
+            case TP_PC_224x96: e = F8((gemm_tiled_pc_f8<7, 2, 4, 4, 2, 3, false>)); break;
+            case TP_PC_128x192: e = F8((gemm_tiled_pc_f8<4, 3, 3, 4, 2, 4, false>)); break;
+        }
     }
-    switch (pick) {
-        case 10:
-            if (epi.a8mx) { const size_t ldsx = lds + 4 * 256; LAUNCH_F8X(2, 4, 4, 4, 2, 2, true, ldsx); }   // (+ the block-scale ring)
-            else LAUNCH_F8(2, 4, 4, 4, 2, 2);
-            break;
-        case 12: LAUNCH_F8(4, 4, 3, 4, 4, 2); break;
-        case 13: LAUNCH_F8(4, 4, 3, 4, 2, 4); break;
-        case 15: LAUNCH_F8(7, 2, 3, 4, 2, 4); break;
-        case 17: LAUNCH_F8(7, 2, 4, 4, 2, 3); break;
-        case 18: LAUNCH_F8(4, 3, 3, 4, 2, 4); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef LAUNCH_F8
-#undef LAUNCH_F8X
+#undef F8V3
+#undef F8
     if (e == hipSuccess) e = hipGetLastError();
     return e;
 }

@@ -461,53 +461,23 @@ __global__ __launch_bounds__(128 * CGM * CGN) void gemm_tiled_v3k(const bf16_t* 
 }
 
 // pick -> instantiation (the tile table of launch_gemm_bf16 continues with these indices)
-hipError_t launch_gemm_v3(int pick, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp, const EpiDev& epi, int tiles_m,
-                          int tiles_n, int kt_per, int S, float* partial, int prof_cls, double prof_work, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    if ((size_t)M * lda * 2 + 4096 >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // 32-bit lane offsets of the activation pieces
-    dim3 grid(tiles_m * tiles_n, S);
-#define LAUNCH_V3(WM_, WN_, CGM_, CGN_, NA_, NB_)                                                                            \
-    do {                                                                                                                     \
-        auto kfn = gemm_tiled_v3<WM_, WN_, CGM_, CGN_, NA_, NB_>;                                                            \
-        const size_t lds = ((size_t)NA_ * CGM_ * WM_ * 16 + (size_t)NB_ * CGN_ * WN_ * 16) * BK * 2;                         \
-        dim3 block(64 * CGM_ * CGN_);                                                                                        \
-        e = LDS_ATTR_160K(kfn);                                                                                                            \
-        if (e == hipSuccess) {                                                                                               \
-            hipEvent_t ea, eb;                                                                                               \
-            if (prof_enabled() && prof_reserve(prof_cls, prof_work, &ea, &eb) >= 0)                                          \
-                hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds, st, ea, eb, 0, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-            else                                                                                                             \
-                hipLaunchKernelGGL(kfn, grid, block, lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-        }                                                                                                                    \
-    } while (0)
-#define LAUNCH_V3K(WM_, WN_, CGM_, CGN_, NST_)                                                                               \
-    do {                                                                                                                     \
-        auto kfn = gemm_tiled_v3k<WM_, WN_, CGM_, CGN_, NST_>;                                                               \
-        const size_t lds = ((size_t)NST_ * (CGM_ * WM_ * 16 + CGN_ * WN_ * 16)) * BK * 2;                                   \
-        dim3 block(128 * CGM_ * CGN_);                                                                                       \
-        e = LDS_ATTR_160K(kfn);                                                                                              \
-        if (e == hipSuccess) {                                                                                               \
-            hipEvent_t ea, eb;                                                                                               \
-            if (prof_enabled() && prof_reserve(prof_cls, prof_work, &ea, &eb) >= 0)                                          \
-                hipExtLaunchKernelGGL(kfn, grid, block, (uint32_t)lds, st, ea, eb, 0, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-            else                                                                                                             \
-                hipLaunchKernelGGL(kfn, grid, block, lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, tiles_m, tiles_n, kt_per, partial); \
-        }                                                                                                                    \
-    } while (0)
-    switch (pick) {
-        case 23: LAUNCH_V3(7, 3, 2, 4, 3, 3); break;          // 224x192, 8 waves of 112x48
-        case 24: LAUNCH_V3(7, 2, 2, 4, 3, 3); break;          // 224x128, 8 waves of 112x32
-        case 25: LAUNCH_V3(8, 2, 2, 4, 3, 3); break;          // 256x128, 8 waves of 128x32
-        case 26: LAUNCH_V3(4, 4, 2, 4, 3, 3); break;          // 128x256, 8 waves of 64x64
-        case 27: LAUNCH_V3(7, 3, 2, 2, 4, 4); break;          // 224x96,  4 waves of 112x48 (one per SIMD): the A/B partner of pick 30
+hipError_t launch_gemm_v3(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp, const EpiDev& epi,
+                          float* partial, int prof_cls, double prof_work, hipStream_t st) {
+    const dim3 grid(p.tiles_m * p.tiles_n, p.S), block(p.block);
+#define V3(KFN) launch_kernel<KFN>(prof_cls, prof_work, grid, block, p.lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, p.tiles_m, p.tiles_n, p.kt_per, partial)
+    hipError_t e = hipErrorInvalidValue;
+    switch (p.pick) {
+        case TP_V3_224x192: e = V3((gemm_tiled_v3<7, 3, 2, 4, 3, 3>)); break;   // 8 waves of 112x48
+        case TP_V3_224x128: e = V3((gemm_tiled_v3<7, 2, 2, 4, 3, 3>)); break;   // 8 waves of 112x32
+        case TP_V3_256x128: e = V3((gemm_tiled_v3<8, 2, 2, 4, 3, 3>)); break;   // 8 waves of 128x32
+        case TP_V3_128x256: e = V3((gemm_tiled_v3<4, 4, 2, 4, 3, 3>)); break;   // 8 waves of 64x64
+        case TP_V3_224x96: e = V3((gemm_tiled_v3<7, 3, 2, 2, 4, 4>)); break;    // 4 waves of 112x48 (one per SIMD): the A/B partner of TP_V3K_224x96
         // (round 5 also instantiated other ring depths -- (2,3), (3,4) -- and 4-wave 112x128 / 224x128 tiles: measured flat / slower, removed in round 6)
-        case 30: LAUNCH_V3K(7, 3, 2, 2, 4); break;                                                              // 224x96,  4 wave PAIRS of 112x48 splitting k (two waves per SIMD)
+        case TP_V3K_224x96: e = V3((gemm_tiled_v3k<7, 3, 2, 2, 4>)); break;     // 4 wave PAIRS of 112x48 splitting k (two waves per SIMD)
         // (224x64 on 4 wave pairs of 112x32 with TWO K slices for o_proj / down at M = 448: 34.4 / 67.3 us against 33.0 / 55.4 on 224x128 x 4 slices --
         //  905-1 107 cycles per k-tile for half the FLOPs of a 1 155-1 400-cycle tile; not kept: profiles/r06_v3_schedule_ab.txt)
-        default: return hipErrorInvalidValue;
     }
-#undef LAUNCH_V3
-#undef LAUNCH_V3K
+#undef V3
     if (e == hipSuccess) e = hipGetLastError();
     return e;
 }

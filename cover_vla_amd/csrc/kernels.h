@@ -17,6 +17,8 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
 hipError_t launch_gemm_skinny_partial(const bf16_t* A, int lda, const bf16_t* Wp, float* ws, size_t ws_bytes, int M, int N,
                                       int K, int* S_out, hipStream_t st, const void* w8 = nullptr, const float* w8s = nullptr);
 #define COVER_GEMM_PLANS 32
+hipError_t gemm_plan_query(const bf16_t* A, int lda, const bf16_t* Wp, const void* C, int ldc, int M, int N, int K, const cover_gemm_epi* epi,
+                           const float* ws, size_t ws_bytes, int variant, int* plan);   // cover_gemm_plan: launch_gemm_bf16's plan, nothing launched
 void gemm_plan_counts(long long* out, int n, int reset);   // per-plan launch counters (tests): see gemm_bf16.hip
 int gemm_v3_probe(unsigned long long* out);                  // 16 words: in-kernel probe of the last gemm_v3.hip launch (g_v3_probe)
 hipError_t launch_quantize_rows_fp8(const bf16_t* W, int ldw, int N, int K, float* scales, bf16_t* Wdq, hipStream_t st);

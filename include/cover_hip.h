@@ -156,6 +156,12 @@ int cover_gemm_bf16(const void* A, int lda, const void* Wp, void* C, int ldc, in
  *   slower, not instantiated).
  * Copies min(n, 32) counters, returns 32. */
 int cover_gemm_plan_counts(long long* counts, int n, int reset);
+/* The plan cover_gemm_bf16 would take for these arguments, without launching anything (test / audit hook). Same arguments as cover_gemm_bf16
+ * with the stream replaced by plan[6]; pointers are only checked for null and alignment, never dereferenced. Returns COVER_OK or COVER_EINVAL
+ * exactly when cover_gemm_bf16 would. plan = {plan-counter slot (the map above; -1: nothing to launch), tile pick (-1: weight streaming),
+ * fp8 self-loading form (0/1), K slices, completion (0 none / 1 splitk_reduce / 2 splitk_reduce_norm), separate norm launch (0/1)}. */
+int cover_gemm_plan(const void* A, int lda, const void* Wp, void* C, int ldc, int M, int N, int K,
+                    const cover_gemm_epi* epi, void* splitk_ws, size_t splitk_ws_bytes, int variant, int plan[6]);
 /* In-kernel probe of the most recent launch of the self-loading tiled GEMM (gemm_v3.hip; plan counters 23..30), written by one thread of
  * its first workgroup: out[0..3] = 100 MHz wall-clock stamps at kernel start / k-loop start / k-loop end / kernel end, out[4..5] = shader
  * cycle counter at k-loop start / end, out[6] = k-tiles of the loop. (out[5] - out[4]) / (out[2] - out[1]) / 10 ns = the clock the loop ran
