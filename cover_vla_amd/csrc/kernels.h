@@ -70,6 +70,8 @@ hipError_t launch_masked_mean_f32(const float* x, const uint8_t* pad, float* y, 
 hipError_t launch_sincos_time_embed(const float* time, int B, int dim, double min_period, double max_period, bf16_t* out,
                                     int ldo, hipStream_t st);
 
+// ---- sample.hip ----------------------------------------------------------------------------------
+hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st);
 // ---- select.hip ----------------------------------------------------------------------------------
 hipError_t launch_token_select(const cover_token_select_args* a, hipStream_t st);
 hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st);

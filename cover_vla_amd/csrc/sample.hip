@@ -1,0 +1,455 @@
+// Filtered inverse-CDF token sampling over a wide logits row (temperature -> top-k -> top-p -> pick, the order of Hugging Face's
+// logits warpers). One 1024-thread block per row, no workspace, nothing data-dependent in the launch: recordable into a hipGraph.
+//
+// Determinism and the summation order (the house rule of select.hip: a sum that decides an index has a fixed result).
+//   Every mass in this file is an EXACT INTEGER sum. A token's weight w = expf((l - max) / T) (fp32, 0 <= w <= 1) is converted once to
+//   Q43 fixed point, q = rint(w * 2^43) (exact for w >= 2^-19, rounded to the nearest 2^-43 below that), and all masses -- total,
+//   per-bin, per-tile, running -- are uint64 sums of q. hi - lo <= 2^20 terms of at most 2^43 cannot overflow 2^63. Integer
+//   addition is associative, so the order in which lanes and waves add (LDS integer atomics) cannot change a result; there is no
+//   floating-point sum anywhere. Error against exact arithmetic on the same fp32 weights: at most 2^-44 per term, 2^-24 of the
+//   mass for 2^20 terms (the kept mass is >= 2^43: the row maximum has w = 1 and every filter keeps it). Thresholds are
+//   compared as integers: top-p keeps the shortest prefix with mass >= ceil(top_p * M) (double product of the fp32 top_p and the
+//   uint64 M); the pick is the first kept index whose running mass is >= floor(u * M_kept) + 1.
+//   Counts are integers as well. Selections (k-th largest logit, the top-p cut, the index of the pick) are radix selections:
+//   a histogram (count and mass per bin, LDS integer atomics) over one digit of an order-preserving 32-bit key, then one wave walks
+//   the bins in key order -- lane j owns a contiguous run of bins, runs are combined with an inclusive shuffle scan, the lane that
+//   holds the crossing walks its run -- and the next digit repeats this inside the chosen bin. Keys: the logit's bits mapped to
+//   an unsigned order (top-k: a comparison of input floats, no arithmetic), the weight's bits (top-p; equal weights by ascending
+//   index), the column index (pick; its first digit -- the mass of each tile of 1024 columns -- is reduced per wave with shuffles on the row).
+//   Candidates: when the first digit shows that at most 4096 elements lie at or above the bin holding the threshold, those elements
+//   are compacted into LDS (in whatever order the atomics grant; every consumer is one of the order-independent integer
+//   reductions above) and the remaining digits run over that list instead of the row: a language model's row needs two or three
+//   passes over its 1 MB, a flat row (cut in the tail, huge k) falls back to one pass per digit.
+#include "common.h"
+#include "kernels.h"
+
+typedef unsigned long long u64;
+#define SMP_BINS 2048
+#define SMP_CAP 4096
+#define SMP_T 1024
+
+struct SampleShared {
+    unsigned cnt[SMP_BINS];
+    u64 mass[SMP_BINS];
+    float list_l[SMP_CAP];
+    int list_i[SMP_CAP];
+    float red[16];
+    unsigned n_list;
+    // result of scan_bins
+    int r_bin;
+    unsigned r_cnt_before, r_cnt_bin, r_cnt_total;
+    u64 r_mass_before, r_mass_bin, r_mass_total, r_need;
+};
+
+// order-preserving image of a float: a > b  <=>  lkey(a) > lkey(b) (-0 == +0)
+__device__ __forceinline__ unsigned lkey(float l) {
+    unsigned u = __float_as_uint(l);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float weight_of(float l, float m, float t) {
+    const float w = expf((l - m) / t);
+    return (w == w) ? w : 0.f;
+}
+// order-preserving key of a weight (>= 0): its bits without the sign bit, so the first digit spans 8 exponent + 3 mantissa bits
+__device__ __forceinline__ unsigned wkey(float w) { return __float_as_uint(w) << 1; }
+__device__ __forceinline__ u64 q43(float w) { return (u64)__float2ull_rn(w * 8796093022208.0f); }
+
+__device__ __forceinline__ u64 shfl_up64(u64 v, int o) {
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    lo = __shfl_up(lo, o);
+    hi = __shfl_up(hi, o);
+    return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 shfl64(u64 v, int l) {
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    lo = __shfl(lo, l);
+    hi = __shfl(hi, l);
+    return ((u64)hi << 32) | lo;
+}
+
+// The elements a stage iterates: columns [0, n) of the row (rel = column - lo), or the compacted candidates in LDS.
+struct SampleSrc {
+    const float* p;   // row + lo
+    int n;
+    bool list;
+};
+
+// f(logit, rel) for every element. Row: scalar head up to the first 16-byte boundary, float4 body (four loads in flight per lane),
+// scalar tail -- any lo / ld works, aligned rows take the vector path.
+template <class F>
+__device__ __forceinline__ void for_each(const SampleShared& s, const SampleSrc& src, F f) {
+    const int tid = threadIdx.x;
+    if (src.list) {
+        const int nl = (int)s.n_list;
+        for (int c = tid; c < nl; c += SMP_T) f(s.list_l[c], s.list_i[c]);
+        return;
+    }
+    const float* p = src.p;
+    const int n = src.n;
+    int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    head = head < n ? head : n;
+    for (int c = tid; c < head; c += SMP_T) f(p[c], c);
+    const int n4 = (n - head) >> 2;
+    const float4* v = (const float4*)(p + head);
+    auto take = [&](const float4& x, int c) {
+        const int i0 = head + 4 * c;
+        f(x.x, i0); f(x.y, i0 + 1); f(x.z, i0 + 2); f(x.w, i0 + 3);
+    };
+    int c = tid;
+    for (; c + 3 * SMP_T < n4; c += 4 * SMP_T) {
+        const float4 x0 = v[c], x1 = v[c + SMP_T], x2 = v[c + 2 * SMP_T], x3 = v[c + 3 * SMP_T];
+        take(x0, c); take(x1, c + SMP_T); take(x2, c + 2 * SMP_T); take(x3, c + 3 * SMP_T);
+    }
+    for (; c < n4; c += SMP_T) take(v[c], c);
+    for (int t = head + 4 * n4 + tid; t < n; t += SMP_T) f(p[t], t);
+}
+// the same for rel in [r0, r1) only
+template <class F>
+__device__ __forceinline__ void for_each_in(const SampleShared& s, const SampleSrc& src, int r0, int r1, F f) {
+    const int tid = threadIdx.x;
+    if (src.list) {
+        const int nl = (int)s.n_list;
+        for (int c = tid; c < nl; c += SMP_T) {
+            const int rel = s.list_i[c];
+            if (rel >= r0 && rel < r1) f(s.list_l[c], rel);
+        }
+        return;
+    }
+    r1 = r1 < src.n ? r1 : src.n;
+    for (int c = r0 + tid; c < r1; c += SMP_T) f(src.p[c], c);
+}
+
+__device__ __forceinline__ void hist_zero(SampleShared& s) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < SMP_BINS; b += SMP_T) {
+        s.cnt[b] = 0u;
+        s.mass[b] = 0ull;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void hist_add(SampleShared& s, int bin, u64 q) {
+    atomicAdd(&s.cnt[bin], 1u);
+    if (q) atomicAdd(&s.mass[bin], q);
+}
+
+// Walk the histogram in key order (DESC: from the top bin down) and find the first bin at which the running count (or mass)
+// reaches `need`. mode 0: need as given; 1: need = ceil(frac * total mass); 2: need = floor(frac * total mass) + 1. need is
+// clamped to [1, total]. Results in s.r_* (the running sums BEFORE the bin, the bin's own, the totals, the need used).
+// Wave 0 works, everyone waits. nbins is a multiple of 64.
+template <bool DESC, bool BY_MASS>
+__device__ __forceinline__ void scan_bins(SampleShared& s, int nbins, u64 need, int mode = 0, double frac = 0.0) {
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x, per = nbins >> 6;
+        auto bin_at = [&](int pos) { return DESC ? nbins - 1 - pos : pos; };
+        unsigned c = 0;
+        u64 m = 0;
+        for (int j = 0; j < per; ++j) {
+            const int b = bin_at(lane * per + j);
+            c += s.cnt[b];
+            m += s.mass[b];
+        }
+        unsigned ci = c;
+        u64 mi = m;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned oc = __shfl_up(ci, o);
+            const u64 om = shfl_up64(mi, o);
+            if (lane >= o) {
+                ci += oc;
+                mi += om;
+            }
+        }
+        const unsigned ctot = __shfl(ci, 63);
+        const u64 mtot = shfl64(mi, 63);
+        if (mode == 1) need = (u64)ceil(frac * (double)mtot);
+        if (mode == 2) need = (u64)floor(frac * (double)mtot) + 1ull;
+        const u64 tot = BY_MASS ? mtot : (u64)ctot;
+        if (need > tot) need = tot;
+        if (need < 1ull) need = 1ull;
+        if (lane == 0) {   // what a caller reads if nothing crosses (empty histogram): the first bin of the walk, nothing before it
+            s.r_bin = bin_at(0);
+            s.r_cnt_before = 0u; s.r_cnt_bin = 0u; s.r_cnt_total = ctot;
+            s.r_mass_before = 0ull; s.r_mass_bin = 0ull; s.r_mass_total = mtot;
+            s.r_need = need;
+        }
+        const u64 inc = BY_MASS ? mi : (u64)ci;
+        const u64 exc = inc - (BY_MASS ? m : (u64)c);
+        if (exc < need && need <= inc) {   // exactly one lane
+            unsigned cc = ci - c;
+            u64 mm = mi - m;
+            for (int j = 0; j < per; ++j) {
+                const int b = bin_at(lane * per + j);
+                const unsigned nc = s.cnt[b];
+                const u64 nm = s.mass[b];
+                const u64 run = BY_MASS ? mm : (u64)cc, v = BY_MASS ? nm : (u64)nc;
+                if (run + v >= need) {
+                    s.r_bin = b;
+                    s.r_cnt_before = cc; s.r_cnt_bin = nc;
+                    s.r_mass_before = mm; s.r_mass_bin = nm;
+                    break;
+                }
+                cc += nc;
+                mm += nm;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// digits of a 32-bit key, most significant first: 11 + 11 + 10 bits
+__device__ __forceinline__ int key_shift(int lev) { return lev == 0 ? 21 : (lev == 1 ? 10 : 0); }
+__device__ __forceinline__ int key_bins(int lev) { return lev == 2 ? 1024 : 2048; }
+__device__ __forceinline__ bool key_in_prefix(unsigned key, unsigned prefix, int lev) {
+    return lev == 0 || (key >> key_shift(lev - 1)) == (prefix >> key_shift(lev - 1));
+}
+__device__ __forceinline__ int key_digit(unsigned key, int lev) { return (int)((key >> key_shift(lev)) & (unsigned)(key_bins(lev) - 1)); }
+
+__global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args a) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = a.logits + (size_t)row * a.ld;
+    const int n = a.hi - a.lo;
+    const bool use_k = a.top_k > 0 && a.top_k < n;
+    const bool use_p = a.top_p < 1.0f;
+    const float T = a.temperature;
+    SampleSrc src{lg + a.lo, n, false};
+    if (tid == 0) s.n_list = 0u;
+
+    // ---- pass 1: the row maximum; with top-k also the first digit of the logit keys (the probe that sizes the candidate list)
+    float m = -INFINITY;
+    if (use_k) {
+        hist_zero(s);
+        for_each(s, src, [&](float l, int rel) {
+            m = fmaxf(m, l);
+            hist_add(s, key_digit(lkey(l), 0), 0ull);
+        });
+    } else {
+        for_each(s, src, [&](float l, int rel) { m = fmaxf(m, l); });
+    }
+    m = block_max(m, s.red);
+
+    // ---- top-k: tk = key of the k-th largest logit; everything with lkey >= tk stays (ties with the k-th value included)
+    unsigned tk = 0u;
+    if (use_k) {
+        scan_bins<true, false>(s, key_bins(0), (u64)a.top_k);
+        const int b0 = s.r_bin;
+        if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {   // block-uniform
+            for_each(s, src, [&](float l, int rel) {
+                if (key_digit(lkey(l), 0) >= b0) {
+                    const unsigned slot = atomicAdd(&s.n_list, 1u);
+                    if (slot < SMP_CAP) {
+                        s.list_l[slot] = l;
+                        s.list_i[slot] = rel;
+                    }
+                }
+            });
+            __syncthreads();
+            src.list = true;
+        }
+        unsigned prefix = 0u;
+        u64 need = (u64)a.top_k;
+        for (int lev = 0; lev < 3; ++lev) {
+            hist_zero(s);
+            for_each(s, src, [&](float l, int rel) {
+                const unsigned key = lkey(l);
+                if (key_in_prefix(key, prefix, lev)) hist_add(s, key_digit(key, lev), 0ull);
+            });
+            scan_bins<true, false>(s, key_bins(lev), need);
+            prefix |= (unsigned)s.r_bin << key_shift(lev);
+            need -= (u64)s.r_cnt_before;
+        }
+        tk = prefix;
+    }
+
+    // ---- top-p: cut = (w*, idx*): kept <=> w > w*  or  (w == w* and rel <= idx*), among the tokens top-k kept
+    unsigned wstar = 0u;
+    int idx_cut = 0x7fffffff;
+    if (use_p) {
+        u64 target = 0ull;   // ceil(top_p * mass kept by top-k); 0 = not known yet
+        if (!src.list) {
+            // probe on the row: first digit of the weights, the mass of everything, and whether the cut's bin and the bins above fit the list
+            hist_zero(s);
+            for_each(s, src, [&](float l, int rel) {
+                if (lkey(l) < tk) return;
+                const float w = weight_of(l, m, T);
+                hist_add(s, key_digit(wkey(w), 0), q43(w));
+            });
+            scan_bins<true, true>(s, key_bins(0), 0ull, 1, (double)a.top_p);
+            target = s.r_need;
+            const int b0 = s.r_bin;
+            if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {
+                for_each(s, src, [&](float l, int rel) {
+                    if (lkey(l) < tk) return;
+                    const float w = weight_of(l, m, T);
+                    if (key_digit(wkey(w), 0) >= b0) {
+                        const unsigned slot = atomicAdd(&s.n_list, 1u);
+                        if (slot < SMP_CAP) {
+                            s.list_l[slot] = l;
+                            s.list_i[slot] = rel;
+                        }
+                    }
+                });
+                __syncthreads();
+                src.list = true;
+            }
+        }
+        unsigned prefix = 0u;
+        u64 need = target, q_tie = 0ull;
+        unsigned n_tie = 0u;
+        for (int lev = 0; lev < 3; ++lev) {
+            hist_zero(s);
+            for_each(s, src, [&](float l, int rel) {
+                if (lkey(l) < tk) return;
+                const float w = weight_of(l, m, T);
+                const unsigned key = wkey(w);
+                if (key_in_prefix(key, prefix, lev)) hist_add(s, key_digit(key, lev), q43(w));
+            });
+            if (lev == 0 && target == 0ull) scan_bins<true, true>(s, key_bins(lev), 0ull, 1, (double)a.top_p);
+            else scan_bins<true, true>(s, key_bins(lev), need);
+            if (lev == 0 && target == 0ull) need = s.r_need;
+            prefix |= (unsigned)s.r_bin << key_shift(lev);
+            need -= s.r_mass_before;
+            n_tie = s.r_cnt_bin;
+            q_tie = n_tie ? s.r_mass_bin / (u64)n_tie : 0ull;
+        }
+        wstar = prefix;
+        // n_tie tokens share the weight at the cut; the first r of them in index order complete the prefix
+        u64 r = q_tie ? (need + q_tie - 1ull) / q_tie : 1ull;
+        r = r < 1ull ? 1ull : (r > (u64)n_tie ? (u64)n_tie : r);
+        if (r < (u64)n_tie) {   // block-uniform; idx* = the r-th smallest index among the tied tokens (two 10-bit digits of rel)
+            int ip = 0;
+            for (int lev = 0; lev < 2; ++lev) {
+                const int sh = lev == 0 ? 10 : 0;
+                hist_zero(s);
+                for_each(s, src, [&](float l, int rel) {
+                    if (lkey(l) < tk) return;
+                    if (wkey(weight_of(l, m, T)) != wstar) return;
+                    if (lev == 1 && (rel >> 10) != (ip >> 10)) return;
+                    hist_add(s, (rel >> sh) & 1023, 0ull);
+                });
+                scan_bins<false, false>(s, 1024, r);
+                ip |= s.r_bin << sh;
+                r -= (u64)s.r_cnt_before;
+            }
+            idx_cut = ip;
+        }
+    }
+
+    // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
+    auto kept_q = [&](float l, int rel, u64& q) -> bool {
+        if (lkey(l) < tk) return false;
+        const float w = weight_of(l, m, T);
+        const unsigned wb = wkey(w);
+        if (wb < wstar || (wb == wstar && rel > idx_cut)) return false;
+        q = q43(w);
+        return true;
+    };
+    // Tiles are cut where the row's float4 body starts (tile 0 = the scalar head, if any), so the 256 columns one wave loads together
+    // lie in one tile: on the row, a wave adds its kept masses and count with shuffles (exact: integers) and one lane adds them to
+    // the tile -- per-element atomics on one address would serialise 64 lanes.
+    int head = 0;
+    if (!src.list) {
+        head = (int)(((16u - (unsigned)((uintptr_t)src.p & 15u)) & 15u) >> 2);
+        head = head < n ? head : n;
+    }
+    const int shift = (1024 - head) & 1023;                 // tile of rel = (rel + shift) >> 10, at most 1025 tiles
+    hist_zero(s);
+    if (src.list) {
+        for_each(s, src, [&](float l, int rel) {
+            u64 q;
+            if (kept_q(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
+        });
+    } else {
+        const float* p = src.p;
+        const int lane = tid & 63;
+        auto one = [&](float l, int rel) {
+            u64 q;
+            if (kept_q(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
+        };
+        for (int c = tid; c < head; c += SMP_T) one(p[c], c);
+        const int n4 = (n - head) >> 2;
+        const float4* v = (const float4*)(p + head);
+        // packed per-lane sum: mass of <= 4 weights (< 2^46) in the low 52 bits, their count above; 64 lanes: mass < 2^52, count <= 256
+        auto packed = [&](const float4& x, int c) -> u64 {
+            const int i0 = head + 4 * c;
+            u64 acc = 0ull, q;
+            if (kept_q(x.x, i0, q)) acc += q + (1ull << 52);
+            if (kept_q(x.y, i0 + 1, q)) acc += q + (1ull << 52);
+            if (kept_q(x.z, i0 + 2, q)) acc += q + (1ull << 52);
+            if (kept_q(x.w, i0 + 3, q)) acc += q + (1ull << 52);
+            return acc;
+        };
+        auto flush = [&](u64 acc, int cb) {   // cb: the wave's first float4 of this load
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                unsigned lo32 = (unsigned)acc, hi32 = (unsigned)(acc >> 32);
+                lo32 = __shfl_xor(lo32, o);
+                hi32 = __shfl_xor(hi32, o);
+                acc += ((u64)hi32 << 32) | lo32;
+            }
+            if (lane == 0 && acc) {
+                const int bin = (head + 4 * cb + shift) >> 10;
+                atomicAdd(&s.cnt[bin], (unsigned)(acc >> 52));
+                const u64 q = acc & ((1ull << 52) - 1ull);
+                if (q) atomicAdd(&s.mass[bin], q);
+            }
+        };
+        const float4 none = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        for (int cb = tid - lane; cb < n4; cb += 4 * SMP_T) {   // cb is wave-uniform: every lane takes part in the shuffles
+            const int c = cb + lane;
+            const bool h0 = c < n4, h1 = c + SMP_T < n4, h2 = c + 2 * SMP_T < n4, h3 = c + 3 * SMP_T < n4;
+            const float4 x0 = h0 ? v[c] : none, x1 = h1 ? v[c + SMP_T] : none, x2 = h2 ? v[c + 2 * SMP_T] : none,
+                         x3 = h3 ? v[c + 3 * SMP_T] : none;
+            flush(h0 ? packed(x0, c) : 0ull, cb);
+            flush(h1 ? packed(x1, c + SMP_T) : 0ull, cb + SMP_T);
+            flush(h2 ? packed(x2, c + 2 * SMP_T) : 0ull, cb + 2 * SMP_T);
+            flush(h3 ? packed(x3, c + 3 * SMP_T) : 0ull, cb + 3 * SMP_T);
+        }
+        for (int c = head + 4 * n4 + tid; c < n; c += SMP_T) one(p[c], c);
+    }
+    scan_bins<false, true>(s, SMP_BINS, 0ull, 2, (double)a.uniform[row]);
+    const int tile = s.r_bin;
+    const unsigned kept = s.r_cnt_total;
+    const u64 need2 = s.r_need - s.r_mass_before;
+    const int t0 = (tile << 10) - shift;
+    hist_zero(s);
+    for_each_in(s, src, t0 < 0 ? 0 : t0, t0 + 1024, [&](float l, int rel) {
+        u64 q;
+        if (kept_q(l, rel, q)) hist_add(s, (rel + shift) & 1023, q);
+    });
+    scan_bins<false, true>(s, 1024, need2);
+    if (tid == 0) {
+        int pick = t0 + s.r_bin;
+        pick = pick < 0 ? 0 : (pick < n ? pick : n - 1);
+        a.token_out[row] = a.lo + pick;
+        if (a.logit_out) a.logit_out[row] = lg[a.lo + pick];
+        if (a.kept_out) a.kept_out[row] = (int)kept;
+    }
+}
+
+__global__ void fill_i32_k(int* p, int n, int v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st) {
+    if (!a->logits || !a->uniform || !a->token_out) return hipErrorInvalidValue;
+    if (a->hi <= a->lo || a->lo < 0 || a->hi - a->lo > (1 << 20) || a->rows < 0) return hipErrorInvalidValue;
+    if (!(a->temperature > 0.f) || !(a->top_p > 0.f) || a->top_k < 0) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    const int n = a->hi - a->lo;
+    const bool filtered = (a->top_k > 0 && a->top_k < n) || a->top_p < 1.0f;
+    if (!filtered && n <= 4096) {   // the unfiltered narrow range is cover_token_select's, bit for bit
+        cover_token_select_args b;
+        b.logits = a->logits; b.ld = a->ld; b.rows = a->rows; b.lo = a->lo; b.hi = a->hi;
+        b.uniform = a->uniform; b.temperature = a->temperature; b.token_out = a->token_out; b.logit_out = a->logit_out;
+        hipError_t e = launch_token_select(&b, st);
+        if (e != hipSuccess) return e;
+        if (a->kept_out) hipLaunchKernelGGL(fill_i32_k, dim3((a->rows + 255) / 256), dim3(256), 0, st, a->kept_out, a->rows, n);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(token_sample_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}

@@ -93,6 +93,7 @@ class OpenVLA:
         self.logits_actions = torch.empty(max_candidates, c["n_bins"], dtype=torch.float32, device=dev)
         self.head_ws_actions = ops.gemm_workspace(max_candidates, c["n_bins"], D, dev)
         self.hn = torch.empty(max_candidates, D, dtype=BF, device=dev)
+        self.kept_sel = torch.empty(max_candidates, dtype=torch.int32, device=dev)   # ops.token_sample's kept-set sizes (last step's)
         self.zero_slots = torch.zeros(max(max_prompts, max_candidates), dtype=torch.int32, device=dev)
         self.bos = torch.tensor([1], dtype=torch.int64, device=dev)
         self._side = None
@@ -194,11 +195,14 @@ class OpenVLA:
     # ---------------------------------------------------------------------------------------------- sampler
     def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
                uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, trace: Optional[dict] = None,
-               force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None):
+               force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
+               top_k: int = 0, top_p: float = 1.0):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
         uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
-        tokenizer vocabulary. force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
+        tokenizer vocabulary; top_k / top_p filter the sampled distribution after the temperature, in the order and with the
+        meaning of Hugging Face's `generate(do_sample=True, top_k, top_p)` (ops.token_sample; 0 / 1.0 = off, the unfiltered
+        ops.token_select path; greedy ignores them). force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
         returning this path's own picks. on_prefill_enqueued: optional callable invoked once the prefill launches are
         queued -- the point where a caller should queue independent side-stream work (the verifier towers): the
         HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not. Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen])."""
@@ -242,9 +246,10 @@ class OpenVLA:
         last_row = (Tp + prompt_of_cand * Lt + cand_len - 1).to(torch.int32)
         pos_all = ((T0 + cand_len)[None, :] + torch.arange(self.n_gen, dtype=torch.int32, device=dev)[:, None]).contiguous()
         u_t = None if uniforms is None else uniforms.to(torch.float32).t().contiguous()
+        filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
             # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
-            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head)
+            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt)
             st = self._dec.get(key)
             if st is None:
                 st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
@@ -258,7 +263,7 @@ class OpenVLA:
             if u_t is not None:
                 st["u"].copy_(u_t)
             body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"])
+                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt)
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -281,15 +286,15 @@ class OpenVLA:
         sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
         fed = tokens if force_tokens is None else force_tokens.t().contiguous()
         self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark)
+                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt)
         return tokens.t().contiguous(), sel.t().contiguous()
 
     def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None):
+                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
         ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace)
+        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
@@ -301,15 +306,20 @@ class OpenVLA:
                                 dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace)
+            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace):
+    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None):
+        """filt: None = today's ops.token_select calls; (top_k, top_p) = ops.token_sample over the same columns."""
         N = h.shape[0]
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
         if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
-            t, _ = ops.token_select(lg, 0, self.c["n_bins"], uniform=uniforms[i], temperature=temperature, out_logit=sel[i])
+            if filt is None:
+                t, _ = ops.token_select(lg, 0, self.c["n_bins"], uniform=uniforms[i], temperature=temperature, out_logit=sel[i])
+            else:
+                t, _, _ = ops.token_sample(lg, 0, self.c["n_bins"], uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
+                                           out_logit=sel[i], out_kept=self.kept_sel[:N])
             torch.add(t, self.action_lo, out=tokens[i])
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
@@ -317,6 +327,9 @@ class OpenVLA:
             trace.setdefault("logits", []).append(lg.clone())
         if uniforms is None:
             ops.token_select(lg, 0, self.c["tok_vocab"], out_tok=tokens[i], out_logit=sel[i])
+        elif filt is not None:
+            ops.token_sample(lg, self.action_lo, self.action_hi, uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
+                             out_tok=tokens[i], out_logit=sel[i], out_kept=self.kept_sel[:N])
         else:
             ops.token_select(lg, self.action_lo, self.action_hi, uniform=uniforms[i], temperature=temperature, out_tok=tokens[i],
                              out_logit=sel[i])

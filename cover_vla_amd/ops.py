@@ -566,6 +566,33 @@ def token_select(logits, lo, hi, uniform=None, temperature=1.0, out_tok=None, ou
     return tok, lg
 
 
+def token_sample(logits, lo, hi, uniform, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logit=None, out_kept=None):
+    """Filtered inverse-CDF sampling over columns [lo, hi) of fp32 logits [rows, >= hi] (cover_token_sample: temperature, then top-k
+    with ties kept, then top-p, then the pick with the host-supplied uniform fp32 [rows] in [0, 1)); hi - lo up to 2^20.
+    Returns (token int64 [rows], its raw logit fp32 [rows], size of the kept set int32 [rows]); out_tok / out_logit / out_kept
+    (contiguous, [rows]) are written in place of fresh tensors, as in token_select. Deterministic, one launch, recordable."""
+    if uniform is None:
+        raise L.CoverError("token_sample needs uniforms (greedy selection is token_select)")
+    if not temperature > 0 or not top_p > 0 or top_k < 0 or hi <= lo or lo < 0:
+        raise L.CoverError(f"token_sample: temperature > 0, top_p > 0, top_k >= 0 and 0 <= lo < hi are required "
+                           f"(got temperature={temperature}, top_k={top_k}, top_p={top_p}, lo={lo}, hi={hi})")
+    _chk_dev(logits, uniform, out_tok, out_logit, out_kept)
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and hi <= logits.shape[1]
+    tok = torch.empty(rows, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
+    lg = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_logit is None else out_logit
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if out_kept is None else out_kept
+    assert tok.dtype == torch.int64 and lg.dtype == torch.float32 and kept.dtype == torch.int32
+    assert tok.is_contiguous() and lg.is_contiguous() and kept.is_contiguous() and tok.numel() == rows == lg.numel() == kept.numel()
+    assert uniform.is_contiguous() and uniform.dtype == torch.float32 and uniform.numel() == rows
+    a = L.TokenSampleArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), temperature, int(top_k), top_p
+    a.token_out, a.logit_out, a.kept_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr()
+    L.check(L.lib().cover_token_sample(C.byref(a), _stream()), "token_sample")
+    return tok, lg, kept
+
+
 def score_select(it, act, group_size):
     """it [members, dim], act [members, N, dim] fp32 -> (scores [N], result int32[4], best f32[2], fused_it, fused_act)."""
     _chk_dev(it, act)

@@ -70,15 +70,25 @@ class PI0FASTTokens:
 
     def generate_tokens(self, images: List[torch.Tensor], img_masks: List[torch.Tensor], tokens: torch.Tensor, pad_mask: torch.Tensor,
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
-                        force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None) -> torch.Tensor:
+                        force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
+                        uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0) -> torch.Tensor:
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
-        (what `generate(do_sample=False)` returns after the prompt). force_tokens (tests): teacher-force the fed-back tokens."""
+        (what `generate(do_sample=False)` returns after the prompt). force_tokens (tests): teacher-force the fed-back tokens.
+        uniforms fp32 [B, max_new_tokens] in [0, 1) on the device: sample instead (`generate(do_sample=True, temperature, top_k,
+        top_p)`: ops.token_sample over the vocabulary, column i drives step i); every row is decoded on its own, rows that share
+        frames and prompt diverge with their uniforms. None = greedy; temperature / top_k / top_p are then unused."""
         dev, c = self.dev, self.c
+        u_t = None
+        if uniforms is not None:
+            if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
+                raise ValueError("uniforms must be [B, max_new_tokens]")
+            u_t = uniforms.to(device=dev, dtype=torch.float32).t().contiguous()       # step-major: row i is step i's [B]
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
-        if force_tokens is None and tokens.shape[0] > 1 and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images):
+        if uniforms is None and force_tokens is None and tokens.shape[0] > 1 and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images):
             key = torch.cat([tokens, pad_mask.to(tokens.dtype)], dim=1).cpu().numpy()
             _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
             if first.shape[0] < tokens.shape[0]:
@@ -127,7 +137,13 @@ class PI0FASTTokens:
             lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
             if trace is not None:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
-            t, _ = ops.token_select(lg, 0, c["vocab"])                                # greedy over the vocabulary
+            if u_t is None:
+                t, _ = ops.token_select(lg, 0, c["vocab"])                            # greedy over the vocabulary
+            else:
+                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p)
+                if trace is not None:
+                    trace.setdefault("picks", []).append(t.clone())
+                    trace.setdefault("kept", []).append(kept)
             if force_tokens is not None:
                 t = force_tokens[:, i].to(dev)
             t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
@@ -166,11 +182,16 @@ class PI0FASTConfig:
     relaxed_action_decoding: bool = True
     resize_imgs_with_padding: Optional[Tuple[int, int]] = (224, 224)
     device: str = "cuda:0"
+    # sampled decoding (`generate(do_sample=True, ...)`): sample_seed None = greedy, the reference's setting
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    sample_seed: Optional[int] = None
 
 
 class PI0FASTPolicy:
     """PI0FASTPolicy.select_action (modeling_pi0fast.py:193-233) on `PI0FASTTokens`: state discretisation + prompt text
-    (`create_input_tokens` :570-640), greedy generation on the device, `extract_actions` (:794-859) and the action queue. The two
+    (`create_input_tokens` :570-640), greedy (or, with `config.sample_seed`, sampled) generation on the device, `extract_actions` (:794-859) and the action queue. The two
     tokenizers are the caller's objects (HF `AutoTokenizer("google/paligemma-3b-pt-224")` and the `physical-intelligence/fast`
     processor in production; `cover_vla_amd.synth.CharTokenizer` in the tests): only the methods the reference calls are used."""
 
@@ -179,6 +200,8 @@ class PI0FASTPolicy:
         self.paligemma_tokenizer, self.fast_tokenizer = paligemma_tokenizer, fast_processor
         self.normalization = normalization or {"state": ("IDENTITY", None, None), "action": ("IDENTITY", None, None)}
         self.pad_token_id = paligemma_tokenizer.pad_token_id if hasattr(paligemma_tokenizer, "pad_token_id") else paligemma_tokenizer.eos_token_id
+        # the source of randomness of sampled decoding: a host generator seeded ONCE, so a seed and an observation sequence fix the actions
+        self._gen = None if config.sample_seed is None else torch.Generator().manual_seed(int(config.sample_seed))
         self.reset()
 
     def reset(self):
@@ -246,9 +269,13 @@ class PI0FASTPolicy:
                 images.append(img.to(dev))
             ids, mask = self.create_input_tokens(state, batch["task"])
             B = ids.shape[0]
+            sampling = {}
+            if self._gen is not None:
+                u = torch.rand(B, self.config.max_decoding_steps, generator=self._gen, dtype=torch.float32)
+                sampling = dict(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)
             toks = self.model.generate_tokens(images, [torch.ones(B, dtype=torch.bool, device=dev) for _ in images], ids.to(dev), mask.to(dev),
                                               self.config.max_decoding_steps, eos_token_id=self.paligemma_tokenizer.eos_token_id,
-                                              pad_token_id=self.pad_token_id)
+                                              pad_token_id=self.pad_token_id, **sampling)
             actions = self.extract_actions(toks.cpu(), self.config.chunk_size, self.config.action_dim)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
             actions = self._unnormalize_action(actions.to(torch.float32))

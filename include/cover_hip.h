@@ -397,6 +397,35 @@ typedef struct cover_token_select_args {
 } cover_token_select_args;
 int cover_token_select(const cover_token_select_args* args, void* stream);
 
+/* Filtered sampling over a wide row (pi0-FAST: the 257 152-entry PaliGemma vocabulary; OpenVLA: the 256 action bins): what
+ * Hugging Face's generate(do_sample=True) applies, in its order -- TemperatureLogitsWarper, TopKLogitsWarper,
+ * TopPLogitsWarper -- followed by this library's inverse-CDF pick with a host-supplied uniform. Per row, over columns [lo, hi)
+ * (hi - lo <= 2^20, any lo / ld):
+ *   1. m = max l_i, weight w_i = expf((l_i - m) / temperature)                                     (temperature > 0)
+ *   2. top_k > 0: keep the tokens whose logit is >= the k-th largest logit (a comparison of the input floats: every token
+ *      tied with the k-th value stays, as in TopKLogitsWarper); top_k == 0 or >= hi - lo keeps all
+ *   3. top_p < 1: order the kept tokens by descending weight, equal weights by ascending index, and keep the shortest prefix
+ *      whose mass reaches top_p x (mass kept by step 2); at least one token stays (TopPLogitsWarper, min_tokens_to_keep = 1);
+ *      top_p >= 1 keeps all                                                                            (top_p > 0)
+ *   4. running sum of the kept weights in index order; token = the first kept index whose running sum exceeds
+ *      uniform[row] x (kept mass), the last kept index if rounding lets none exceed it.
+ * Deterministic: the same row, uniform and parameters give the same token in every launch and at every row position. All masses
+ * are exact integer sums of Q43 fixed-point weights (rint(w x 2^43)), so no summation order can change a result; the error
+ * against exact sums of the fp32 weights is below 2^-24 of the kept mass (csrc/sample.hip states the scheme in full).
+ * One launch, no workspace, no host round trip: recordable into a hipGraph. With both filters off and hi - lo <= 4096 the call
+ * is cover_token_select's sampling path, bit for bit. kept_out (optional) receives the size of the kept set. */
+typedef struct cover_token_sample_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    const float* uniform;   /* [rows] in [0,1), required */
+    float temperature;
+    int top_k;              /* 0 = off */
+    float top_p;            /* >= 1 = off */
+    int64_t* token_out;     /* [rows] */
+    float* logit_out;       /* [rows] selected raw logit (optional) */
+    int* kept_out;          /* [rows] size of the kept set (optional) */
+} cover_token_sample_args;
+int cover_token_sample(const cover_token_sample_args* args, void* stream);
+
 /* K20: fuse + score + grouped arg-max (efficient_ensemble_merged.py:404-448). it: [n_members][512] image-text
  * embeddings (unit rows), act: [n_members][N][512]; scores_out [N]; result_out int32 [4] =
  * {global_idx, group_idx, idx_in_group, 0}; best_out float [2] = {max_score, best_group_mean}. First index wins ties

@@ -1,6 +1,10 @@
 """pi0-FAST token path at full size on one MI355X (secondary measurement; bench.py is the contractual line): PaliGemma-3B geometry
-(SigLIP-So400m 224^2 + Gemma-2B, vocabulary 257152), B = 40 candidates = 8 rephrased prompts x 5 samples (greedy decoding is a
-function of the prompt: 8 distinct generations), prompt 48 tokens, NEW action tokens per candidate (default 32), synthetic weights."""
+(SigLIP-So400m 224^2 + Gemma-2B, vocabulary 257152), B = 40 candidates = 8 rephrased prompts x 5 samples, prompt 48 tokens, NEW
+action tokens per candidate (default 32), synthetic weights.
+  default        greedy: decoding is a function of the prompt, 8 distinct generations are decoded and broadcast
+  SAMPLE=1       sampled (TEMPERATURE, TOP_K, TOP_P; defaults 1.0 / 50 / 0.95): max_batch = B, every candidate decodes on its own
+                 with uniforms from a seeded generator; the line also counts the distinct token rows among the B candidates
+  SAMPLE=both    greedy and sampled alternating, ROUNDS (default 3) lines of each: the spread of repeated runs in one process"""
 import os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,7 +23,9 @@ sd["projector.weight"] = g.w(c["lm_dim"], c["vit_dim"]); sd["projector.bias"] = 
 for k, v in synth.decoder_state(g, dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"], rms_base=0.0, vocab=c["vocab"]).items():
     sd["lm." + k] = v
 B, P, L = 40, 8, 48
-model = PI0FASTTokens(sd, c, device="cuda:0", max_batch=P, max_prompt=L, max_new_tokens=max(NEW, 8))
+SAMPLE = os.environ.get("SAMPLE", "0")
+TEMPERATURE, TOP_K, TOP_P = float(os.environ.get("TEMPERATURE", "1.0")), int(os.environ.get("TOP_K", "50")), float(os.environ.get("TOP_P", "0.95"))
+model = PI0FASTTokens(sd, c, device="cuda:0", max_batch=P if SAMPLE == "0" else B, max_prompt=L, max_new_tokens=max(NEW, 8))
 del sd; torch.cuda.empty_cache()
 gen = torch.Generator().manual_seed(0)
 img = (torch.rand(1, 3, 224, 224, generator=gen) * 2 - 1).repeat(B, 1, 1, 1).to(dev)
@@ -31,17 +37,27 @@ for p in range(P):
         toks[p * (B // P) + s, :n] = row; pad[p * (B // P) + s, :n] = 1
 toks, pad = toks.to(dev), pad.to(dev)
 ones = [torch.ones(B, dtype=torch.bool, device=dev)]
-def step():
-    return model.generate_tokens([img], ones, toks, pad, NEW, eos_token_id=-1)      # no early stop: NEW tokens for every row
-for _ in range(2): out = step()
-torch.cuda.synchronize()
-n = 5
-t0 = time.perf_counter()
-for _ in range(n): out = step()
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / n
-assert out.shape == (B, NEW)
+uni = torch.rand(B, NEW, generator=torch.Generator().manual_seed(1)).to(dev)
+def step(sampled):
+    kw = dict(uniforms=uni, temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P) if sampled else {}
+    return model.generate_tokens([img], ones, toks, pad, NEW, eos_token_id=-1, **kw)      # no early stop: NEW tokens for every row
 wbytes = 2.0 * (c["layers"] * (c["lm_dim"] * (c["Hq"] + 2 * c["Hkv"]) * c["D"] + c["Hq"] * c["D"] * c["lm_dim"] + 3 * c["lm_dim"] * c["lm_mlp"]) + c["vocab"] * c["lm_dim"])
-print(json.dumps({"profile": "pi0-FAST tokens", "B": B, "distinct_prompts": P, "new_tokens": NEW, "ms_per_decision": round(dt * 1e3, 2),
-                  "candidates_per_s": round(B / dt, 1), "decode_weight_GB_per_step": round(wbytes / 1e9, 2),
-                  "hbm_floor_ms_decode": round((NEW - 1) * wbytes / 8e12 * 1e3, 2)}))
+def measure(sampled, n=5):
+    for _ in range(2): out = step(sampled)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n): out = step(sampled)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / n
+    assert out.shape == (B, NEW)
+    rec = {"profile": "pi0-FAST tokens", "B": B, "distinct_prompts": P, "new_tokens": NEW, "ms_per_decision": round(dt * 1e3, 2),
+           "candidates_per_s": round(B / dt, 1), "decode_weight_GB_per_step": round(wbytes / 1e9, 2),
+           "hbm_floor_ms_decode": round((NEW - 1) * wbytes / 8e12 * 1e3, 2), "mode": "sampled" if sampled else "greedy"}
+    if sampled:
+        rec.update(temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, distinct_token_rows=len({tuple(r) for r in out.cpu().tolist()}))
+    print(json.dumps(rec), flush=True)
+if SAMPLE == "both":
+    for _ in range(int(os.environ.get("ROUNDS", "3"))):
+        measure(False); measure(True)
+else:
+    measure(SAMPLE != "0")
