@@ -114,6 +114,16 @@ class TokenSampleArgs(C.Structure):
                 ("token_out", c_p), ("logit_out", c_p), ("kept_out", c_p)]
 
 
+class TokenSampleScoredArgs(C.Structure):
+    _fields_ = TokenSampleArgs._fields_ + [("logprob_out", c_p)]
+
+
+class TokenLogprobArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i),
+                ("temperature", c_f), ("top_k", c_i), ("top_p", c_f),
+                ("token", c_p), ("logprob_out", c_p), ("kept_out", c_p)]
+
+
 class ScoreSelectArgs(C.Structure):
     _fields_ = [("it", c_p), ("act", c_p), ("n_members", c_i), ("N", c_i), ("dim", c_i), ("group_size", c_i),
                 ("scores_out", c_p), ("result_out", c_p), ("best_out", c_p), ("fused_it_out", c_p),
@@ -168,7 +178,8 @@ _STRUCTS = {
     "cover_gemm_epi": GemmEpi, "cover_kv_segment": KvSegment, "cover_attn_args": AttnArgs,
     "cover_rope_args": RopeArgs, "cover_patchify_args": PatchifyArgs, "cover_gemm_f32_args": GemmF32Args,
     "cover_mha_f32_args": MhaF32Args, "cover_token_select_args": TokenSelectArgs,
-    "cover_token_sample_args": TokenSampleArgs,
+    "cover_token_sample_args": TokenSampleArgs, "cover_token_sample_scored_args": TokenSampleScoredArgs,
+    "cover_token_logprob_args": TokenLogprobArgs,
     "cover_score_select_args": ScoreSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
@@ -220,6 +231,8 @@ SYMBOLS = {
     "cover_sincos_time_embed": (c_i, [c_p, c_i, c_i, C.c_double, C.c_double, c_p, c_i, c_p]),
     "cover_token_select": (c_i, [_P(TokenSelectArgs), c_p]),
     "cover_token_sample": (c_i, [_P(TokenSampleArgs), c_p]),
+    "cover_token_sample_scored": (c_i, [_P(TokenSampleScoredArgs), c_p]),
+    "cover_token_logprob": (c_i, [_P(TokenLogprobArgs), c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_tokens_to_histories": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_f, c_p, c_p, c_p]),

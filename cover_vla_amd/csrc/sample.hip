@@ -206,15 +206,32 @@ __device__ __forceinline__ bool key_in_prefix(unsigned key, unsigned prefix, int
 }
 __device__ __forceinline__ int key_digit(unsigned key, int lev) { return (int)((key >> key_shift(lev)) & (unsigned)(key_bins(lev) - 1)); }
 
-__global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args a) {
-    __shared__ SampleShared s;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* lg = a.logits + (size_t)row * a.ld;
-    const int n = a.hi - a.lo;
-    const bool use_k = a.top_k > 0 && a.top_k < n;
-    const bool use_p = a.top_p < 1.0f;
-    const float T = a.temperature;
-    SampleSrc src{lg + a.lo, n, false};
+// The kept set of one row (steps 1-3 of cover_token_sample), as every entry point of this file sees it: column rel of [lo, hi) with logit l
+// is kept  <=>  lkey(l) >= tk  and  ( wkey(w) > wstar  or  (wkey(w) == wstar and rel <= idx_cut) ),  w = weight_of(l, m, T).
+// A pure function of (l, rel) and five block-uniform values, so the sampler (which walks the row or the compacted list) and the
+// scorer (which looks at one given column) cannot disagree about membership.
+struct KeptSet {
+    float m, T;          // row maximum, temperature
+    unsigned tk;         // key of the k-th largest logit (0: top-k off)
+    unsigned wstar;      // key of the weight at the top-p cut (0: top-p off)
+    int idx_cut;         // last kept index among the tokens that weigh exactly w* (0x7fffffff: all of them)
+    __device__ __forceinline__ bool kept(float l, int rel, u64& q) const {
+        if (lkey(l) < tk) return false;
+        const float w = weight_of(l, m, T);
+        const unsigned wb = wkey(w);
+        if (wb < wstar || (wb == wstar && rel > idx_cut)) return false;
+        q = q43(w);
+        return true;
+    }
+};
+
+// Steps 1-3: row maximum, k-th value, top-p cut. May compact the candidates into LDS and switch src to that list (src.list);
+// every thread of the block calls this, the result is block-uniform.
+__device__ __forceinline__ KeptSet kept_set(SampleShared& s, SampleSrc& src, int top_k, float top_p, float T) {
+    const int tid = threadIdx.x;
+    const int n = src.n;
+    const bool use_k = top_k > 0 && top_k < n;
+    const bool use_p = top_p < 1.0f;
     if (tid == 0) s.n_list = 0u;
 
     // ---- pass 1: the row maximum; with top-k also the first digit of the logit keys (the probe that sizes the candidate list)
@@ -233,7 +250,7 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
     // ---- top-k: tk = key of the k-th largest logit; everything with lkey >= tk stays (ties with the k-th value included)
     unsigned tk = 0u;
     if (use_k) {
-        scan_bins<true, false>(s, key_bins(0), (u64)a.top_k);
+        scan_bins<true, false>(s, key_bins(0), (u64)top_k);
         const int b0 = s.r_bin;
         if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {   // block-uniform
             for_each(s, src, [&](float l, int rel) {
@@ -249,7 +266,7 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
             src.list = true;
         }
         unsigned prefix = 0u;
-        u64 need = (u64)a.top_k;
+        u64 need = (u64)top_k;
         for (int lev = 0; lev < 3; ++lev) {
             hist_zero(s);
             for_each(s, src, [&](float l, int rel) {
@@ -276,7 +293,7 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
                 const float w = weight_of(l, m, T);
                 hist_add(s, key_digit(wkey(w), 0), q43(w));
             });
-            scan_bins<true, true>(s, key_bins(0), 0ull, 1, (double)a.top_p);
+            scan_bins<true, true>(s, key_bins(0), 0ull, 1, (double)top_p);
             target = s.r_need;
             const int b0 = s.r_bin;
             if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {
@@ -306,7 +323,7 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
                 const unsigned key = wkey(w);
                 if (key_in_prefix(key, prefix, lev)) hist_add(s, key_digit(key, lev), q43(w));
             });
-            if (lev == 0 && target == 0ull) scan_bins<true, true>(s, key_bins(lev), 0ull, 1, (double)a.top_p);
+            if (lev == 0 && target == 0ull) scan_bins<true, true>(s, key_bins(lev), 0ull, 1, (double)top_p);
             else scan_bins<true, true>(s, key_bins(lev), need);
             if (lev == 0 && target == 0ull) need = s.r_need;
             prefix |= (unsigned)s.r_bin << key_shift(lev);
@@ -336,37 +353,35 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
             idx_cut = ip;
         }
     }
+    return KeptSet{m, T, tk, wstar, idx_cut};
+}
 
-    // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
-    auto kept_q = [&](float l, int rel, u64& q) -> bool {
-        if (lkey(l) < tk) return false;
-        const float w = weight_of(l, m, T);
-        const unsigned wb = wkey(w);
-        if (wb < wstar || (wb == wstar && rel > idx_cut)) return false;
-        q = q43(w);
-        return true;
-    };
-    // Tiles are cut where the row's float4 body starts (tile 0 = the scalar head, if any), so the 256 columns one wave loads together
-    // lie in one tile: on the row, a wave adds its kept masses and count with shuffles (exact: integers) and one lane adds them to
-    // the tile -- per-element atomics on one address would serialise 64 lanes.
+// Count and Q43 mass of the kept tokens per tile of 1024 columns, into the histogram (the caller scans it: the totals are the size and
+// the mass of the kept set, the crossing tile is the first digit of the pick). Returns the tile shift: tile of rel = (rel + shift) >> 10.
+// Tiles are cut where the row's float4 body starts (tile 0 = the scalar head, if any), so the 256 columns one wave loads together
+// lie in one tile: on the row, a wave adds its kept masses and count with shuffles (exact: integers) and one lane adds them to
+// the tile -- per-element atomics on one address would serialise 64 lanes.
+__device__ __forceinline__ int kept_tiles(SampleShared& s, const SampleSrc& src, const KeptSet& ks) {
+    const int tid = threadIdx.x;
+    const int n = src.n;
     int head = 0;
     if (!src.list) {
         head = (int)(((16u - (unsigned)((uintptr_t)src.p & 15u)) & 15u) >> 2);
         head = head < n ? head : n;
     }
-    const int shift = (1024 - head) & 1023;                 // tile of rel = (rel + shift) >> 10, at most 1025 tiles
+    const int shift = (1024 - head) & 1023;                 // at most 1025 tiles
     hist_zero(s);
     if (src.list) {
         for_each(s, src, [&](float l, int rel) {
             u64 q;
-            if (kept_q(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
+            if (ks.kept(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
         });
     } else {
         const float* p = src.p;
         const int lane = tid & 63;
         auto one = [&](float l, int rel) {
             u64 q;
-            if (kept_q(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
+            if (ks.kept(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
         };
         for (int c = tid; c < head; c += SMP_T) one(p[c], c);
         const int n4 = (n - head) >> 2;
@@ -375,10 +390,10 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
         auto packed = [&](const float4& x, int c) -> u64 {
             const int i0 = head + 4 * c;
             u64 acc = 0ull, q;
-            if (kept_q(x.x, i0, q)) acc += q + (1ull << 52);
-            if (kept_q(x.y, i0 + 1, q)) acc += q + (1ull << 52);
-            if (kept_q(x.z, i0 + 2, q)) acc += q + (1ull << 52);
-            if (kept_q(x.w, i0 + 3, q)) acc += q + (1ull << 52);
+            if (ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
+            if (ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
+            if (ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
+            if (ks.kept(x.w, i0 + 3, q)) acc += q + (1ull << 52);
             return acc;
         };
         auto flush = [&](u64 acc, int cb) {   // cb: the wave's first float4 of this load
@@ -409,23 +424,69 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
         }
         for (int c = head + 4 * n4 + tid; c < n; c += SMP_T) one(p[c], c);
     }
+    return shift;
+}
+
+// lp = x_t - log(sum over KEPT of exp(x_i)) for a column of the row with logit l at rel, -inf if it is not kept. x_t is the fp32 exponent the
+// weights are made of, the sum is the exact Q43 mass of the kept set (>= 2^43: the row maximum weighs 1 and is always kept); the
+// logarithm and the difference are taken in double, once per row, and rounded to fp32 once.
+__device__ __forceinline__ float kept_logprob(const KeptSet& ks, float l, int rel, u64 mass) {
+    u64 q;
+    if (!ks.kept(l, rel, q)) return -INFINITY;
+    const float x = (l - ks.m) / ks.T;
+    return (float)((double)x - (log((double)mass) - 43.0 * 0.693147180559945309417232121458));
+}
+
+template <bool SCORED>
+__global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args a, float* logprob_out) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = a.logits + (size_t)row * a.ld;
+    const int n = a.hi - a.lo;
+    SampleSrc src{lg + a.lo, n, false};
+    const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
+
+    // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
+    const int shift = kept_tiles(s, src, ks);
     scan_bins<false, true>(s, SMP_BINS, 0ull, 2, (double)a.uniform[row]);
     const int tile = s.r_bin;
     const unsigned kept = s.r_cnt_total;
+    const u64 mass = s.r_mass_total;
     const u64 need2 = s.r_need - s.r_mass_before;
     const int t0 = (tile << 10) - shift;
     hist_zero(s);
     for_each_in(s, src, t0 < 0 ? 0 : t0, t0 + 1024, [&](float l, int rel) {
         u64 q;
-        if (kept_q(l, rel, q)) hist_add(s, (rel + shift) & 1023, q);
+        if (ks.kept(l, rel, q)) hist_add(s, (rel + shift) & 1023, q);
     });
     scan_bins<false, true>(s, 1024, need2);
     if (tid == 0) {
         int pick = t0 + s.r_bin;
         pick = pick < 0 ? 0 : (pick < n ? pick : n - 1);
         a.token_out[row] = a.lo + pick;
-        if (a.logit_out) a.logit_out[row] = lg[a.lo + pick];
+        const float l = lg[a.lo + pick];
+        if (a.logit_out) a.logit_out[row] = l;
         if (a.kept_out) a.kept_out[row] = (int)kept;
+        if (SCORED) logprob_out[row] = kept_logprob(ks, l, pick, mass);
+    }
+}
+
+// Scores given tokens: the kept set and its mass as the sampler computes them (the same two device functions), no pick.
+__global__ __launch_bounds__(SMP_T) void token_logprob_k(cover_token_logprob_args a) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x;
+    const float* lg = a.logits + (size_t)row * a.ld;
+    const int n = a.hi - a.lo;
+    SampleSrc src{lg + a.lo, n, false};
+    const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
+    kept_tiles(s, src, ks);
+    scan_bins<false, true>(s, SMP_BINS, 1ull);
+    if (threadIdx.x == 0) {
+        const long long t = (long long)a.token[row];
+        float lp = -INFINITY;
+        if (t >= (long long)a.lo && t < (long long)a.hi) lp = kept_logprob(ks, lg[t], (int)(t - a.lo), s.r_mass_total);
+        a.logprob_out[row] = lp;
+        if (a.kept_out) a.kept_out[row] = (int)s.r_cnt_total;
     }
 }
 
@@ -434,10 +495,23 @@ __global__ void fill_i32_k(int* p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
-hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st) {
+static bool sample_params_ok(int lo, int hi, int rows, float temperature, int top_k, float top_p) {
+    if (hi <= lo || lo < 0 || hi - lo > (1 << 20) || rows < 0) return false;
+    return temperature > 0.f && top_p > 0.f && top_k >= 0;
+}
+
+hipError_t launch_token_logprob(const cover_token_logprob_args* a, hipStream_t st) {
+    if (!a->logits || !a->token || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_logprob_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}
+
+// logprob_out == nullptr: cover_token_sample; otherwise cover_token_sample_scored (the same launch with one more store per row)
+static hipError_t launch_token_sample_impl(const cover_token_sample_args* a, float* logprob_out, hipStream_t st) {
     if (!a->logits || !a->uniform || !a->token_out) return hipErrorInvalidValue;
-    if (a->hi <= a->lo || a->lo < 0 || a->hi - a->lo > (1 << 20) || a->rows < 0) return hipErrorInvalidValue;
-    if (!(a->temperature > 0.f) || !(a->top_p > 0.f) || a->top_k < 0) return hipErrorInvalidValue;
+    if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     const int n = a->hi - a->lo;
     const bool filtered = (a->top_k > 0 && a->top_k < n) || a->top_p < 1.0f;
@@ -447,9 +521,28 @@ hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st)
         b.uniform = a->uniform; b.temperature = a->temperature; b.token_out = a->token_out; b.logit_out = a->logit_out;
         hipError_t e = launch_token_select(&b, st);
         if (e != hipSuccess) return e;
+        if (logprob_out) {   // cover_token_select keeps no mass: score its picks in a second launch (which also writes the kept count)
+            cover_token_logprob_args c;
+            c.logits = a->logits; c.ld = a->ld; c.rows = a->rows; c.lo = a->lo; c.hi = a->hi;
+            c.temperature = a->temperature; c.top_k = a->top_k; c.top_p = a->top_p;
+            c.token = a->token_out; c.logprob_out = logprob_out; c.kept_out = a->kept_out;
+            return launch_token_logprob(&c, st);
+        }
         if (a->kept_out) hipLaunchKernelGGL(fill_i32_k, dim3((a->rows + 255) / 256), dim3(256), 0, st, a->kept_out, a->rows, n);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(token_sample_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    if (logprob_out) hipLaunchKernelGGL(token_sample_k<true>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
+    else hipLaunchKernelGGL(token_sample_k<false>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
     return hipGetLastError();
+}
+
+hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st) { return launch_token_sample_impl(a, nullptr, st); }
+
+hipError_t launch_token_sample_scored(const cover_token_sample_scored_args* a, hipStream_t st) {
+    if (!a->logprob_out) return hipErrorInvalidValue;
+    cover_token_sample_args b;
+    b.logits = a->logits; b.ld = a->ld; b.rows = a->rows; b.lo = a->lo; b.hi = a->hi;
+    b.uniform = a->uniform; b.temperature = a->temperature; b.top_k = a->top_k; b.top_p = a->top_p;
+    b.token_out = a->token_out; b.logit_out = a->logit_out; b.kept_out = a->kept_out;
+    return launch_token_sample_impl(&b, a->logprob_out, st);
 }

@@ -30,6 +30,26 @@ def bridge_statistics() -> dict:
     return _STATS
 
 
+def sequence_logprob(logprobs, tokens=None, pad_token_id=None, length_normalize=False):
+    """Per-candidate sequence log-probability from the per-step values OpenVLA.sample / PI0FASTTokens.generate_tokens return with
+    return_logprobs: logprobs [N, steps] (torch tensor on any device, or numpy) -> [N] of the same kind, the sum over steps. With
+    tokens [N, steps] and pad_token_id the steps whose token is the pad are left out (generate_tokens already gives them 0.0; this
+    also serves values scored elsewhere, where a pad scores -inf); length_normalize divides by the number of counted steps (at least 1).
+    Index bookkeeping on N x steps values."""
+    if isinstance(logprobs, np.ndarray):
+        count = np.ones(logprobs.shape, dtype=bool)
+        if tokens is not None and pad_token_id is not None:
+            count = np.asarray(tokens) != pad_token_id
+        total = np.where(count, logprobs, 0.0).sum(axis=1)
+        return total / np.maximum(count.sum(axis=1), 1) if length_normalize else total
+    import torch
+    count = torch.ones_like(logprobs, dtype=torch.bool)
+    if tokens is not None and pad_token_id is not None:
+        count = tokens.to(logprobs.device) != pad_token_id
+    total = torch.where(count, logprobs, torch.zeros_like(logprobs)).sum(dim=1)
+    return total / count.sum(dim=1).clamp(min=1).to(total.dtype) if length_normalize else total
+
+
 def denormalize_bound(data, data_min, data_max, clip_min=-1.0, clip_max=1.0):
     return (data - clip_min) / (clip_max - clip_min) * (data_max - data_min) + data_min
 

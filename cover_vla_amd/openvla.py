@@ -196,7 +196,7 @@ class OpenVLA:
     def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
                uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, trace: Optional[dict] = None,
                force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
-               top_k: int = 0, top_p: float = 1.0):
+               top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
         uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
@@ -205,7 +205,11 @@ class OpenVLA:
         ops.token_select path; greedy ignores them). force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
         returning this path's own picks. on_prefill_enqueued: optional callable invoked once the prefill launches are
         queued -- the point where a caller should queue independent side-stream work (the verifier towers): the
-        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not. Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen])."""
+        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not. Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen]).
+        return_logprobs: a third tensor fp32 [N, n_gen], the log-probability of each pick under the distribution it was drawn from
+        (sampled: temperature, top_k, top_p over the action bins, cover_token_sample_scored / cover_token_logprob; greedy: temperature 1,
+        no filters, over the tokenizer vocabulary the arg-max runs over). With force_tokens it is still this path's own picks that are
+        scored. The default launches exactly what it launched without the argument."""
         c, dev = self.c, self.dev
         P, Lt = prompt_tokens.shape
         N = P * n_samples
@@ -249,13 +253,14 @@ class OpenVLA:
         filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
             # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
-            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt)
+            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ())
             st = self._dec.get(key)
             if st is None:
                 st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
                           pos_all=torch.empty_like(pos_all), tokens=torch.empty(self.n_gen, N, dtype=torch.int64, device=dev),
                           sel=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev),
                           u=None if u_t is None else torch.empty_like(u_t),
+                          lps=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None,
                           prompt_slots=torch.arange(P, dtype=torch.int32, device=dev), prompt_lens=torch.empty(P, dtype=torch.int32, device=dev))
                 self._dec[key] = st
             st["cand_len"].copy_(cand_len); st["last_row"].copy_(last_row); st["pos_all"].copy_(pos_all)
@@ -263,7 +268,7 @@ class OpenVLA:
             if u_t is not None:
                 st["u"].copy_(u_t)
             body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt)
+                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"])
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -280,21 +285,26 @@ class OpenVLA:
                 cur.wait_stream(self._cap)
             else:
                 st["graph"].launch()
+                if return_logprobs:
+                    return st["tokens"].t().contiguous(), st["sel"].t().contiguous(), st["lps"].t().contiguous()
                 return st["tokens"].t().contiguous(), st["sel"].t().contiguous()
         # step-major buffers: row i of each is contiguous, so the kernels of step i read / write them in place (no per-step slice copies)
         tokens = torch.empty(self.n_gen, N, dtype=torch.int64, device=dev)
         sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
+        lps = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None
         fed = tokens if force_tokens is None else force_tokens.t().contiguous()
         self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt)
+                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps)
+        if return_logprobs:
+            return tokens.t().contiguous(), sel.t().contiguous(), lps.t().contiguous()
         return tokens.t().contiguous(), sel.t().contiguous()
 
     def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None):
+                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
         ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt)
+        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
@@ -306,20 +316,25 @@ class OpenVLA:
                                 dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt)
+            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None):
-        """filt: None = today's ops.token_select calls; (top_k, top_p) = ops.token_sample over the same columns."""
+    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None):
+        """filt: None = today's ops.token_select calls; (top_k, top_p) = ops.token_sample over the same columns. lps fp32 [n_gen, N] or
+        None: row i receives the log-probability of step i's picks (the scored sampler where ops.token_sample picks, one
+        ops.token_logprob launch behind an ops.token_select pick)."""
+        lp = None if lps is None else lps[i]
         N = h.shape[0]
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
         if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
             if filt is None:
                 t, _ = ops.token_select(lg, 0, self.c["n_bins"], uniform=uniforms[i], temperature=temperature, out_logit=sel[i])
+                if lp is not None:
+                    ops.token_logprob(lg, 0, self.c["n_bins"], t, temperature=temperature, out=lp)
             else:
                 t, _, _ = ops.token_sample(lg, 0, self.c["n_bins"], uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
-                                           out_logit=sel[i], out_kept=self.kept_sel[:N])
+                                           out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=lp)
             torch.add(t, self.action_lo, out=tokens[i])
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
@@ -327,12 +342,16 @@ class OpenVLA:
             trace.setdefault("logits", []).append(lg.clone())
         if uniforms is None:
             ops.token_select(lg, 0, self.c["tok_vocab"], out_tok=tokens[i], out_logit=sel[i])
+            if lp is not None:
+                ops.token_logprob(lg, 0, self.c["tok_vocab"], tokens[i], out=lp)
         elif filt is not None:
             ops.token_sample(lg, self.action_lo, self.action_hi, uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
-                             out_tok=tokens[i], out_logit=sel[i], out_kept=self.kept_sel[:N])
+                             out_tok=tokens[i], out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=lp)
         else:
             ops.token_select(lg, self.action_lo, self.action_hi, uniform=uniforms[i], temperature=temperature, out_tok=tokens[i],
                              out_logit=sel[i])
+            if lp is not None:
+                ops.token_logprob(lg, self.action_lo, self.action_hi, tokens[i], temperature=temperature, out=lp)
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

@@ -566,17 +566,20 @@ def token_select(logits, lo, hi, uniform=None, temperature=1.0, out_tok=None, ou
     return tok, lg
 
 
-def token_sample(logits, lo, hi, uniform, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logit=None, out_kept=None):
+def token_sample(logits, lo, hi, uniform, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logit=None, out_kept=None,
+                 out_logprob=None):
     """Filtered inverse-CDF sampling over columns [lo, hi) of fp32 logits [rows, >= hi] (cover_token_sample: temperature, then top-k
     with ties kept, then top-p, then the pick with the host-supplied uniform fp32 [rows] in [0, 1)); hi - lo up to 2^20.
     Returns (token int64 [rows], its raw logit fp32 [rows], size of the kept set int32 [rows]); out_tok / out_logit / out_kept
-    (contiguous, [rows]) are written in place of fresh tensors, as in token_select. Deterministic, one launch, recordable."""
+    (contiguous, [rows]) are written in place of fresh tensors, as in token_select. Deterministic, one launch, recordable.
+    out_logprob fp32 [rows] (contiguous): also filled with the log-probability of each pick under the distribution it was drawn from
+    (cover_token_sample_scored; the pick, its logit and the kept count are the plain call's, bit for bit)."""
     if uniform is None:
         raise L.CoverError("token_sample needs uniforms (greedy selection is token_select)")
     if not temperature > 0 or not top_p > 0 or top_k < 0 or hi <= lo or lo < 0:
         raise L.CoverError(f"token_sample: temperature > 0, top_p > 0, top_k >= 0 and 0 <= lo < hi are required "
                            f"(got temperature={temperature}, top_k={top_k}, top_p={top_p}, lo={lo}, hi={hi})")
-    _chk_dev(logits, uniform, out_tok, out_logit, out_kept)
+    _chk_dev(logits, uniform, out_tok, out_logit, out_kept, out_logprob)
     rows = logits.shape[0]
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and hi <= logits.shape[1]
     tok = torch.empty(rows, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
@@ -585,12 +588,40 @@ def token_sample(logits, lo, hi, uniform, temperature=1.0, top_k=0, top_p=1.0, o
     assert tok.dtype == torch.int64 and lg.dtype == torch.float32 and kept.dtype == torch.int32
     assert tok.is_contiguous() and lg.is_contiguous() and kept.is_contiguous() and tok.numel() == rows == lg.numel() == kept.numel()
     assert uniform.is_contiguous() and uniform.dtype == torch.float32 and uniform.numel() == rows
-    a = L.TokenSampleArgs()
+    a = L.TokenSampleArgs() if out_logprob is None else L.TokenSampleScoredArgs()
     a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
     a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), temperature, int(top_k), top_p
     a.token_out, a.logit_out, a.kept_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr()
-    L.check(L.lib().cover_token_sample(C.byref(a), _stream()), "token_sample")
+    if out_logprob is None:
+        L.check(L.lib().cover_token_sample(C.byref(a), _stream()), "token_sample")
+    else:
+        assert out_logprob.dtype == torch.float32 and out_logprob.is_contiguous() and out_logprob.numel() == rows
+        a.logprob_out = out_logprob.data_ptr()
+        L.check(L.lib().cover_token_sample_scored(C.byref(a), _stream()), "token_sample_scored")
     return tok, lg, kept
+
+
+def token_logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, out=None, out_kept=None):
+    """Log-probability fp32 [rows] of tokens int64 [rows] under the distribution token_sample draws from with the same parameters
+    over columns [lo, hi) (cover_token_logprob: softmax of logits / temperature over the set top-k and top-p keep): -inf for a token
+    that is filtered out or lies outside [lo, hi) (a pad id). out fp32 [rows] / out_kept int32 [rows] (contiguous) are written in
+    place. Deterministic, one launch, recordable; on token_sample's own picks it equals that call's out_logprob bit for bit."""
+    if not temperature > 0 or not top_p > 0 or top_k < 0 or hi <= lo or lo < 0:
+        raise L.CoverError(f"token_logprob: temperature > 0, top_p > 0, top_k >= 0 and 0 <= lo < hi are required "
+                           f"(got temperature={temperature}, top_k={top_k}, top_p={top_p}, lo={lo}, hi={hi})")
+    _chk_dev(logits, tokens, out, out_kept)
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and hi <= logits.shape[1]
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() == rows
+    lp = torch.empty(rows, dtype=torch.float32, device=logits.device) if out is None else out
+    assert lp.dtype == torch.float32 and lp.is_contiguous() and lp.numel() == rows
+    assert out_kept is None or (out_kept.dtype == torch.int32 and out_kept.is_contiguous() and out_kept.numel() == rows)
+    a = L.TokenLogprobArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.temperature, a.top_k, a.top_p = temperature, int(top_k), top_p
+    a.token, a.logprob_out, a.kept_out = tokens.data_ptr(), lp.data_ptr(), _ptr(out_kept)
+    L.check(L.lib().cover_token_logprob(C.byref(a), _stream()), "token_logprob")
+    return lp
 
 
 def score_select(it, act, group_size):

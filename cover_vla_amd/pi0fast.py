@@ -72,14 +72,18 @@ class PI0FASTTokens:
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0) -> torch.Tensor:
+                        top_p: float = 1.0, return_logprobs: bool = False):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
         (what `generate(do_sample=False)` returns after the prompt). force_tokens (tests): teacher-force the fed-back tokens.
         uniforms fp32 [B, max_new_tokens] in [0, 1) on the device: sample instead (`generate(do_sample=True, temperature, top_k,
         top_p)`: ops.token_sample over the vocabulary, column i drives step i); every row is decoded on its own, rows that share
-        frames and prompt diverge with their uniforms. None = greedy; temperature / top_k / top_p are then unused."""
+        frames and prompt diverge with their uniforms. None = greedy; temperature / top_k / top_p are then unused.
+        return_logprobs: returns (tokens, logprobs fp32 [B, max_new_tokens]): the log-probability of each step's own pick under the
+        distribution it came from (sampled: temperature, top_k, top_p over the vocabulary; greedy: temperature 1, unfiltered). Steps
+        at which a row emits `pad_token_id` because it has finished, and steps the early stop skips, carry 0.0: a row sum is the
+        sequence log-probability. The default launches exactly what it launched without the argument."""
         dev, c = self.dev, self.c
         u_t = None
         if uniforms is not None:
@@ -98,8 +102,11 @@ class PI0FASTTokens:
                 first, inv = first[order], rank[inv.reshape(-1)]
                 fi = torch.from_numpy(np.ascontiguousarray(first)).to(dev)
                 sub_out = self.generate_tokens([im[fi] for im in images], [m[fi] for m in img_masks], tokens[fi], pad_mask[fi],
-                                               max_new_tokens, eos_token_id, pad_token_id, None, trace)
-                return sub_out[torch.from_numpy(np.ascontiguousarray(inv.reshape(-1))).to(dev)]
+                                               max_new_tokens, eos_token_id, pad_token_id, None, trace, return_logprobs=return_logprobs)
+                back = torch.from_numpy(np.ascontiguousarray(inv.reshape(-1))).to(dev)
+                if return_logprobs:
+                    return sub_out[0][back], sub_out[1][back]
+                return sub_out[back]
         B, L = tokens.shape
         if B > self.max_batch or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
             raise ValueError("batch / prompt length / new tokens / cameras exceed the sizes this model was built for")
@@ -129,6 +136,8 @@ class PI0FASTTokens:
         ops.copy_rows(xf, h, B, D, last, None)
         out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
+        lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
+        lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
         logits = torch.empty(B, self.lm_head.N, dtype=torch.float32, device=dev)
         head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
 
@@ -139,11 +148,15 @@ class PI0FASTTokens:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
             if u_t is None:
                 t, _ = ops.token_select(lg, 0, c["vocab"])                            # greedy over the vocabulary
+                if lp is not None:
+                    ops.token_logprob(lg, 0, c["vocab"], t, out=lp)
             else:
-                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p)
+                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p, out_logprob=lp)
                 if trace is not None:
                     trace.setdefault("picks", []).append(t.clone())
                     trace.setdefault("kept", []).append(kept)
+            if lp is not None:
+                lps[:, i].copy_(torch.where(done, torch.zeros_like(lp), lp))          # a finished row's pad is not a choice: 0
             if force_tokens is not None:
                 t = force_tokens[:, i].to(dev)
             t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
@@ -165,6 +178,8 @@ class PI0FASTTokens:
                               write_t_off=i - 1)
             self.lm.forward(xd, [g], final_norm=False)
             pick(xd, i)
+        if return_logprobs:
+            return out, lps
         return out
 
 
@@ -187,6 +202,7 @@ class PI0FASTConfig:
     top_k: int = 0
     top_p: float = 1.0
     sample_seed: Optional[int] = None
+    return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
 
 
 class PI0FASTPolicy:
@@ -202,6 +218,7 @@ class PI0FASTPolicy:
         self.pad_token_id = paligemma_tokenizer.pad_token_id if hasattr(paligemma_tokenizer, "pad_token_id") else paligemma_tokenizer.eos_token_id
         # the source of randomness of sampled decoding: a host generator seeded ONCE, so a seed and an observation sequence fix the actions
         self._gen = None if config.sample_seed is None else torch.Generator().manual_seed(int(config.sample_seed))
+        self.last_sequence_logprobs = None        # fp32 [B] on the device, set by a generation that ran with config.return_logprobs
         self.reset()
 
     def reset(self):
@@ -269,13 +286,17 @@ class PI0FASTPolicy:
                 images.append(img.to(dev))
             ids, mask = self.create_input_tokens(state, batch["task"])
             B = ids.shape[0]
-            sampling = {}
+            sampling = dict(return_logprobs=True) if self.config.return_logprobs else {}
             if self._gen is not None:
                 u = torch.rand(B, self.config.max_decoding_steps, generator=self._gen, dtype=torch.float32)
-                sampling = dict(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)
+                sampling.update(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)
             toks = self.model.generate_tokens(images, [torch.ones(B, dtype=torch.bool, device=dev) for _ in images], ids.to(dev), mask.to(dev),
                                               self.config.max_decoding_steps, eos_token_id=self.paligemma_tokenizer.eos_token_id,
                                               pad_token_id=self.pad_token_id, **sampling)
+            if self.config.return_logprobs:
+                from .host import sequence_logprob
+                toks, lps = toks
+                self.last_sequence_logprobs = sequence_logprob(lps)
             actions = self.extract_actions(toks.cpu(), self.config.chunk_size, self.config.action_dim)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
             actions = self._unnormalize_action(actions.to(torch.float32))

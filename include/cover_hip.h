@@ -426,6 +426,50 @@ typedef struct cover_token_sample_args {
 } cover_token_sample_args;
 int cover_token_sample(const cover_token_sample_args* args, void* stream);
 
+/* Per-token log-probabilities under the distribution cover_token_sample draws from (what Hugging Face's
+ * compute_transition_scores gives on the processed scores: the warpers set filtered logits to -inf before the softmax).
+ * Per row, over columns [lo, hi) with the parameters and steps of cover_token_sample:
+ *   x_i   = (l_i - m) / temperature,  m = max l_i over [lo, hi)
+ *   KEPT  = the set steps 2-3 keep (top-k with ties, then top-p); all of [lo, hi) with both filters off
+ *   lp(t) = x_t - log( sum_{i in KEPT} exp(x_i) )     if t is in KEPT
+ *         = -inf                                      if t is in [lo, hi) but not in KEPT, or t is outside [lo, hi)
+ * The sampler and the scorer share one implementation of KEPT (csrc/sample.hip), so membership means the same in both. The sum is
+ * the exact integer Q43 mass of the kept set; x_t is the fp32 exponent of the weights; the logarithm and the difference are
+ * taken in double once per row and rounded to fp32 once. No floating-point sum over columns: the value cannot depend on a
+ * summation order, a row position or a launch. Error against exact arithmetic on the fp32 logits:
+ * 5.1e-6 + 2^-23 |x_t| + 2^-24 |lp| (tests/logprob_ref.py derives it).
+ *
+ * cover_token_sample_scored: cover_token_sample (the same pick, logit_out and kept_out, bit for bit) plus
+ * logprob_out[row] = lp(pick). The same single launch, except with both filters off and hi - lo <= 4096: cover_token_select
+ * makes that pick and keeps no mass, so its picks are scored by a second small launch (cover_token_logprob's kernel). */
+typedef struct cover_token_sample_scored_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    const float* uniform;   /* [rows] in [0,1), required */
+    float temperature;
+    int top_k;              /* 0 = off */
+    float top_p;            /* >= 1 = off */
+    int64_t* token_out;     /* [rows] */
+    float* logit_out;       /* [rows] selected raw logit (optional) */
+    int* kept_out;          /* [rows] size of the kept set (optional) */
+    float* logprob_out;     /* [rows] lp(pick), required */
+} cover_token_sample_scored_args;
+int cover_token_sample_scored(const cover_token_sample_scored_args* args, void* stream);
+
+/* Scores given tokens (teacher-forced sequences, greedy picks): logprob_out[row] = lp(token[row]). No uniform, no pick. A token
+ * outside [lo, hi) (a pad id, a negative id) yields -inf and reads nothing. One block per row, one launch, no workspace:
+ * recordable into a hipGraph; hi - lo <= 2^20, any lo / ld. On the scored sampler's own picks the result is that call's
+ * logprob_out, bit for bit. */
+typedef struct cover_token_logprob_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    float temperature;
+    int top_k;              /* 0 = off */
+    float top_p;            /* >= 1 = off */
+    const int64_t* token;   /* [rows] */
+    float* logprob_out;     /* [rows] */
+    int* kept_out;          /* [rows] size of the kept set (optional) */
+} cover_token_logprob_args;
+int cover_token_logprob(const cover_token_logprob_args* args, void* stream);
+
 /* K20: fuse + score + grouped arg-max (efficient_ensemble_merged.py:404-448). it: [n_members][512] image-text
  * embeddings (unit rows), act: [n_members][N][512]; scores_out [N]; result_out int32 [4] =
  * {global_idx, group_idx, idx_in_group, 0}; best_out float [2] = {max_score, best_group_mean}. First index wins ties

@@ -2,7 +2,8 @@
 five (temperature, top_k, top_p) settings of tests/sampling_ref.py, next to the greedy pick (token_argmax_wide_k) and the lm_head GEMM
 of the same decode step (40 x 2048 bf16 times the 257 152 x 2048 tied embedding). Rows are shaped like a language model's (randn
 plus 40 boosted columns); FLAT=1 adds i.i.d. Gaussian rows, where the top-p cut falls into the tail and the kernel takes one
-pass over the row per digit.
+pass over the row per digit. Every setting is timed three ways: the plain sampler, the scored sampler (out_logprob: the same launch with
+one logarithm and one store per row more) and ops.token_logprob on the picks just made (the same passes without the pick).
     python tools/bench_token_sample.py                  event-timed microseconds per launch, one JSON line
     rocprofv3 --kernel-trace --stats -d D -o ts -- python tools/bench_token_sample.py
     python tools/bench_token_sample.py --from-db D/.../ts_results.db      per-setting averages from that trace (dispatch order)"""
@@ -23,9 +24,10 @@ def from_db(path):
     cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
     ncol = "name" if "name" in cols else "kernel_name"
     rows = cur.execute(f"select {ncol}, start, end from kernels order by start").fetchall()
-    smp = [(e - s) / 1e3 for n, s, e in rows if "token_sample_k" in n]
+    # dispatch order: per setting REPS plain (token_sample_k<false>), REPS scored (token_sample_k<true>), REPS token_logprob_k
+    smp = [(e - s) / 1e3 for n, s, e in rows if "token_sample_k" in n or "token_logprob_k" in n]
     out = {}
-    labels = [f"T={t} k={k} p={p}" for t, k, p in SETTINGS] + [f"flat T={t} k={k} p={p}" for t, k, p in SETTINGS]
+    labels = [f"{tag}T={t} k={k} p={p}{col}" for tag in ("", "flat ") for t, k, p in SETTINGS for col in ("", " scored", " logprob")]
     for i in range(0, len(smp) - REPS + 1, REPS):
         grp = smp[i:i + REPS][2:]                                       # the first two launches of a setting warm it up
         out[labels[i // REPS]] = round(sum(grp) / len(grp), 2)
@@ -53,6 +55,7 @@ def main():
     tok = torch.empty(ROWS, dtype=torch.int64, device=dev)
     lg = torch.empty(ROWS, dtype=torch.float32, device=dev)
     kept = torch.empty(ROWS, dtype=torch.int32, device=dev)
+    lp = torch.empty(ROWS, dtype=torch.float32, device=dev)
 
     def timed(fn):
         for _ in range(2):
@@ -70,6 +73,10 @@ def main():
         for t, k, p in SETTINGS:
             res[f"{tag}T={t} k={k} p={p}"] = timed(lambda: ops.token_sample(xd, 0, V, u, temperature=t, top_k=k, top_p=p, out_tok=tok,
                                                                               out_logit=lg, out_kept=kept))
+            res[f"{tag}T={t} k={k} p={p} scored"] = timed(lambda: ops.token_sample(xd, 0, V, u, temperature=t, top_k=k, top_p=p, out_tok=tok,
+                                                                                     out_logit=lg, out_kept=kept, out_logprob=lp))
+            res[f"{tag}T={t} k={k} p={p} logprob"] = timed(lambda: ops.token_logprob(xd, 0, V, tok, temperature=t, top_k=k, top_p=p, out=lp,
+                                                                                       out_kept=kept))
             res[f"{tag}T={t} k={k} p={p} median kept"] = int(kept.median())
     res["greedy token_select (token_argmax_wide_k)"] = timed(lambda: ops.token_select(inputs[0][1], 0, V, out_tok=tok, out_logit=lg))
     w = (0.02 * torch.randn(V, K, generator=g)).to(torch.bfloat16).to(dev)
