@@ -266,6 +266,12 @@ int cover_token_logprob(const cover_token_logprob_args* a, void* stream) {
            "token_logprob (token and logprob_out required, temperature > 0, top_p > 0, top_k >= 0, 0 < hi - lo <= 2^20)");
     return COVER_OK;
 }
+int cover_decode_feedback(const cover_decode_feedback_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_decode_feedback: null args");
+    HIPCHK(launch_decode_feedback(a, ST(stream)),
+           "decode_feedback (pick, done and tok_out required, lp and lp_out together, x_out needs a 16-byte aligned table, dim % 8 == 0, ldo % 8 == 0, vocab > 0)");
+    return COVER_OK;
+}
 int cover_score_select(const cover_score_select_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_score_select: null args");
     HIPCHK(launch_score_select(a, ST(stream)), "score_select (N % group_size == 0, fused_*_out required)");
@@ -805,7 +811,7 @@ size_t cover_sizeof(const char* n) {
 #define SZ(T) if (!strcmp(n, #T)) return sizeof(T)
     SZ(cover_gemm_epi); SZ(cover_kv_segment); SZ(cover_attn_args); SZ(cover_rope_args); SZ(cover_patchify_args);
     SZ(cover_gemm_f32_args); SZ(cover_mha_f32_args); SZ(cover_token_select_args); SZ(cover_token_sample_args); SZ(cover_score_select_args);
-    SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args);
+    SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_decode_feedback_args);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
 #undef SZ

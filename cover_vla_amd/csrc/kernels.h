@@ -46,6 +46,7 @@ hipError_t launch_rope_kv_write(const cover_rope_args* a, hipStream_t st);
 hipError_t launch_rope_kv_write_pair(const cover_rope_args* a0, const cover_rope_args* a1, hipStream_t st);
 hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids, int n, float scale, bf16_t* out,
                                int ldo, hipStream_t st);
+hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st);
 hipError_t launch_patchify(const cover_patchify_args* a, hipStream_t st);
 hipError_t launch_copy_rows_bf16(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int rows, int cols,
                                  const int* src_row_idx, const int* dst_row_idx, hipStream_t st);

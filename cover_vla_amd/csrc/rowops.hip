@@ -375,25 +375,68 @@ hipError_t launch_rope_kv_write(const cover_rope_args* a, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------
 // gathers / copies / casts
 // ---------------------------------------------------------------------------------------------------
+// one table row -> one bf16 row of bf16(table[id][:] * scale), 16 bytes per lane (NULLABLE and src NULL: a zero row)
+template <bool NULLABLE>
+__device__ __forceinline__ void embed_row(const bf16_t* __restrict__ src, int dim, float scale, bf16_t* __restrict__ out, size_t off) {
+    for (int c = threadIdx.x; c < (dim >> 3); c += blockDim.x) {
+        float v[8];
+        if (!NULLABLE || src) {
+            load_row8<false>(src, (size_t)c * 8, v);
+            if (scale != 1.0f) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] *= scale;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        }
+        store_row8(out, off + c * 8, v);
+    }
+}
 __global__ void embed_gather_k(const bf16_t* __restrict__ table, int dim, const int64_t* __restrict__ ids, float scale,
                                bf16_t* __restrict__ out, int ldo) {
     const int i = blockIdx.x;
-    const bf16_t* src = table + (size_t)ids[i] * dim;
-    for (int c = threadIdx.x; c < (dim >> 3); c += blockDim.x) {
-        float v[8];
-        load_row8<false>(src, (size_t)c * 8, v);
-        if (scale != 1.0f) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] *= scale;
-        }
-        store_row8(out, (size_t)i * ldo + c * 8, v);
-    }
+    embed_row<false>(table + (size_t)ids[i] * dim, dim, scale, out, (size_t)i * ldo);
 }
 hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids, int n, float scale, bf16_t* out, int ldo,
                                hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (dim % 8) return hipErrorInvalidValue;
     hipLaunchKernelGGL(embed_gather_k, dim3(n), dim3(128), 0, st, table, dim, ids, scale, out, ldo);
+    return hipGetLastError();
+}
+
+// The per-step bookkeeping of an autoregressive decode loop in one launch (cover_decode_feedback): one block per candidate row.
+// Thread 0 settles the row's token (forced token, pad after EOS), stores it and the step's log-probability, updates the row's done
+// byte and the step's live counter; the block then gathers the token's embedding row for the next step (embed_gather_k's arithmetic).
+// A row touches only its own done byte, token and log-probability cells: no ordering between blocks is needed.
+__global__ __launch_bounds__(128) void decode_feedback_k(cover_decode_feedback_args a) {
+    __shared__ long long s_tok;
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const bool was_done = a.done[b] != 0;
+        long long t = a.force ? a.force[(long long)b * a.force_stride] : a.pick[b];
+        if (a.lp_out) a.lp_out[(long long)b * a.ld_lp] = was_done ? 0.0f : a.lp[b];
+        if (was_done) t = a.pad;
+        a.tok_out[(long long)b * a.ld_tok] = t;
+        const bool now_done = was_done || t == a.eos;
+        a.done[b] = now_done ? 1 : 0;
+        if (a.live && !now_done) atomicAdd(a.live, 1);
+        s_tok = t;
+    }
+    if (!a.x_out) return;
+    __syncthreads();
+    const long long t = s_tok;
+    const bf16_t* src = (t >= 0 && t < a.vocab) ? (const bf16_t*)a.table + (size_t)t * a.dim : nullptr;   // outside the table: a zero row, nothing read
+    embed_row<true>(src, a.dim, a.scale, (bf16_t*)a.x_out, (size_t)b * a.ldo);
+}
+hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st) {
+    if (a->rows < 0 || !a->pick || !a->done || !a->tok_out || (a->lp == nullptr) != (a->lp_out == nullptr)) return hipErrorInvalidValue;
+    if (a->x_out && (!a->table || a->dim <= 0 || (a->dim & 7) || a->vocab <= 0 || a->ldo < a->dim || (a->ldo & 7) ||
+                     ((((uintptr_t)a->table) | ((uintptr_t)a->x_out)) & 15)))
+        return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(decode_feedback_k, dim3(a->rows), dim3(128), 0, st, *a);
     return hipGetLastError();
 }
 

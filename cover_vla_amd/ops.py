@@ -624,6 +624,47 @@ def token_logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, o
     return lp
 
 
+def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp_out=None, table=None, scale=1.0, x_out=None,
+                    live=None):
+    """The bookkeeping between two decode steps in one launch (cover_decode_feedback). Per row b: t = force[b] if given else pick[b];
+    lp_out[b, step] = 0.0 if done[b] else lp[b]; t = pad if done[b]; tok_out[b, step] = t; done[b] |= t == eos;
+    x_out[b] = bf16(table[t] * scale) (embed_gather on the emitted ids; an id outside the table gives a zero row); live[step] += not done[b].
+    pick int64 [rows] contiguous; done torch.bool [rows], in place; tok_out int64 / lp_out fp32 [rows, >= step + 1] with unit column
+    stride (any row stride); force int64 [rows] with any stride (a column view); live int32 [>= step + 1], zeroed by the caller.
+    x_out bf16 [rows, dim] or None (no embedding: the last step). Recordable, no workspace. Returns x_out."""
+    _chk_dev(pick, done, tok_out, force, lp, lp_out, table, x_out, live)
+    rows = pick.numel()
+    assert pick.dtype == torch.int64 and pick.is_contiguous() and done.dtype == torch.bool and done.is_contiguous() and done.numel() == rows
+    assert tok_out.dtype == torch.int64 and tok_out.dim() == 2 and tok_out.shape[0] == rows and 0 <= step < tok_out.shape[1]
+    assert tok_out.stride(1) == 1 or tok_out.shape[1] == 1
+    if (lp is None) != (lp_out is None):
+        raise L.CoverError("decode_feedback: lp and lp_out are given together")
+    a = L.DecodeFeedbackArgs()
+    a.pick, a.done, a.rows = pick.data_ptr(), done.data_ptr(), rows
+    a.tok_out, a.ld_tok = tok_out.data_ptr() + 8 * step, tok_out.stride(0)
+    a.eos, a.pad = int(eos), int(pad)
+    if force is not None:
+        assert force.dtype == torch.int64 and force.dim() == 1 and force.numel() == rows
+        a.force, a.force_stride = force.data_ptr(), force.stride(0)
+    if lp is not None:
+        assert lp.dtype == torch.float32 and lp.is_contiguous() and lp.numel() == rows
+        assert lp_out.dtype == torch.float32 and lp_out.dim() == 2 and lp_out.shape[0] == rows and step < lp_out.shape[1]
+        assert lp_out.stride(1) == 1 or lp_out.shape[1] == 1
+        a.lp, a.lp_out, a.ld_lp = lp.data_ptr(), lp_out.data_ptr() + 4 * step, lp_out.stride(0)
+    if x_out is not None:
+        if table is None:
+            raise L.CoverError("decode_feedback: x_out needs the embedding table")
+        assert table.dtype == torch.bfloat16 and table.dim() == 2 and table.is_contiguous()
+        assert x_out.dtype == torch.bfloat16 and x_out.dim() == 2 and x_out.shape == (rows, table.shape[1]) and x_out.stride(1) == 1
+        a.table, a.vocab, a.dim, a.scale = table.data_ptr(), table.shape[0], table.shape[1], scale
+        a.x_out, a.ldo = x_out.data_ptr(), x_out.stride(0)
+    if live is not None:
+        assert live.dtype == torch.int32 and live.dim() == 1 and live.is_contiguous() and step < live.numel()
+        a.live = live.data_ptr() + 4 * step
+    L.check(L.lib().cover_decode_feedback(C.byref(a), _stream()), "decode_feedback")
+    return x_out
+
+
 def score_select(it, act, group_size):
     """it [members, dim], act [members, N, dim] fp32 -> (scores [N], result int32[4], best f32[2], fused_it, fused_act)."""
     _chk_dev(it, act)

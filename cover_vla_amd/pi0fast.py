@@ -21,6 +21,7 @@ vocabulary. Work that is done once instead of per step: the prefix (image + prom
 """
 from __future__ import annotations
 
+import os
 from collections import deque
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -32,11 +33,30 @@ from . import ops
 from .models import BF, Decoder, KvGeometry, VitTower
 
 
+def prefix_groups(tokens, pad_mask) -> Tuple[np.ndarray, np.ndarray]:
+    """Rows of (tokens [B, L], pad_mask [B, L]) (integers; tensors or arrays) that are equal in both form a group; groups are numbered
+    in order of first occurrence. Returns (first int64 [P]: the first row of each group, slot int64 [B]: the group of each row), so
+    tokens[first][slot] == tokens. Host index bookkeeping on B x 2L integers: the ordering rule of greedy de-duplication below."""
+    tk = tokens.detach().cpu().numpy() if isinstance(tokens, torch.Tensor) else np.asarray(tokens)
+    pm = pad_mask.detach().cpu().numpy() if isinstance(pad_mask, torch.Tensor) else np.asarray(pad_mask)
+    if tk.ndim != 2 or pm.shape != tk.shape:
+        raise ValueError("prefix_groups: tokens and pad_mask must be [B, L] of one shape")
+    key = np.concatenate([tk.astype(np.int64), pm.astype(np.int64)], axis=1)
+    _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first)                             # distinct rows in order of first occurrence
+    rank = np.empty_like(order)
+    rank[order] = np.arange(order.shape[0])
+    return first[order].astype(np.int64), rank[inv.reshape(-1)].astype(np.int64)
+
+
 class PI0FASTTokens:
     def __init__(self, sd: Dict[str, torch.Tensor], c: dict, *, device="cuda:0", max_batch=64, max_prompt=96, max_new_tokens=256,
-                 n_cams=1):
+                 n_cams=1, max_prompts=None):
         """sd: neutral state dict with vision.*, projector.*, lm.* (cover_vla_amd.synth.pi0_state layout / loader output);
-        c: size dict (lm_dim, lm_mlp, layers, Hq, Hkv, D, vocab, vit_*, patch, image)."""
+        c: size dict (lm_dim, lm_mlp, layers, Hq, Hkv, D, vocab, vit_*, patch, image).
+        max_prompts: slots of the prefix region of the KV cache (None = max_batch). `generate_tokens(share_prefix=True)` holds one
+        prefix per DISTINCT (frames, prompt): a model for 8 prompts x 5 samples is built with max_prompts=8, max_batch=40. Calls
+        without share_prefix prefill every row, so they need max_prompts >= their batch."""
         self.c, self.dev = dict(c), torch.device(device)
         dev = self.dev
         sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
@@ -48,7 +68,8 @@ class PI0FASTTokens:
         self.embed = sd["lm.embed_tokens.weight"].to(BF).contiguous().to(dev)
         self.lm_head = ops.pack_linear(self.embed)                       # tied (PaliGemma ties lm_head to embed_tokens)
         self.Tp_cap = self.n_img * n_cams + max_prompt
-        geom = KvGeometry(c["Hkv"], c["D"], [max_batch, max_batch], [self.Tp_cap, max_new_tokens])
+        self.max_prompts = max_batch if max_prompts is None else int(max_prompts)
+        geom = KvGeometry(c["Hkv"], c["D"], [self.max_prompts, max_batch], [self.Tp_cap, max_new_tokens])
         self.lm = Decoder(sub("lm."), dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"],
                           act="gelu_tanh", norm="gemma", eps=1e-6, rope="hf", n_pos=self.Tp_cap + max_new_tokens + 8, device=device,
                           cache=geom)
@@ -72,7 +93,7 @@ class PI0FASTTokens:
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0, return_logprobs: bool = False):
+                        top_p: float = 1.0, return_logprobs: bool = False, share_prefix: bool = False):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -83,13 +104,20 @@ class PI0FASTTokens:
         return_logprobs: returns (tokens, logprobs fp32 [B, max_new_tokens]): the log-probability of each step's own pick under the
         distribution it came from (sampled: temperature, top_k, top_p over the vocabulary; greedy: temperature 1, unfiltered). Steps
         at which a row emits `pad_token_id` because it has finished, and steps the early stop skips, carry 0.0: a row sum is the
-        sequence log-probability. The default launches exactly what it launched without the argument."""
+        sequence log-probability. The default launches exactly what it launched without the argument.
+        share_prefix: rows with equal (frames, prompt) share ONE prefilled prefix (greedy, sampled and forced alike): the prefill
+        runs over the P distinct rows, every candidate row still decodes and picks on its own, reading its prompt's prefix K/V through
+        the segment's slot_of_batch. Needs P <= max_prompts and B <= max_batch. GEMM row counts differ from the per-row path, so
+        results agree with it to bf16 rounding (bit for bit when P == B). The default launches exactly what it launched before."""
         dev, c = self.dev, self.c
         u_t = None
         if uniforms is not None:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
                 raise ValueError("uniforms must be [B, max_new_tokens]")
             u_t = uniforms.to(device=dev, dtype=torch.float32).t().contiguous()       # step-major: row i is step i's [B]
+        if share_prefix:
+            return self._generate_shared(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens,
+                                         trace, u_t, temperature, top_k, top_p, return_logprobs)
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
         if uniforms is None and force_tokens is None and tokens.shape[0] > 1 and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images):
@@ -108,7 +136,7 @@ class PI0FASTTokens:
                     return sub_out[0][back], sub_out[1][back]
                 return sub_out[back]
         B, L = tokens.shape
-        if B > self.max_batch or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
+        if B > min(self.max_batch, self.max_prompts) or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
             raise ValueError("batch / prompt length / new tokens / cameras exceed the sizes this model was built for")
         if len(images) != len(img_masks) or not all(bool(m.to(torch.bool).all()) for m in img_masks):
             raise NotImplementedError("masked-out cameras are not supported on the pi0-FAST path (prepare_images :494-536 "
@@ -182,6 +210,110 @@ class PI0FASTTokens:
             return out, lps
         return out
 
+    def _generate_shared(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace,
+                         u_t, temperature, top_k, top_p, return_logprobs):
+        """generate_tokens(share_prefix=True): region 0 of the cache holds the P distinct prefixes (slots 0..P-1, in order of first
+        occurrence), region 1 every candidate's own tokens (slot b). Between two steps one ops.decode_feedback launch settles the
+        token, the log-probability, the done flag, the live count and the next step's embedding row; COVER_FAST_FEEDBACK=0 (read
+        per call) issues the torch statements of the per-row path instead."""
+        dev, c = self.dev, self.c
+        B, L = tokens.shape
+        if B > self.max_batch or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
+            raise ValueError("batch / prompt length / new tokens / cameras exceed the sizes this model was built for")
+        if len(images) != len(img_masks) or not all(bool(m.to(torch.bool).all()) for m in img_masks):
+            raise NotImplementedError("masked-out cameras are not supported on the pi0-FAST path (prepare_images :494-536 "
+                                      "produces all-True masks for present cameras)")
+        same = [bool(torch.equal(im[:1].expand_as(im), im)) for im in images]      # the evaluation driver's case: one frame for all rows
+        if all(same):
+            first, slot = prefix_groups(tokens, pad_mask)
+        else:                                                                      # rows with frames of their own: every row is its own group
+            first = slot = np.arange(B, dtype=np.int64)
+        P = int(first.shape[0])
+        if P > self.max_prompts:
+            raise ValueError(f"{P} distinct prompts exceed the {self.max_prompts} prefix slots this model was built for (max_prompts)")
+        fi = torch.from_numpy(np.ascontiguousarray(first)).to(dev)
+        slot_t = torch.from_numpy(np.ascontiguousarray(slot)).to(device=dev, dtype=torch.int32)
+        D = c["lm_dim"]
+        n_img_all = self.n_img * len(images)
+        Tp = n_img_all + L
+        # ---- prefill of the P distinct rows
+        x = torch.empty(P, Tp, D, dtype=BF, device=dev)
+        for ci, im in enumerate(images):
+            tok = self._image_tokens(im[:1] if same[ci] else im[fi])
+            x[:, ci * self.n_img:(ci + 1) * self.n_img].copy_(tok.expand(P, -1, -1) if same[ci] else tok)   # device copy, no arithmetic
+        te = ops.embed_gather(self.embed, tokens[fi].reshape(-1).contiguous(), self.emb_scale)
+        x[:, n_img_all:].copy_(te.view(P, L, D))
+        plen = (n_img_all + pad_mask.to(torch.int32).sum(dim=1)).to(torch.int32).contiguous()          # [B] valid keys: a contiguous prefix
+        plen_p = plen[fi].contiguous()
+        pos = (1 + torch.arange(Tp, dtype=torch.int32, device=dev))[None].expand(P, Tp).contiguous()   # 1-indexed (:352-354)
+        g0 = self.lm.group(P, Tp, pos.view(-1), [dict(region=0, length=Tp, len_of_batch=plen_p)], 0)
+        xf = x.view(P * Tp, D)
+        if trace is not None:
+            trace["prefix_embs"] = x.clone()
+            trace["prefill_rows"], trace["prefix_slots"] = P * Tp, P
+        self.lm.forward(xf, [g0], final_norm=False)
+        # ---- first new token: the last valid position of every candidate's prompt
+        last = (slot_t * Tp + plen - 1).to(torch.int32)
+        h = torch.empty(B, D, dtype=BF, device=dev)
+        ops.copy_rows(xf, h, B, D, last, None)
+        if trace is not None:
+            trace["first_hidden"] = h.clone()
+        fused = os.environ.get("COVER_FAST_FEEDBACK", "1") != "0"
+        out = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int64, device=dev)   # steps the early stop skips: pad
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        live = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev) if fused else None   # live[i]: rows still running after step i
+        lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
+        lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
+        force = force_tokens.to(device=dev, dtype=torch.int64) if force_tokens is not None else None
+        logits = torch.empty(B, self.lm_head.N, dtype=torch.float32, device=dev)
+        head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
+        tsel = torch.empty(B, dtype=torch.int64, device=dev)
+        xd = torch.empty(B, D, dtype=BF, device=dev)
+
+        def pick(hidden, i):
+            hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
+            lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
+            if trace is not None:
+                trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
+            if u_t is None:
+                t, _ = ops.token_select(lg, 0, c["vocab"], out_tok=tsel)             # greedy over the vocabulary
+                if lp is not None:
+                    ops.token_logprob(lg, 0, c["vocab"], t, out=lp)
+            else:
+                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p, out_tok=tsel,
+                                              out_logprob=lp)
+                if trace is not None:
+                    trace.setdefault("picks", []).append(t.clone())
+                    trace.setdefault("kept", []).append(kept)
+            if fused:      # the statements of the else branch and the next step's embed_gather, one launch
+                ops.decode_feedback(t, done, out, i, eos_token_id, pad_token_id, force=None if force is None else force[:, i], lp=lp,
+                                    lp_out=lps, table=self.embed, scale=self.emb_scale, x_out=xd if i + 1 < max_new_tokens else None,
+                                    live=live)
+                return
+            if lp is not None:
+                lps[:, i].copy_(torch.where(done, torch.zeros_like(lp), lp))          # a finished row's pad is not a choice: 0
+            if force is not None:
+                t = force[:, i]
+            t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
+            out[:, i].copy_(t)
+            done.logical_or_(t == eos_token_id)
+
+        pick(h, 0)
+        seg0 = dict(region=0, length=Tp, len_of_batch=plen, slot_of_batch=slot_t)    # its prompt's prefix, wherever that was prefilled
+        for i in range(1, max_new_tokens):
+            if force is None and self.eos_check_every > 0 and i % self.eos_check_every == 0:
+                if (int(live[i - 1]) == 0) if fused else bool(done.all()):           # one 4-byte (1-byte) D2H
+                    break
+            if not fused:
+                ops.embed_gather(self.embed, out[:, i - 1].contiguous(), self.emb_scale, out=xd)
+            pos_i = (plen + i).to(torch.int32).contiguous()                           # token i-1 sits at 1-indexed position plen + i
+            g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
+            self.lm.forward(xd, [g], final_norm=False)
+            pick(xd, i)
+        if return_logprobs:
+            return out, lps
+        return out
+
 
 @dataclass
 class PI0FASTConfig:
@@ -203,6 +335,7 @@ class PI0FASTConfig:
     top_p: float = 1.0
     sample_seed: Optional[int] = None
     return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
+    share_prefix: bool = False          # candidates with equal frames and prompt share one prefill (generate_tokens(share_prefix=True))
 
 
 class PI0FASTPolicy:
@@ -287,6 +420,8 @@ class PI0FASTPolicy:
             ids, mask = self.create_input_tokens(state, batch["task"])
             B = ids.shape[0]
             sampling = dict(return_logprobs=True) if self.config.return_logprobs else {}
+            if self.config.share_prefix:
+                sampling.update(share_prefix=True)
             if self._gen is not None:
                 u = torch.rand(B, self.config.max_decoding_steps, generator=self._gen, dtype=torch.float32)
                 sampling.update(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)

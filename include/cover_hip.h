@@ -470,6 +470,30 @@ typedef struct cover_token_logprob_args {
 } cover_token_logprob_args;
 int cover_token_logprob(const cover_token_logprob_args* args, void* stream);
 
+/* The bookkeeping between two steps of an autoregressive decode loop (pi0-FAST generate_tokens), one launch, one block per
+ * candidate row, no workspace: recordable into a hipGraph. Per row b, in this order:
+ *   t = force ? force[b * force_stride] : pick[b];  lp_out[b * ld_lp] = done[b] ? 0.0f : lp[b];  if (done[b]) t = pad;
+ *   tok_out[b * ld_tok] = t;  done[b] |= (t == eos);  x_out[b][:] = bf16(table[t][:] * scale);  *live += !done[b];
+ * tok_out / lp_out point at this step's column of row-major [rows, ld] buffers. x_out is cover_embed_gather's arithmetic on the
+ * emitted ids, except that an id outside [0, vocab) yields a zero row and reads nothing. live (optional) is this step's counter of
+ * rows still running, zeroed by the caller: reading it back replaces a reduction over done. */
+typedef struct cover_decode_feedback_args {
+    const int64_t* pick;      /* [rows] this step's selection */
+    const int64_t* force;     /* [rows] with element stride force_stride: teacher-forced tokens (optional) */
+    long long force_stride;
+    const float* lp;          /* [rows] log-probability of pick (optional, together with lp_out) */
+    float* lp_out; long long ld_lp;
+    uint8_t* done;            /* [rows] bytes 0 / 1, updated in place */
+    int64_t* tok_out; long long ld_tok;
+    long long eos, pad;
+    const void* table;        /* bf16 [vocab][dim], 16-byte aligned (required with x_out) */
+    int vocab, dim; float scale;
+    void* x_out; int ldo;     /* bf16 [rows][ldo] next step's input rows; NULL: none (the last step) */
+    int* live;                /* optional */
+    int rows;
+} cover_decode_feedback_args;
+int cover_decode_feedback(const cover_decode_feedback_args* args, void* stream);
+
 /* K20: fuse + score + grouped arg-max (efficient_ensemble_merged.py:404-448). it: [n_members][512] image-text
  * embeddings (unit rows), act: [n_members][N][512]; scores_out [N]; result_out int32 [4] =
  * {global_idx, group_idx, idx_in_group, 0}; best_out float [2] = {max_score, best_group_mean}. First index wins ties
