@@ -226,6 +226,7 @@ SYMBOLS = {
     "cover_cast_f32_to_bf16": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "cover_cast_bf16_to_f32": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
     "cover_gemm_f32": (c_i, [_P(GemmF32Args), c_p]),
+    "cover_gemm_f32_plan": (c_i, [_P(GemmF32Args), _P(c_i)]),
     "cover_layernorm_f32": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),
     "cover_layernorm_f32_grouped": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_ll, c_p]),
     "cover_softmax_rows_f32": (c_i, [c_p, c_i, c_i, c_i, c_f, c_p]),

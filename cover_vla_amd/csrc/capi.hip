@@ -191,6 +191,14 @@ int cover_gemm_f32(const cover_gemm_f32_args* a, void* stream) {
     HIPCHK(launch_gemm_f32(a, ST(stream)), "gemm_f32");
     return COVER_OK;
 }
+int cover_gemm_f32_plan(const cover_gemm_f32_args* a, int* plan) {
+    if (!a || !plan) return fail(COVER_EINVAL, "cover_gemm_f32_plan: null pointer");
+    if (!a->A || !a->B || !a->C) return fail(COVER_EINVAL, "cover_gemm_f32: null pointer");
+    int deep = 0;
+    plan[0] = (a->M <= 0 || a->N <= 0) ? -1 : gemm_f32_plan(a, &deep);
+    plan[1] = deep;
+    return COVER_OK;
+}
 int cover_layernorm_f32(const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int rows, int dim,
                         float eps, void* stream) {
     HIPCHK(launch_layernorm_f32(x, ldx, w, b, y, ldy, rows, dim, eps, ST(stream)), "layernorm_f32");

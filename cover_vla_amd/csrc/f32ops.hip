@@ -183,8 +183,10 @@ __global__ __launch_bounds__(256) void gemm_f32_direct_k(cover_gemm_f32_args a) 
     }
 }
 
-hipError_t launch_gemm_f32(const cover_gemm_f32_args* a, hipStream_t st) {
-    if (a->M <= 0 || a->N <= 0) return hipSuccess;
+// Which instantiation launch_gemm_f32 runs for these arguments (pure host code: pointers are only checked for alignment). *deep = the UNR = 8
+// window of the direct kernel (experiment knob, off by default).
+int gemm_f32_plan(const cover_gemm_f32_args* a, int* deep) {
+    if (deep) *deep = 0;
     const int nb = a->batch > 0 ? a->batch : 1;
     const long long blocks64 = (long long)((a->N + 63) / 64) * ((a->M + 63) / 64) * nb;
     const bool k_contig = a->a_k_stride == 1 && a->b_k_stride == 1 && (a->K & 15) == 0 && a->K >= 64 && (a->a_row_stride & 3) == 0 &&
@@ -198,28 +200,42 @@ hipError_t launch_gemm_f32(const cover_gemm_f32_args* a, hipStream_t st) {
         // experiment knob COVER_F32_UNR=8: eight steps in flight for K >= 512. Measured (round 4): the verifier tail got SLOWER, 0.563 vs 0.525 ms
         // -- the deeper window costs occupancy (126 registers: 3 waves per SIMD instead of 6) and these grids live off occupancy. Default 4.
         static const char* unr_env = getenv("COVER_F32_UNR");
-        const bool deep = a->K >= 512 && unr_env && unr_env[0] == '8';
-        if (a->M <= 16) {
+        if (deep) *deep = (a->K >= 512 && unr_env && unr_env[0] == '8') ? 1 : 0;
+        return a->M <= 16 ? COVER_GEMM_F32_DIRECT_FM1 : COVER_GEMM_F32_DIRECT_FM2;
+    }
+    if (blocks64 >= 256) return COVER_GEMM_F32_TILE64;
+    // small grids are bound by one global-load latency per k-step: a 128-deep step puts 4x the loads in flight
+    return a->K >= 256 ? COVER_GEMM_F32_TILE32_K128 : COVER_GEMM_F32_TILE32_K32;
+}
+
+hipError_t launch_gemm_f32(const cover_gemm_f32_args* a, hipStream_t st) {
+    if (a->M <= 0 || a->N <= 0) return hipSuccess;
+    const int nb = a->batch > 0 ? a->batch : 1;
+    int deep = 0;
+    const int plan = gemm_f32_plan(a, &deep);
+    const dim3 grid32((a->N + 31) / 32, (a->M + 31) / 32, nb);
+    switch (plan) {
+        case COVER_GEMM_F32_DIRECT_FM1: {
             dim3 grid((a->N + 31) / 32, (a->M + 15) / 16, nb);
             if (deep) hipLaunchKernelGGL((gemm_f32_direct_k<1, 8>), grid, dim3(256), 0, st, *a);
             else hipLaunchKernelGGL((gemm_f32_direct_k<1, 4>), grid, dim3(256), 0, st, *a);
-        } else {
-            dim3 grid((a->N + 31) / 32, (a->M + 31) / 32, nb);
-            if (deep) hipLaunchKernelGGL((gemm_f32_direct_k<2, 8>), grid, dim3(256), 0, st, *a);
-            else hipLaunchKernelGGL((gemm_f32_direct_k<2, 4>), grid, dim3(256), 0, st, *a);
+            break;
         }
-        return hipGetLastError();
-    }
-    if (blocks64 >= 256) {
-        dim3 grid((a->N + 63) / 64, (a->M + 63) / 64, nb);
-        hipLaunchKernelGGL((gemm_f32_k<64, 64, 32>), grid, dim3(256), 0, st, *a);
-    } else if (a->K >= 256) {
-        // small grids are bound by one global-load latency per k-step: a 128-deep step puts 4x the loads in flight
-        dim3 grid((a->N + 31) / 32, (a->M + 31) / 32, nb);
-        hipLaunchKernelGGL((gemm_f32_k<32, 32, 128>), grid, dim3(256), 0, st, *a);
-    } else {
-        dim3 grid((a->N + 31) / 32, (a->M + 31) / 32, nb);
-        hipLaunchKernelGGL((gemm_f32_k<32, 32, 32>), grid, dim3(256), 0, st, *a);
+        case COVER_GEMM_F32_DIRECT_FM2:
+            if (deep) hipLaunchKernelGGL((gemm_f32_direct_k<2, 8>), grid32, dim3(256), 0, st, *a);
+            else hipLaunchKernelGGL((gemm_f32_direct_k<2, 4>), grid32, dim3(256), 0, st, *a);
+            break;
+        case COVER_GEMM_F32_TILE64: {
+            dim3 grid((a->N + 63) / 64, (a->M + 63) / 64, nb);
+            hipLaunchKernelGGL((gemm_f32_k<64, 64, 32>), grid, dim3(256), 0, st, *a);
+            break;
+        }
+        case COVER_GEMM_F32_TILE32_K128:
+            hipLaunchKernelGGL((gemm_f32_k<32, 32, 128>), grid32, dim3(256), 0, st, *a);
+            break;
+        default:
+            hipLaunchKernelGGL((gemm_f32_k<32, 32, 32>), grid32, dim3(256), 0, st, *a);
+            break;
     }
     return hipGetLastError();
 }
@@ -349,7 +365,7 @@ hipError_t launch_act_f32(const float* x, int ldx, float* y, int ldy, int rows, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// small multi-head attention: one block per (batch, head); Tq*Tk <= 4096, Dh <= 128
+// small multi-head attention: one block per (batch, head); Tq*Tk <= 8192 (the score tile lives in LDS: 32 KiB)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mha_f32_k(cover_mha_f32_args a) {
     extern __shared__ float sc[];  // [Tq][Tk]

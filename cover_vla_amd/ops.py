@@ -444,7 +444,7 @@ def gemm_f32(a, b, *, bias=None, act="none", alpha=1.0, residual=None, out=None,
 
 
 def gemm_f32_raw(a_ptr, a_rs, a_ks, b_ptr, b_rs, b_ks, c_ptr, c_rs, M, N, K, *, bias=None, residual_ptr=None, ld_res=0,
-                 act="none", alpha=1.0, batch=1, a_bs=0, b_bs=0, c_bs=0):
+                 act="none", alpha=1.0, batch=1, a_bs=0, b_bs=0, c_bs=0, bias_bs=0):
     """Pointer-level form of gemm_f32 (element strides) for strided / batched views that torch cannot express."""
     g = L.GemmF32Args()
     g.A, g.a_row_stride, g.a_k_stride = a_ptr, a_rs, a_ks
@@ -453,7 +453,25 @@ def gemm_f32_raw(a_ptr, a_rs, a_ks, b_ptr, b_rs, b_ks, c_ptr, c_rs, M, N, K, *, 
     g.bias, g.residual, g.ld_residual = _ptr(bias), residual_ptr, ld_res
     g.M, g.N, g.K, g.act, g.alpha = M, N, K, ACT[act], alpha
     g.batch, g.a_batch_stride, g.b_batch_stride, g.c_batch_stride = batch, a_bs, b_bs, c_bs
+    g.bias_batch_stride = bias_bs
     L.check(L.lib().cover_gemm_f32(C.byref(g), _stream()), "gemm_f32")
+
+
+GEMM_F32_PLANS = ("DIRECT_FM1", "DIRECT_FM2", "TILE64", "TILE32_K128", "TILE32_K32")   # COVER_GEMM_F32_* (include/cover_hip.h)
+
+
+def gemm_f32_plan(a_ptr, a_rs, a_ks, b_ptr, b_rs, b_ks, c_ptr, c_rs, M, N, K, *, batch=1, a_bs=0, b_bs=0, c_bs=0):
+    """(plan name, deep) cover_gemm_f32 would take for these pointers (only null / alignment matter) and element strides: no launch,
+    no GPU. plan name is one of GEMM_F32_PLANS (None: nothing to launch), deep = the COVER_F32_UNR=8 window."""
+    g = L.GemmF32Args()
+    g.A, g.a_row_stride, g.a_k_stride = a_ptr, a_rs, a_ks
+    g.B, g.b_row_stride, g.b_k_stride = b_ptr, b_rs, b_ks
+    g.C, g.c_row_stride = c_ptr, c_rs
+    g.M, g.N, g.K, g.alpha = M, N, K, 1.0
+    g.batch, g.a_batch_stride, g.b_batch_stride, g.c_batch_stride = batch, a_bs, b_bs, c_bs
+    out = (C.c_int * 2)()
+    L.check(L.lib().cover_gemm_f32_plan(C.byref(g), out), "gemm_f32_plan")
+    return (GEMM_F32_PLANS[out[0]] if out[0] >= 0 else None), bool(out[1])
 
 
 def layernorm_f32(x, w, b, eps=1e-5, out=None):

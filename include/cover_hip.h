@@ -333,7 +333,8 @@ typedef struct cover_gemm_f32_args {
     const float* B; long long b_row_stride, b_k_stride;   /* B[n,k]  (nn.Linear weight: row stride K, k stride 1) */
     float* C; long long c_row_stride;                     /* C[m,n] */
     const float* bias;      /* [N] or NULL */
-    const float* residual;  /* [M, c_row_stride-compatible ld_residual] or NULL: C = residual + val */
+    const float* residual;  /* [M, ld_residual] or NULL: C = residual + val. Row stride ld_residual (need not equal c_row_stride); batch z
+                             * reads residual + z * c_batch_stride: the residual shares C's BATCH stride (it may be C itself) */
     long long ld_residual;
     int M, N, K;
     int act;
@@ -342,6 +343,18 @@ typedef struct cover_gemm_f32_args {
     long long bias_batch_stride; /* bias of batch z = bias + z * bias_batch_stride (0: one bias for every batch) */
 } cover_gemm_f32_args;
 int cover_gemm_f32(const cover_gemm_f32_args* args, void* stream);
+/* The kernel cover_gemm_f32 would run for these arguments, without launching anything and without a GPU (test / audit hook; pointers
+ * are only checked for null and alignment, never dereferenced). plan[0] = COVER_GEMM_F32_* (-1: M or N <= 0, nothing to launch),
+ * plan[1] = 1 when the direct kernel takes the eight-step window of the COVER_F32_UNR=8 experiment knob. Reads COVER_F32_DIRECT_MAX per
+ * call, as cover_gemm_f32 does. */
+enum {
+    COVER_GEMM_F32_DIRECT_FM1 = 0,   /* gemm_f32_direct_k<1>: k-contiguous aligned operands, K % 16 == 0, K >= 64, M <= 16 */
+    COVER_GEMM_F32_DIRECT_FM2 = 1,   /* gemm_f32_direct_k<2>: the same, M > 16 */
+    COVER_GEMM_F32_TILE64 = 2,       /* gemm_f32_k<64,64,32>: any strides, >= 256 blocks of 64x64 */
+    COVER_GEMM_F32_TILE32_K128 = 3,  /* gemm_f32_k<32,32,128>: small grid, K >= 256 */
+    COVER_GEMM_F32_TILE32_K32 = 4    /* gemm_f32_k<32,32,32> */
+};
+int cover_gemm_f32_plan(const cover_gemm_f32_args* args, int plan[2]);
 int cover_layernorm_f32(const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int rows, int dim,
                         float eps, void* stream);
 /* the same over stacked row groups with their own affine parameters (ensemble members batched into one launch):
