@@ -285,9 +285,9 @@ class OpenVLA:
                 cur.wait_stream(self._cap)
             else:
                 st["graph"].launch()
-                if return_logprobs:
-                    return st["tokens"].t().contiguous(), st["sel"].t().contiguous(), st["lps"].t().contiguous()
-                return st["tokens"].t().contiguous(), st["sel"].t().contiguous()
+            if return_logprobs:                                         # the eager pass before a capture has filled the same buffers
+                return st["tokens"].t().contiguous(), st["sel"].t().contiguous(), st["lps"].t().contiguous()
+            return st["tokens"].t().contiguous(), st["sel"].t().contiguous()
         # step-major buffers: row i of each is contiguous, so the kernels of step i read / write them in place (no per-step slice copies)
         tokens = torch.empty(self.n_gen, N, dtype=torch.int64, device=dev)
         sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
@@ -320,38 +320,23 @@ class OpenVLA:
             mark(f"decode{i}")
 
     def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None):
-        """filt: None = today's ops.token_select calls; (top_k, top_p) = ops.token_sample over the same columns. lps fp32 [n_gen, N] or
-        None: row i receives the log-probability of step i's picks (the scored sampler where ops.token_sample picks, one
-        ops.token_logprob launch behind an ops.token_select pick)."""
-        lp = None if lps is None else lps[i]
+        """Norm, head GEMM, one ops.pick_token. filt: None = the unfiltered ops.token_select pick; (top_k, top_p) = ops.token_sample over
+        the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks."""
         N = h.shape[0]
+        u = None if uniforms is None else uniforms[i]
+        # out_kept: written by the filtered pick (ops.token_sample) only
+        out = dict(out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=None if lps is None else lps[i])
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
         if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
-            if filt is None:
-                t, _ = ops.token_select(lg, 0, self.c["n_bins"], uniform=uniforms[i], temperature=temperature, out_logit=sel[i])
-                if lp is not None:
-                    ops.token_logprob(lg, 0, self.c["n_bins"], t, temperature=temperature, out=lp)
-            else:
-                t, _, _ = ops.token_sample(lg, 0, self.c["n_bins"], uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
-                                           out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=lp)
+            t, _, _ = ops.pick_token(lg, 0, self.c["n_bins"], u, temperature, filt, **out)
             torch.add(t, self.action_lo, out=tokens[i])
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
         if trace is not None and "events" not in trace:
             trace.setdefault("logits", []).append(lg.clone())
-        if uniforms is None:
-            ops.token_select(lg, 0, self.c["tok_vocab"], out_tok=tokens[i], out_logit=sel[i])
-            if lp is not None:
-                ops.token_logprob(lg, 0, self.c["tok_vocab"], tokens[i], out=lp)
-        elif filt is not None:
-            ops.token_sample(lg, self.action_lo, self.action_hi, uniforms[i], temperature=temperature, top_k=filt[0], top_p=filt[1],
-                             out_tok=tokens[i], out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=lp)
-        else:
-            ops.token_select(lg, self.action_lo, self.action_hi, uniform=uniforms[i], temperature=temperature, out_tok=tokens[i],
-                             out_logit=sel[i])
-            if lp is not None:
-                ops.token_logprob(lg, self.action_lo, self.action_hi, tokens[i], temperature=temperature, out=lp)
+        lo, hi = (0, self.c["tok_vocab"]) if uniforms is None else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
+        ops.pick_token(lg, lo, hi, u, temperature, filt, out_tok=tokens[i], **out)
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

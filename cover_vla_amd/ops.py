@@ -642,6 +642,23 @@ def token_logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, o
     return lp
 
 
+def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None):
+    """One decode step's pick over columns [lo, hi), the three-way choice of every token head. Returns (token, its logit, kept or None).
+    uniform None: greedy token_select (temperature and filt are unused); uniform with filt None: token_select's unfiltered inverse-CDF
+    sample; uniform with filt = (top_k, top_p): ONE token_sample call, whose kept count is returned. out_logprob fp32 [rows]: filled with
+    the log-probability of each pick under the distribution it came from (greedy: temperature 1, unfiltered), by token_sample itself or
+    by one token_logprob launch behind token_select. The out_* rows are the wrappers' own; no arithmetic or allocation of its own."""
+    if uniform is not None and filt is not None:
+        return token_sample(logits, lo, hi, uniform, temperature=temperature, top_k=filt[0], top_p=filt[1], out_tok=out_tok,
+                            out_logit=out_logit, out_kept=out_kept, out_logprob=out_logprob)
+    if uniform is None:
+        temperature = 1.0
+    tok, lg = token_select(logits, lo, hi, uniform=uniform, temperature=temperature, out_tok=out_tok, out_logit=out_logit)
+    if out_logprob is not None:
+        token_logprob(logits, lo, hi, tok, temperature=temperature, out=out_logprob)
+    return tok, lg, None
+
+
 def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp_out=None, table=None, scale=1.0, x_out=None,
                     live=None):
     """The bookkeeping between two decode steps in one launch (cover_decode_feedback). Per row b: t = force[b] if given else pick[b];

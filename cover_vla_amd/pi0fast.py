@@ -109,162 +109,95 @@ class PI0FASTTokens:
         runs over the P distinct rows, every candidate row still decodes and picks on its own, reading its prompt's prefix K/V through
         the segment's slot_of_batch. Needs P <= max_prompts and B <= max_batch. GEMM row counts differ from the per-row path, so
         results agree with it to bf16 rounding (bit for bit when P == B). The default launches exactly what it launched before."""
-        dev, c = self.dev, self.c
+        dev = self.dev
         u_t = None
         if uniforms is not None:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
                 raise ValueError("uniforms must be [B, max_new_tokens]")
             u_t = uniforms.to(device=dev, dtype=torch.float32).t().contiguous()       # step-major: row i is step i's [B]
-        if share_prefix:
-            return self._generate_shared(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens,
-                                         trace, u_t, temperature, top_k, top_p, return_logprobs)
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
-        if uniforms is None and force_tokens is None and tokens.shape[0] > 1 and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images):
-            key = torch.cat([tokens, pad_mask.to(tokens.dtype)], dim=1).cpu().numpy()
-            _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        if (not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
+                and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images)):
+            first, slot = prefix_groups(tokens, pad_mask)
             if first.shape[0] < tokens.shape[0]:
-                order = np.argsort(first)                     # distinct rows in order of first occurrence
-                rank = np.empty_like(order)
-                rank[order] = np.arange(order.shape[0])
-                first, inv = first[order], rank[inv.reshape(-1)]
-                fi = torch.from_numpy(np.ascontiguousarray(first)).to(dev)
+                fi = torch.from_numpy(first).to(dev)
                 sub_out = self.generate_tokens([im[fi] for im in images], [m[fi] for m in img_masks], tokens[fi], pad_mask[fi],
                                                max_new_tokens, eos_token_id, pad_token_id, None, trace, return_logprobs=return_logprobs)
-                back = torch.from_numpy(np.ascontiguousarray(inv.reshape(-1))).to(dev)
+                back = torch.from_numpy(slot).to(dev)
                 if return_logprobs:
                     return sub_out[0][back], sub_out[1][back]
                 return sub_out[back]
-        B, L = tokens.shape
-        if B > min(self.max_batch, self.max_prompts) or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
-            raise ValueError("batch / prompt length / new tokens / cameras exceed the sizes this model was built for")
-        if len(images) != len(img_masks) or not all(bool(m.to(torch.bool).all()) for m in img_masks):
-            raise NotImplementedError("masked-out cameras are not supported on the pi0-FAST path (prepare_images :494-536 "
-                                      "produces all-True masks for present cameras)")
-        D = c["lm_dim"]
-        n_img_all = self.n_img * len(images)
-        Tp = n_img_all + L
-        x = torch.empty(B, Tp, D, dtype=BF, device=dev)
-        for ci, im in enumerate(images):
-            same = bool(torch.equal(im[:1].expand_as(im), im))            # the evaluation driver's case: one frame for all rows
-            tok = self._image_tokens(im[:1] if same else im)
-            x[:, ci * self.n_img:(ci + 1) * self.n_img].copy_(tok.expand(B, -1, -1) if same else tok)   # device copy, no arithmetic
-        te = ops.embed_gather(self.embed, tokens.reshape(-1).contiguous(), self.emb_scale)
-        x[:, n_img_all:].copy_(te.view(B, L, D))
-        if trace is not None:
-            trace["prefix_embs"] = x.clone()
-        plen = (n_img_all + pad_mask.to(torch.int32).sum(dim=1)).to(torch.int32).contiguous()          # valid keys: a contiguous prefix
-        pos = (1 + torch.arange(Tp, dtype=torch.int32, device=dev))[None].expand(B, Tp).contiguous()   # 1-indexed (:352-354)
-        g0 = self.lm.group(B, Tp, pos.view(-1), [dict(region=0, length=Tp, len_of_batch=plen)], 0)
-        xf = x.view(B * Tp, D)
-        self.lm.forward(xf, [g0], final_norm=False)
-        # ---- first new token: the last valid prefix position of every row
-        last = (torch.arange(B, device=dev, dtype=torch.int32) * Tp + plen - 1).to(torch.int32)
-        h = torch.empty(B, D, dtype=BF, device=dev)
-        ops.copy_rows(xf, h, B, D, last, None)
-        out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
-        lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
-        lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
-        logits = torch.empty(B, self.lm_head.N, dtype=torch.float32, device=dev)
-        head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
+        return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
+                              temperature, top_k, top_p, return_logprobs, share_prefix)
 
-        def pick(hidden, i):
-            hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
-            lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
-            if trace is not None:
-                trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
-            if u_t is None:
-                t, _ = ops.token_select(lg, 0, c["vocab"])                            # greedy over the vocabulary
-                if lp is not None:
-                    ops.token_logprob(lg, 0, c["vocab"], t, out=lp)
-            else:
-                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p, out_logprob=lp)
-                if trace is not None:
-                    trace.setdefault("picks", []).append(t.clone())
-                    trace.setdefault("kept", []).append(kept)
-            if lp is not None:
-                lps[:, i].copy_(torch.where(done, torch.zeros_like(lp), lp))          # a finished row's pad is not a choice: 0
-            if force_tokens is not None:
-                t = force_tokens[:, i].to(dev)
-            t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
-            out[:, i].copy_(t)
-            done.logical_or_(t == eos_token_id)
-
-        pick(h, 0)
-        xd = torch.empty(B, D, dtype=BF, device=dev)
-        # HF generate(do_sample=False) stops once every row has emitted EOS (modeling_pi0fast.py:861-946 runs it with
-        # max_new_tokens = max_decoding_steps = 256, a FAST sequence is a few dozen tokens): `done.all()` is read back every
-        # `eos_check_every` steps (one 1-byte D2H) and the rest of `out` is the pad the finished rows would have emitted anyway
-        out[:, 1:].fill_(pad_token_id)
-        for i in range(1, max_new_tokens):
-            if force_tokens is None and self.eos_check_every > 0 and i % self.eos_check_every == 0 and bool(done.all()):
-                break
-            ops.embed_gather(self.embed, out[:, i - 1].contiguous(), self.emb_scale, out=xd)
-            pos_i = (plen + i).to(torch.int32).contiguous()                           # token i-1 sits at 1-indexed position plen + i
-            g = self.lm.group(B, 1, pos_i, [dict(region=0, length=Tp, len_of_batch=plen), dict(region=1, length=i)], 1,
-                              write_t_off=i - 1)
-            self.lm.forward(xd, [g], final_norm=False)
-            pick(xd, i)
-        if return_logprobs:
-            return out, lps
-        return out
-
-    def _generate_shared(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace,
-                         u_t, temperature, top_k, top_p, return_logprobs):
-        """generate_tokens(share_prefix=True): region 0 of the cache holds the P distinct prefixes (slots 0..P-1, in order of first
-        occurrence), region 1 every candidate's own tokens (slot b). Between two steps one ops.decode_feedback launch settles the
-        token, the log-probability, the done flag, the live count and the next step's embedding row; COVER_FAST_FEEDBACK=0 (read
-        per call) issues the torch statements of the per-row path instead."""
+    def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
+                  temperature, top_k, top_p, return_logprobs, share):
+        """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
+        share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
+        `eos_check_every` steps, the `done.all()` read-back.
+        share True: the P distinct prefixes (slots 0..P-1, in order of first occurrence) are prefilled once and every row reads its
+        prompt's through segment 0's slot_of_batch; between two steps ONE ops.decode_feedback launch settles the token, the
+        log-probability, the done flag, the live count and the next step's embedding row. COVER_FAST_FEEDBACK=0 (read per call) issues
+        the torch statements of the other path instead."""
         dev, c = self.dev, self.c
         B, L = tokens.shape
-        if B > self.max_batch or L > self.max_prompt or max_new_tokens > self.max_new or len(images) > self.n_cams:
+        if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
+                or max_new_tokens > self.max_new or len(images) > self.n_cams):
             raise ValueError("batch / prompt length / new tokens / cameras exceed the sizes this model was built for")
         if len(images) != len(img_masks) or not all(bool(m.to(torch.bool).all()) for m in img_masks):
             raise NotImplementedError("masked-out cameras are not supported on the pi0-FAST path (prepare_images :494-536 "
                                       "produces all-True masks for present cameras)")
         same = [bool(torch.equal(im[:1].expand_as(im), im)) for im in images]      # the evaluation driver's case: one frame for all rows
-        if all(same):
-            first, slot = prefix_groups(tokens, pad_mask)
-        else:                                                                      # rows with frames of their own: every row is its own group
-            first = slot = np.arange(B, dtype=np.int64)
-        P = int(first.shape[0])
-        if P > self.max_prompts:
-            raise ValueError(f"{P} distinct prompts exceed the {self.max_prompts} prefix slots this model was built for (max_prompts)")
-        fi = torch.from_numpy(np.ascontiguousarray(first)).to(dev)
-        slot_t = torch.from_numpy(np.ascontiguousarray(slot)).to(device=dev, dtype=torch.int32)
+        P = B
+        take = lambda t: t                           # the rows that are prefilled: all of them, or (share) the first of each group
+        slot_t = torch.arange(B, device=dev, dtype=torch.int32)
+        if share:
+            first = slot = np.arange(B, dtype=np.int64)                              # rows with frames of their own: every row is its own group
+            if all(same):
+                first, slot = prefix_groups(tokens, pad_mask)
+            P = int(first.shape[0])
+            if P > self.max_prompts:
+                raise ValueError(f"{P} distinct prompts exceed the {self.max_prompts} prefix slots this model was built for (max_prompts)")
+            fi = torch.from_numpy(first).to(dev)
+            take = lambda t: t[fi]
+            slot_t = torch.from_numpy(slot).to(device=dev, dtype=torch.int32)
         D = c["lm_dim"]
         n_img_all = self.n_img * len(images)
         Tp = n_img_all + L
-        # ---- prefill of the P distinct rows
+        # ---- prefill of the P prefix rows
         x = torch.empty(P, Tp, D, dtype=BF, device=dev)
         for ci, im in enumerate(images):
-            tok = self._image_tokens(im[:1] if same[ci] else im[fi])
+            tok = self._image_tokens(im[:1] if same[ci] else take(im))
             x[:, ci * self.n_img:(ci + 1) * self.n_img].copy_(tok.expand(P, -1, -1) if same[ci] else tok)   # device copy, no arithmetic
-        te = ops.embed_gather(self.embed, tokens[fi].reshape(-1).contiguous(), self.emb_scale)
+        te = ops.embed_gather(self.embed, take(tokens).reshape(-1).contiguous(), self.emb_scale)
         x[:, n_img_all:].copy_(te.view(P, L, D))
-        plen = (n_img_all + pad_mask.to(torch.int32).sum(dim=1)).to(torch.int32).contiguous()          # [B] valid keys: a contiguous prefix
-        plen_p = plen[fi].contiguous()
-        pos = (1 + torch.arange(Tp, dtype=torch.int32, device=dev))[None].expand(P, Tp).contiguous()   # 1-indexed (:352-354)
-        g0 = self.lm.group(P, Tp, pos.view(-1), [dict(region=0, length=Tp, len_of_batch=plen_p)], 0)
-        xf = x.view(P * Tp, D)
         if trace is not None:
             trace["prefix_embs"] = x.clone()
             trace["prefill_rows"], trace["prefix_slots"] = P * Tp, P
+        plen = (n_img_all + pad_mask.to(torch.int32).sum(dim=1)).to(torch.int32).contiguous()          # [B] valid keys: a contiguous prefix
+        pos = (1 + torch.arange(Tp, dtype=torch.int32, device=dev))[None].expand(P, Tp).contiguous()   # 1-indexed (:352-354)
+        g0 = self.lm.group(P, Tp, pos.view(-1), [dict(region=0, length=Tp, len_of_batch=take(plen).contiguous())], 0)
+        xf = x.view(P * Tp, D)
         self.lm.forward(xf, [g0], final_norm=False)
-        # ---- first new token: the last valid position of every candidate's prompt
+        # ---- first new token: the last valid position of every row's prompt
         last = (slot_t * Tp + plen - 1).to(torch.int32)
         h = torch.empty(B, D, dtype=BF, device=dev)
         ops.copy_rows(xf, h, B, D, last, None)
         if trace is not None:
             trace["first_hidden"] = h.clone()
-        fused = os.environ.get("COVER_FAST_FEEDBACK", "1") != "0"
-        out = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int64, device=dev)   # steps the early stop skips: pad
+        fused = share and os.environ.get("COVER_FAST_FEEDBACK", "1") != "0"
+        # HF generate(do_sample=False) stops once every row has emitted EOS (modeling_pi0fast.py:861-946 runs it with
+        # max_new_tokens = max_decoding_steps = 256, a FAST sequence is a few dozen tokens): every `eos_check_every` steps `done.all()`
+        # (fused: live[i - 1]) is read back, and the rest of `out` is the pad the finished rows would have emitted anyway
+        out = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         live = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev) if fused else None   # live[i]: rows still running after step i
         lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
         lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
-        force = force_tokens.to(device=dev, dtype=torch.int64) if force_tokens is not None else None
+        force = force_tokens
+        if share and force is not None:
+            force = force.to(device=dev, dtype=torch.int64)                          # the per-row form moves one column per step
         logits = torch.empty(B, self.lm_head.N, dtype=torch.float32, device=dev)
         head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
         tsel = torch.empty(B, dtype=torch.int64, device=dev)
@@ -275,17 +208,13 @@ class PI0FASTTokens:
             lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
             if trace is not None:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
-            if u_t is None:
-                t, _ = ops.token_select(lg, 0, c["vocab"], out_tok=tsel)             # greedy over the vocabulary
-                if lp is not None:
-                    ops.token_logprob(lg, 0, c["vocab"], t, out=lp)
-            else:
-                t, _, kept = ops.token_sample(lg, 0, c["vocab"], u_t[i], temperature=temperature, top_k=top_k, top_p=top_p, out_tok=tsel,
-                                              out_logprob=lp)
-                if trace is not None:
-                    trace.setdefault("picks", []).append(t.clone())
-                    trace.setdefault("kept", []).append(kept)
-            if fused:      # the statements of the else branch and the next step's embed_gather, one launch
+            # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
+            t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
+                                        out_logprob=lp)
+            if u_t is not None and trace is not None:
+                trace.setdefault("picks", []).append(t.clone())
+                trace.setdefault("kept", []).append(kept)
+            if fused:      # the statements below and the next step's embed_gather, one launch
                 ops.decode_feedback(t, done, out, i, eos_token_id, pad_token_id, force=None if force is None else force[:, i], lp=lp,
                                     lp_out=lps, table=self.embed, scale=self.emb_scale, x_out=xd if i + 1 < max_new_tokens else None,
                                     live=live)
@@ -293,13 +222,15 @@ class PI0FASTTokens:
             if lp is not None:
                 lps[:, i].copy_(torch.where(done, torch.zeros_like(lp), lp))          # a finished row's pad is not a choice: 0
             if force is not None:
-                t = force[:, i]
+                t = force[:, i].to(dev)
             t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
             out[:, i].copy_(t)
             done.logical_or_(t == eos_token_id)
 
         pick(h, 0)
-        seg0 = dict(region=0, length=Tp, len_of_batch=plen, slot_of_batch=slot_t)    # its prompt's prefix, wherever that was prefilled
+        seg0 = dict(region=0, length=Tp, len_of_batch=plen)
+        if share:
+            seg0["slot_of_batch"] = slot_t                                           # its prompt's prefix, wherever that was prefilled
         for i in range(1, max_new_tokens):
             if force is None and self.eos_check_every > 0 and i % self.eos_check_every == 0:
                 if (int(live[i - 1]) == 0) if fused else bool(done.all()):           # one 4-byte (1-byte) D2H

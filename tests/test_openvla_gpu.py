@@ -252,6 +252,34 @@ def test_openvla_decode_graph_replay_equals_eager_loop(dev, own_kv, horizon):
     assert all(st["graph"] is not None for st in model._dec.values()) and len(model._dec) == 2      # sampled and greedy shapes
 
 
+def test_openvla_decode_graph_first_call_runs_the_body_twice(dev):
+    """A shape's first sample() runs _decode_body for the eager pass and for the recording and returns the static buffers the eager
+    pass filled; the second call replays (no _decode_body). Both return what the eager loop (decode_graph off) returns, bit for bit:
+    greedy, and sampled with return_logprobs."""
+    from cover_vla_amd.openvla import OpenVLA
+    c, sd, frame, toks, lens, u = _case(seed=13)
+    kw = dict(device="cuda:0", max_prompts=4, max_candidates=8, max_text=toks.shape[1])
+    eager = OpenVLA(sd, c, **kw)
+    eager.decode_graph = False
+    model = OpenVLA(sd, c, **kw)
+    assert model.decode_graph
+    inner, runs = model._decode_body, []
+    model._decode_body = lambda *a, **k: (runs.append(1), inner(*a, **k))[1]
+    f, tk, ln = frame.to(dev), toks.to(dev), lens.to(dev)
+    for skw in (dict(), dict(uniforms=u.to(dev), temperature=0.9, top_k=20, top_p=0.9, return_logprobs=True)):
+        first = model.sample(f, tk, ln, 2, **skw)
+        assert len(runs) == 2, "first call of a shape: one eager pass + one recorded pass"
+        second = model.sample(f, tk, ln, 2, **skw)
+        assert len(runs) == 2, "second call: replay only"
+        want = eager.sample(f, tk, ln, 2, **skw)
+        assert len(first) == len(second) == len(want) == (3 if skw else 2)
+        for a, b, w in zip(first, second, want):
+            assert a.dtype == w.dtype and torch.equal(a, b) and torch.equal(a, w)
+            if a.dtype == torch.float32:
+                assert torch.equal(a.view(torch.int32), w.view(torch.int32)) and torch.equal(b.view(torch.int32), w.view(torch.int32))
+        del runs[:]
+
+
 def test_openvla_decode_graph_survives_a_larger_prompt_batch(dev):
     """A decode graph captured for a small (P, Lt) holds the decoder workspace's device pointer. A later decision with more prompt rows
     (larger P x Lt prefill) must not move that workspace under it: the workspace is sized once for T0 + max_prompts x max_text rows

@@ -142,3 +142,60 @@ def test_generate_tokens_and_sample_signatures():
     assert p["top_k"].default == 0 and p["top_p"].default == 1.0
     cfg = PI0FASTConfig()
     assert (cfg.temperature, cfg.top_k, cfg.top_p, cfg.sample_seed) == (1.0, 0, 1.0, None)
+
+
+def test_pick_token_dispatch(monkeypatch):
+    """ops.pick_token issues the launches its callers issued, with their arguments and nothing else: greedy = token_select, then
+    token_logprob at temperature 1 unfiltered whatever temperature was passed; sampled unfiltered = token_select, then token_logprob
+    at the same temperature; sampled filtered = ONE token_sample that carries out_kept / out_logprob."""
+    import inspect
+    from cover_vla_amd import ops
+    calls = []
+    tok, lgt, kept, lpv = torch.zeros(2, dtype=torch.int64), torch.zeros(2), torch.zeros(2, dtype=torch.int32), torch.zeros(2)
+
+    def rec(name, uniform, temperature, top_k, top_p, **outs):
+        return (name, uniform is None, temperature, top_k, top_p, tuple(sorted(k for k, v in outs.items() if v is not None)))
+
+    def select(logits, lo, hi, uniform=None, temperature=1.0, out_tok=None, out_logit=None):
+        calls.append((lo, hi) + rec("token_select", uniform, temperature, None, None, out_tok=out_tok, out_logit=out_logit))
+        return tok, lgt
+
+    def sample(logits, lo, hi, uniform, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logit=None, out_kept=None, out_logprob=None):
+        calls.append((lo, hi) + rec("token_sample", uniform, temperature, top_k, top_p, out_tok=out_tok, out_logit=out_logit, out_kept=out_kept,
+                                    out_logprob=out_logprob))
+        return tok, lgt, kept
+
+    def logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, out=None, out_kept=None):
+        assert tokens is tok                                      # the pick that was just made
+        calls.append((lo, hi) + rec("token_logprob", None, temperature, top_k, top_p, out=out, out_kept=out_kept))
+        return out
+
+    fakes = dict(token_select=select, token_sample=sample, token_logprob=logprob)
+    for name, fn in inspect.getmembers(ops, inspect.isfunction):
+        if fn.__module__ == ops.__name__ and not name.startswith("_") and name != "pick_token":
+            monkeypatch.setattr(ops, name, fakes.get(name) or (lambda *a, _n=name, **k: calls.append(_n)))
+    lg, u = torch.zeros(2, 16), torch.zeros(2)
+    sel = lambda lo, hi, greedy, T, *outs: (lo, hi, "token_select", greedy, T, None, None, outs)
+    lpc = lambda lo, hi, T: (lo, hi, "token_logprob", True, T, 0, 1.0, ("out",))
+    for lo, hi in ((0, 16), (3, 11)):
+        for with_lp in (False, True):
+            lp = lpv if with_lp else None
+            # greedy: temperature and filt are ignored, the log-probability runs at temperature 1
+            for filt in (None, (5, 0.5)):
+                del calls[:]
+                r = ops.pick_token(lg, lo, hi, None, 0.7, filt, out_tok=tok, out_logit=lgt, out_kept=kept, out_logprob=lp)
+                assert r[0] is tok and r[1] is lgt and r[2] is None
+                assert calls == [sel(lo, hi, True, 1.0, "out_logit", "out_tok")] + ([lpc(lo, hi, 1.0)] if with_lp else [])
+            # sampled unfiltered
+            del calls[:]
+            r = ops.pick_token(lg, lo, hi, u, 0.7, None, out_logit=lgt, out_kept=kept, out_logprob=lp)
+            assert r[0] is tok and r[1] is lgt and r[2] is None
+            assert calls == [sel(lo, hi, False, 0.7, "out_logit")] + ([lpc(lo, hi, 0.7)] if with_lp else [])
+            # sampled filtered: one call, also with filters that filter nothing
+            for k, p in ((5, 0.5), (0, 1.0)):
+                del calls[:]
+                r = ops.pick_token(lg, lo, hi, u, 0.7, (k, p), out_tok=tok, out_kept=kept, out_logprob=lp)
+                assert r[0] is tok and r[1] is lgt and r[2] is kept
+                assert calls == [(lo, hi, "token_sample", False, 0.7, k, p, ("out_kept",) + (("out_logprob",) if with_lp else ()) + ("out_tok",))]
+    del calls[:]
+    assert ops.pick_token(lg, 0, 16)[2] is None and calls == [sel(0, 16, True, 1.0)]      # the defaults: greedy, fresh tensors

@@ -139,6 +139,56 @@ def test_unfiltered_narrow_range_is_token_select(dev):
         assert torch.equal(t0, t2) and torch.equal(l0.view(torch.int32), l2.view(torch.int32))
 
 
+def test_pick_token_equals_the_direct_calls(dev):
+    """ops.pick_token against the calls it stands for, bit for bit on tok, logit, kept and logprob: greedy, sampled unfiltered and
+    sampled filtered, with and without out_logprob, into fresh tensors and into rows of [steps, rows] buffers."""
+    rows, V, T, k, p = 5, 300, 0.8, 20, 0.9
+    g = torch.Generator().manual_seed(31)
+    lg = (torch.randn(rows, V, generator=g) * 3).to(dev)
+    u = torch.rand(rows, generator=g).to(dev)
+    bits = lambda t: t.view(torch.int32)
+    for lo, hi in ((0, V), (44, V)):
+        for mode in ("greedy", "unfiltered", "filtered"):
+            # the direct calls
+            if mode == "filtered":
+                w_lp = torch.empty(rows, dtype=torch.float32, device=dev)
+                w_tok, w_logit, w_kept = ops.token_sample(lg, lo, hi, u, temperature=T, top_k=k, top_p=p, out_logprob=w_lp)
+                plain = ops.token_sample(lg, lo, hi, u, temperature=T, top_k=k, top_p=p)
+                assert torch.equal(plain[0], w_tok) and torch.equal(plain[2], w_kept)
+            else:
+                kw = dict() if mode == "greedy" else dict(uniform=u, temperature=T)
+                w_tok, w_logit = ops.token_select(lg, lo, hi, **kw)
+                w_lp = ops.token_logprob(lg, lo, hi, w_tok, temperature=1.0 if mode == "greedy" else T)
+                w_kept = None
+            assert ((w_tok >= lo) & (w_tok < hi)).all() and torch.isfinite(w_lp).all()
+            args = (None, 1.7, (3, 0.2)) if mode == "greedy" else (u, T, (k, p) if mode == "filtered" else None)   # greedy ignores both
+            for with_lp in (False, True):
+                for prealloc in (False, True):
+                    out = {}
+                    if prealloc:
+                        bufs = dict(out_tok=torch.full((3, rows), -7, dtype=torch.int64, device=dev),
+                                    out_logit=torch.full((3, rows), 9.0, dtype=torch.float32, device=dev),
+                                    out_kept=torch.full((3, rows), -7, dtype=torch.int32, device=dev))
+                        out = {n: b[1] for n, b in bufs.items()}
+                    lp_buf = torch.full((3, rows), 9.0, dtype=torch.float32, device=dev)
+                    if with_lp:
+                        out["out_logprob"] = lp_buf[1]
+                    tok, logit, kept = ops.pick_token(lg, lo, hi, *args, **out)
+                    case = (lo, hi, mode, with_lp, prealloc)
+                    assert torch.equal(tok, w_tok) and torch.equal(bits(logit), bits(w_logit)), case
+                    assert (kept is None) == (mode != "filtered") and (kept is None or torch.equal(kept, w_kept)), case
+                    if with_lp:
+                        assert torch.equal(bits(lp_buf[1]), bits(w_lp)), case
+                    assert (lp_buf[0] == 9.0).all() and (lp_buf[2] == 9.0).all() and (with_lp or (lp_buf[1] == 9.0).all()), case
+                    if prealloc:
+                        assert tok.data_ptr() == out["out_tok"].data_ptr() and logit.data_ptr() == out["out_logit"].data_ptr()
+                        assert kept is None or kept.data_ptr() == out["out_kept"].data_ptr()
+                        for n, b in bufs.items():
+                            sentinel = 9.0 if n == "out_logit" else -7
+                            assert (b[0] == sentinel).all() and (b[2] == sentinel).all(), (case, n)
+                        assert mode == "filtered" or (bufs["out_kept"] == -7).all(), case   # only token_sample writes a kept count
+
+
 # ------------------------------------------------------------------------------------------------ 4. determinism
 def test_deterministic_across_launch_shapes_and_graph_replay(dev):
     V = R.WIDE_V
