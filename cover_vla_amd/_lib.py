@@ -124,6 +124,13 @@ class TokenLogprobArgs(C.Structure):
                 ("token", c_p), ("logprob_out", c_p), ("kept_out", c_p)]
 
 
+class TokenTopnArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i),
+                ("temperature", c_f), ("top_k", c_i), ("top_p", c_f), ("n", c_i),
+                ("token_out", c_p), ("ld_tok", c_ll), ("logprob_out", c_p), ("ld_lp", c_ll),
+                ("entropy_out", c_p), ("kept_out", c_p)]
+
+
 class DecodeFeedbackArgs(C.Structure):
     _fields_ = [("pick", c_p), ("force", c_p), ("force_stride", c_ll), ("lp", c_p), ("lp_out", c_p), ("ld_lp", c_ll),
                 ("done", c_p), ("tok_out", c_p), ("ld_tok", c_ll), ("eos", c_ll), ("pad", c_ll),
@@ -186,7 +193,7 @@ _STRUCTS = {
     "cover_rope_args": RopeArgs, "cover_patchify_args": PatchifyArgs, "cover_gemm_f32_args": GemmF32Args,
     "cover_mha_f32_args": MhaF32Args, "cover_token_select_args": TokenSelectArgs,
     "cover_token_sample_args": TokenSampleArgs, "cover_token_sample_scored_args": TokenSampleScoredArgs,
-    "cover_token_logprob_args": TokenLogprobArgs, "cover_decode_feedback_args": DecodeFeedbackArgs,
+    "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_score_select_args": ScoreSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
@@ -241,6 +248,7 @@ SYMBOLS = {
     "cover_token_sample": (c_i, [_P(TokenSampleArgs), c_p]),
     "cover_token_sample_scored": (c_i, [_P(TokenSampleScoredArgs), c_p]),
     "cover_token_logprob": (c_i, [_P(TokenLogprobArgs), c_p]),
+    "cover_token_topn": (c_i, [_P(TokenTopnArgs), c_p]),
     "cover_decode_feedback": (c_i, [_P(DecodeFeedbackArgs), c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),

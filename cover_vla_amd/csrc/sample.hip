@@ -20,6 +20,12 @@
 //   are compacted into LDS (in whatever order the atomics grant; every consumer is one of the order-independent integer
 //   reductions above) and the remaining digits run over that list instead of the row: a language model's row needs two or three
 //   passes over its 1 MB, a flat row (cut in the tail, huge k) falls back to one pass per digit.
+//   Top-n and entropy (token_topn_k): the ranks are one more radix selection, over the logit keys restricted to the kept set (count
+//   only), ties at the n-th rank cut by the index walk of the top-p tie; the at most 64 selected entries are ordered by one wave.
+//   The entropy H = -sum p_i log p_i over the kept set, with p_i = w_i / W and x_i = (l_i - max) / T = log w_i, is
+//   log W + (sum w_i * -x_i) / W. The second sum is integer as well: S = sum rint(w_i * -x_i * 2^43), the fp32 product (<= 1/e)
+//   converted once as q43 converts a weight; 2^20 terms below 2^42 cannot overflow. H = fp32(log(M / 2^43) + S / M) in double, once
+//   per row, M the Q43 kept mass. Error: M as above; each term of S carries the fp32 rounding of x (twice), of expf and of the product.
 #include "common.h"
 #include "kernels.h"
 
@@ -490,6 +496,147 @@ __global__ __launch_bounds__(SMP_T) void token_logprob_k(cover_token_logprob_arg
     }
 }
 
+// The n most probable kept tokens of a row with their log-probabilities, and the entropy of the kept distribution. The kept set and
+// its mass are token_logprob_k's (the same device functions in the same order), so a reported log-probability is that kernel's value.
+struct TopnShared {
+    u64 ent;             // S: Q43 sum of w * (-x) over the kept set
+    unsigned cnt;
+    float l[64];
+    int rel[64];
+};
+
+__global__ __launch_bounds__(SMP_T) void token_topn_k(cover_token_topn_args a) {
+    __shared__ SampleShared s;
+    __shared__ TopnShared t;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float* lg = a.logits + (size_t)row * a.ld;
+    const int n = a.hi - a.lo;
+    SampleSrc src{lg + a.lo, n, false};
+    const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
+    kept_tiles(s, src, ks);
+    scan_bins<false, true>(s, SMP_BINS, 1ull);
+    const unsigned kept = s.r_cnt_total;
+    const u64 mass = s.r_mass_total;
+    if (tid == 0) {
+        t.ent = 0ull;
+        t.cnt = 0u;
+    }
+
+    // ---- rank selection: thr = key of the want-th largest logit of the kept set (three digits of lkey); the first pass also sums S
+    const unsigned want = kept < (unsigned)a.n ? kept : (unsigned)a.n;
+    unsigned prefix = 0u, n_tie = 0u;
+    u64 need = (u64)want;
+    for (int lev = 0; lev < 3; ++lev) {
+        u64 ent = 0ull;
+        hist_zero(s);
+        for_each(s, src, [&](float l, int rel) {
+            u64 q;
+            if (!ks.kept(l, rel, q)) return;
+            const unsigned key = lkey(l);
+            if (key_in_prefix(key, prefix, lev)) hist_add(s, key_digit(key, lev), 0ull);
+            if (lev == 0) {
+                const float x = (l - ks.m) / ks.T, w = weight_of(l, ks.m, ks.T);
+                if (w > 0.f) ent += q43(w * -x);   // w == 0: an -inf logit (or x < -104), the term is 0 and 0 * inf is not formed
+            }
+        });
+        if (lev == 0) {   // per wave: integer shuffles, then one LDS atomic
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                unsigned lo32 = (unsigned)ent, hi32 = (unsigned)(ent >> 32);
+                lo32 = __shfl_xor(lo32, o);
+                hi32 = __shfl_xor(hi32, o);
+                ent += ((u64)hi32 << 32) | lo32;
+            }
+            if (lane == 0 && ent) atomicAdd(&t.ent, ent);
+        }
+        scan_bins<true, false>(s, key_bins(lev), need);
+        prefix |= (unsigned)s.r_bin << key_shift(lev);
+        need -= (u64)s.r_cnt_before;
+        n_tie = s.r_cnt_bin;
+        if (lev == 0 && !src.list && s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {   // block-uniform; the list is free: kept_set left the row in place
+            const int b0 = s.r_bin;
+            for_each(s, src, [&](float l, int rel) {
+                u64 q;
+                if (!ks.kept(l, rel, q)) return;
+                if (key_digit(lkey(l), 0) >= b0) {
+                    const unsigned slot = atomicAdd(&s.n_list, 1u);
+                    if (slot < SMP_CAP) {
+                        s.list_l[slot] = l;
+                        s.list_i[slot] = rel;
+                    }
+                }
+            });
+            __syncthreads();
+            src.list = true;
+        }
+    }
+    const unsigned thr = prefix;
+    // n_tie kept tokens share the logit at the threshold; the first `need` of them in index order complete the ranks
+    int idx_cut = 0x7fffffff;
+    if (need < (u64)n_tie) {   // block-uniform; the need-th smallest index among them (two 10-bit digits of rel, as kept_set's idx_cut)
+        u64 r = need < 1ull ? 1ull : need;
+        int ip = 0;
+        for (int lev = 0; lev < 2; ++lev) {
+            const int sh = lev == 0 ? 10 : 0;
+            hist_zero(s);
+            for_each(s, src, [&](float l, int rel) {
+                u64 q;
+                if (lkey(l) != thr || !ks.kept(l, rel, q)) return;
+                if (lev == 1 && (rel >> 10) != (ip >> 10)) return;
+                hist_add(s, (rel >> sh) & 1023, 0ull);
+            });
+            scan_bins<false, false>(s, 1024, r);
+            ip |= s.r_bin << sh;
+            r -= (u64)s.r_cnt_before;
+        }
+        idx_cut = ip;
+    }
+
+    // ---- exactly `want` entries reach LDS (in whatever order the atomics grant); one wave ranks them
+    for_each(s, src, [&](float l, int rel) {
+        u64 q;
+        const unsigned key = lkey(l);
+        if (key < thr || (key == thr && rel > idx_cut) || !ks.kept(l, rel, q)) return;
+        const unsigned slot = atomicAdd(&t.cnt, 1u);
+        if (slot < 64u) {
+            t.l[slot] = l;
+            t.rel[slot] = rel;
+        }
+    });
+    __syncthreads();
+    if (tid < 64) {
+        const int cnt = (int)(t.cnt < 64u ? t.cnt : 64u);
+        const bool have = tid < cnt;
+        const float l = have ? t.l[tid] : 0.f;
+        const int rel = have ? t.rel[tid] : 0x7fffffff;
+        const unsigned key = have ? lkey(l) : 0u;
+        int rank = 0;
+        for (int e = 0; e < 64; ++e) {   // (key descending, index ascending): rank = the number of entries ahead of this one
+            const unsigned ke = __shfl(key, e);
+            const int re = __shfl(rel, e);
+            if (e < cnt && (ke > key || (ke == key && re < rel))) ++rank;
+        }
+        int64_t* tok = a.token_out + (size_t)row * a.ld_tok;
+        float* lp = a.logprob_out + (size_t)row * a.ld_lp;
+        if (have && rank < a.n) {
+            tok[rank] = (int64_t)(a.lo + rel);
+            lp[rank] = kept_logprob(ks, l, rel, mass);
+        }
+        if (tid >= cnt && tid < a.n) {
+            tok[tid] = -1;
+            lp[tid] = -INFINITY;
+        }
+        if (tid == 0) {
+            if (a.entropy_out) {
+                // H = log(sum w) + (sum w * -x) / (sum w) over the kept set: both sums exact integers, the rest double, one fp32 rounding
+                const double M = (double)mass;
+                a.entropy_out[row] = mass ? (float)(log(M) - 43.0 * 0.693147180559945309417232121458 + (double)t.ent / M) : 0.f;
+            }
+            if (a.kept_out) a.kept_out[row] = (int)kept;
+        }
+    }
+}
+
 __global__ void fill_i32_k(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -505,6 +652,15 @@ hipError_t launch_token_logprob(const cover_token_logprob_args* a, hipStream_t s
     if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     hipLaunchKernelGGL(token_logprob_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_topn(const cover_token_topn_args* a, hipStream_t st) {
+    if (!a->logits || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
+    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_topn_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
     return hipGetLastError();
 }
 

@@ -15,7 +15,7 @@ import json
 import math
 import os
 from collections import deque
-from typing import List, Optional, Sequence
+from typing import Any, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -48,6 +48,34 @@ def sequence_logprob(logprobs, tokens=None, pad_token_id=None, length_normalize=
         count = tokens.to(logprobs.device) != pad_token_id
     total = torch.where(count, logprobs, torch.zeros_like(logprobs)).sum(dim=1)
     return total / count.sum(dim=1).clamp(min=1).to(total.dtype) if length_normalize else total
+
+
+class TopLogprobs(NamedTuple):
+    """What OpenVLA.sample / PI0FASTTokens.generate_tokens append with top_logprobs = n: per candidate and step the n most probable
+    tokens of the distribution the step's pick came from (descending logit, equal logits by ascending id), their log-probabilities
+    and the entropy of that distribution in nats. Slots beyond the kept set carry token -1 / log-probability -inf."""
+    tokens: Any        # int64 [N, steps, n]
+    logprobs: Any      # fp32 [N, steps, n]
+    entropy: Any       # fp32 [N, steps]
+
+
+def step_entropy_summary(entropy, tokens=None, pad_id=None):
+    """Per-candidate (mean, max) of the per-step entropies over the steps the candidate was live: entropy [N, steps] (torch tensor on
+    any device, or numpy) -> two [N] of the same kind. With tokens [N, steps] and pad_id the steps whose emitted token is the pad are
+    left out (a finished pi0-FAST row; generate_tokens gives them entropy 0.0); a candidate with no live step gets 0.0 for both.
+    Index bookkeeping on N x steps values."""
+    if isinstance(entropy, np.ndarray):
+        live = np.ones(entropy.shape, dtype=bool)
+        if tokens is not None and pad_id is not None:
+            live = np.asarray(tokens) != pad_id
+        mean = np.where(live, entropy, 0.0).sum(axis=1) / np.maximum(live.sum(axis=1), 1)
+        return mean, np.where(live, entropy, 0.0).max(axis=1)
+    import torch
+    live = torch.ones_like(entropy, dtype=torch.bool)
+    if tokens is not None and pad_id is not None:
+        live = tokens.to(entropy.device) != pad_id
+    kept = torch.where(live, entropy, torch.zeros_like(entropy))
+    return kept.sum(dim=1) / live.sum(dim=1).clamp(min=1).to(kept.dtype), kept.max(dim=1).values
 
 
 def denormalize_bound(data, data_min, data_max, clip_min=-1.0, clip_max=1.0):

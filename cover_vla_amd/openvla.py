@@ -25,6 +25,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .host import TopLogprobs
 from .models import BF, Decoder, KvGeometry, VitTower, _f32
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -196,7 +197,7 @@ class OpenVLA:
     def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
                uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, trace: Optional[dict] = None,
                force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
-               top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False):
+               top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False, top_logprobs: int = 0):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
         uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
@@ -209,8 +210,15 @@ class OpenVLA:
         return_logprobs: a third tensor fp32 [N, n_gen], the log-probability of each pick under the distribution it was drawn from
         (sampled: temperature, top_k, top_p over the action bins, cover_token_sample_scored / cover_token_logprob; greedy: temperature 1,
         no filters, over the tokenizer vocabulary the arg-max runs over). With force_tokens it is still this path's own picks that are
-        scored. The default launches exactly what it launched without the argument."""
+        scored. The default launches exactly what it launched without the argument.
+        top_logprobs = n in 1..64: appends host.TopLogprobs(tokens int64 [N, n_gen, n], logprobs fp32 [N, n_gen, n], entropy fp32
+        [N, n_gen]) to the return: per step the n most probable tokens of the distribution return_logprobs documents (descending logit,
+        equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities (cover_token_logprob's, bit for
+        bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used. 0: today's launches."""
         c, dev = self.c, self.dev
+        n_top = int(top_logprobs)
+        if not 0 <= n_top <= 64:
+            raise ValueError("top_logprobs must be in 0..64")
         P, Lt = prompt_tokens.shape
         N = P * n_samples
 
@@ -253,7 +261,7 @@ class OpenVLA:
         filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
             # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
-            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ())
+            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ())
             st = self._dec.get(key)
             if st is None:
                 st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
@@ -261,6 +269,7 @@ class OpenVLA:
                           sel=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev),
                           u=None if u_t is None else torch.empty_like(u_t),
                           lps=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None,
+                          top=self._top_bufs(N, n_top),
                           prompt_slots=torch.arange(P, dtype=torch.int32, device=dev), prompt_lens=torch.empty(P, dtype=torch.int32, device=dev))
                 self._dec[key] = st
             st["cand_len"].copy_(cand_len); st["last_row"].copy_(last_row); st["pos_all"].copy_(pos_all)
@@ -268,7 +277,7 @@ class OpenVLA:
             if u_t is not None:
                 st["u"].copy_(u_t)
             body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"])
+                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"])
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -285,26 +294,42 @@ class OpenVLA:
                 cur.wait_stream(self._cap)
             else:
                 st["graph"].launch()
-            if return_logprobs:                                         # the eager pass before a capture has filled the same buffers
-                return st["tokens"].t().contiguous(), st["sel"].t().contiguous(), st["lps"].t().contiguous()
-            return st["tokens"].t().contiguous(), st["sel"].t().contiguous()
+            # the eager pass before a capture has filled the same buffers
+            return self._sample_result(st["tokens"], st["sel"], st["lps"], st["top"])
         # step-major buffers: row i of each is contiguous, so the kernels of step i read / write them in place (no per-step slice copies)
         tokens = torch.empty(self.n_gen, N, dtype=torch.int64, device=dev)
         sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
         lps = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None
+        top = self._top_bufs(N, n_top)
         fed = tokens if force_tokens is None else force_tokens.t().contiguous()
         self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps)
-        if return_logprobs:
-            return tokens.t().contiguous(), sel.t().contiguous(), lps.t().contiguous()
-        return tokens.t().contiguous(), sel.t().contiguous()
+                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top)
+        return self._sample_result(tokens, sel, lps, top)
+
+    def _top_bufs(self, N, n_top):
+        """Step-major buffers of sample(top_logprobs=n): (tokens [n_gen, N, n], logprobs [n_gen, N, n], entropy [n_gen, N]), None for n = 0."""
+        if not n_top:
+            return None
+        return (torch.empty(self.n_gen, N, n_top, dtype=torch.int64, device=self.dev),
+                torch.empty(self.n_gen, N, n_top, dtype=torch.float32, device=self.dev),
+                torch.empty(self.n_gen, N, dtype=torch.float32, device=self.dev))
+
+    @staticmethod
+    def _sample_result(tokens, sel, lps, top):
+        """Candidate-major copies of the step-major buffers: what sample returns."""
+        out = (tokens.t().contiguous(), sel.t().contiguous())
+        if lps is not None:
+            out += (lps.t().contiguous(),)
+        if top is not None:
+            out += (TopLogprobs(top[0].transpose(0, 1).contiguous(), top[1].transpose(0, 1).contiguous(), top[2].t().contiguous()),)
+        return out
 
     def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None):
+                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
         ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps)
+        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
@@ -316,12 +341,13 @@ class OpenVLA:
                                 dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps)
+            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None):
+    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None):
         """Norm, head GEMM, one ops.pick_token. filt: None = the unfiltered ops.token_select pick; (top_k, top_p) = ops.token_sample over
-        the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks."""
+        the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks.
+        top (tokens, logprobs, entropy) or None: slab i receives ops.token_topn of the distribution the pick came from."""
         N = h.shape[0]
         u = None if uniforms is None else uniforms[i]
         # out_kept: written by the filtered pick (ops.token_sample) only
@@ -331,12 +357,24 @@ class OpenVLA:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
             t, _, _ = ops.pick_token(lg, 0, self.c["n_bins"], u, temperature, filt, **out)
             torch.add(t, self.action_lo, out=tokens[i])
+            if top is not None:
+                self._head_topn(lg, 0, self.c["n_bins"], uniforms is None, temperature, filt, top, i)
+                top[0][i].add_((top[0][i] >= 0) * self.action_lo)          # ids as the tokens are; the -1 padding stays
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
         if trace is not None and "events" not in trace:
             trace.setdefault("logits", []).append(lg.clone())
         lo, hi = (0, self.c["tok_vocab"]) if uniforms is None else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
         ops.pick_token(lg, lo, hi, u, temperature, filt, out_tok=tokens[i], **out)
+        if top is not None:
+            self._head_topn(lg, lo, hi, uniforms is None, temperature, filt, top, i)
+
+    @staticmethod
+    def _head_topn(lg, lo, hi, greedy, temperature, filt, top, i):
+        """One ops.token_topn launch on step i's logits; greedy: temperature 1, unfiltered (what return_logprobs scores a greedy pick under)."""
+        k, p = (0, 1.0) if greedy or filt is None else filt
+        ops.token_topn(lg, lo, hi, top[0].shape[2], 1.0 if greedy else temperature, k, p, out_tok=top[0][i], out_logprob=top[1][i],
+                       out_entropy=top[2][i])
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

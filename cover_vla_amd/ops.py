@@ -642,6 +642,43 @@ def token_logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, o
     return lp
 
 
+def token_topn(logits, lo, hi, n, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logprob=None, out_entropy=None, out_kept=None):
+    """The n (1..64) most probable tokens of every row under the distribution token_sample draws from with the same parameters over
+    columns [lo, hi), their log-probabilities and the entropy of that distribution (cover_token_topn). Returns (tokens int64 [rows, n],
+    logprobs fp32 [rows, n], entropy fp32 [rows]): ranks by descending logit, equal logits by ascending index; a row whose kept set
+    has fewer than n members is padded with token -1 / log-probability -inf; entropy in nats over the kept set. A log-probability is
+    token_logprob's for that token, bit for bit. out_tok / out_logprob ([rows, n], unit column stride, any row stride >= n: a step's
+    slab of a [steps, rows, n] buffer), out_entropy fp32 / out_kept int32 ([rows], contiguous) are written in place.
+    Deterministic, one launch, recordable."""
+    if not temperature > 0 or not top_p > 0 or top_k < 0 or hi <= lo or lo < 0:
+        raise L.CoverError(f"token_topn: temperature > 0, top_p > 0, top_k >= 0 and 0 <= lo < hi are required "
+                           f"(got temperature={temperature}, top_k={top_k}, top_p={top_p}, lo={lo}, hi={hi})")
+    if not 1 <= int(n) <= 64:
+        raise L.CoverError(f"token_topn: 1 <= n <= 64 is required (got n={n})")
+    n = int(n)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
+        raise L.CoverError("token_topn: logits must be fp32 [rows, >= hi] with unit column stride")
+    rows = logits.shape[0]
+    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, n) or (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n)):
+            raise L.CoverError(f"token_topn: {name} must be {dt} [rows, n] with unit column stride and a row stride >= n")
+    for name, t, dt in (("out_entropy", out_entropy, torch.float32), ("out_kept", out_kept, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise L.CoverError(f"token_topn: {name} must be contiguous {dt} [rows]")
+    _chk_dev(logits, out_tok, out_logprob, out_entropy, out_kept)
+    tok = torch.empty(rows, n, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
+    lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if out_logprob is None else out_logprob
+    ent = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_entropy is None else out_entropy
+    a = L.TokenTopnArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.temperature, a.top_k, a.top_p, a.n = temperature, int(top_k), top_p, n
+    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
+    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
+    a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    L.check(L.lib().cover_token_topn(C.byref(a), _stream()), "token_topn")
+    return tok, lp, ent
+
+
 def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None):
     """One decode step's pick over columns [lo, hi), the three-way choice of every token head. Returns (token, its logit, kept or None).
     uniform None: greedy token_select (temperature and filt are unused); uniform with filt None: token_select's unfiltered inverse-CDF

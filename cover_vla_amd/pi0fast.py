@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .host import TopLogprobs
 from .models import BF, Decoder, KvGeometry, VitTower
 
 
@@ -93,7 +94,7 @@ class PI0FASTTokens:
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0, return_logprobs: bool = False, share_prefix: bool = False):
+                        top_p: float = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -108,8 +109,15 @@ class PI0FASTTokens:
         share_prefix: rows with equal (frames, prompt) share ONE prefilled prefix (greedy, sampled and forced alike): the prefill
         runs over the P distinct rows, every candidate row still decodes and picks on its own, reading its prompt's prefix K/V through
         the segment's slot_of_batch. Needs P <= max_prompts and B <= max_batch. GEMM row counts differ from the per-row path, so
-        results agree with it to bf16 rounding (bit for bit when P == B). The default launches exactly what it launched before."""
+        results agree with it to bf16 rounding (bit for bit when P == B). The default launches exactly what it launched before.
+        top_logprobs = n in 1..64: appends host.TopLogprobs(tokens int64 [B, max_new_tokens, n], logprobs fp32 [B, max_new_tokens, n],
+        entropy fp32 [B, max_new_tokens]) to the return: per step the n most probable tokens of the distribution return_logprobs
+        documents (descending logit, equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities
+        (cover_token_logprob's, bit for bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used.
+        Steps after a row's EOS, and steps the early stop skips, carry -1 / -inf / 0.0. 0: today's launches."""
         dev = self.dev
+        if not 0 <= int(top_logprobs) <= 64:
+            raise ValueError("top_logprobs must be in 0..64")
         u_t = None
         if uniforms is not None:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
@@ -123,16 +131,17 @@ class PI0FASTTokens:
             if first.shape[0] < tokens.shape[0]:
                 fi = torch.from_numpy(first).to(dev)
                 sub_out = self.generate_tokens([im[fi] for im in images], [m[fi] for m in img_masks], tokens[fi], pad_mask[fi],
-                                               max_new_tokens, eos_token_id, pad_token_id, None, trace, return_logprobs=return_logprobs)
+                                               max_new_tokens, eos_token_id, pad_token_id, None, trace, return_logprobs=return_logprobs,
+                                               top_logprobs=top_logprobs)
                 back = torch.from_numpy(slot).to(dev)
-                if return_logprobs:
-                    return sub_out[0][back], sub_out[1][back]
-                return sub_out[back]
+                if not isinstance(sub_out, tuple):
+                    return sub_out[back]
+                return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
         return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix)
+                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs))
 
     def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share):
+                  temperature, top_k, top_p, return_logprobs, share, n_top=0):
         """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
@@ -195,6 +204,10 @@ class PI0FASTTokens:
         live = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev) if fused else None   # live[i]: rows still running after step i
         lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
         lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
+        # step-major [steps, B, n]: slab i is what step i's ops.token_topn writes; steps that never run keep the padding
+        top_tok = torch.full((max_new_tokens, B, n_top), -1, dtype=torch.int64, device=dev) if n_top else None
+        top_lp = torch.full((max_new_tokens, B, n_top), float("-inf"), dtype=torch.float32, device=dev) if n_top else None
+        top_ent = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev) if n_top else None
         force = force_tokens
         if share and force is not None:
             force = force.to(device=dev, dtype=torch.int64)                          # the per-row form moves one column per step
@@ -211,6 +224,9 @@ class PI0FASTTokens:
             # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
             t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
                                         out_logprob=lp)
+            if n_top:     # the distribution out_logprob scores the pick under (greedy: temperature 1, unfiltered)
+                ops.token_topn(lg, 0, c["vocab"], n_top, 1.0 if u_t is None else temperature, 0 if u_t is None else top_k,
+                               1.0 if u_t is None else top_p, out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
             if u_t is not None and trace is not None:
                 trace.setdefault("picks", []).append(t.clone())
                 trace.setdefault("kept", []).append(kept)
@@ -241,9 +257,18 @@ class PI0FASTTokens:
             g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
             self.lm.forward(xd, [g], final_norm=False)
             pick(xd, i)
-        if return_logprobs:
-            return out, lps
-        return out
+        if not return_logprobs and not n_top:
+            return out
+        res = (out, lps) if return_logprobs else (out,)
+        if n_top:
+            # a row is finished at step i once an earlier step emitted EOS: its pad is not a choice (index bookkeeping on the emitted tokens)
+            eos = out == eos_token_id
+            fin = (eos.cumsum(dim=1) - eos.to(torch.int64)) > 0                      # [B, steps]
+            tt, tl, te = top_tok.transpose(0, 1), top_lp.transpose(0, 1), top_ent.t()
+            res += (TopLogprobs(torch.where(fin[:, :, None], torch.full_like(tt, -1), tt),
+                                torch.where(fin[:, :, None], torch.full_like(tl, float("-inf")), tl),
+                                torch.where(fin, torch.zeros_like(te), te)),)
+        return res
 
 
 @dataclass
@@ -266,6 +291,7 @@ class PI0FASTConfig:
     top_p: float = 1.0
     sample_seed: Optional[int] = None
     return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
+    top_logprobs: int = 0               # keep the n most probable tokens / log-probabilities / entropy of every step (last_top_logprobs)
     share_prefix: bool = False          # candidates with equal frames and prompt share one prefill (generate_tokens(share_prefix=True))
 
 
@@ -283,6 +309,7 @@ class PI0FASTPolicy:
         # the source of randomness of sampled decoding: a host generator seeded ONCE, so a seed and an observation sequence fix the actions
         self._gen = None if config.sample_seed is None else torch.Generator().manual_seed(int(config.sample_seed))
         self.last_sequence_logprobs = None        # fp32 [B] on the device, set by a generation that ran with config.return_logprobs
+        self.last_top_logprobs = None             # host.TopLogprobs on the device, set by a generation that ran with config.top_logprobs > 0
         self.reset()
 
     def reset(self):
@@ -351,6 +378,8 @@ class PI0FASTPolicy:
             ids, mask = self.create_input_tokens(state, batch["task"])
             B = ids.shape[0]
             sampling = dict(return_logprobs=True) if self.config.return_logprobs else {}
+            if self.config.top_logprobs:
+                sampling.update(top_logprobs=self.config.top_logprobs)
             if self.config.share_prefix:
                 sampling.update(share_prefix=True)
             if self._gen is not None:
@@ -359,6 +388,9 @@ class PI0FASTPolicy:
             toks = self.model.generate_tokens(images, [torch.ones(B, dtype=torch.bool, device=dev) for _ in images], ids.to(dev), mask.to(dev),
                                               self.config.max_decoding_steps, eos_token_id=self.paligemma_tokenizer.eos_token_id,
                                               pad_token_id=self.pad_token_id, **sampling)
+            if self.config.top_logprobs:
+                toks, self.last_top_logprobs = toks[:-1], toks[-1]
+                toks = toks if self.config.return_logprobs else toks[0]
             if self.config.return_logprobs:
                 from .host import sequence_logprob
                 toks, lps = toks

@@ -483,6 +483,37 @@ typedef struct cover_token_logprob_args {
 } cover_token_logprob_args;
 int cover_token_logprob(const cover_token_logprob_args* args, void* stream);
 
+/* The n most probable tokens of each row under the distribution cover_token_sample draws from, with their log-probabilities, and the
+ * entropy of that distribution (a sampler's top_logprobs). Per row, over columns [lo, hi) with KEPT, x_i and lp() of
+ * cover_token_logprob for the same (temperature, top_k, top_p):
+ *   ranking       the columns of KEPT by descending input logit (a comparison of the input floats, -0 == +0, no arithmetic), equal
+ *                 logits by ascending index;
+ *   token_out[row, j]   = the absolute column id of rank j            for j < min(n, |KEPT|),   -1   for the remaining slots
+ *   logprob_out[row, j] = lp(token_out[row, j]), bit for bit the value cover_token_logprob returns for that token with the same
+ *                         parameters (the same code on the same integer mass),                  -inf for the remaining slots
+ *   entropy_out[row]    = H = -sum_{i in KEPT} p_i log p_i in nats, p_i = exp(lp(i))            (optional)
+ *   kept_out[row]       = |KEPT|, cover_token_logprob's                                          (optional)
+ * H has no floating-point sum over columns: with w_i = expf(x_i), M = sum rint(w_i 2^43) (the kept mass) and
+ * S = sum rint(w_i (-x_i) 2^43) (the fp32 product converted once), both exact integer sums,
+ * H = fp32( log(M / 2^43) + S / M ) in double, once per row. Error against exact arithmetic on the fp32 logits:
+ * 5.2e-6 + (1.05e-5 + 2^-24) H (tests/topn_ref.py derives it). 0 <= H <= log |KEPT| up to that error.
+ * One 1024-thread block per row, one launch, no workspace, nothing data-dependent in the launch: recordable into a hipGraph and
+ * deterministic (the same row and parameters give the same outputs at every row position, base alignment and launch).
+ * 1 <= n <= 64; hi - lo <= 2^20, any lo / ld; token_out / logprob_out are [rows, n] with unit column stride and row strides
+ * ld_tok / ld_lp >= n (elements), e.g. a step's slab of a [steps, rows, n] buffer. */
+typedef struct cover_token_topn_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    float temperature;
+    int top_k;              /* 0 = off */
+    float top_p;            /* >= 1 = off */
+    int n;                  /* alternatives per row, 1..64 */
+    int64_t* token_out; long long ld_tok;     /* [rows, n] */
+    float* logprob_out; long long ld_lp;      /* [rows, n] */
+    float* entropy_out;     /* [rows] (optional) */
+    int* kept_out;          /* [rows] size of the kept set (optional) */
+} cover_token_topn_args;
+int cover_token_topn(const cover_token_topn_args* args, void* stream);
+
 /* The bookkeeping between two steps of an autoregressive decode loop (pi0-FAST generate_tokens), one launch, one block per
  * candidate row, no workspace: recordable into a hipGraph. Per row b, in this order:
  *   t = force ? force[b * force_stride] : pick[b];  lp_out[b * ld_lp] = done[b] ? 0.0f : lp[b];  if (done[b]) t = pad;
