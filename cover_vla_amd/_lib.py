@@ -144,6 +144,14 @@ class ScoreSelectArgs(C.Structure):
                 ("fused_act_out", c_p)]
 
 
+class PriorSelectArgs(C.Structure):
+    _fields_ = [("scores", c_p), ("logprobs", c_p), ("lp_n_stride", c_ll), ("lp_t_stride", c_ll),
+                ("tokens", c_p), ("tok_n_stride", c_ll), ("tok_t_stride", c_ll), ("pad_token_id", c_ll),
+                ("N", c_i), ("steps", c_i), ("group_size", c_i), ("top_m", c_i), ("beta", c_f), ("length_normalize", c_i),
+                ("prior_out", c_p), ("combined_out", c_p), ("group_mean_out", c_p), ("result_out", c_p), ("best_out", c_p),
+                ("ranked_out", c_p)]
+
+
 class Workspace(C.Structure):
     _fields_ = [("ptr", c_p), ("bytes", C.c_size_t)]
 
@@ -194,7 +202,7 @@ _STRUCTS = {
     "cover_mha_f32_args": MhaF32Args, "cover_token_select_args": TokenSelectArgs,
     "cover_token_sample_args": TokenSampleArgs, "cover_token_sample_scored_args": TokenSampleScoredArgs,
     "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs, "cover_decode_feedback_args": DecodeFeedbackArgs,
-    "cover_score_select_args": ScoreSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
+    "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
 }
@@ -252,6 +260,7 @@ SYMBOLS = {
     "cover_decode_feedback": (c_i, [_P(DecodeFeedbackArgs), c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
+    "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),
     "cover_tokens_to_histories": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_f, c_p, c_p, c_p]),
     "cover_tokens_to_histories_steps": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
     "cover_actions_to_histories": (c_i, [c_p, c_ll, c_ll, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_p, c_p]),

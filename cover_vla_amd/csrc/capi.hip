@@ -316,6 +316,13 @@ int cover_group_argmax(const float* scores, int N, int group_size, int* result_o
     HIPCHK(launch_group_argmax(scores, N, group_size, result_out, best_out, ST(stream)), "group_argmax");
     return COVER_OK;
 }
+int cover_prior_select(const cover_prior_select_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_prior_select: null args");
+    HIPCHK(launch_prior_select(a, ST(stream)),
+           "prior_select (N % group_size == 0, N / group_size <= 4096, group_size <= 4096, 1 <= steps <= 4096, 0 <= top_m <= min(group_size, 64), "
+           "beta finite and >= 0, scores / logprobs / prior_out / combined_out / result_out / best_out required, ranked_out with top_m > 0)");
+    return COVER_OK;
+}
 
 int cover_resample_axis(const void* in, int in_is_f32, void* out, int out_is_f32, int Hin, int Win, int C, int Hout, int Wout,
                         int axis, const int* bounds, const void* coefs, int ksize, int fixed_point, void* stream) {
@@ -825,7 +832,7 @@ size_t cover_sizeof(const char* n) {
 #define SZ(T) if (!strcmp(n, #T)) return sizeof(T)
     SZ(cover_gemm_epi); SZ(cover_kv_segment); SZ(cover_attn_args); SZ(cover_rope_args); SZ(cover_patchify_args);
     SZ(cover_gemm_f32_args); SZ(cover_mha_f32_args); SZ(cover_token_select_args); SZ(cover_token_sample_args); SZ(cover_score_select_args);
-    SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_decode_feedback_args);
+    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_decode_feedback_args);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
 #undef SZ

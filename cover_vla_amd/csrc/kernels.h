@@ -87,6 +87,7 @@ hipError_t launch_actions_to_histories(const float* actions, long long n_stride,
                                        const float* lo_hi, const float* past, int n_past, float pad_value, float* hist,
                                        uint8_t* pad, hipStream_t st);
 hipError_t launch_group_argmax(const float* scores, int N, int gs, int* result, float* best, hipStream_t st);
+hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st);
 size_t gemm_workspace_bytes(int M, int N, int K);
 
 // ---- image.hip -----------------------------------------------------------------------------------

@@ -216,6 +216,71 @@ hipError_t launch_group_argmax(const float* scores, int N, int gs, int* result, 
     hipLaunchKernelGGL(group_argmax_k, dim3(1), dim3(256), 0, st, scores, N, gs, result, best);
     return hipGetLastError();
 }
+// Prior-weighted selection: the grouped arg-max of score + beta * (sum of the candidate's per-step log-probabilities), with the best
+// top_m of the winning group ranked. One block, as group_argmax_k; the group stage IS group_argmax_dev on the combined scores, so
+// beta == 0 selects what group_argmax_k selects, bit for bit. Every sum that decides an index is one fp32 chain in index order.
+__global__ __launch_bounds__(1024) void prior_select_k(cover_prior_select_args a) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float gmean[4096];
+    __shared__ float win[4096];   // the winning group's combined scores
+    // 1. prior and combined score, one thread per candidate: adds in step order from 0.0f, pad steps left out
+    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+        const float* lp = a.logprobs + (long long)n * a.lp_n_stride;
+        const int64_t* tk = a.tokens ? a.tokens + (long long)n * a.tok_n_stride : nullptr;
+        float s = 0.f;
+        int cnt = 0;
+        for (int t = 0; t < a.steps; ++t) {
+            if (tk && (long long)tk[(long long)t * a.tok_t_stride] == a.pad_token_id) continue;
+            s += lp[(long long)t * a.lp_t_stride];
+            ++cnt;
+        }
+        if (a.length_normalize) s = s / (float)(cnt > 1 ? cnt : 1);
+        a.prior_out[n] = s;
+        // beta == 0: no product, so a -inf prior cannot make a NaN; otherwise two roundings. Plain operators under `fp contract(off)`:
+        // __fmul_rn / __fadd_rn are inline header functions whose multiply and add hipcc contracts into ONE v_fma_f32 (one rounding)
+        float cmb = a.scores[n];
+        if (a.beta != 0.0f) {
+#pragma clang fp contract(off)
+            const float prod = a.beta * s;
+            cmb = cmb + prod;
+        }
+        a.combined_out[n] = cmb;
+    }
+    __syncthreads();   // combined_out is read back below by other threads of this block
+    // 2. group means -> winning group -> winner inside it
+    group_argmax_dev(a.combined_out, a.N, a.group_size, a.result_out, a.best_out, gmean, sv, si);
+    const int G = a.N / a.group_size, gs = a.group_size;
+    if (a.group_mean_out)
+        for (int gi = threadIdx.x; gi < G; gi += blockDim.x) a.group_mean_out[gi] = gmean[gi];
+    if (a.top_m <= 0) return;
+    // 3. ranks inside the winning group: rank(j) = how many members come before j in (descending value, ascending index) order
+    __syncthreads();   // result_out[1] was written by thread 0
+    int bg = a.result_out[1];
+    bg = bg < 0 ? 0 : (bg > G - 1 ? G - 1 : bg);
+    const float* c = a.combined_out + (long long)bg * gs;
+    for (int j = threadIdx.x; j < gs; j += blockDim.x) win[j] = c[j];
+    __syncthreads();
+    for (int j = threadIdx.x; j < gs; j += blockDim.x) {
+        const float v = win[j];
+        int rank = 0;
+        for (int k = 0; k < gs; ++k) {
+            const float o = win[k];
+            rank += (o > v || (o == v && k < j)) ? 1 : 0;
+        }
+        if (rank < a.top_m) a.ranked_out[rank] = bg * gs + j;
+    }
+}
+hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st) {
+    if (a->N < 1 || a->group_size < 1 || a->N % a->group_size != 0 || a->N / a->group_size > 4096 || a->group_size > 4096)
+        return hipErrorInvalidValue;
+    if (a->steps < 1 || a->steps > 4096 || a->top_m < 0 || a->top_m > 64 || a->top_m > a->group_size) return hipErrorInvalidValue;
+    if (!(a->beta >= 0.0f) || !(a->beta <= 3.402823466e+38f)) return hipErrorInvalidValue;   // finite, >= 0 (a NaN fails both)
+    if (!a->scores || !a->logprobs || !a->prior_out || !a->combined_out || !a->result_out || !a->best_out) return hipErrorInvalidValue;
+    if (a->top_m > 0 && !a->ranked_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prior_select_k, dim3(1), dim3(1024), 0, st, *a);
+    return hipGetLastError();
+}
 hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st) {
     if (a->N <= 0 || a->group_size <= 0 || a->N % a->group_size != 0 || a->N / a->group_size > 4096 || a->dim <= 0 || a->dim > 4096)
         return hipErrorInvalidValue;

@@ -141,12 +141,19 @@ def process_inputs(action_queue: Sequence[np.ndarray], verifier_action: bool, ac
 
 def verify_and_select(verifier, raw_image, task_description: str, task_list: Sequence[str], action_queue, action_history,
                       samples_per_prompt: int, n_action_steps: int = 4, threshold: float = 0.1, stats=None,
-                      process_image: bool = True):
+                      process_image: bool = True, candidate_prior=None, prior_beta: float = 0.0):
     """run_simpler_eval_with_openpi.py:329-401: stage 1 scores candidate 0 under the current instruction; if its score
     is < threshold, stage 2 scores all candidates grouped per prompt; then the gripper majority vote inside the winner's
     prompt group and extraction of the winner's remaining steps.
     action_queue: n_action_steps arrays [B,7] (host). Returns dict(execute_action, max_score, max_instruction,
-    global_action_idx, remaining (deque of [1,7]), history_row)."""
+    global_action_idx, remaining (deque of [1,7]), history_row, prior_beta).
+    candidate_prior ([B] sequence log-probabilities of the candidates under the policy, e.g. PI0FASTPolicy.last_sequence_logprobs, or
+    [B, steps] per-step values) with prior_beta > 0: stage 2 selects on score + prior_beta * prior (stage 1 scores one candidate: a
+    prior cannot change it). The two keywords reach the verifier only then, so a verifier that does not know them keeps working;
+    max_score is then the winner's combined score and the dict also carries the winner's `prior`."""
+    if not (prior_beta >= 0.0 and math.isfinite(prior_beta)):
+        raise ValueError(f"verify_and_select: prior_beta must be finite and >= 0 (got {prior_beta})")
+    use_prior = candidate_prior is not None and prior_beta > 0
     B = len(task_list)
     num_past = min(len(action_history), 6)
     hist_v = process_inputs(action_queue, True, action_history, n_action_steps, stats)
@@ -157,11 +164,14 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     max_score, max_instruction, max_hist, gidx = verifier.compute_max_similarity_scores_batch(
         images=images[0:1], instructions=[task_description], all_action_histories=hist_v[0:1],
         cfg_repeat_language_instructions=1)
+    stage2 = False
     if max_score < threshold:
         max_score, _, max_hist, gidx = verifier.compute_max_similarity_scores_batch(
             images=images, instructions=[task_description] * B, all_action_histories=hist_v,
-            cfg_repeat_language_instructions=samples_per_prompt)
+            cfg_repeat_language_instructions=samples_per_prompt,
+            **(dict(candidate_prior=candidate_prior, prior_beta=prior_beta) if use_prior else {}))
         max_instruction = task_list[int(gidx)]
+        stage2 = True
     gidx = int(gidx)
     hist_e = process_inputs(action_queue, False, action_history, n_action_steps, stats)
     execute_action = hist_e[gidx][num_past].copy()
@@ -176,8 +186,19 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
         execute_action[-1] = 1.0 if execute_action[-1] >= 0 else -1.0
     execute_action[-1] = float(np.sign(execute_action[-1]))
     remaining = deque(np.asarray(action_queue[t])[gidx:gidx + 1] for t in range(1, n_action_steps))
-    return dict(execute_action=execute_action, max_score=max_score, max_instruction=max_instruction,
-                global_action_idx=gidx, remaining=remaining, history_row=max_hist[num_past].copy())
+    out = dict(execute_action=execute_action, max_score=max_score, max_instruction=max_instruction,
+               global_action_idx=gidx, remaining=remaining, history_row=max_hist[num_past].copy(), prior_beta=float(prior_beta))
+    if use_prior and stage2:
+        out["prior"] = _winner_prior(candidate_prior, gidx)
+    return out
+
+
+def _winner_prior(candidate_prior, gidx: int) -> float:
+    """The selected candidate's sequence log-probability, for the record: [B] as given, [B, steps] summed over its steps."""
+    p = candidate_prior[gidx]
+    if hasattr(p, "detach"):
+        p = p.detach().cpu().numpy()
+    return float(np.asarray(p, dtype=np.float64).sum())
 
 
 class EpisodeLog:

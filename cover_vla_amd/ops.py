@@ -794,6 +794,59 @@ def group_argmax(scores, group_size):
     return result, best
 
 
+def prior_select(scores, logprobs, group_size, beta, *, tokens=None, pad_token_id=None, length_normalize=False, top_m=0):
+    """Grouped arg-max of scores + beta * sequence log-probability, with the best top_m of the winning group (cover_prior_select).
+    scores fp32 [N] contiguous; logprobs fp32 [N] (a prior that is summed already) or [N, steps] with ANY strides -- the candidate-major
+    tensor OpenVLA.sample / generate_tokens return, or the transposed view of a step-major [steps, N] buffer: strides are passed, nothing
+    is copied. tokens int64 of logprobs' shape (any strides) with pad_token_id: steps whose token is the pad are not counted;
+    length_normalize divides the sum by the number of counted steps (at least 1). Returns a dict of device tensors: prior [N], combined
+    [N], group_mean [N / group_size], result int32 [4] and best fp32 [2] as group_argmax gives them (on combined), ranked int32 [top_m]
+    global indices by descending combined score, equal values by ascending index. The prior is one fp32 chain of adds in step order and
+    combined = scores exactly when beta == 0, else round(scores + round(beta * prior)): the results are fixed bit patterns.
+    One launch, no workspace, recordable."""
+    import math
+    if not (torch.is_tensor(scores) and torch.is_tensor(logprobs)) or scores.dtype != torch.float32 or logprobs.dtype != torch.float32:
+        raise L.CoverError("prior_select: scores and logprobs must be fp32 tensors")
+    if scores.dim() != 1 or scores.numel() < 1 or not scores.is_contiguous():
+        raise L.CoverError("prior_select: scores must be contiguous fp32 [N], N >= 1")
+    N = scores.numel()
+    if logprobs.dim() not in (1, 2) or logprobs.shape[0] != N or (logprobs.dim() == 2 and not 1 <= logprobs.shape[1] <= 4096):
+        raise L.CoverError(f"prior_select: logprobs must be [N] or [N, 1..4096 steps] with N = {N} (got {tuple(logprobs.shape)})")
+    steps = 1 if logprobs.dim() == 1 else logprobs.shape[1]
+    if (tokens is None) != (pad_token_id is None):
+        raise L.CoverError("prior_select: tokens and pad_token_id are given together")
+    if tokens is not None and (not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.shape != logprobs.shape):
+        raise L.CoverError("prior_select: tokens must be int64 of logprobs' shape")
+    group_size, top_m = int(group_size), int(top_m)
+    if group_size < 1 or N % group_size != 0 or N // group_size > 4096 or group_size > 4096:
+        raise L.CoverError(f"prior_select: N % group_size == 0, N / group_size <= 4096 and group_size <= 4096 are required "
+                           f"(got N={N}, group_size={group_size})")
+    if not 0 <= top_m <= min(group_size, 64):
+        raise L.CoverError(f"prior_select: 0 <= top_m <= min(group_size, 64) is required (got top_m={top_m}, group_size={group_size})")
+    beta = float(beta)
+    if not (math.isfinite(beta) and beta >= 0.0 and math.isfinite(C.c_float(beta).value)):
+        raise L.CoverError(f"prior_select: beta must be finite and >= 0 (got {beta})")
+    _chk_dev(scores, logprobs, tokens)
+    if logprobs.device != scores.device or (tokens is not None and tokens.device != scores.device):
+        raise L.CoverError("prior_select: scores, logprobs and tokens must be on one device")
+    dev = scores.device
+    out = {"prior": torch.empty(N, dtype=torch.float32, device=dev), "combined": torch.empty(N, dtype=torch.float32, device=dev),
+           "group_mean": torch.empty(N // group_size, dtype=torch.float32, device=dev),
+           "result": torch.empty(4, dtype=torch.int32, device=dev), "best": torch.empty(2, dtype=torch.float32, device=dev),
+           "ranked": torch.empty(top_m, dtype=torch.int32, device=dev)}
+    a = L.PriorSelectArgs()
+    a.scores, a.logprobs = scores.data_ptr(), logprobs.data_ptr()
+    a.lp_n_stride, a.lp_t_stride = logprobs.stride(0), (logprobs.stride(1) if logprobs.dim() == 2 else 0)
+    if tokens is not None:
+        a.tokens, a.pad_token_id = tokens.data_ptr(), int(pad_token_id)
+        a.tok_n_stride, a.tok_t_stride = tokens.stride(0), (tokens.stride(1) if tokens.dim() == 2 else 0)
+    a.N, a.steps, a.group_size, a.top_m, a.beta, a.length_normalize = N, steps, group_size, top_m, beta, int(bool(length_normalize))
+    a.prior_out, a.combined_out, a.group_mean_out = out["prior"].data_ptr(), out["combined"].data_ptr(), out["group_mean"].data_ptr()
+    a.result_out, a.best_out, a.ranked_out = out["result"].data_ptr(), out["best"].data_ptr(), (out["ranked"].data_ptr() if top_m else None)
+    L.check(L.lib().cover_prior_select(C.byref(a), _stream()), "prior_select")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ graphs / timers
 class Graph:
     """hipGraph captured from whatever runs on the current stream inside the `with` block."""

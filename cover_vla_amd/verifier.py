@@ -456,10 +456,17 @@ class EfficientEnsembleMerged:
             its[i] = m.image_text(pf, tf)[0]
         return its
 
-    def score_histories(self, its: torch.Tensor, all_action_histories, group_size=1, pad: Optional[torch.Tensor] = None):
+    def score_histories(self, its: torch.Tensor, all_action_histories, group_size=1, pad: Optional[torch.Tensor] = None, *,
+                        prior: Optional[torch.Tensor] = None, prior_beta: float = 0.0, length_normalize: bool = False,
+                        prior_tokens: Optional[torch.Tensor] = None, pad_token_id: Optional[int] = None, top_m: int = 0):
         """Trajectory encoder per candidate + fusion + scoring + grouped arg-max against precomputed image-text embeddings.
         all_action_histories: list of [h<=10, 7] host arrays (reference format), OR an already padded DEVICE tensor
-        fp32 [N,10,7] together with its padding mask `pad` uint8 [N,10] (ops.tokens_to_histories): no host round trip."""
+        fp32 [N,10,7] together with its padding mask `pad` uint8 [N,10] (ops.tokens_to_histories): no host round trip.
+        prior (device fp32 [N] or [N, steps]: the candidates' log-probabilities under the policy, see ops.prior_select for the layouts,
+        prior_tokens / pad_token_id and length_normalize) makes the decision the grouped arg-max of scores + prior_beta * prior: one
+        ops.prior_select launch behind ops.score_select then supplies `result` / `best` (best[0] is the winner's COMBINED score) and the
+        dict gains prior, combined, group_mean and ranked (the best top_m of the winning group). top_m > 0 without a prior ranks by the
+        verifier score alone (beta 0). With prior None and top_m == 0 (the default) nothing else is launched or returned."""
         if torch.is_tensor(all_action_histories) and all_action_histories.is_cuda:
             hb = all_action_histories.contiguous()
         else:
@@ -477,12 +484,25 @@ class EfficientEnsembleMerged:
             for i, m in enumerate(self.trainable_models):
                 acts[i] = m.trajectory(hb, pad)
         scores, result, best, fit, fact = ops.score_select(its, acts, group_size)
-        return {"scores": scores, "result": result, "best": best, "its": its, "acts": acts, "fused_it": fit, "fused_act": fact}
+        out = {"scores": scores, "result": result, "best": best, "its": its, "acts": acts, "fused_it": fit, "fused_act": fact}
+        if prior is not None or top_m:
+            if prior is None:           # rank by the verifier score alone: beta 0 never reads the (summed) prior into the decision
+                sel = ops.prior_select(scores, scores, group_size, 0.0, top_m=top_m)
+                del sel["prior"]        # (the scores stood in for the unread log-probabilities)
+            else:
+                sel = ops.prior_select(scores, prior, group_size, prior_beta, tokens=prior_tokens, pad_token_id=pad_token_id,
+                                       length_normalize=length_normalize, top_m=top_m)
+            out.update(sel)
+        return out
 
-    def score_features(self, patch_features, text_features, all_action_histories, group_size=1):
+    def score_features(self, patch_features, text_features, all_action_histories, group_size=1, candidate_prior=None, prior_beta=0.0):
         """Scores every candidate history against ONE (image, text) pair given its features. Returns a dict with the
-        device tensors (scores [N], result int32[4], best f32[2]) plus per-member embeddings."""
-        return self.score_histories(self.image_text_embeddings(patch_features, text_features), all_action_histories, group_size)
+        device tensors (scores [N], result int32[4], best f32[2]) plus per-member embeddings. candidate_prior ([N] or [N, steps]
+        log-probabilities, host or device) with prior_beta: the decision is made on scores + prior_beta * prior (score_histories)."""
+        if candidate_prior is not None:
+            candidate_prior = torch.as_tensor(candidate_prior, dtype=torch.float32).to(self._dev)
+        return self.score_histories(self.image_text_embeddings(patch_features, text_features), all_action_histories, group_size,
+                                    prior=candidate_prior, prior_beta=prior_beta)
 
     def fuse_embeddings(self, image, instruction, action_histories):
         """efficient_ensemble_merged.py:249-293 -> (fused_image_text [N,512] (the one pair's embedding, a row per history),
@@ -515,12 +535,14 @@ class EfficientEnsembleMerged:
         return self.extract_shared_features(img_tensor, toks)
 
     def compute_max_similarity_scores_batch(self, images, instructions, all_action_histories,
-                                            cfg_repeat_language_instructions=1):
+                                            cfg_repeat_language_instructions=1, candidate_prior=None, prior_beta=0.0):
         """efficient_ensemble_merged.py:309-454. The reference scores candidates against the FIRST (image, text) pair only
-        (reference_scores = similarity_matrix[0], :421-425), on both of its encode paths, so one pair is encoded here."""
+        (reference_scores = similarity_matrix[0], :421-425), on both of its encode paths, so one pair is encoded here.
+        candidate_prior ([N] or [N, steps] policy log-probabilities) with prior_beta selects on score + prior_beta * prior; the
+        returned max_score is then the winner's COMBINED score, not its cosine score."""
         group_size = cfg_repeat_language_instructions
         pf, tf = self._encode_pair(images[0], instructions[0])
-        r = self.score_features(pf, tf, all_action_histories, group_size)
+        r = self.score_features(pf, tf, all_action_histories, group_size, candidate_prior=candidate_prior, prior_beta=prior_beta)
         result = r["result"].cpu()
         best = r["best"].cpu()
         gidx, gbest = int(result[0]), int(result[1])

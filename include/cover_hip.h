@@ -576,6 +576,39 @@ int cover_actions_to_histories(const float* actions, long long n_stride, long lo
 /* grouped arg-max over already-computed (e.g. all-gathered) scores: same selection rule as above */
 int cover_group_argmax(const float* scores, int N, int group_size, int* result_out, float* best_out, void* stream);
 
+/* Prior-weighted selection: the grouped arg-max of combined[n] = scores[n] + beta * prior[n], where prior[n] is the candidate's sequence
+ * log-probability under the policy, summed here from its per-step values, plus the best top_m members of the winning group in rank
+ * order. One launch, no workspace, recordable. Arithmetic (every sum that decides an index has a fixed result):
+ *   prior[n]    = fp32 sum of the counted logprobs[n][t] in step order t = 0, 1, ..., one chain of adds from 0.0f; a step is counted
+ *                 unless `tokens` is given and tokens[n][t] == pad_token_id; with length_normalize the sum is divided once by
+ *                 (float)max(count, 1); a candidate with no counted step has prior 0.0. steps = 1 takes a prior that is summed already.
+ *   combined[n] = scores[n] exactly when beta == 0.0f (no product: a -inf prior cannot make a NaN), else
+ *                 round(scores[n] + round(beta * prior[n])): two fp32 roundings, never an fma. A -inf prior gives -inf.
+ *   groups      = cover_group_argmax on combined (the same device code): group mean = index-order fp32 sum / group_size, first
+ *                 maximum wins; a group holding a -inf has mean -inf; if every group does, group 0 wins.
+ *   ranked[r]   = global index of the member of the winning group with rank r < top_m in (descending combined, ascending index)
+ *                 order, so ranked[0] == result_out[0].
+ * The two stride pairs (in elements) read candidate-major [N][steps] and step-major [steps][N] buffers alike, without a copy.
+ * COVER_EINVAL unless N >= 1, group_size >= 1, N % group_size == 0, N / group_size <= 4096, group_size <= 4096, 1 <= steps <= 4096,
+ * 0 <= top_m <= min(group_size, 64), beta finite and >= 0, the required pointers non-null and ranked_out non-null when top_m > 0. */
+typedef struct cover_prior_select_args {
+    const float* scores;            /* [N] verifier scores */
+    const float* logprobs;          /* element (n, t) at logprobs[n * lp_n_stride + t * lp_t_stride] */
+    long long lp_n_stride, lp_t_stride;
+    const int64_t* tokens;          /* optional, element (n, t) at tokens[n * tok_n_stride + t * tok_t_stride] */
+    long long tok_n_stride, tok_t_stride;
+    long long pad_token_id;         /* with tokens: steps whose token equals it are not counted */
+    int N, steps, group_size, top_m;
+    float beta; int length_normalize;
+    float* prior_out;               /* [N] */
+    float* combined_out;            /* [N] */
+    float* group_mean_out;          /* [N / group_size], optional */
+    int* result_out;                /* int32 [4] = {global_idx, group_idx, idx_in_group, 0}, as cover_group_argmax */
+    float* best_out;                /* float [2] = {combined of the winner, mean of its group} */
+    int* ranked_out;                /* int32 [top_m] global indices, optional when top_m == 0 */
+} cover_prior_select_args;
+int cover_prior_select(const cover_prior_select_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Composite forwards: the per-layer Python loops of the reference (18-layer loop in
  * paligemma_with_expert.py:258-349, HF/timm encoder loops) run here in C++ so that a whole tower / prefill /
