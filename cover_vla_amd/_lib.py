@@ -131,6 +131,25 @@ class TokenTopnArgs(C.Structure):
                 ("entropy_out", c_p), ("kept_out", c_p)]
 
 
+class TokenSampleRowsArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i),
+                ("uniform", c_p), ("temperature", c_p), ("top_k", c_p), ("top_p", c_p),
+                ("token_out", c_p), ("logit_out", c_p), ("kept_out", c_p), ("logprob_out", c_p)]
+
+
+class TokenLogprobRowsArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i),
+                ("temperature", c_p), ("top_k", c_p), ("top_p", c_p),
+                ("token", c_p), ("logprob_out", c_p), ("kept_out", c_p)]
+
+
+class TokenTopnRowsArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i),
+                ("temperature", c_p), ("top_k", c_p), ("top_p", c_p), ("n", c_i),
+                ("token_out", c_p), ("ld_tok", c_ll), ("logprob_out", c_p), ("ld_lp", c_ll),
+                ("entropy_out", c_p), ("kept_out", c_p)]
+
+
 class DecodeFeedbackArgs(C.Structure):
     _fields_ = [("pick", c_p), ("force", c_p), ("force_stride", c_ll), ("lp", c_p), ("lp_out", c_p), ("ld_lp", c_ll),
                 ("done", c_p), ("tok_out", c_p), ("ld_tok", c_ll), ("eos", c_ll), ("pad", c_ll),
@@ -201,7 +220,9 @@ _STRUCTS = {
     "cover_rope_args": RopeArgs, "cover_patchify_args": PatchifyArgs, "cover_gemm_f32_args": GemmF32Args,
     "cover_mha_f32_args": MhaF32Args, "cover_token_select_args": TokenSelectArgs,
     "cover_token_sample_args": TokenSampleArgs, "cover_token_sample_scored_args": TokenSampleScoredArgs,
-    "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs, "cover_decode_feedback_args": DecodeFeedbackArgs,
+    "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs,
+    "cover_token_sample_rows_args": TokenSampleRowsArgs, "cover_token_logprob_rows_args": TokenLogprobRowsArgs,
+    "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
@@ -257,6 +278,9 @@ SYMBOLS = {
     "cover_token_sample_scored": (c_i, [_P(TokenSampleScoredArgs), c_p]),
     "cover_token_logprob": (c_i, [_P(TokenLogprobArgs), c_p]),
     "cover_token_topn": (c_i, [_P(TokenTopnArgs), c_p]),
+    "cover_token_sample_rows": (c_i, [_P(TokenSampleRowsArgs), c_p]),
+    "cover_token_logprob_rows": (c_i, [_P(TokenLogprobRowsArgs), c_p]),
+    "cover_token_topn_rows": (c_i, [_P(TokenTopnRowsArgs), c_p]),
     "cover_decode_feedback": (c_i, [_P(DecodeFeedbackArgs), c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),

@@ -443,18 +443,19 @@ __device__ __forceinline__ float kept_logprob(const KeptSet& ks, float l, int re
     return (float)((double)x - (log((double)mass) - 43.0 * 0.693147180559945309417232121458));
 }
 
-template <bool SCORED>
-__global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args a, float* logprob_out) {
-    __shared__ SampleShared s;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* lg = a.logits + (size_t)row * a.ld;
-    const int n = a.hi - a.lo;
-    SampleSrc src{lg + a.lo, n, false};
-    const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
+// One row of the sampler: steps 1-4 of cover_token_sample over columns [lo, hi) of lg with the uniform u. Every thread of the block calls
+// this; thread 0 stores. logprob_out == nullptr: no score. token_sample_k and token_sample_rows_k are this function with the launch's and
+// the row's parameters respectively, so a row means the same in both.
+__device__ __forceinline__ void sample_row(SampleShared& s, const float* lg, int lo, int hi, float temperature, int top_k, float top_p, float u,
+                                           int row, int64_t* token_out, float* logit_out, int* kept_out, float* logprob_out) {
+    const int tid = threadIdx.x;
+    const int n = hi - lo;
+    SampleSrc src{lg + lo, n, false};
+    const KeptSet ks = kept_set(s, src, top_k, top_p, temperature);
 
     // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
     const int shift = kept_tiles(s, src, ks);
-    scan_bins<false, true>(s, SMP_BINS, 0ull, 2, (double)a.uniform[row]);
+    scan_bins<false, true>(s, SMP_BINS, 0ull, 2, (double)u);
     const int tile = s.r_bin;
     const unsigned kept = s.r_cnt_total;
     const u64 mass = s.r_mass_total;
@@ -469,31 +470,42 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
     if (tid == 0) {
         int pick = t0 + s.r_bin;
         pick = pick < 0 ? 0 : (pick < n ? pick : n - 1);
-        a.token_out[row] = a.lo + pick;
-        const float l = lg[a.lo + pick];
-        if (a.logit_out) a.logit_out[row] = l;
-        if (a.kept_out) a.kept_out[row] = (int)kept;
-        if (SCORED) logprob_out[row] = kept_logprob(ks, l, pick, mass);
+        token_out[row] = lo + pick;
+        const float l = lg[lo + pick];
+        if (logit_out) logit_out[row] = l;
+        if (kept_out) kept_out[row] = (int)kept;
+        if (logprob_out) logprob_out[row] = kept_logprob(ks, l, pick, mass);
     }
 }
 
-// Scores given tokens: the kept set and its mass as the sampler computes them (the same two device functions), no pick.
-__global__ __launch_bounds__(SMP_T) void token_logprob_k(cover_token_logprob_args a) {
+template <bool SCORED>
+__global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args a, float* logprob_out) {
     __shared__ SampleShared s;
     const int row = blockIdx.x;
-    const float* lg = a.logits + (size_t)row * a.ld;
-    const int n = a.hi - a.lo;
-    SampleSrc src{lg + a.lo, n, false};
-    const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
+    sample_row(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, a.temperature, a.top_k, a.top_p, a.uniform[row], row, a.token_out, a.logit_out,
+               a.kept_out, SCORED ? logprob_out : nullptr);
+}
+
+// Scores given tokens: the kept set and its mass as the sampler computes them (the same two device functions), no pick.
+__device__ __forceinline__ void logprob_row(SampleShared& s, const float* lg, int lo, int hi, float temperature, int top_k, float top_p,
+                                            int row, const int64_t* token, float* logprob_out, int* kept_out) {
+    const int n = hi - lo;
+    SampleSrc src{lg + lo, n, false};
+    const KeptSet ks = kept_set(s, src, top_k, top_p, temperature);
     kept_tiles(s, src, ks);
     scan_bins<false, true>(s, SMP_BINS, 1ull);
     if (threadIdx.x == 0) {
-        const long long t = (long long)a.token[row];
+        const long long t = (long long)token[row];
         float lp = -INFINITY;
-        if (t >= (long long)a.lo && t < (long long)a.hi) lp = kept_logprob(ks, lg[t], (int)(t - a.lo), s.r_mass_total);
-        a.logprob_out[row] = lp;
-        if (a.kept_out) a.kept_out[row] = (int)s.r_cnt_total;
+        if (t >= (long long)lo && t < (long long)hi) lp = kept_logprob(ks, lg[t], (int)(t - lo), s.r_mass_total);
+        logprob_out[row] = lp;
+        if (kept_out) kept_out[row] = (int)s.r_cnt_total;
     }
+}
+__global__ __launch_bounds__(SMP_T) void token_logprob_k(cover_token_logprob_args a) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x;
+    logprob_row(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, a.temperature, a.top_k, a.top_p, row, a.token, a.logprob_out, a.kept_out);
 }
 
 // The n most probable kept tokens of a row with their log-probabilities, and the entropy of the kept distribution. The kept set and
@@ -505,10 +517,9 @@ struct TopnShared {
     int rel[64];
 };
 
-__global__ __launch_bounds__(SMP_T) void token_topn_k(cover_token_topn_args a) {
-    __shared__ SampleShared s;
-    __shared__ TopnShared t;
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+// One row of cover_token_topn; a carries the row's (temperature, top_k, top_p): the launch's in token_topn_k, the row's own in token_topn_rows_k.
+__device__ __forceinline__ void topn_row(SampleShared& s, TopnShared& t, const cover_token_topn_args& a, int row) {
+    const int tid = threadIdx.x, lane = tid & 63;
     const float* lg = a.logits + (size_t)row * a.ld;
     const int n = a.hi - a.lo;
     SampleSrc src{lg + a.lo, n, false};
@@ -636,6 +647,119 @@ __global__ __launch_bounds__(SMP_T) void token_topn_k(cover_token_topn_args a) {
         }
     }
 }
+__global__ __launch_bounds__(SMP_T) void token_topn_k(cover_token_topn_args a) {
+    __shared__ SampleShared s;
+    __shared__ TopnShared t;
+    topn_row(s, t, a, blockIdx.x);
+}
+
+// ---- parameters per row (cover_token_*_rows) --------------------------------------------------------------------------------
+// A row's (temperature, top_k, top_p) come from device arrays; everything else is the scalar kernels' row functions above, so a row
+// computes what the scalar kernel computes for it. Block-uniform: every thread reads the same three words.
+struct RowParams {
+    float T;
+    int k;
+    float p;
+    int mode;   // 0: sampled, 1: greedy (temperature 0; T / k / p are then 1 / 0 / 1, what a greedy pick is scored under), 2: invalid
+};
+__device__ __forceinline__ RowParams row_params(const float* temperature, const int* top_k, const float* top_p, int row) {
+    RowParams r{1.0f, 0, 1.0f, 0};
+    const float T = temperature[row];
+    if (T == 0.0f) {   // top_k[row] / top_p[row] are not read
+        r.mode = 1;
+        return r;
+    }
+    if (!(T > 0.0f)) {   // negative or NaN
+        r.mode = 2;
+        return r;
+    }
+    r.T = T;
+    if (top_k) r.k = top_k[row];
+    if (top_p) r.p = top_p[row];
+    if (r.k < 0 || !(r.p > 0.0f)) r.mode = 2;
+    return r;
+}
+
+__global__ __launch_bounds__(SMP_T) void token_sample_rows_k(cover_token_sample_rows_args a) {
+    __shared__ SampleShared s;
+    __shared__ int first;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    if (rp.mode == 2) {   // block-uniform
+        if (tid == 0) {
+            a.token_out[row] = -1;
+            if (a.logit_out) a.logit_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+            if (a.logprob_out) a.logprob_out[row] = NAN;
+        }
+        return;
+    }
+    const float* lg = a.logits + (size_t)row * a.ld;
+    if (rp.mode == 0) {
+        sample_row(s, lg, a.lo, a.hi, rp.T, rp.k, rp.p, a.uniform[row], row, a.token_out, a.logit_out, a.kept_out, a.logprob_out);
+        return;
+    }
+    // greedy: the first arg-max of the input floats; its log-probability is logprob_row's at temperature 1, unfiltered (the same calls)
+    const int n = a.hi - a.lo;
+    SampleSrc src{lg + a.lo, n, false};
+    if (tid == 0) first = 0x7fffffff;
+    const KeptSet ks = kept_set(s, src, 0, 1.0f, 1.0f);   // the row maximum (NaNs never win, as in token_select_k); syncs the block
+    kept_tiles(s, src, ks);
+    scan_bins<false, true>(s, SMP_BINS, 1ull);
+    int mine = 0x7fffffff;
+    for_each(s, src, [&](float l, int rel) {
+        if (l == ks.m && rel < mine) mine = rel;
+    });
+    if (mine != 0x7fffffff) atomicMin(&first, mine);
+    __syncthreads();
+    if (tid == 0) {
+        int pick = first;
+        pick = pick < n ? pick : 0;   // a row of NaNs has no maximum
+        a.token_out[row] = a.lo + pick;
+        const float l = lg[a.lo + pick];
+        if (a.logit_out) a.logit_out[row] = l;
+        if (a.kept_out) a.kept_out[row] = n;
+        if (a.logprob_out) a.logprob_out[row] = kept_logprob(ks, l, pick, s.r_mass_total);
+    }
+}
+
+__global__ __launch_bounds__(SMP_T) void token_logprob_rows_k(cover_token_logprob_rows_args a) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    if (rp.mode == 2) {
+        if (threadIdx.x == 0) {
+            a.logprob_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+        }
+        return;
+    }
+    logprob_row(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, rp.T, rp.k, rp.p, row, a.token, a.logprob_out, a.kept_out);
+}
+
+__global__ __launch_bounds__(SMP_T) void token_topn_rows_k(cover_token_topn_rows_args a) {
+    __shared__ SampleShared s;
+    __shared__ TopnShared t;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    if (rp.mode == 2) {
+        if (tid < a.n) {
+            a.token_out[(size_t)row * a.ld_tok + tid] = -1;
+            a.logprob_out[(size_t)row * a.ld_lp + tid] = -INFINITY;
+        }
+        if (tid == 0) {
+            if (a.entropy_out) a.entropy_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+        }
+        return;
+    }
+    cover_token_topn_args b;
+    b.logits = a.logits; b.ld = a.ld; b.rows = a.rows; b.lo = a.lo; b.hi = a.hi;
+    b.temperature = rp.T; b.top_k = rp.k; b.top_p = rp.p; b.n = a.n;
+    b.token_out = a.token_out; b.ld_tok = a.ld_tok; b.logprob_out = a.logprob_out; b.ld_lp = a.ld_lp;
+    b.entropy_out = a.entropy_out; b.kept_out = a.kept_out;
+    topn_row(s, t, b, row);
+}
 
 __global__ void fill_i32_k(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -689,6 +813,34 @@ static hipError_t launch_token_sample_impl(const cover_token_sample_args* a, flo
     }
     if (logprob_out) hipLaunchKernelGGL(token_sample_k<true>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
     else hipLaunchKernelGGL(token_sample_k<false>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
+    return hipGetLastError();
+}
+
+// the per-row parameters live on the device: only the launch's own shape is checked here, a bad row reports itself (see row_params)
+static bool sample_rows_ok(int lo, int hi, int rows) { return hi > lo && lo >= 0 && hi - lo <= (1 << 20) && rows >= 0; }
+
+hipError_t launch_token_sample_rows(const cover_token_sample_rows_args* a, hipStream_t st) {
+    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_sample_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_logprob_rows(const cover_token_logprob_rows_args* a, hipStream_t st) {
+    if (!a->logits || !a->temperature || !a->token || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_logprob_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_topn_rows(const cover_token_topn_rows_args* a, hipStream_t st) {
+    if (!a->logits || !a->temperature || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
+    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_topn_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
     return hipGetLastError();
 }
 

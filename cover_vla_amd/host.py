@@ -59,6 +59,29 @@ class TopLogprobs(NamedTuple):
     entropy: Any       # fp32 [N, steps]
 
 
+def sampling_ladder(n_prompts: int, n_samples: int, temperature, top_k=0, top_p=1.0):
+    """The per-candidate sampling parameters of a best-of-N proposal ladder: every prompt's n_samples candidates get the same ladder
+    (typically one greedy candidate, temperature 0, then samples at rising temperatures or looser filters). Each argument is a scalar
+    or a length-n_samples sequence; returns (temperature float32, top_k int32, top_p float32) numpy arrays [n_prompts * n_samples] in
+    which candidate i carries entry i % n_samples -- the "candidate i belongs to prompt i // n_samples" order of OpenVLA.sample, whose
+    temperature / top_k / top_p arguments take these arrays. Values must be finite with temperature >= 0, top_k >= 0 (an integer) and
+    top_p > 0. Index bookkeeping only."""
+    if int(n_prompts) < 1 or int(n_samples) < 1:
+        raise ValueError("sampling_ladder: n_prompts and n_samples must be >= 1")
+    out = []
+    for name, v, dt, ok in (("temperature", temperature, np.float32, lambda a: a >= 0), ("top_k", top_k, np.int32, lambda a: a >= 0),
+                            ("top_p", top_p, np.float32, lambda a: a > 0)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(int(n_samples), float(a))
+        if a.shape != (int(n_samples),):
+            raise ValueError(f"sampling_ladder: {name} must be a scalar or have one entry per sample ({n_samples}), got shape {a.shape}")
+        if not np.all(np.isfinite(a)) or not np.all(ok(a)) or (dt is np.int32 and np.any(a != np.rint(a))):
+            raise ValueError(f"sampling_ladder: {name} out of range (temperature >= 0, integer top_k >= 0, top_p > 0, all finite)")
+        out.append(np.tile(a, int(n_prompts)).astype(dt))
+    return tuple(out)
+
+
 def step_entropy_summary(entropy, tokens=None, pad_id=None):
     """Per-candidate (mean, max) of the per-step entropies over the steps the candidate was live: entropy [N, steps] (torch tensor on
     any device, or numpy) -> two [N] of the same kind. With tokens [N, steps] and pad_id the steps whose emitted token is the pad are

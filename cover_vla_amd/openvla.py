@@ -26,6 +26,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .host import TopLogprobs
+from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower, _f32
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -195,9 +196,9 @@ class OpenVLA:
 
     # ---------------------------------------------------------------------------------------------- sampler
     def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
-               uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, trace: Optional[dict] = None,
+               uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, trace: Optional[dict] = None,
                force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
-               top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False, top_logprobs: int = 0):
+               top_k: RowParam = 0, top_p: RowParam = 1.0, return_logprobs: bool = False, top_logprobs: int = 0):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
         uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
@@ -214,7 +215,16 @@ class OpenVLA:
         top_logprobs = n in 1..64: appends host.TopLogprobs(tokens int64 [N, n_gen, n], logprobs fp32 [N, n_gen, n], entropy fp32
         [N, n_gen]) to the return: per step the n most probable tokens of the distribution return_logprobs documents (descending logit,
         equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities (cover_token_logprob's, bit for
-        bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used. 0: today's launches."""
+        bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used. 0: today's launches.
+        Parameters per candidate: temperature, top_k and top_p each accept a scalar or a length-N sequence / tensor (host.sampling_ladder
+        builds them). All scalars is the path above, untouched. As soon as one of the three is per candidate, all three are validated on
+        the host (temperature >= 0, top_k >= 0, top_p > 0, all finite, else CoverError; a device tensor of any numeric dtype is read back
+        once for it, so no pick is ever the -1 of an invalid row), broadcast to fp32 / int32 / fp32 [N] device tensors and every step's pick is ONE ops.token_sample_rows launch (ops.pick_token(row_params=)); uniforms is then
+        required, return_logprobs is that launch's log-probability and top_logprobs is ops.token_topn_rows. In this mode EVERY row picks
+        over the action bins [action_lo, action_hi), the launch's range: a candidate with temperature 0 is greedy and takes the arg-max
+        over the 256 action bins (its log-probability: temperature 1, unfiltered, over those bins), whereas an all-greedy call
+        (uniforms=None) keeps its arg-max over the tokenizer vocabulary. The decode graph is keyed on the fact "per-row parameters", not
+        on their values: the three tensors are static buffers filled before each replay, so a new ladder is not a new capture."""
         c, dev = self.c, self.dev
         n_top = int(top_logprobs)
         if not 0 <= n_top <= 64:
@@ -258,10 +268,18 @@ class OpenVLA:
         last_row = (Tp + prompt_of_cand * Lt + cand_len - 1).to(torch.int32)
         pos_all = ((T0 + cand_len)[None, :] + torch.arange(self.n_gen, dtype=torch.int32, device=dev)[:, None]).contiguous()
         u_t = None if uniforms is None else uniforms.to(torch.float32).t().contiguous()
-        filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
+        rp = None
+        if any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
+            if uniforms is None:
+                raise ValueError("per-candidate temperature / top_k / top_p need uniforms (a greedy candidate is a temperature of 0)")
+            rp = ops.row_param_tensors(N, temperature, top_k, top_p, dev)
+            temperature, filt = None, None
+        else:
+            filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
             # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
-            key = (P, n_samples, Lt, uniforms is None, float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ())
+            # per-row parameters: the key carries the fact, the values live in static buffers (st["rp"]) like the uniforms
+            key = (P, n_samples, Lt, uniforms is None, "rows" if rp is not None else float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ())
             st = self._dec.get(key)
             if st is None:
                 st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
@@ -269,15 +287,18 @@ class OpenVLA:
                           sel=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev),
                           u=None if u_t is None else torch.empty_like(u_t),
                           lps=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None,
-                          top=self._top_bufs(N, n_top),
+                          top=self._top_bufs(N, n_top), rp=None if rp is None else tuple(torch.empty_like(t) for t in rp),
                           prompt_slots=torch.arange(P, dtype=torch.int32, device=dev), prompt_lens=torch.empty(P, dtype=torch.int32, device=dev))
                 self._dec[key] = st
             st["cand_len"].copy_(cand_len); st["last_row"].copy_(last_row); st["pos_all"].copy_(pos_all)
             st["prompt_lens"].copy_(prompt_lens.to(torch.int32))
             if u_t is not None:
                 st["u"].copy_(u_t)
+            if rp is not None:
+                for dst, src in zip(st["rp"], rp):
+                    dst.copy_(src)
             body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"])
+                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"], rp=st["rp"])
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -303,7 +324,7 @@ class OpenVLA:
         top = self._top_bufs(N, n_top)
         fed = tokens if force_tokens is None else force_tokens.t().contiguous()
         self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top)
+                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top, rp=rp)
         return self._sample_result(tokens, sel, lps, top)
 
     def _top_bufs(self, N, n_top):
@@ -325,11 +346,11 @@ class OpenVLA:
         return out
 
     def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None):
+                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None, rp=None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
         ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top)
+        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top, rp)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
@@ -341,24 +362,27 @@ class OpenVLA:
                                 dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top)
+            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top, rp)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None):
+    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None, rp=None):
         """Norm, head GEMM, one ops.pick_token. filt: None = the unfiltered ops.token_select pick; (top_k, top_p) = ops.token_sample over
         the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks.
-        top (tokens, logprobs, entropy) or None: slab i receives ops.token_topn of the distribution the pick came from."""
+        top (tokens, logprobs, entropy) or None: slab i receives ops.token_topn of the distribution the pick came from.
+        rp (temperature, top_k, top_p) device tensors [N] or None: the pick is ops.token_sample_rows, the top-n ops.token_topn_rows."""
         N = h.shape[0]
         u = None if uniforms is None else uniforms[i]
         # out_kept: written by the filtered pick (ops.token_sample) only
         out = dict(out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=None if lps is None else lps[i])
+        if rp is not None:
+            out["row_params"] = rp
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
         if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
             t, _, _ = ops.pick_token(lg, 0, self.c["n_bins"], u, temperature, filt, **out)
             torch.add(t, self.action_lo, out=tokens[i])
             if top is not None:
-                self._head_topn(lg, 0, self.c["n_bins"], uniforms is None, temperature, filt, top, i)
+                self._head_topn(lg, 0, self.c["n_bins"], uniforms is None, temperature, filt, top, i, rp)
                 top[0][i].add_((top[0][i] >= 0) * self.action_lo)          # ids as the tokens are; the -1 padding stays
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
@@ -367,11 +391,15 @@ class OpenVLA:
         lo, hi = (0, self.c["tok_vocab"]) if uniforms is None else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
         ops.pick_token(lg, lo, hi, u, temperature, filt, out_tok=tokens[i], **out)
         if top is not None:
-            self._head_topn(lg, lo, hi, uniforms is None, temperature, filt, top, i)
+            self._head_topn(lg, lo, hi, uniforms is None, temperature, filt, top, i, rp)
 
     @staticmethod
-    def _head_topn(lg, lo, hi, greedy, temperature, filt, top, i):
-        """One ops.token_topn launch on step i's logits; greedy: temperature 1, unfiltered (what return_logprobs scores a greedy pick under)."""
+    def _head_topn(lg, lo, hi, greedy, temperature, filt, top, i, rp=None):
+        """One ops.token_topn launch on step i's logits; greedy: temperature 1, unfiltered (what return_logprobs scores a greedy pick under).
+        rp: ops.token_topn_rows with the parameters of every row its own."""
+        if rp is not None:
+            ops.token_topn_rows(lg, lo, hi, top[0].shape[2], rp[0], rp[1], rp[2], out_tok=top[0][i], out_logprob=top[1][i], out_entropy=top[2][i])
+            return
         k, p = (0, 1.0) if greedy or filt is None else filt
         ops.token_topn(lg, lo, hi, top[0].shape[2], 1.0 if greedy else temperature, k, p, out_tok=top[0][i], out_logprob=top[1][i],
                        out_entropy=top[2][i])

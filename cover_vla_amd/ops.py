@@ -7,8 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -679,12 +680,172 @@ def token_topn(logits, lo, hi, n, temperature=1.0, top_k=0, top_p=1.0, out_tok=N
     return tok, lp, ent
 
 
-def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None):
+def _row_params(what, rows, temperature, top_k, top_p):
+    """The per-row parameter arguments of the *_rows wrappers, checked on the host: (temperature, top_k, top_p, upload). A device tensor
+    must be contiguous fp32 / int32 / fp32 [rows] and passes as it is (its values are the kernel's to judge: an invalid row reports
+    itself). A Python sequence, numpy array or CPU tensor is validated here -- every temperature >= 0, top_p > 0, top_k >= 0, all
+    finite -- and comes back as a CPU tensor of the right dtype for the caller to upload once the other arguments have passed."""
+    out = []
+    for name, v, dt, ok, rule in (("temperature", temperature, torch.float32, lambda a: a >= 0, ">= 0 (0 marks a greedy row)"),
+                                  ("top_k", top_k, torch.int32, lambda a: a >= 0, ">= 0"), ("top_p", top_p, torch.float32, lambda a: a > 0, "> 0")):
+        if v is None:
+            if name == "temperature":
+                raise L.CoverError(f"{what}: temperature [rows] is required")
+            out.append(None)
+        elif isinstance(v, torch.Tensor) and v.is_cuda:
+            if v.dtype != dt or v.dim() != 1 or v.numel() != rows or not v.is_contiguous():
+                raise L.CoverError(f"{what}: {name} must be a contiguous {dt} device tensor [rows = {rows}]")
+            out.append(v)
+        else:
+            try:
+                a = np.asarray(v.numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise L.CoverError(f"{what}: {name} must be numeric [rows]") from e
+            if a.shape != (rows,):
+                raise L.CoverError(f"{what}: {name} must have one entry per row ({rows}), got shape {a.shape}")
+            if not np.all(np.isfinite(a)) or not np.all(ok(a)) or (dt == torch.int32 and (np.any(a != np.rint(a)) or np.any(a > 2 ** 31 - 1))):
+                raise L.CoverError(f"{what}: every {name} must be finite and {rule}")
+            out.append(torch.from_numpy(a).to(dt))
+    return out
+
+
+# a sampling parameter of the models: one scalar, or one entry per row (sequence, numpy array, CPU or device tensor of any numeric dtype)
+RowParam = Union[float, int, Sequence[float], np.ndarray, torch.Tensor]
+
+
+def is_per_row(v) -> bool:
+    """Is a sampling parameter given per row (a sequence, an array or a tensor with a dimension) and not as one scalar?"""
+    if isinstance(v, (torch.Tensor, np.ndarray)):
+        return v.ndim > 0
+    return isinstance(v, (list, tuple))
+
+
+def row_param_tensors(rows, temperature, top_k, top_p, device):
+    """(temperature fp32, top_k int32, top_p fp32) device tensors [rows] from arguments that are each a scalar or one entry per row:
+    what the models hand to pick_token(row_params=). Every value is validated on the host as in token_sample_rows -- a device tensor (of any
+    numeric dtype) is read back once for it -- so a call that returns never leads to an invalid row: the models feed each pick to an
+    embedding gather, which the -1 of an invalid row must not reach."""
+    def wide(v):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+        return np.full(rows, float(v)) if not is_per_row(v) else v
+    params = _row_params("row_param_tensors", rows, wide(temperature), wide(top_k), wide(top_p))
+    return tuple(_upload_row_params(params, device))
+
+
+def _upload_row_params(params, device):
+    return [p if p is None or p.is_cuda else p.to(device) for p in params]
+
+
+def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=None, out_tok=None, out_logit=None, out_kept=None,
+                      out_logprob=None):
+    """token_sample with the parameters of every row its own (cover_token_sample_rows): temperature fp32 / top_k int32 / top_p fp32 device
+    tensors [rows] (top_k None = 0, top_p None = 1 for every row); a Python sequence or CPU tensor is validated on the host
+    (temperature >= 0, top_p > 0, top_k >= 0, all finite) and uploaded. temperature[r] > 0: row r is token_sample's row with its
+    parameters, always on the integer masses (no token_select detour for a narrow unfiltered range). temperature[r] == 0: a greedy row,
+    token = the first arg-max over [lo, hi), kept = hi - lo, log-probability at temperature 1 unfiltered; its top_k / top_p / uniform
+    entries are not read. A row whose device-side parameters are invalid writes token -1, logit / log-probability NaN, kept 0.
+    Returns (token int64 [rows], its raw logit fp32 [rows], kept int32 [rows]); out_* as in token_sample. One launch, recordable,
+    deterministic: a row's result does not depend on the other rows of the launch."""
+    if uniform is None:
+        raise L.CoverError("token_sample_rows needs uniforms [rows] (a greedy row ignores its entry)")
+    if hi <= lo or lo < 0:
+        raise L.CoverError(f"token_sample_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
+        raise L.CoverError("token_sample_rows: logits must be fp32 [rows, >= hi] with unit column stride")
+    rows = logits.shape[0]
+    params = _row_params("token_sample_rows", rows, temperature, top_k, top_p)
+    if uniform.dtype != torch.float32 or uniform.numel() != rows or not uniform.is_contiguous():
+        raise L.CoverError("token_sample_rows: uniform must be contiguous fp32 [rows]")
+    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logit", out_logit, torch.float32), ("out_kept", out_kept, torch.int32),
+                        ("out_logprob", out_logprob, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise L.CoverError(f"token_sample_rows: {name} must be contiguous {dt} [rows]")
+    _chk_dev(logits, uniform, out_tok, out_logit, out_kept, out_logprob)
+    T, k, p = _upload_row_params(params, logits.device)
+    tok = torch.empty(rows, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
+    lg = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_logit is None else out_logit
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if out_kept is None else out_kept
+    a = L.TokenSampleRowsArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), T.data_ptr(), _ptr(k), _ptr(p)
+    a.token_out, a.logit_out, a.kept_out, a.logprob_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr(), _ptr(out_logprob)
+    L.check(L.lib().cover_token_sample_rows(C.byref(a), _stream()), "token_sample_rows")
+    return tok, lg, kept
+
+
+def token_logprob_rows(logits, lo, hi, tokens, temperature, top_k=None, top_p=None, out=None, out_kept=None):
+    """token_logprob with the parameters of every row its own (cover_token_logprob_rows; the parameter arguments as in
+    token_sample_rows). A greedy row (temperature 0) is scored at temperature 1, unfiltered; a row with invalid device-side parameters
+    gives NaN and kept 0. On token_sample_rows' own picks it equals that call's out_logprob bit for bit."""
+    if hi <= lo or lo < 0:
+        raise L.CoverError(f"token_logprob_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
+        raise L.CoverError("token_logprob_rows: logits must be fp32 [rows, >= hi] with unit column stride")
+    rows = logits.shape[0]
+    params = _row_params("token_logprob_rows", rows, temperature, top_k, top_p)
+    if tokens.dtype != torch.int64 or tokens.numel() != rows or not tokens.is_contiguous():
+        raise L.CoverError("token_logprob_rows: tokens must be contiguous int64 [rows]")
+    for name, t, dt in (("out", out, torch.float32), ("out_kept", out_kept, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise L.CoverError(f"token_logprob_rows: {name} must be contiguous {dt} [rows]")
+    _chk_dev(logits, tokens, out, out_kept)
+    T, k, p = _upload_row_params(params, logits.device)
+    lp = torch.empty(rows, dtype=torch.float32, device=logits.device) if out is None else out
+    a = L.TokenLogprobRowsArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.temperature, a.top_k, a.top_p = T.data_ptr(), _ptr(k), _ptr(p)
+    a.token, a.logprob_out, a.kept_out = tokens.data_ptr(), lp.data_ptr(), _ptr(out_kept)
+    L.check(L.lib().cover_token_logprob_rows(C.byref(a), _stream()), "token_logprob_rows")
+    return lp
+
+
+def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_tok=None, out_logprob=None, out_entropy=None, out_kept=None):
+    """token_topn with the parameters of every row its own (cover_token_topn_rows; the parameter arguments as in token_sample_rows).
+    A greedy row (temperature 0) is ranked at temperature 1, unfiltered; a row with invalid device-side parameters gives -1 / -inf in
+    every slot, entropy NaN and kept 0. Returns (tokens int64 [rows, n], logprobs fp32 [rows, n], entropy fp32 [rows])."""
+    if hi <= lo or lo < 0:
+        raise L.CoverError(f"token_topn_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
+    if not 1 <= int(n) <= 64:
+        raise L.CoverError(f"token_topn_rows: 1 <= n <= 64 is required (got n={n})")
+    n = int(n)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
+        raise L.CoverError("token_topn_rows: logits must be fp32 [rows, >= hi] with unit column stride")
+    rows = logits.shape[0]
+    params = _row_params("token_topn_rows", rows, temperature, top_k, top_p)
+    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, n) or (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n)):
+            raise L.CoverError(f"token_topn_rows: {name} must be {dt} [rows, n] with unit column stride and a row stride >= n")
+    for name, t, dt in (("out_entropy", out_entropy, torch.float32), ("out_kept", out_kept, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise L.CoverError(f"token_topn_rows: {name} must be contiguous {dt} [rows]")
+    _chk_dev(logits, out_tok, out_logprob, out_entropy, out_kept)
+    T, k, p = _upload_row_params(params, logits.device)
+    tok = torch.empty(rows, n, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
+    lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if out_logprob is None else out_logprob
+    ent = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_entropy is None else out_entropy
+    a = L.TokenTopnRowsArgs()
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    a.temperature, a.top_k, a.top_p, a.n = T.data_ptr(), _ptr(k), _ptr(p), n
+    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
+    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
+    a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    L.check(L.lib().cover_token_topn_rows(C.byref(a), _stream()), "token_topn_rows")
+    return tok, lp, ent
+
+
+def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None,
+               row_params=None):
     """One decode step's pick over columns [lo, hi), the three-way choice of every token head. Returns (token, its logit, kept or None).
     uniform None: greedy token_select (temperature and filt are unused); uniform with filt None: token_select's unfiltered inverse-CDF
     sample; uniform with filt = (top_k, top_p): ONE token_sample call, whose kept count is returned. out_logprob fp32 [rows]: filled with
     the log-probability of each pick under the distribution it came from (greedy: temperature 1, unfiltered), by token_sample itself or
-    by one token_logprob launch behind token_select. The out_* rows are the wrappers' own; no arithmetic or allocation of its own."""
+    by one token_logprob launch behind token_select. The out_* rows are the wrappers' own; no arithmetic or allocation of its own.
+    row_params = (temperature, top_k, top_p) device tensors [rows]: ONE token_sample_rows call with the parameters of every row its own
+    (uniform is required, temperature and filt are unused; a row with temperature 0 is greedy); its kept count is returned."""
+    if row_params is not None:
+        return token_sample_rows(logits, lo, hi, uniform, row_params[0], row_params[1], row_params[2], out_tok=out_tok, out_logit=out_logit,
+                                 out_kept=out_kept, out_logprob=out_logprob)
     if uniform is not None and filt is not None:
         return token_sample(logits, lo, hi, uniform, temperature=temperature, top_k=filt[0], top_p=filt[1], out_tok=out_tok,
                             out_logit=out_logit, out_kept=out_kept, out_logprob=out_logprob)

@@ -31,6 +31,7 @@ import torch
 
 from . import ops
 from .host import TopLogprobs
+from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower
 
 
@@ -93,8 +94,8 @@ class PI0FASTTokens:
     def generate_tokens(self, images: List[torch.Tensor], img_masks: List[torch.Tensor], tokens: torch.Tensor, pad_mask: torch.Tensor,
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
-                        uniforms: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0):
+                        uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, top_k: RowParam = 0,
+                        top_p: RowParam = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -114,7 +115,15 @@ class PI0FASTTokens:
         entropy fp32 [B, max_new_tokens]) to the return: per step the n most probable tokens of the distribution return_logprobs
         documents (descending logit, equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities
         (cover_token_logprob's, bit for bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used.
-        Steps after a row's EOS, and steps the early stop skips, carry -1 / -inf / 0.0. 0: today's launches."""
+        Steps after a row's EOS, and steps the early stop skips, carry -1 / -inf / 0.0. 0: today's launches.
+        Parameters per row: temperature, top_k and top_p each accept a scalar or a length-B sequence / tensor. All scalars is the path
+        above, untouched. As soon as one of the three is per row, all three are validated on the host (temperature >= 0, top_k >= 0,
+        top_p > 0, all finite, else CoverError; a device tensor of any numeric dtype is read back once for it, so no pick is ever the -1
+        of an invalid row), broadcast to fp32 / int32 / fp32 [B] device tensors and every step's pick is
+        ONE ops.token_sample_rows launch over the vocabulary (ops.pick_token(row_params=)): uniforms is then required, a row with
+        temperature 0 is greedy (the arg-max, scored at temperature 1 unfiltered; its uniforms are not read), return_logprobs is that
+        launch's log-probability and top_logprobs is ops.token_topn_rows. Rows are decoded on their own, as in sampling (no greedy
+        de-duplication); share_prefix works as before."""
         dev = self.dev
         if not 0 <= int(top_logprobs) <= 64:
             raise ValueError("top_logprobs must be in 0..64")
@@ -123,6 +132,11 @@ class PI0FASTTokens:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
                 raise ValueError("uniforms must be [B, max_new_tokens]")
             u_t = uniforms.to(device=dev, dtype=torch.float32).t().contiguous()       # step-major: row i is step i's [B]
+        rp = None
+        if any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
+            if uniforms is None:
+                raise ValueError("per-row temperature / top_k / top_p need uniforms (a greedy row is a temperature of 0)")
+            rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
         if (not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
@@ -138,17 +152,18 @@ class PI0FASTTokens:
                     return sub_out[back]
                 return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
         return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs))
+                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp)
 
     def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share, n_top=0):
+                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None):
         """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
         share True: the P distinct prefixes (slots 0..P-1, in order of first occurrence) are prefilled once and every row reads its
         prompt's through segment 0's slot_of_batch; between two steps ONE ops.decode_feedback launch settles the token, the
         log-probability, the done flag, the live count and the next step's embedding row. COVER_FAST_FEEDBACK=0 (read per call) issues
-        the torch statements of the other path instead."""
+        the torch statements of the other path instead.
+        rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused)."""
         dev, c = self.dev, self.c
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
@@ -222,11 +237,16 @@ class PI0FASTTokens:
             if trace is not None:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
             # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
-            t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
-                                        out_logprob=lp)
-            if n_top:     # the distribution out_logprob scores the pick under (greedy: temperature 1, unfiltered)
-                ops.token_topn(lg, 0, c["vocab"], n_top, 1.0 if u_t is None else temperature, 0 if u_t is None else top_k,
-                               1.0 if u_t is None else top_p, out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
+            if rp is not None:     # one ops.token_sample_rows launch; ops.token_topn_rows ranks under each row's own distribution
+                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp)
+                if n_top:
+                    ops.token_topn_rows(lg, 0, c["vocab"], n_top, rp[0], rp[1], rp[2], out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
+            else:
+                t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
+                                            out_logprob=lp)
+                if n_top:     # the distribution out_logprob scores the pick under (greedy: temperature 1, unfiltered)
+                    ops.token_topn(lg, 0, c["vocab"], n_top, 1.0 if u_t is None else temperature, 0 if u_t is None else top_k,
+                                   1.0 if u_t is None else top_p, out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
             if u_t is not None and trace is not None:
                 trace.setdefault("picks", []).append(t.clone())
                 trace.setdefault("kept", []).append(kept)
@@ -286,9 +306,10 @@ class PI0FASTConfig:
     resize_imgs_with_padding: Optional[Tuple[int, int]] = (224, 224)
     device: str = "cuda:0"
     # sampled decoding (`generate(do_sample=True, ...)`): sample_seed None = greedy, the reference's setting
-    temperature: float = 1.0
-    top_k: int = 0
-    top_p: float = 1.0
+    # each of the three: a scalar, or one entry per row of the batch (generate_tokens' per-row form; 0.0 in temperature = a greedy row)
+    temperature: RowParam = 1.0
+    top_k: RowParam = 0
+    top_p: RowParam = 1.0
     sample_seed: Optional[int] = None
     return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
     top_logprobs: int = 0               # keep the n most probable tokens / log-probabilities / entropy of every step (last_top_logprobs)

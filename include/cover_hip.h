@@ -514,6 +514,64 @@ typedef struct cover_token_topn_args {
 } cover_token_topn_args;
 int cover_token_topn(const cover_token_topn_args* args, void* stream);
 
+/* Sampling parameters per row: cover_token_sample_scored, cover_token_logprob and cover_token_topn with temperature / top_k / top_p
+ * read from device arrays [rows], so one launch serves a ladder of proposal distributions (one greedy candidate per prompt, the other
+ * samples at rising temperatures or looser filters) and a captured graph does not depend on the values. One 1024-thread block per row,
+ * one launch, no workspace, no host round trip, nothing data-dependent in the launch: recordable. hi - lo <= 2^20, any lo / ld.
+ * What a row computes depends on that row's logits, uniform and parameters alone -- never on the other rows of the launch, the row's
+ * position or the width of the range (there is no cover_token_select detour for narrow unfiltered rows):
+ *   temperature[r] > 0    a sampled row: steps 1-4 of cover_token_sample with (temperature[r], top_k[r], top_p[r]) on the Q43 integer
+ *                         masses. token_out / logit_out / kept_out / logprob_out are what cover_token_sample_scored writes for that row
+ *                         wherever that call runs its own kernel (a filtered row, or hi - lo > 4096), bit for bit; logprob_out is
+ *                         cover_token_logprob of the pick with the row's parameters, bit for bit, always.
+ *   temperature[r] == 0   a greedy row: token_out = the first arg-max of the input floats over [lo, hi) (cover_token_select's greedy rule:
+ *                         the lowest index among equal maxima), logit_out its logit, kept_out = hi - lo, logprob_out = lp(token) at
+ *                         temperature 1 with both filters off (cover_token_logprob's value, bit for bit). top_k[r], top_p[r] and
+ *                         uniform[r] are not read. cover_token_logprob_rows / cover_token_topn_rows score and rank a greedy row at
+ *                         temperature 1, unfiltered.
+ *   invalid               temperature[r] < 0 or NaN, top_p[r] <= 0 or NaN, top_k[r] < 0 (the arrays live on the device: the host cannot
+ *                         validate them). The row reads no logits and writes token_out = -1, logit_out = logprob_out = NaN, kept_out = 0
+ *                         (topn: every slot -1 / -inf, entropy_out = NaN, kept_out = 0). No trap; the other rows are unaffected.
+ *                         The id -1 is the caller's to handle before an embedding lookup: cover_decode_feedback turns it into a zero
+ *                         row, cover_embed_gather checks no id.
+ * Null required pointers and a bad lo / hi / rows / n / stride return COVER_EINVAL, as in the scalar calls. */
+typedef struct cover_token_sample_rows_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    const float* uniform;       /* [rows] in [0,1), required; a greedy row ignores its entry */
+    const float* temperature;   /* [rows], required; 0.0f marks a greedy row */
+    const int* top_k;           /* [rows] or NULL = 0 for every row */
+    const float* top_p;         /* [rows] or NULL = 1 for every row */
+    int64_t* token_out;         /* [rows] */
+    float* logit_out;           /* [rows] selected raw logit (optional) */
+    int* kept_out;              /* [rows] size of the kept set (optional) */
+    float* logprob_out;         /* [rows] lp(pick) (optional) */
+} cover_token_sample_rows_args;
+int cover_token_sample_rows(const cover_token_sample_rows_args* args, void* stream);
+
+typedef struct cover_token_logprob_rows_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    const float* temperature;   /* [rows], required; 0.0f: scored at temperature 1, unfiltered */
+    const int* top_k;           /* [rows] or NULL = 0 for every row */
+    const float* top_p;         /* [rows] or NULL = 1 for every row */
+    const int64_t* token;       /* [rows] */
+    float* logprob_out;         /* [rows] */
+    int* kept_out;              /* [rows] size of the kept set (optional) */
+} cover_token_logprob_rows_args;
+int cover_token_logprob_rows(const cover_token_logprob_rows_args* args, void* stream);
+
+typedef struct cover_token_topn_rows_args {
+    const float* logits; long long ld; int rows; int lo, hi;
+    const float* temperature;   /* [rows], required; 0.0f: ranked at temperature 1, unfiltered */
+    const int* top_k;           /* [rows] or NULL = 0 for every row */
+    const float* top_p;         /* [rows] or NULL = 1 for every row */
+    int n;                      /* alternatives per row, 1..64 */
+    int64_t* token_out; long long ld_tok;     /* [rows, n] */
+    float* logprob_out; long long ld_lp;      /* [rows, n] */
+    float* entropy_out;         /* [rows] (optional) */
+    int* kept_out;              /* [rows] size of the kept set (optional) */
+} cover_token_topn_rows_args;
+int cover_token_topn_rows(const cover_token_topn_rows_args* args, void* stream);
+
 /* The bookkeeping between two steps of an autoregressive decode loop (pi0-FAST generate_tokens), one launch, one block per
  * candidate row, no workspace: recordable into a hipGraph. Per row b, in this order:
  *   t = force ? force[b * force_stride] : pick[b];  lp_out[b * ld_lp] = done[b] ? 0.0f : lp[b];  if (done[b]) t = pad;
