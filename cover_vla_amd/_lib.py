@@ -253,7 +253,9 @@ SYMBOLS = {
     "cover_decode_own_attention": (c_i, [_P(OwnAttnArgs), c_p]),
     "cover_layernorm_bf16": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),
     "cover_rmsnorm_bf16": (c_i, [c_p, c_i, c_i, c_p, c_f, c_i, c_p, c_i, c_i, c_i, c_f, c_p]),
+    "cover_rmsnorm_bf16_q8": (c_i, [c_p, c_i, c_i, c_p, c_f, c_i, c_p, c_i, c_i, c_i, c_f, c_p, c_i, c_p, c_p]),
     "cover_rope_kv_write": (c_i, [_P(RopeArgs), c_p]),
+    "cover_rope_kv_write_pair": (c_i, [_P(RopeArgs), _P(RopeArgs), c_p]),
     "cover_embed_gather": (c_i, [c_p, c_i, c_p, c_i, c_f, c_p, c_i, c_p]),
     "cover_patchify": (c_i, [_P(PatchifyArgs), c_p]),
     "cover_copy_rows_bf16": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),

@@ -146,9 +146,20 @@ int cover_rmsnorm_bf16(const void* x, int x_f32, int ldx, const float* w, float 
     HIPCHK(launch_rmsnorm(x, x_f32, ldx, w, w_offset, style, (bf16_t*)y, ldy, rows, dim, eps, ST(stream)), "rmsnorm_bf16");
     return COVER_OK;
 }
+int cover_rmsnorm_bf16_q8(const void* x, int x_f32, int ldx, const float* w, float w_offset, int style, void* y, int ldy,
+                          int rows, int dim, float eps, void* q8, int ld8, float* q8s, void* stream) {
+    if (!q8 || !q8s) return fail(COVER_EINVAL, "cover_rmsnorm_bf16_q8: null q8 / q8s");
+    HIPCHK(launch_rmsnorm(x, x_f32, ldx, w, w_offset, style, (bf16_t*)y, ldy, rows, dim, eps, ST(stream), (uint8_t*)q8, ld8, q8s), "rmsnorm_bf16_q8");
+    return COVER_OK;
+}
 int cover_rope_kv_write(const cover_rope_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_rope_kv_write: null args");
     HIPCHK(launch_rope_kv_write(a, ST(stream)), "rope_kv_write");
+    return COVER_OK;
+}
+int cover_rope_kv_write_pair(const cover_rope_args* a0, const cover_rope_args* a1, void* stream) {
+    if (!a0 || !a1) return fail(COVER_EINVAL, "cover_rope_kv_write_pair: null args");
+    HIPCHK(launch_rope_kv_write_pair(a0, a1, ST(stream)), "rope_kv_write_pair");
     return COVER_OK;
 }
 int cover_embed_gather(const void* table, int dim, const int64_t* ids, int n, float scale, void* out, int ldo,

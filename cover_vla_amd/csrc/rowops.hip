@@ -150,10 +150,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_k(const void* __restrict__ x
     }
 }
 
+// the 16-byte row accesses of the norms and the gather: an aligned base and a row stride that keeps every row aligned
+static bool rows16_ok(const void* p, int ld, int elems_per_16) { return p && (((uintptr_t)p) & 15) == 0 && ld % elems_per_16 == 0; }
+
 hipError_t launch_layernorm_bf16(const bf16_t* x, int ldx, const float* w, const float* b, bf16_t* y, int ldy, int rows,
                                  int dim, float eps, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
     if (dim % 8 || dim > NORM_MAX_CHUNKS * 256 * 8) return hipErrorInvalidValue;
+    if (!rows16_ok(x, ldx, 8) || !rows16_ok(y, ldy, 8)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(layernorm_bf16_k, dim3(rows), dim3(256), 0, st, x, ldx, w, b, y, ldy, dim, eps);
     return hipGetLastError();
 }
@@ -161,8 +165,9 @@ hipError_t launch_rmsnorm(const void* x, int x_f32, int ldx, const float* w, flo
                           int rows, int dim, float eps, hipStream_t st, uint8_t* q8, int ld8, float* q8s) {
     if (rows <= 0) return hipSuccess;
     if (dim % 8 || dim > NORM_MAX_CHUNKS * 256 * 8) return hipErrorInvalidValue;
+    if (!rows16_ok(x, ldx, x_f32 ? 4 : 8) || !rows16_ok(y, ldy, 8)) return hipErrorInvalidValue;
     if (q8 && q8s) {
-        if ((dim & 127) || ld8 < dim || (ld8 & 15)) return hipErrorInvalidValue;
+        if ((dim & 127) || ld8 < dim || (ld8 & 15) || (((uintptr_t)q8) & 7)) return hipErrorInvalidValue;
         if (x_f32)
             hipLaunchKernelGGL((rmsnorm_bf16_k<true, true>), dim3(rows), dim3(256), 0, st, x, ldx, w, w_offset, style, y, ldy, dim, eps, q8, ld8, q8s);
         else
@@ -402,6 +407,7 @@ hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids,
                                hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (dim % 8) return hipErrorInvalidValue;
+    if (!rows16_ok(table, dim, 8) || !rows16_ok(out, ldo, 8) || ldo < dim) return hipErrorInvalidValue;
     hipLaunchKernelGGL(embed_gather_k, dim3(n), dim3(128), 0, st, table, dim, ids, scale, out, ldo);
     return hipGetLastError();
 }

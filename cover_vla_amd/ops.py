@@ -313,21 +313,42 @@ def layernorm(x, w, b, eps, out=None):
     return out
 
 
-def rmsnorm(x, w, eps, w_offset=0.0, style=0, out=None):
+def rmsnorm(x, w, eps, w_offset=0.0, style=0, out=None, q8=False):
+    """q8: also return the e4m3 twin of the output rows and its row scales (cover_rmsnorm_bf16_q8; quantize_act_fp8's form). True allocates
+    them, a (q uint8 [rows, ld8], scales fp32 [rows]) pair is written in place."""
     _chk_dev(x, w)
     if out is None:
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if q8 is not False and q8 is not None:
+        if q8 is True:
+            q8 = (torch.empty(x.shape[0], (x.shape[1] + 127) // 128 * 128, dtype=torch.uint8, device=x.device),
+                  torch.empty(x.shape[0], dtype=torch.float32, device=x.device))
+        q, qs = q8
+        _chk_dev(q, qs)
+        L.check(L.lib().cover_rmsnorm_bf16_q8(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, x.stride(0), _ptr(w), w_offset,
+                                              style, out.data_ptr(), out.stride(0), x.shape[0], x.shape[1], eps, q.data_ptr(), q.stride(0),
+                                              qs.data_ptr(), _stream()), "rmsnorm_bf16_q8")
+        return out, q, qs
     L.check(L.lib().cover_rmsnorm_bf16(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, x.stride(0), _ptr(w), w_offset,
                                        style, out.data_ptr(), out.stride(0), x.shape[0], x.shape[1], eps, _stream()),
             "rmsnorm_bf16")
     return out
 
 
-def rope_kv_write(qkv, B, T, Hq, Hkv, D, *, positions=None, cos=None, sin=None, rope_mode=0, k_cache=None,
-                  k_strides=(0, 0, 0), k_offset=0, vt_cache=None, vt_strides=(0, 0, 0), vt_offset=0, slot_of_batch=None,
-                  t_offset_of_batch=None, t_offset=0):
-    _chk_dev(qkv, vt_cache)
+def rope_args(qkv, B, T, Hq, Hkv, D, *, positions=None, cos=None, sin=None, rope_mode=0, k_cache=None,
+              k_strides=(0, 0, 0), k_offset=0, vt_cache=None, vt_strides=(0, 0, 0), vt_offset=0, slot_of_batch=None,
+              t_offset_of_batch=None, t_offset=0, partial=None, bias=None) -> "L.RopeArgs":
+    """cover_rope_args of one row group. partial fp32 [n_splits, B * T, (Hq + 2 Hkv) * D] (+ bias fp32 [(Hq + 2 Hkv) * D]): the values are
+    bf16(sum_s partial[s] + bias) instead of what qkv holds (the split-K fold); q is still written to qkv."""
+    _chk_dev(qkv, vt_cache, partial, bias)
     a = L.RopeArgs()
+    a._keep = (qkv, positions, cos, sin, k_cache, vt_cache, slot_of_batch, t_offset_of_batch, partial, bias)   # the struct holds raw addresses
+    if partial is not None:
+        assert partial.dtype == torch.float32 and partial.is_contiguous() and partial.shape[1:] == (B * T, (Hq + 2 * Hkv) * D)
+        assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == (Hq + 2 * Hkv) * D)
+        a.n_splits, a.partial, a.bias = partial.shape[0], partial.data_ptr(), _ptr(bias)
+    else:
+        assert bias is None, "bias is part of the split-K fold: it needs partial"
     a.qkv, a.ld_qkv = qkv.data_ptr(), qkv.stride(0)
     a.B, a.T, a.Hq, a.Hkv, a.D = B, T, Hq, Hkv, D
     a.positions = _ptr(positions)
@@ -341,7 +362,18 @@ def rope_kv_write(qkv, B, T, Hq, Hkv, D, *, positions=None, cos=None, sin=None, 
     a.slot_of_batch = _ptr(slot_of_batch)
     a.t_offset_of_batch = _ptr(t_offset_of_batch)
     a.t_offset = t_offset
+    return a
+
+
+def rope_kv_write(qkv, B, T, Hq, Hkv, D, **kw):
+    """RoPE + K / V^T placement of one row group; keywords as in rope_args."""
+    a = rope_args(qkv, B, T, Hq, Hkv, D, **kw)
     L.check(L.lib().cover_rope_kv_write(C.byref(a), _stream()), "rope_kv_write")
+
+
+def rope_kv_write_pair(a0, a1):
+    """two row groups (two rope_args results) in one launch: cover_rope_kv_write_pair"""
+    L.check(L.lib().cover_rope_kv_write_pair(C.byref(a0), C.byref(a1), _stream()), "rope_kv_write_pair")
 
 
 def embed_gather(table, ids, scale=1.0, out=None):

@@ -273,6 +273,13 @@ int cover_layernorm_bf16(const void* x, int ldx, const float* w, const float* b,
  * x_f32 = 1: x is fp32 (pi0 suffix embeddings enter the expert's first norm un-rounded). */
 int cover_rmsnorm_bf16(const void* x, int x_f32, int ldx, const float* w, float w_offset, int style, void* y, int ldy,
                        int rows, int dim, float eps, void* stream);
+/* The same launch with the e4m3 twin of the y rows the decoder's fp8 profile uses: q8 [rows, ld8] holds e4m3(y / q8s[row]) in
+ * cover_quantize_act_fp8's byte order (same bytes and scales as that call on y), q8s [rows] the power-of-two row scales.
+ * dim % 128 == 0, ld8 >= dim, ld8 % 16 == 0; bytes past dim of a q8 row are not written. */
+int cover_rmsnorm_bf16_q8(const void* x, int x_f32, int ldx, const float* w, float w_offset, int style, void* y, int ldy,
+                          int rows, int dim, float eps, void* q8, int ld8, float* q8s, void* stream);
+/* The norm launches read and write 16 bytes per lane: x, y (and the embedding table / out of cover_embed_gather) must be 16-byte
+ * aligned and the row strides multiples of 8 elements (4 for fp32 x); anything else returns COVER_EINVAL and nothing runs. */
 
 /* RoPE + KV placement. Replaces apply_rope (paligemma_with_expert.py:34-57) and the dict/concat KV cache
  * (:288-308) with in-place appends into a static cache. qkv rows = [B*T][ (Hq+2*Hkv)*D ].
@@ -300,6 +307,8 @@ typedef struct cover_rope_args {
     const float* bias;           /* [N] or NULL */
 } cover_rope_args;
 int cover_rope_kv_write(const cover_rope_args* args, void* stream);
+/* two row groups of one pass in one launch (the decoder's prefill): the same cells as two cover_rope_kv_write calls */
+int cover_rope_kv_write_pair(const cover_rope_args* args0, const cover_rope_args* args1, void* stream);
 
 /* token embedding gather (K4: modeling_pi0.py:549-553): out[i] = bf16(table[ids[i]] * scale) */
 int cover_embed_gather(const void* table, int dim, const int64_t* ids, int n, float scale, void* out, int ldo,
