@@ -249,6 +249,9 @@ SYMBOLS = {
     "cover_gemm_plan": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, _P(GemmEpi), c_p, C.c_size_t, c_i, C.POINTER(c_i)]),
     "cover_gemm_probe": (c_i, [C.POINTER(C.c_ulonglong)]),
     "cover_attention_bf16": (c_i, [_P(AttnArgs), c_p]),
+    "cover_attention_plan": (c_i, [_P(AttnArgs), _P(c_i)]),
+    "cover_attention_bf16_pair": (c_i, [_P(AttnArgs), _P(AttnArgs), c_p]),
+    "cover_attention_pair_plan": (c_i, [_P(AttnArgs), _P(AttnArgs), _P(c_i)]),
     "cover_decode_attention_fused": (c_i, [_P(DecodeAttnArgs), c_p]),
     "cover_decode_own_attention": (c_i, [_P(OwnAttnArgs), c_p]),
     "cover_layernorm_bf16": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p]),

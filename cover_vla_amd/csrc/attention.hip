@@ -418,6 +418,7 @@ __global__ __launch_bounds__(256) void attn_shared_k(AttnDev a) {
             iseg = 3;   // done: keep fetching the last tile
         }
     };
+    const bool any_keys = iseg < 3;   // (taken BEFORE the cursor moves: with three key tiles or fewer the prologue below already leaves it at "done")
     int cstage = 0;
 #ifdef COVER_AT_DEBUG   // where a tile's time goes (thread 0 of every workgroup; 100 MHz ticks summed over the tiles): wait | barrier | DMA issue | S^T | softmax | PV
     unsigned long long seg_t[6] = {0, 0, 0, 0, 0, 0}, tp = 0;
@@ -504,7 +505,7 @@ __global__ __launch_bounds__(256) void attn_shared_k(AttnDev a) {
 #endif
         cstage = cstage == NST - 1 ? 0 : cstage + 1;
     };
-    if (iseg < 3) {
+    if (any_keys) {
 #pragma unroll
         for (int i = 0; i < DIST; ++i) issue_next();   // tiles 0 .. DIST - 1
     }
@@ -535,7 +536,7 @@ __global__ __launch_bounds__(256) void attn_shared_k(AttnDev a) {
     for (int db = 0; db < DB; ++db) asm volatile("" : "+v"(oacc[db]));
     asm volatile("" : "+v"(m_run), "+v"(l_run));
     ATT(2);   // (Q fragments and the resumed state landed)
-    if (iseg < 3) {
+    if (any_keys) {
         for (int t0 = 0; t0 < len0; t0 += 32) tile(len0, t0);
         for (int t0 = 0; t0 < len1; t0 += 32) tile(len1, t0);
         for (int t0 = 0; t0 < len2; t0 += 32) tile(len2, t0);
@@ -606,17 +607,6 @@ __global__ __launch_bounds__(256) void attn_shared_k(AttnDev a) {
     }
     ATT(5);
 }
-// when launch_d takes the workgroup-shared form: MHA at D = 128, length masks, enough query rows per (batch entry, head) to share the keys, enough
-// workgroups to fill the chip (COVER_ATTN_SHARED=0: never)
-static bool attn_shared_ok(const cover_attn_args* x) {
-    static const char* env = getenv("COVER_ATTN_SHARED");
-    if (env && env[0] == '0') return false;
-    if (x->D != 128 || x->Hq != x->Hkv || x->Tq < 48 || x->n_seg < 1 || x->n_seg > 3) return false;
-    for (int i = 0; i < x->n_seg; ++i)
-        if (x->seg[i].mask_mode != COVER_MASK_LEN) return false;
-    return (long long)((x->Tq + 63) / 64) * x->Hq * x->B >= 128;
-}
-
 template <int D, bool KSPLIT, int NWS = 4, bool MXO = false>
 __global__ __launch_bounds__((KSPLIT && D > 128) ? 64 * NWS : 512) void attn_kernel(AttnDev a) {
     attn_body<D, KSPLIT, NWS, MXO>(a, blockIdx.x, blockIdx.y, blockIdx.z);
@@ -635,78 +625,119 @@ __global__ __launch_bounds__(512) void attn_kernel_dual(AttnDev a0, AttnDev a1, 
     }
 }
 
-template <int D>
-static hipError_t launch_dual_d(const AttnDev& a0, const AttnDev& a1, hipStream_t st) {
-    const int t0 = (a0.R + 15) / 16, t1 = (a1.R + 15) / 16;
-    const size_t lds = (size_t)(4 * (D / 16) * 4 * 64 + 2 * 4 * 16) * sizeof(float);
-    dim3 grid(t0 * a0.B + t1 * a1.B, a0.Hkv), block(256);
-    hipLaunchKernelGGL((attn_kernel_dual<D>), grid, block, lds, st, a0, a1, t0, t0 * a0.B, t1);
-    return hipGetLastError();
+// ---------------------------------------------------------------------------------------------------
+// Host side. ONE decision function (attn_decide) picks the launch form from the problem's integers; the launch (launch_attention_bf16) and the
+// plan query (attention_plan -> cover_attention_plan) both call it, as gemm_bf16.hip does for the GEMMs: a test that asks for the plan sees
+// what the launch does. The experiment knobs are read once per process.
+// ---------------------------------------------------------------------------------------------------
+struct AttnEnv {
+    bool shared_off, pair_off, has_ks_max;
+    long long ks_max, nw8_max;
+};
+static const AttnEnv& attn_env() {
+    static const AttnEnv e = [] {
+        AttnEnv v;
+        const char* sh = getenv("COVER_ATTN_SHARED");
+        const char* pr = getenv("COVER_ATTN_PAIR");
+        const char* mx = getenv("COVER_ATTN_KSPLIT_MAX");
+        const char* n8 = getenv("COVER_ATTN_NW8_MAX");
+        v.shared_off = sh && sh[0] == '0';
+        v.pair_off = pr && pr[0] == '0';
+        v.has_ks_max = mx != nullptr;
+        v.ks_max = mx ? atoll(mx) : 1023;
+        v.nw8_max = n8 ? atoll(n8) : 0;
+        return v;
+    }();
+    return e;
 }
-
-template <int D>
-static hipError_t launch_d(const AttnDev& a, hipStream_t st) {
-    const int tiles = (a.R + 15) / 16;
-    const long long qtiles = (long long)tiles * a.Hkv * a.B;
-    static const char* e_max = getenv("COVER_ATTN_KSPLIT_MAX");
-    static const char* e_nw8 = getenv("COVER_ATTN_NW8_MAX");
-    long long ks_max = e_max ? atoll(e_max) : 1023;
-    const long long nw8_max = e_nw8 ? atoll(e_nw8) : 0;
-    // a pass RESUMED from a state (the chained decode pass of large-N candidate decode: 8 prompts x 64 samples x 32 heads = 1024 query
-    // tiles over ~280 keys) is a chain of ~10 dependent key tiles per wave: split the keys over the block's waves there too
-    // (config 5: 24.7 -> see profiles/ us per layer)
-    if (a.si_o != nullptr && !e_max && D <= 128) ks_max = 4095;
-    if (a.shared) {
-        dim3 grid((a.Tq + 63) / 64, a.Hq, a.B);
-        if (a.o8) hipLaunchKernelGGL((attn_shared_k<true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((attn_shared_k<false>), grid, dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    if (a.o8) {   // block-scaled output: the key-split kernel with four waves at D = 128 only (attention_mx_ok below says when)
-        if constexpr (D == 128) {
-            if (qtiles > ks_max) return hipErrorInvalidValue;
-            const size_t lds = (size_t)(4 * (D / 16) * 4 * 64 + 2 * 4 * 16) * sizeof(float);
-            hipLaunchKernelGGL((attn_kernel<D, true, 4, true>), dim3(tiles, a.Hkv, a.B), dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    if (qtiles <= ks_max) {
-        // too few query tiles to fill the chip (single-token decode, ViT-sized sequences): split the key tiles over the
-        // 4 (or, when even 4 waves per tile leave most CUs idle and D allows the LDS merge buffer, 8) waves of a block
-        const int nw = (qtiles <= nw8_max && D <= 128) ? 8 : 4;
-        const size_t lds = (size_t)(nw * (D / 16) * 4 * 64 + 2 * nw * 16) * sizeof(float);
-        dim3 grid(tiles, a.Hkv, a.B), block(64 * nw);
-        if (nw == 8) {
-            if constexpr (D <= 128) hipLaunchKernelGGL((attn_kernel<D, true, 8>), grid, block, lds, st, a);
-        } else {
-            hipLaunchKernelGGL((attn_kernel<D, true, 4>), grid, block, lds, st, a);
-        }
-    } else {
-        const int nw = tiles >= 4 ? 4 : tiles;
-        dim3 grid((tiles + nw - 1) / nw, a.Hkv, a.B), block(64 * nw);
-        hipLaunchKernelGGL((attn_kernel<D, false>), grid, block, 0, st, a);
-    }
-    return hipGetLastError();
+static long long attn_qtiles(const cover_attn_args* x) {
+    const int G = x->Hq / x->Hkv;
+    return (long long)((x->Tq * G + 15) / 16) * x->Hkv * x->B;
+}
+// most query tiles the key-split form takes. A pass RESUMED from a state (the chained decode pass of large-N candidate decode: 8 prompts x 64
+// samples x 32 heads = 1024 query tiles over ~280 keys) is a chain of ~10 dependent key tiles per wave: split the keys over the block's waves
+// there too (config 5: 24.7 -> see profiles/ us per layer)
+static long long attn_ks_max(const cover_attn_args* x) {
+    const AttnEnv& e = attn_env();
+    return (x->state_in_o != nullptr && !e.has_ks_max && x->D <= 128) ? 4095 : e.ks_max;
+}
+// when the launch takes the workgroup-shared form: MHA at D = 128, length masks, enough query rows per (batch entry, head) to share the keys, enough
+// workgroups to fill the chip (COVER_ATTN_SHARED=0: never)
+static bool attn_shared_ok(const cover_attn_args* x) {
+    if (attn_env().shared_off) return false;
+    if (x->D != 128 || x->Hq != x->Hkv || x->Tq < 48 || x->n_seg < 1 || x->n_seg > 3) return false;
+    for (int i = 0; i < x->n_seg; ++i)
+        if (x->seg[i].mask_mode != COVER_MASK_LEN) return false;
+    return (long long)((x->Tq + 63) / 64) * x->Hq * x->B >= 128;
 }
 
 // Can this problem write its output block-scaled (cover_attn_args.out8)? MHA at D = 128 (a head = four 32-column blocks = one 128-deep k-tile of the consuming
-// GEMM), whole rows of Hq * D bytes, final output (no state_out), and few enough query tiles for the key-split kernel (as launch_d decides).
+// GEMM), whole rows of Hq * D bytes, final output (no state_out), and few enough query tiles for the key-split kernel, or the shared form (as attn_decide decides).
 bool attention_mx_ok(const cover_attn_args* x) {
-    if (x->D != 128 || x->Hq != x->Hkv || x->state_out_o != nullptr || x->B <= 0 || x->Tq <= 0) return false;
+    if (x->D != 128 || x->Hq != x->Hkv || x->Hkv <= 0 || x->state_out_o != nullptr || x->B <= 0 || x->Tq <= 0) return false;
     if (x->o_h_stride != 128 || x->o_t_stride != (long long)x->Hq * 128 || (x->o_b_stride % x->o_t_stride) != 0) return false;
-    static const char* e_max = getenv("COVER_ATTN_KSPLIT_MAX");
-    const long long ks_max = (x->state_in_o != nullptr && !e_max) ? 4095 : (e_max ? atoll(e_max) : 1023);
-    const long long qtiles = (long long)((x->Tq + 15) / 16) * x->Hkv * x->B;
-    return qtiles <= ks_max || attn_shared_ok(x);
+    return attn_qtiles(x) <= attn_ks_max(x) || attn_shared_ok(x);
 }
 
+// form: -1 nothing to launch, 0 per-tile un-split, 1 key-split over 4 waves, 2 key-split over 8 waves, 3 workgroup-shared keys
+struct AttnPlan {
+    int form, mxo, nw;
+    dim3 grid;
+    size_t lds;
+};
+static hipError_t attn_decide(const cover_attn_args* x, AttnPlan& p) {
+    p.form = -1; p.mxo = 0; p.nw = 0; p.grid = dim3(0, 0, 0); p.lds = 0;
+    const int G = x->Hq / x->Hkv, R = x->Tq * G;
+    if (x->B <= 0 || R <= 0) return hipSuccess;
+    const int D = x->D;
+    if (D != 64 && D != 96 && D != 128 && D != 256) return hipErrorInvalidValue;
+    const bool o8 = x->out8 != nullptr && x->out8_mx != nullptr;   // (attention_mx_ok held: build_attn_dev)
+    const int tiles = (R + 15) / 16;
+    const long long qtiles = (long long)tiles * x->Hkv * x->B;
+    const long long ks_max = attn_ks_max(x);
+    p.mxo = o8 ? 1 : 0;
+    if (attn_shared_ok(x)) {
+        p.form = 3; p.nw = 4;
+        p.grid = dim3((x->Tq + 63) / 64, x->Hq, x->B);
+        return hipSuccess;
+    }
+    if (o8) {   // block-scaled output: the key-split kernel with four waves at D = 128 only (attention_mx_ok says when)
+        if (D != 128 || qtiles > ks_max) return hipErrorInvalidValue;
+        p.form = 1; p.nw = 4;
+    } else if (qtiles <= ks_max) {
+        // too few query tiles to fill the chip (single-token decode, ViT-sized sequences): split the key tiles over the
+        // 4 (or, when even 4 waves per tile leave most CUs idle and D allows the LDS merge buffer, 8) waves of a block
+        p.nw = (qtiles <= attn_env().nw8_max && D <= 128) ? 8 : 4;
+        p.form = p.nw == 8 ? 2 : 1;
+    } else {
+        p.form = 0;
+        p.nw = tiles >= 4 ? 4 : tiles;
+        p.grid = dim3((tiles + p.nw - 1) / p.nw, x->Hkv, x->B);
+        return hipSuccess;
+    }
+    p.grid = dim3(tiles, x->Hkv, x->B);
+    p.lds = (size_t)(p.nw * (D / 16) * 4 * 64 + 2 * p.nw * 16) * sizeof(float);
+    return hipSuccess;
+}
+// one launch of two problems (attn_kernel_dual): both in key-split mode with 4 waves at the same D <= 128 and kv head count, plain bf16 outputs
+// (the dual kernel has no block-scaled store: a problem with out8 takes its own launch). COVER_ATTN_PAIR=0: never.
+static bool attn_pair_dual(const cover_attn_args* x0, const cover_attn_args* x1) {
+    const AttnEnv& e = attn_env();
+    const bool o8 = (x0->out8 && x0->out8_mx) || (x1->out8 && x1->out8_mx);
+    return x0->D == x1->D && x0->Hkv == x1->Hkv && x0->B > 0 && x1->B > 0 && x0->Tq > 0 && x1->Tq > 0 && attn_qtiles(x0) <= e.ks_max &&
+           attn_qtiles(x1) <= e.ks_max && (x0->D == 64 || x0->D == 96 || x0->D == 128) && !o8 && !e.pair_off;
+}
+
+static bool off16(const void* p) { return ((uintptr_t)p & 15) != 0; }
 static hipError_t build_attn_dev(const cover_attn_args* x, AttnDev& a) {
-    if (x->n_seg < 1 || x->n_seg > 3 || x->Hq % x->Hkv != 0) return hipErrorInvalidValue;
+    if (x->n_seg < 1 || x->n_seg > 3 || x->Hkv <= 0 || x->Hq % x->Hkv != 0) return hipErrorInvalidValue;
     a.q = (const bf16_t*)x->q;
     a.out = (bf16_t*)x->out;
     a.q_b = x->q_b_stride; a.q_t = x->q_t_stride; a.q_h = x->q_h_stride;
     a.o_b = x->o_b_stride; a.o_t = x->o_t_stride; a.o_h = x->o_h_stride;
+    // the kernels load q, K and V^T 16 bytes at a time, store `out` 8 bytes at a time and move the state's o rows as float4 (its (m, l) pairs as floats)
+    if (off16(a.q) || ((a.q_b | a.q_t | a.q_h) & 7)) return hipErrorInvalidValue;
+    if (((uintptr_t)a.out & 7) || ((a.o_b | a.o_t | a.o_h) & 3)) return hipErrorInvalidValue;
     a.B = x->B; a.Tq = x->Tq; a.Hq = x->Hq; a.Hkv = x->Hkv;
     a.G = x->Hq / x->Hkv;
     a.R = x->Tq * a.G;
@@ -714,6 +745,7 @@ static hipError_t build_attn_dev(const cover_attn_args* x, AttnDev& a) {
     a.n_seg = x->n_seg;
     a.si_o = x->state_in_o; a.si_ml = x->state_in_ml; a.so_o = x->state_out_o; a.so_ml = x->state_out_ml;
     if ((a.si_o == nullptr) != (a.si_ml == nullptr) || (a.so_o == nullptr) != (a.so_ml == nullptr)) return hipErrorInvalidValue;
+    if (off16(a.si_o) || off16(a.so_o) || ((uintptr_t)a.si_ml & 7) || ((uintptr_t)a.so_ml & 7)) return hipErrorInvalidValue;
     a.o8 = (uint8_t*)x->out8; a.o8mx = (uint8_t*)x->out8_mx; a.o8_rows = x->out8_rows;
     if (!a.o8 || !a.o8mx) { a.o8 = nullptr; a.o8mx = nullptr; }
     if (a.o8 && !attention_mx_ok(x)) return hipErrorInvalidValue;
@@ -727,42 +759,95 @@ static hipError_t build_attn_dev(const cover_attn_args* x, AttnDev& a) {
         d.slot_of_batch = s.slot_of_batch; d.len_of_batch = s.len_of_batch; d.vis_len = s.vis_len;
         d.len = s.len; d.mode = s.mask_mode; d.causal_off = s.causal_offset;
         if (d.mode == COVER_MASK_VISLEN && d.vis_len == nullptr) return hipErrorInvalidValue;
+        if (off16(d.k) || off16(d.vt) || ((d.k_slot | d.k_t | d.k_h | d.vt_slot | d.vt_h | d.vt_d) & 7)) return hipErrorInvalidValue;
     }
     return hipSuccess;
 }
 
-hipError_t launch_attention_bf16(const cover_attn_args* x, hipStream_t st) {
+// cover_attention_plan: what launch_attention_bf16 would do with these arguments, nothing launched, no device pointer dereferenced
+hipError_t attention_plan(const cover_attn_args* x, int* plan) {
     AttnDev a;
+    AttnPlan p;
     hipError_t e = build_attn_dev(x, a);
+    if (e == hipSuccess) e = attn_decide(x, p);
     if (e != hipSuccess) return e;
-    if (a.B <= 0 || a.R <= 0) return hipSuccess;
+    plan[0] = p.form; plan[1] = p.mxo; plan[2] = (int)(p.grid.x * p.grid.y * p.grid.z); plan[3] = p.nw;
+    return hipSuccess;
+}
+// cover_attention_pair_plan: 1 = one dual launch, 0 = two launches (either of which may have nothing to launch)
+hipError_t attention_pair_plan(const cover_attn_args* x0, const cover_attn_args* x1, int* dual) {
+    AttnDev a;
+    AttnPlan p;
+    hipError_t e = build_attn_dev(x0, a);
+    if (e == hipSuccess) e = attn_decide(x0, p);
+    if (e == hipSuccess) e = build_attn_dev(x1, a);
+    if (e == hipSuccess) e = attn_decide(x1, p);
+    if (e != hipSuccess) return e;
+    *dual = attn_pair_dual(x0, x1) ? 1 : 0;
+    return hipSuccess;
+}
+
+template <int D>
+static void launch_d(const AttnDev& a, const AttnPlan& p, hipStream_t st) {
+    const dim3 block(64 * p.nw);
+    if (p.form == 3) {
+        if (p.mxo) hipLaunchKernelGGL((attn_shared_k<true>), p.grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_shared_k<false>), p.grid, block, 0, st, a);
+    } else if (p.form == 1 && p.mxo) {
+        if constexpr (D == 128) hipLaunchKernelGGL((attn_kernel<D, true, 4, true>), p.grid, block, p.lds, st, a);
+    } else if (p.form == 2) {
+        if constexpr (D <= 128) hipLaunchKernelGGL((attn_kernel<D, true, 8>), p.grid, block, p.lds, st, a);
+    } else if (p.form == 1) {
+        hipLaunchKernelGGL((attn_kernel<D, true, 4>), p.grid, block, p.lds, st, a);
+    } else {
+        hipLaunchKernelGGL((attn_kernel<D, false>), p.grid, block, 0, st, a);
+    }
+}
+static hipError_t launch_planned(const cover_attn_args* x, const AttnDev& a, const AttnPlan& p, hipStream_t st) {
+    if (p.form < 0) return hipSuccess;
     const int pid = prof_enabled() ? prof_open(st, 2, 0.0) : -1;
     switch (x->D) {
-        case 64: e = launch_d<64>(a, st); break;
-        case 96: e = launch_d<96>(a, st); break;
-        case 128: e = launch_d<128>(a, st); break;
-        case 256: e = launch_d<256>(a, st); break;
-        default: e = hipErrorInvalidValue;
+        case 64: launch_d<64>(a, p, st); break;
+        case 96: launch_d<96>(a, p, st); break;
+        case 128: launch_d<128>(a, p, st); break;
+        default: launch_d<256>(a, p, st); break;
     }
+    const hipError_t e = hipGetLastError();
     prof_close(st, pid);
     return e;
 }
 
-// Both problems in one launch when both would run in key-split mode with 4 waves (else: two launches).
+hipError_t launch_attention_bf16(const cover_attn_args* x, hipStream_t st) {
+    AttnDev a;
+    AttnPlan p;
+    hipError_t e = build_attn_dev(x, a);
+    if (e == hipSuccess) e = attn_decide(x, p);
+    if (e != hipSuccess) return e;
+    return launch_planned(x, a, p, st);
+}
+
+template <int D>
+static hipError_t launch_dual_d(const AttnDev& a0, const AttnDev& a1, hipStream_t st) {
+    const int t0 = (a0.R + 15) / 16, t1 = (a1.R + 15) / 16;
+    const size_t lds = (size_t)(4 * (D / 16) * 4 * 64 + 2 * 4 * 16) * sizeof(float);
+    dim3 grid(t0 * a0.B + t1 * a1.B, a0.Hkv), block(256);
+    hipLaunchKernelGGL((attn_kernel_dual<D>), grid, block, lds, st, a0, a1, t0, t0 * a0.B, t1);
+    return hipGetLastError();
+}
+
+// Both problems in one launch when both would run in key-split mode with 4 waves (attn_pair_dual; else: two launches). Both problems are validated
+// and planned before either runs: an invalid second problem leaves the first one's output untouched.
 hipError_t launch_attention_bf16_pair(const cover_attn_args* x0, const cover_attn_args* x1, hipStream_t st) {
     AttnDev a0, a1;
+    AttnPlan p0, p1;
     hipError_t e = build_attn_dev(x0, a0);
+    if (e == hipSuccess) e = attn_decide(x0, p0);
     if (e == hipSuccess) e = build_attn_dev(x1, a1);
+    if (e == hipSuccess) e = attn_decide(x1, p1);
     if (e != hipSuccess) return e;
-    static const char* e_max = getenv("COVER_ATTN_KSPLIT_MAX");
-    static const char* e_pair = getenv("COVER_ATTN_PAIR");
-    const long long ks_max = e_max ? atoll(e_max) : 1023;
-    const long long q0 = (long long)((a0.R + 15) / 16) * a0.Hkv * a0.B, q1 = (long long)((a1.R + 15) / 16) * a1.Hkv * a1.B;
-    const bool pair = x0->D == x1->D && a0.Hkv == a1.Hkv && a0.B > 0 && a1.B > 0 && a0.R > 0 && a1.R > 0 && q0 <= ks_max && q1 <= ks_max &&
-                      (x0->D == 64 || x0->D == 96 || x0->D == 128) && !(e_pair && e_pair[0] == '0');
-    if (!pair) {
-        e = launch_attention_bf16(x0, st);
-        return e == hipSuccess ? launch_attention_bf16(x1, st) : e;
+    if (!attn_pair_dual(x0, x1)) {
+        e = launch_planned(x0, a0, p0, st);
+        return e == hipSuccess ? launch_planned(x1, a1, p1, st) : e;
     }
     const int pid = prof_enabled() ? prof_open(st, 2, 0.0) : -1;
     switch (x0->D) {

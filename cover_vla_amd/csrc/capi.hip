@@ -123,6 +123,21 @@ int cover_attention_bf16(const cover_attn_args* a, void* stream) {
     return COVER_OK;
 }
 
+int cover_attention_plan(const cover_attn_args* a, int* plan) {
+    if (!a || !plan) return fail(COVER_EINVAL, "cover_attention_plan: null pointer");
+    HIPCHK(attention_plan(a, plan), "attention_bf16 (D must be 64/96/128/256, 1..3 segments)");
+    return COVER_OK;
+}
+int cover_attention_bf16_pair(const cover_attn_args* a0, const cover_attn_args* a1, void* stream) {
+    if (!a0 || !a1) return fail(COVER_EINVAL, "cover_attention_bf16_pair: null args");
+    HIPCHK(launch_attention_bf16_pair(a0, a1, ST(stream)), "attention_bf16_pair (D must be 64/96/128/256, 1..3 segments)");
+    return COVER_OK;
+}
+int cover_attention_pair_plan(const cover_attn_args* a0, const cover_attn_args* a1, int* dual) {
+    if (!a0 || !a1 || !dual) return fail(COVER_EINVAL, "cover_attention_pair_plan: null pointer");
+    HIPCHK(attention_pair_plan(a0, a1, dual), "attention_bf16_pair (D must be 64/96/128/256, 1..3 segments)");
+    return COVER_OK;
+}
 int cover_decode_attention_fused(const cover_decode_attn_args* a, void* stream) {
     if (!a || !a->out || (a->n_splits <= 0 && !a->qkv) || (a->n_splits > 0 && !a->partial))
         return fail(COVER_EINVAL, "cover_decode_attention_fused: null pointer");

@@ -235,13 +235,15 @@ def fill_segment(s: L.KvSegment, seg: Segment) -> None:
     s.causal_offset = seg.causal_offset
 
 
-def attention(q: torch.Tensor, q_strides: Sequence[int], out: Optional[torch.Tensor], o_strides: Sequence[int], B: int, Tq: int,
-              Hq: int, Hkv: int, D: int, scale: float, segments: Sequence[Segment], state_in=None, state_out=None, out8=None):
-    """state_in / state_out: optional (o fp32 [B,Tq,Hq,D], ml fp32 [B,Tq,Hq,2]) pairs chaining calls over KV segments.
+def attention_args(q: torch.Tensor, q_strides: Sequence[int], out: Optional[torch.Tensor], o_strides: Sequence[int], B: int, Tq: int,
+                   Hq: int, Hkv: int, D: int, scale: float, segments: Sequence[Segment], state_in=None, state_out=None, out8=None) -> "L.AttnArgs":
+    """cover_attn_args of one problem (the struct holds raw addresses: it keeps its tensors alive).
+    state_in / state_out: optional (o fp32 [B,Tq,Hq,D], ml fp32 [B,Tq,Hq,2]) pairs chaining calls over KV segments.
     out8 = (q uint8 [rows, Hq * D], mx uint8 [Hq * D / 128, rows, 4]): the output rows block-quantised (quantize_act_fp8_mx's form) INSTEAD of `out`
     (MHA, D = 128, few query tiles: cover_attn_args.out8)."""
     _chk_dev(q, out)
     a = L.AttnArgs()
+    a._keep = (q, out, out8, state_in, state_out, list(segments))
     a.q, a.out = q.data_ptr(), _ptr(out)
     if out8 is not None:
         _chk_dev(out8[0], out8[1])
@@ -255,10 +257,45 @@ def attention(q: torch.Tensor, q_strides: Sequence[int], out: Optional[torch.Ten
     a.o_b_stride, a.o_t_stride, a.o_h_stride = o_strides
     a.B, a.Tq, a.Hq, a.Hkv, a.D, a.scale = B, Tq, Hq, Hkv, D, scale
     a.n_seg = len(segments)
-    for i, sg in enumerate(segments):
+    for i, sg in enumerate(segments[:3]):    # (the struct has three slots; n_seg above keeps the true count, which the library refuses when it is not 1..3)
         fill_segment(a.seg[i], sg)
+    return a
+
+
+def attention(q: torch.Tensor, q_strides: Sequence[int], out: Optional[torch.Tensor], o_strides: Sequence[int], B: int, Tq: int,
+              Hq: int, Hkv: int, D: int, scale: float, segments: Sequence[Segment], state_in=None, state_out=None, out8=None):
+    """cover_attention_bf16; arguments as in attention_args."""
+    a = attention_args(q, q_strides, out, o_strides, B, Tq, Hq, Hkv, D, scale, segments, state_in, state_out, out8)
     L.check(L.lib().cover_attention_bf16(C.byref(a), _stream()), "attention_bf16")
     return out
+
+
+ATTN_FORMS = {-1: None, 0: "PER_TILE", 1: "KSPLIT4", 2: "KSPLIT8", 3: "SHARED"}
+
+
+def attention_plan_of(a: "L.AttnArgs"):
+    """(form name or None when nothing would be launched, block-scaled output, workgroups, waves per workgroup) of an attention_args result:
+    cover_attention_plan, nothing launched. Raises CoverError exactly when attention would."""
+    plan = (C.c_int * 4)()
+    L.check(L.lib().cover_attention_plan(C.byref(a), plan), "attention_plan")
+    return ATTN_FORMS[plan[0]], bool(plan[1]), int(plan[2]), int(plan[3])
+
+
+def attention_plan(*args, **kw):
+    """attention_plan_of for the arguments of ops.attention"""
+    return attention_plan_of(attention_args(*args, **kw))
+
+
+def attention_pair(a0: "L.AttnArgs", a1: "L.AttnArgs") -> None:
+    """two problems (two attention_args results), in one launch when both run key-split: cover_attention_bf16_pair"""
+    L.check(L.lib().cover_attention_bf16_pair(C.byref(a0), C.byref(a1), _stream()), "attention_bf16_pair")
+
+
+def attention_pair_plan(a0: "L.AttnArgs", a1: "L.AttnArgs") -> bool:
+    """True: attention_pair runs one dual launch; False: two launches (cover_attention_pair_plan, nothing launched)"""
+    dual = C.c_int(0)
+    L.check(L.lib().cover_attention_pair_plan(C.byref(a0), C.byref(a1), C.byref(dual)), "attention_pair_plan")
+    return bool(dual.value)
 
 
 def decode_attention_fused(qkv, N, H, D, scale, segments, write_t, out, *, positions=None, cos=None, sin=None, rope_mode=0,

@@ -178,6 +178,18 @@ int cover_gemm_probe(unsigned long long* out);
  * (make_att_2d_masks, modeling_pi0.py:98-128).
  * K is read row-major [slot][t][h][d]; V is read TRANSPOSED [slot][h][d][t] (written by cover_rope_kv_write),
  * so both MFMA operands are 16-byte contiguous per lane with no LDS transpose.
+ *
+ * Alignment (checked; COVER_EINVAL and nothing runs otherwise): q, every segment's k and vt are loaded 16 bytes at a time -- bases on 16 bytes,
+ * every q / k / vt stride a multiple of 8 elements; `out` is stored 8 bytes at a time -- base on 8 bytes (NULL passes), every o_*_stride a
+ * multiple of 4 (elements, or bytes with out8); the state's o tensors move as float4 -- state_in_o / state_out_o on 16 bytes, the (m, l)
+ * pairs state_in_ml / state_out_ml on 8.
+ * V^T capacity: the cache is read in whole 32-key tiles, so every [d] row of vt must have readable elements up to the next multiple of 32 past the
+ * segment's (largest) length: vt_d_stride >= ceil(len / 32) * 32 for a dense cache. K rows at or past the length are never read (the load
+ * index is clamped to len - 1), K rows between a causal / vis_len bound and the length are.
+ * Tail values: a masked key's probability is exactly 0 and is MULTIPLIED with the V^T element, so any FINITE value in the V^T tail (stale
+ * keys, +-3e38) leaves the output bits unchanged; a NaN or an infinity there turns the whole output row into NaN (0 * inf). Nothing clears
+ * or tests for it: keep the tail of a V^T cache finite (cover_rope_kv_write only ever writes finite values into a zero-initialised cache).
+ * Masked K rows inside the length may hold anything finite as well: their scores are replaced by -inf before the softmax.
  * ------------------------------------------------------------------------------------------------ */
 enum cover_mask_mode { COVER_MASK_LEN = 0, COVER_MASK_CAUSAL = 1, COVER_MASK_VISLEN = 2 };
 typedef struct cover_kv_segment {
@@ -214,11 +226,27 @@ typedef struct cover_attn_args {
     /* Optional MX block-scaled output INSTEAD of `out` (config 5: the o_proj operand without a quantiser launch; no reference arithmetic):
      * out8 = e4m3 rows addressed with the o_*_stride values in BYTES, out8_mx = E8M0 scales [Hq * D / 128][out8_rows][4] as cover_quantize_act_fp8_mx
      * lays them out (row = byte offset of (b, t) / o_t_stride), exactly what that function makes of the bf16 rows `out` would have received.
-     * MHA, D = 128, o_h_stride = 128, o_t_stride = Hq * 128, no state_out, at most 1023 query tiles (4095 with state_in): otherwise COVER_EINVAL. */
+     * MHA, D = 128, o_h_stride = 128, o_t_stride = Hq * 128, o_b_stride a multiple of o_t_stride, no state_out, B and Tq not 0, and either at most
+     * 1023 query tiles (4095 with state_in) or a problem that takes the shared-keys form (cover_attention_plan form 3: any number of tiles):
+     * otherwise COVER_EINVAL. */
     void* out8; void* out8_mx;
     int out8_rows; int _pad2;
 } cover_attn_args;
 int cover_attention_bf16(const cover_attn_args* args, void* stream);
+/* The launch form cover_attention_bf16 would take for these arguments, without launching anything (test / audit hook; pointers are only checked
+ * for null and alignment, never dereferenced). Returns COVER_OK or COVER_EINVAL exactly when cover_attention_bf16 would.
+ * plan[0] = form: -1 nothing to launch (B or Tq is 0), 0 one wave per 16 query rows walking every key, 1 key tiles split over the 4 waves of a
+ *   workgroup (at most 1023 query tiles = ceil(Tq * Hq / Hkv / 16) * Hkv * B; 4095 when resumed from state_in at D <= 128), 2 the same over 8 waves
+ *   (experiment knob only), 3 workgroup-shared keys (D = 128, MHA, COVER_MASK_LEN segments only, Tq >= 48, ceil(Tq / 64) * Hq * B >= 128);
+ * plan[1] = 1 for block-scaled output (out8); plan[2] = workgroups; plan[3] = waves per workgroup. */
+int cover_attention_plan(const cover_attn_args* args, int plan[4]);
+/* Two independent problems. ONE launch exactly when: same D in {64, 96, 128}, same Hkv, neither problem empty, each at most 1023 query tiles
+ * (state_in does not raise that bound here), neither has out8. Nothing else is looked at: the one launch runs form 1's arithmetic (keys split over 4
+ * waves) for both problems, also for a problem that alone would take the shared form (form 3) -- same result up to the order of the fp32 sums.
+ * Otherwise two launches, each as cover_attention_bf16 would run it. Both problems are validated before anything runs.
+ * cover_attention_pair_plan: *dual = 1 for the one launch, 0 for two; same status as cover_attention_bf16_pair. */
+int cover_attention_bf16_pair(const cover_attn_args* a0, const cover_attn_args* a1, void* stream);
+int cover_attention_pair_plan(const cover_attn_args* a0, const cover_attn_args* a1, int* dual);
 
 /* Fused single-token decode attention (OpenVLA-style candidate decode): RoPE + KV append + attention over
  * [seg[0]: ONE slot (slot 0) shared by all N candidates | seg[1]: per-prompt slot | seg[2]: the candidate's own tokens,
