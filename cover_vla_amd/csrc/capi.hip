@@ -322,6 +322,24 @@ int cover_token_topn_rows(const cover_token_topn_rows_args* a, void* stream) {
            "token_topn_rows (temperature, token_out and logprob_out required, 1 <= n <= 64, ld_tok >= n, ld_lp >= n, 0 < hi - lo <= 2^20)");
     return COVER_OK;
 }
+int cover_token_sample_rows_allowed(const cover_token_sample_rows_args* a, const cover_token_allow* al, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_token_sample_rows_allowed: null args");
+    HIPCHK(launch_token_sample_rows_allowed(a, al, ST(stream)),
+           "token_sample_rows_allowed (as token_sample_rows; allow and bits required, bits 4-byte aligned, n_sets >= 1, ld_words >= ceil(hi / 32))");
+    return COVER_OK;
+}
+int cover_token_logprob_rows_allowed(const cover_token_logprob_rows_args* a, const cover_token_allow* al, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_token_logprob_rows_allowed: null args");
+    HIPCHK(launch_token_logprob_rows_allowed(a, al, ST(stream)),
+           "token_logprob_rows_allowed (as token_logprob_rows; allow and bits required, bits 4-byte aligned, n_sets >= 1, ld_words >= ceil(hi / 32))");
+    return COVER_OK;
+}
+int cover_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_token_topn_rows_allowed: null args");
+    HIPCHK(launch_token_topn_rows_allowed(a, al, ST(stream)),
+           "token_topn_rows_allowed (as token_topn_rows; allow and bits required, bits 4-byte aligned, n_sets >= 1, ld_words >= ceil(hi / 32))");
+    return COVER_OK;
+}
 int cover_decode_feedback(const cover_decode_feedback_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_decode_feedback: null args");
     HIPCHK(launch_decode_feedback(a, ST(stream)),
@@ -874,7 +892,7 @@ size_t cover_sizeof(const char* n) {
 #define SZ(T) if (!strcmp(n, #T)) return sizeof(T)
     SZ(cover_gemm_epi); SZ(cover_kv_segment); SZ(cover_attn_args); SZ(cover_rope_args); SZ(cover_patchify_args);
     SZ(cover_gemm_f32_args); SZ(cover_mha_f32_args); SZ(cover_token_select_args); SZ(cover_token_sample_args); SZ(cover_score_select_args);
-    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_decode_feedback_args);
+    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_decode_feedback_args);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
 #undef SZ

@@ -82,6 +82,9 @@ hipError_t launch_token_topn(const cover_token_topn_args* a, hipStream_t st);
 hipError_t launch_token_sample_rows(const cover_token_sample_rows_args* a, hipStream_t st);
 hipError_t launch_token_logprob_rows(const cover_token_logprob_rows_args* a, hipStream_t st);
 hipError_t launch_token_topn_rows(const cover_token_topn_rows_args* a, hipStream_t st);
+hipError_t launch_token_sample_rows_allowed(const cover_token_sample_rows_args* a, const cover_token_allow* al, hipStream_t st);
+hipError_t launch_token_logprob_rows_allowed(const cover_token_logprob_rows_args* a, const cover_token_allow* al, hipStream_t st);
+hipError_t launch_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, hipStream_t st);
 // ---- select.hip ----------------------------------------------------------------------------------
 hipError_t launch_token_select(const cover_token_select_args* a, hipStream_t st);
 hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st);

@@ -75,16 +75,79 @@ __device__ __forceinline__ u64 shfl64(u64 v, int l) {
 }
 
 // The elements a stage iterates: columns [0, n) of the row (rel = column - lo), or the compacted candidates in LDS.
-struct SampleSrc {
+template <bool ALLOW>
+struct SampleSrcT {
     const float* p;   // row + lo
     int n;
     bool list;
+    static constexpr bool allow = false;
 };
+// The allowed variant (cover_token_*_rows_allowed): the row restricted to the columns whose bit is set in the row's allow set. A column
+// whose bit is clear never reaches a per-element functor, so counts, masses, the candidate list and the tile digit see allowed
+// columns only; the compacted list holds allowed elements and needs no mask afterwards.
+template <>
+struct SampleSrcT<true> {
+    const float* p;
+    int n;
+    bool list;
+    const unsigned* bits;   // the row's set: bit (c & 31) of word (c >> 5) for the ABSOLUTE column c
+    int lo;                 // column of rel 0
+    int cnt;                // allowed columns in [lo, hi): what n is wherever n is a count
+    int first;              // rel of the first allowed column
+    static constexpr bool allow = true;
+};
+typedef SampleSrcT<false> SampleSrc;
+typedef SampleSrcT<true> SampleSrcAllow;
+
+// the number of elements a filter can keep: the columns of the range, or the allowed ones among them
+template <class Src>
+__device__ __forceinline__ int src_count(const Src& src) {
+    if constexpr (Src::allow) return src.cnt;
+    else return src.n;
+}
+// is column rel allowed (one word read)
+template <class Src>
+__device__ __forceinline__ bool allow1(const Src& src, int rel) {
+    if constexpr (Src::allow) {
+        const unsigned a = (unsigned)(src.lo + rel);
+        return (src.bits[a >> 5] >> (a & 31u)) & 1u;
+    } else {
+        return true;
+    }
+}
+// bits 0..3: are columns rel .. rel + 3 allowed (all four inside the range). lo and the alignment head are arbitrary, so the four may
+// straddle a word: the covering word, and the next one only then, are read once for the group.
+template <class Src>
+__device__ __forceinline__ unsigned allow4(const Src& src, int rel) {
+    if constexpr (Src::allow) {
+        const unsigned a = (unsigned)(src.lo + rel), sh = a & 31u;
+        const unsigned* w = src.bits + (a >> 5);
+        unsigned m = w[0] >> sh;
+        if (sh > 28u) m |= w[1] << (32u - sh);
+        return m & 15u;
+    } else {
+        return 15u;
+    }
+}
+
+// What a row function is handed next to the range: nothing, or the row's set as allow_row found it.
+template <bool ALLOW>
+struct AllowRow {};
+template <>
+struct AllowRow<true> {
+    const unsigned* bits;
+    int cnt, first;
+};
+template <bool ALLOW>
+__device__ __forceinline__ SampleSrcT<ALLOW> make_src(const float* p, int n, int lo, const AllowRow<ALLOW>& ar) {
+    if constexpr (ALLOW) return SampleSrcT<true>{p, n, false, ar.bits, lo, ar.cnt, ar.first};
+    else return SampleSrcT<false>{p, n, false};
+}
 
 // f(logit, rel) for every element. Row: scalar head up to the first 16-byte boundary, float4 body (four loads in flight per lane),
 // scalar tail -- any lo / ld works, aligned rows take the vector path.
-template <class F>
-__device__ __forceinline__ void for_each(const SampleShared& s, const SampleSrc& src, F f) {
+template <class Src, class F>
+__device__ __forceinline__ void for_each(const SampleShared& s, const Src& src, F f) {
     const int tid = threadIdx.x;
     if (src.list) {
         const int nl = (int)s.n_list;
@@ -95,6 +158,33 @@ __device__ __forceinline__ void for_each(const SampleShared& s, const SampleSrc&
     const int n = src.n;
     int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
     head = head < n ? head : n;
+    if constexpr (Src::allow) {   // the same walk; the mask words of a group are loaded with its float4, all in flight together
+        for (int c = tid; c < head; c += SMP_T)
+            if (allow1(src, c)) f(p[c], c);
+        const int n4 = (n - head) >> 2;
+        const float4* v = (const float4*)(p + head);
+        auto take = [&](const float4& x, unsigned m, int c) {
+            const int i0 = head + 4 * c;
+            if (m & 1u) f(x.x, i0);
+            if (m & 2u) f(x.y, i0 + 1);
+            if (m & 4u) f(x.z, i0 + 2);
+            if (m & 8u) f(x.w, i0 + 3);
+        };
+        int c = tid;
+        for (; c + 3 * SMP_T < n4; c += 4 * SMP_T) {
+            const unsigned m0 = allow4(src, head + 4 * c), m1 = allow4(src, head + 4 * (c + SMP_T)),
+                           m2 = allow4(src, head + 4 * (c + 2 * SMP_T)), m3 = allow4(src, head + 4 * (c + 3 * SMP_T));
+            const float4 x0 = v[c], x1 = v[c + SMP_T], x2 = v[c + 2 * SMP_T], x3 = v[c + 3 * SMP_T];
+            take(x0, m0, c); take(x1, m1, c + SMP_T); take(x2, m2, c + 2 * SMP_T); take(x3, m3, c + 3 * SMP_T);
+        }
+        for (; c < n4; c += SMP_T) {
+            const unsigned m = allow4(src, head + 4 * c);
+            take(v[c], m, c);
+        }
+        for (int t = head + 4 * n4 + tid; t < n; t += SMP_T)
+            if (allow1(src, t)) f(p[t], t);
+        return;
+    }
     for (int c = tid; c < head; c += SMP_T) f(p[c], c);
     const int n4 = (n - head) >> 2;
     const float4* v = (const float4*)(p + head);
@@ -111,8 +201,8 @@ __device__ __forceinline__ void for_each(const SampleShared& s, const SampleSrc&
     for (int t = head + 4 * n4 + tid; t < n; t += SMP_T) f(p[t], t);
 }
 // the same for rel in [r0, r1) only
-template <class F>
-__device__ __forceinline__ void for_each_in(const SampleShared& s, const SampleSrc& src, int r0, int r1, F f) {
+template <class Src, class F>
+__device__ __forceinline__ void for_each_in(const SampleShared& s, const Src& src, int r0, int r1, F f) {
     const int tid = threadIdx.x;
     if (src.list) {
         const int nl = (int)s.n_list;
@@ -123,7 +213,8 @@ __device__ __forceinline__ void for_each_in(const SampleShared& s, const SampleS
         return;
     }
     r1 = r1 < src.n ? r1 : src.n;
-    for (int c = r0 + tid; c < r1; c += SMP_T) f(src.p[c], c);
+    for (int c = r0 + tid; c < r1; c += SMP_T)
+        if (allow1(src, c)) f(src.p[c], c);
 }
 
 __device__ __forceinline__ void hist_zero(SampleShared& s) {
@@ -233,9 +324,10 @@ struct KeptSet {
 
 // Steps 1-3: row maximum, k-th value, top-p cut. May compact the candidates into LDS and switch src to that list (src.list);
 // every thread of the block calls this, the result is block-uniform.
-__device__ __forceinline__ KeptSet kept_set(SampleShared& s, SampleSrc& src, int top_k, float top_p, float T) {
+template <class Src>
+__device__ __forceinline__ KeptSet kept_set(SampleShared& s, Src& src, int top_k, float top_p, float T) {
     const int tid = threadIdx.x;
-    const int n = src.n;
+    const int n = src_count(src);
     const bool use_k = top_k > 0 && top_k < n;
     const bool use_p = top_p < 1.0f;
     if (tid == 0) s.n_list = 0u;
@@ -367,7 +459,8 @@ __device__ __forceinline__ KeptSet kept_set(SampleShared& s, SampleSrc& src, int
 // Tiles are cut where the row's float4 body starts (tile 0 = the scalar head, if any), so the 256 columns one wave loads together
 // lie in one tile: on the row, a wave adds its kept masses and count with shuffles (exact: integers) and one lane adds them to
 // the tile -- per-element atomics on one address would serialise 64 lanes.
-__device__ __forceinline__ int kept_tiles(SampleShared& s, const SampleSrc& src, const KeptSet& ks) {
+template <class Src>
+__device__ __forceinline__ int kept_tiles(SampleShared& s, const Src& src, const KeptSet& ks) {
     const int tid = threadIdx.x;
     const int n = src.n;
     int head = 0;
@@ -389,13 +482,22 @@ __device__ __forceinline__ int kept_tiles(SampleShared& s, const SampleSrc& src,
             u64 q;
             if (ks.kept(l, rel, q)) hist_add(s, (rel + shift) >> 10, q);
         };
-        for (int c = tid; c < head; c += SMP_T) one(p[c], c);
+        for (int c = tid; c < head; c += SMP_T)
+            if (allow1(src, c)) one(p[c], c);
         const int n4 = (n - head) >> 2;
         const float4* v = (const float4*)(p + head);
         // packed per-lane sum: mass of <= 4 weights (< 2^46) in the low 52 bits, their count above; 64 lanes: mass < 2^52, count <= 256
         auto packed = [&](const float4& x, int c) -> u64 {
             const int i0 = head + 4 * c;
             u64 acc = 0ull, q;
+            if constexpr (Src::allow) {
+                const unsigned m = allow4(src, i0);
+                if ((m & 1u) && ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
+                if ((m & 2u) && ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
+                if ((m & 4u) && ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
+                if ((m & 8u) && ks.kept(x.w, i0 + 3, q)) acc += q + (1ull << 52);
+                return acc;
+            }
             if (ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
             if (ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
             if (ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
@@ -428,7 +530,8 @@ __device__ __forceinline__ int kept_tiles(SampleShared& s, const SampleSrc& src,
             flush(h2 ? packed(x2, c + 2 * SMP_T) : 0ull, cb + 2 * SMP_T);
             flush(h3 ? packed(x3, c + 3 * SMP_T) : 0ull, cb + 3 * SMP_T);
         }
-        for (int c = head + 4 * n4 + tid; c < n; c += SMP_T) one(p[c], c);
+        for (int c = head + 4 * n4 + tid; c < n; c += SMP_T)
+            if (allow1(src, c)) one(p[c], c);
     }
     return shift;
 }
@@ -446,11 +549,13 @@ __device__ __forceinline__ float kept_logprob(const KeptSet& ks, float l, int re
 // One row of the sampler: steps 1-4 of cover_token_sample over columns [lo, hi) of lg with the uniform u. Every thread of the block calls
 // this; thread 0 stores. logprob_out == nullptr: no score. token_sample_k and token_sample_rows_k are this function with the launch's and
 // the row's parameters respectively, so a row means the same in both.
+template <bool ALLOW = false>
 __device__ __forceinline__ void sample_row(SampleShared& s, const float* lg, int lo, int hi, float temperature, int top_k, float top_p, float u,
-                                           int row, int64_t* token_out, float* logit_out, int* kept_out, float* logprob_out) {
+                                           int row, int64_t* token_out, float* logit_out, int* kept_out, float* logprob_out,
+                                           const AllowRow<ALLOW>& ar = AllowRow<ALLOW>{}) {
     const int tid = threadIdx.x;
     const int n = hi - lo;
-    SampleSrc src{lg + lo, n, false};
+    SampleSrcT<ALLOW> src = make_src<ALLOW>(lg + lo, n, lo, ar);
     const KeptSet ks = kept_set(s, src, top_k, top_p, temperature);
 
     // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
@@ -470,6 +575,8 @@ __device__ __forceinline__ void sample_row(SampleShared& s, const float* lg, int
     if (tid == 0) {
         int pick = t0 + s.r_bin;
         pick = pick < 0 ? 0 : (pick < n ? pick : n - 1);
+        if constexpr (ALLOW)   // a row without mass (its allowed columns all NaN or -inf) crosses nowhere: the first allowed column
+            if (!allow1(src, pick)) pick = src.first;
         token_out[row] = lo + pick;
         const float l = lg[lo + pick];
         if (logit_out) logit_out[row] = l;
@@ -487,17 +594,20 @@ __global__ __launch_bounds__(SMP_T) void token_sample_k(cover_token_sample_args 
 }
 
 // Scores given tokens: the kept set and its mass as the sampler computes them (the same two device functions), no pick.
+template <bool ALLOW = false>
 __device__ __forceinline__ void logprob_row(SampleShared& s, const float* lg, int lo, int hi, float temperature, int top_k, float top_p,
-                                            int row, const int64_t* token, float* logprob_out, int* kept_out) {
+                                            int row, const int64_t* token, float* logprob_out, int* kept_out,
+                                            const AllowRow<ALLOW>& ar = AllowRow<ALLOW>{}) {
     const int n = hi - lo;
-    SampleSrc src{lg + lo, n, false};
+    SampleSrcT<ALLOW> src = make_src<ALLOW>(lg + lo, n, lo, ar);
     const KeptSet ks = kept_set(s, src, top_k, top_p, temperature);
     kept_tiles(s, src, ks);
     scan_bins<false, true>(s, SMP_BINS, 1ull);
     if (threadIdx.x == 0) {
         const long long t = (long long)token[row];
         float lp = -INFINITY;
-        if (t >= (long long)lo && t < (long long)hi) lp = kept_logprob(ks, lg[t], (int)(t - lo), s.r_mass_total);
+        if (t >= (long long)lo && t < (long long)hi && allow1(src, (int)(t - lo)))   // a token that is not allowed: nothing is read for it
+            lp = kept_logprob(ks, lg[t], (int)(t - lo), s.r_mass_total);
         logprob_out[row] = lp;
         if (kept_out) kept_out[row] = (int)s.r_cnt_total;
     }
@@ -518,11 +628,13 @@ struct TopnShared {
 };
 
 // One row of cover_token_topn; a carries the row's (temperature, top_k, top_p): the launch's in token_topn_k, the row's own in token_topn_rows_k.
-__device__ __forceinline__ void topn_row(SampleShared& s, TopnShared& t, const cover_token_topn_args& a, int row) {
+template <bool ALLOW = false>
+__device__ __forceinline__ void topn_row(SampleShared& s, TopnShared& t, const cover_token_topn_args& a, int row,
+                                         const AllowRow<ALLOW>& ar = AllowRow<ALLOW>{}) {
     const int tid = threadIdx.x, lane = tid & 63;
     const float* lg = a.logits + (size_t)row * a.ld;
     const int n = a.hi - a.lo;
-    SampleSrc src{lg + a.lo, n, false};
+    SampleSrcT<ALLOW> src = make_src<ALLOW>(lg + a.lo, n, a.lo, ar);
     const KeptSet ks = kept_set(s, src, a.top_k, a.top_p, a.temperature);
     kept_tiles(s, src, ks);
     scan_bins<false, true>(s, SMP_BINS, 1ull);
@@ -761,6 +873,127 @@ __global__ __launch_bounds__(SMP_T) void token_topn_rows_k(cover_token_topn_rows
     topn_row(s, t, b, row);
 }
 
+// ---- allowed-token sets per row (cover_token_*_rows_allowed) ------------------------------------------------------------------
+// The row's set: counts the allowed columns of [lo, hi) and finds the first of them (one pass over the words that cover the range, edge
+// words trimmed to it; integer LDS atomics). false: the row is invalid (set index outside [0, n_sets), or no allowed column in range).
+// Every thread of the block calls this; block-uniform.
+__device__ __forceinline__ bool allow_row(SampleShared& s, const cover_token_allow& al, int lo, int hi, int row, AllowRow<true>& ar) {
+    const int tid = threadIdx.x;
+    const int set = al.set_of_row ? al.set_of_row[row] : 0;
+    if (set < 0 || set >= al.n_sets) return false;
+    const unsigned* bits = al.bits + (size_t)set * (size_t)al.ld_words;
+    if (tid == 0) {
+        s.r_cnt_total = 0u;
+        s.r_bin = 0x7fffffff;
+    }
+    __syncthreads();
+    const int w0 = lo >> 5, w1 = (hi - 1) >> 5;
+    unsigned cnt = 0u;
+    int first = 0x7fffffff;
+    for (int w = w0 + tid; w <= w1; w += SMP_T) {   // ascending per thread: its first hit is its lowest
+        unsigned v = bits[w];
+        if (w == w0) v &= 0xffffffffu << (lo & 31);
+        if (w == w1 && (hi & 31)) v &= (1u << (hi & 31)) - 1u;
+        cnt += (unsigned)__popc(v);
+        if (v && first == 0x7fffffff) first = (w << 5) + (__ffs((int)v) - 1) - lo;
+    }
+    if (cnt) {
+        atomicAdd(&s.r_cnt_total, cnt);
+        atomicMin(&s.r_bin, first);
+    }
+    __syncthreads();
+    ar.bits = bits;
+    ar.cnt = (int)s.r_cnt_total;
+    ar.first = s.r_bin;
+    __syncthreads();   // the row functions write s.r_* again
+    return ar.cnt > 0;
+}
+
+// The three kernels below are token_*_rows_k above with the row's set looked up first and handed to the same row functions.
+__global__ __launch_bounds__(SMP_T) void token_sample_rows_allowed_k(cover_token_sample_rows_args a, cover_token_allow al) {
+    __shared__ SampleShared s;
+    __shared__ int first;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<true> ar;
+    if (rp.mode == 2 || !allow_row(s, al, a.lo, a.hi, row, ar)) {   // block-uniform
+        if (tid == 0) {
+            a.token_out[row] = -1;
+            if (a.logit_out) a.logit_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+            if (a.logprob_out) a.logprob_out[row] = NAN;
+        }
+        return;
+    }
+    const float* lg = a.logits + (size_t)row * a.ld;
+    if (rp.mode == 0) {
+        sample_row<true>(s, lg, a.lo, a.hi, rp.T, rp.k, rp.p, a.uniform[row], row, a.token_out, a.logit_out, a.kept_out, a.logprob_out, ar);
+        return;
+    }
+    // greedy: the first arg-max of the input floats; its log-probability is logprob_row's at temperature 1, unfiltered (the same calls)
+    const int n = a.hi - a.lo;
+    SampleSrcT<true> src = make_src<true>(lg + a.lo, n, a.lo, ar);
+    if (tid == 0) first = 0x7fffffff;
+    const KeptSet ks = kept_set(s, src, 0, 1.0f, 1.0f);   // the row maximum (NaNs never win, as in token_select_k); syncs the block
+    kept_tiles(s, src, ks);
+    scan_bins<false, true>(s, SMP_BINS, 1ull);
+    int mine = 0x7fffffff;
+    for_each(s, src, [&](float l, int rel) {
+        if (l == ks.m && rel < mine) mine = rel;
+    });
+    if (mine != 0x7fffffff) atomicMin(&first, mine);
+    __syncthreads();
+    if (tid == 0) {
+        int pick = first;
+        pick = pick < n ? pick : src.first;   // allowed columns all NaN: no maximum
+        a.token_out[row] = a.lo + pick;
+        const float l = lg[a.lo + pick];
+        if (a.logit_out) a.logit_out[row] = l;
+        if (a.kept_out) a.kept_out[row] = src_count(src);
+        if (a.logprob_out) a.logprob_out[row] = kept_logprob(ks, l, pick, s.r_mass_total);
+    }
+}
+
+__global__ __launch_bounds__(SMP_T) void token_logprob_rows_allowed_k(cover_token_logprob_rows_args a, cover_token_allow al) {
+    __shared__ SampleShared s;
+    const int row = blockIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<true> ar;
+    if (rp.mode == 2 || !allow_row(s, al, a.lo, a.hi, row, ar)) {
+        if (threadIdx.x == 0) {
+            a.logprob_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+        }
+        return;
+    }
+    logprob_row<true>(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, rp.T, rp.k, rp.p, row, a.token, a.logprob_out, a.kept_out, ar);
+}
+
+__global__ __launch_bounds__(SMP_T) void token_topn_rows_allowed_k(cover_token_topn_rows_args a, cover_token_allow al) {
+    __shared__ SampleShared s;
+    __shared__ TopnShared t;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<true> ar;
+    if (rp.mode == 2 || !allow_row(s, al, a.lo, a.hi, row, ar)) {
+        if (tid < a.n) {
+            a.token_out[(size_t)row * a.ld_tok + tid] = -1;
+            a.logprob_out[(size_t)row * a.ld_lp + tid] = -INFINITY;
+        }
+        if (tid == 0) {
+            if (a.entropy_out) a.entropy_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+        }
+        return;
+    }
+    cover_token_topn_args b;
+    b.logits = a.logits; b.ld = a.ld; b.rows = a.rows; b.lo = a.lo; b.hi = a.hi;
+    b.temperature = rp.T; b.top_k = rp.k; b.top_p = rp.p; b.n = a.n;
+    b.token_out = a.token_out; b.ld_tok = a.ld_tok; b.logprob_out = a.logprob_out; b.ld_lp = a.ld_lp;
+    b.entropy_out = a.entropy_out; b.kept_out = a.kept_out;
+    topn_row<true>(s, t, b, row, ar);
+}
+
 __global__ void fill_i32_k(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -841,6 +1074,37 @@ hipError_t launch_token_topn_rows(const cover_token_topn_rows_args* a, hipStream
     if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     hipLaunchKernelGGL(token_topn_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
+    return hipGetLastError();
+}
+
+// the set itself lives on the device as well: the launch checks its shape, a row whose set index or set is unusable reports itself
+static bool allow_ok(const cover_token_allow* al, int hi) {
+    if (!al || !al->bits || ((uintptr_t)al->bits & 3u)) return false;
+    return al->n_sets >= 1 && al->ld_words >= (long long)((hi + 31) / 32);
+}
+
+hipError_t launch_token_sample_rows_allowed(const cover_token_sample_rows_args* a, const cover_token_allow* al, hipStream_t st) {
+    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_sample_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_logprob_rows_allowed(const cover_token_logprob_rows_args* a, const cover_token_allow* al, hipStream_t st) {
+    if (!a->logits || !a->temperature || !a->token || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_logprob_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, hipStream_t st) {
+    if (!a->logits || !a->temperature || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_topn_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
     return hipGetLastError();
 }
 

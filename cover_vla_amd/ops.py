@@ -806,8 +806,71 @@ def _upload_row_params(params, device):
     return [p if p is None or p.is_cuda else p.to(device) for p in params]
 
 
+class TokenAllow:
+    """Allowed-token sets for the *_rows calls (cover_token_allow): bits uint32 (or int32) device tensor [n_sets, words] with unit column
+    stride, bit (c & 31) of word (c >> 5) of a set = column c may be drawn (token_allow_sets builds it); set_of_row int32 device tensor
+    [rows] naming each row's set, None = set 0 for every row. A holder of the caller's tensors: the kernels read their current contents,
+    so both may be rewritten between launches and graph replays."""
+
+    def __init__(self, bits, set_of_row=None):
+        if not isinstance(bits, torch.Tensor) or bits.dtype not in (torch.uint32, torch.int32) or bits.dim() != 2 or bits.shape[0] < 1 \
+                or (bits.shape[1] > 1 and bits.stride(1) != 1):
+            raise L.CoverError("TokenAllow: bits must be a uint32 tensor [n_sets >= 1, words] with unit column stride")
+        if set_of_row is not None and (not isinstance(set_of_row, torch.Tensor) or set_of_row.dtype != torch.int32 or set_of_row.dim() != 1
+                                       or not set_of_row.is_contiguous()):
+            raise L.CoverError("TokenAllow: set_of_row must be a contiguous int32 tensor [rows]")
+        self.bits = bits
+        self.set_of_row = set_of_row
+
+    @property
+    def n_sets(self):
+        return self.bits.shape[0]
+
+
+def token_allow_sets(vocab, sets, device=None):
+    """Build the bit masks of TokenAllow on the host: sets is a sequence of sets, each a sequence of ids and / or half-open (a, b) ranges
+    of ids. Returns a uint32 tensor [n_sets, ceil(vocab / 32)] (on device if given). ValueError on an id outside [0, vocab)."""
+    vocab = int(vocab)
+    if vocab < 1 or len(sets) < 1:
+        raise ValueError("token_allow_sets: vocab >= 1 and at least one set are required")
+    words = (vocab + 31) // 32
+    on = np.zeros((len(sets), words * 32), dtype=bool)
+    for i, entries in enumerate(sets):
+        for e in entries:
+            if isinstance(e, (tuple, list)):
+                if len(e) != 2:
+                    raise ValueError(f"token_allow_sets: a range is (a, b), got {e!r}")
+                a, b = int(e[0]), int(e[1])
+                if not 0 <= a <= b <= vocab:
+                    raise ValueError(f"token_allow_sets: range ({a}, {b}) leaves [0, {vocab})")
+                on[i, a:b] = True
+            else:
+                t = int(e)
+                if not 0 <= t < vocab:
+                    raise ValueError(f"token_allow_sets: id {t} is outside [0, {vocab})")
+                on[i, t] = True
+    bits = np.packbits(on.reshape(len(sets), words, 32), axis=2, bitorder="little").view("<u4").reshape(len(sets), words)
+    out = torch.from_numpy(np.ascontiguousarray(bits).view(np.int32)).view(torch.uint32)
+    return out if device is None else out.to(device)
+
+
+def _allow_arg(what, allow, rows, hi, logits):
+    """The cover_token_allow of a launch from a TokenAllow, shapes checked on the host (the contents are the kernel's to judge)."""
+    if not isinstance(allow, TokenAllow):
+        raise L.CoverError(f"{what}: allow must be an ops.TokenAllow")
+    if allow.bits.shape[1] * 32 < hi:
+        raise L.CoverError(f"{what}: allow.bits has {allow.bits.shape[1]} words per set, columns below hi = {hi} need {(hi + 31) // 32}")
+    if allow.set_of_row is not None and allow.set_of_row.numel() != rows:
+        raise L.CoverError(f"{what}: allow.set_of_row must have one entry per row ({rows})")
+    _chk_dev(logits, allow.bits, allow.set_of_row)
+    al = L.TokenAllow()
+    al.bits, al.ld_words, al.n_sets = allow.bits.data_ptr(), max(allow.bits.stride(0), allow.bits.shape[1]), allow.bits.shape[0]
+    al.set_of_row = _ptr(allow.set_of_row)
+    return al
+
+
 def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=None, out_tok=None, out_logit=None, out_kept=None,
-                      out_logprob=None):
+                      out_logprob=None, allow=None):
     """token_sample with the parameters of every row its own (cover_token_sample_rows): temperature fp32 / top_k int32 / top_p fp32 device
     tensors [rows] (top_k None = 0, top_p None = 1 for every row); a Python sequence or CPU tensor is validated on the host
     (temperature >= 0, top_p > 0, top_k >= 0, all finite) and uploaded. temperature[r] > 0: row r is token_sample's row with its
@@ -815,7 +878,10 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
     token = the first arg-max over [lo, hi), kept = hi - lo, log-probability at temperature 1 unfiltered; its top_k / top_p / uniform
     entries are not read. A row whose device-side parameters are invalid writes token -1, logit / log-probability NaN, kept 0.
     Returns (token int64 [rows], its raw logit fp32 [rows], kept int32 [rows]); out_* as in token_sample. One launch, recordable,
-    deterministic: a row's result does not depend on the other rows of the launch."""
+    deterministic: a row's result does not depend on the other rows of the launch.
+    allow = TokenAllow: cover_token_sample_rows_allowed, the same on each row restricted to the columns of its set (max, top-k, top-p, pick,
+    kept and log-probability over the allowed columns only; disallowed columns are never looked at); a row whose set index is out of
+    range or whose set has no column in [lo, hi) is an invalid row. None issues exactly the unmasked call."""
     if uniform is None:
         raise L.CoverError("token_sample_rows needs uniforms [rows] (a greedy row ignores its entry)")
     if hi <= lo or lo < 0:
@@ -839,14 +905,19 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
     a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
     a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), T.data_ptr(), _ptr(k), _ptr(p)
     a.token_out, a.logit_out, a.kept_out, a.logprob_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr(), _ptr(out_logprob)
+    if allow is not None:
+        al = _allow_arg("token_sample_rows", allow, rows, hi, logits)
+        L.check(L.lib().cover_token_sample_rows_allowed(C.byref(a), C.byref(al), _stream()), "token_sample_rows_allowed")
+        return tok, lg, kept
     L.check(L.lib().cover_token_sample_rows(C.byref(a), _stream()), "token_sample_rows")
     return tok, lg, kept
 
 
-def token_logprob_rows(logits, lo, hi, tokens, temperature, top_k=None, top_p=None, out=None, out_kept=None):
+def token_logprob_rows(logits, lo, hi, tokens, temperature, top_k=None, top_p=None, out=None, out_kept=None, allow=None):
     """token_logprob with the parameters of every row its own (cover_token_logprob_rows; the parameter arguments as in
     token_sample_rows). A greedy row (temperature 0) is scored at temperature 1, unfiltered; a row with invalid device-side parameters
-    gives NaN and kept 0. On token_sample_rows' own picks it equals that call's out_logprob bit for bit."""
+    gives NaN and kept 0. On token_sample_rows' own picks it equals that call's out_logprob bit for bit. allow = TokenAllow:
+    cover_token_logprob_rows_allowed, scored under the row restricted to its set; a token that is not allowed gets -inf."""
     if hi <= lo or lo < 0:
         raise L.CoverError(f"token_logprob_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
@@ -865,14 +936,20 @@ def token_logprob_rows(logits, lo, hi, tokens, temperature, top_k=None, top_p=No
     a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
     a.temperature, a.top_k, a.top_p = T.data_ptr(), _ptr(k), _ptr(p)
     a.token, a.logprob_out, a.kept_out = tokens.data_ptr(), lp.data_ptr(), _ptr(out_kept)
+    if allow is not None:
+        al = _allow_arg("token_logprob_rows", allow, rows, hi, logits)
+        L.check(L.lib().cover_token_logprob_rows_allowed(C.byref(a), C.byref(al), _stream()), "token_logprob_rows_allowed")
+        return lp
     L.check(L.lib().cover_token_logprob_rows(C.byref(a), _stream()), "token_logprob_rows")
     return lp
 
 
-def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_tok=None, out_logprob=None, out_entropy=None, out_kept=None):
+def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_tok=None, out_logprob=None, out_entropy=None, out_kept=None,
+                    allow=None):
     """token_topn with the parameters of every row its own (cover_token_topn_rows; the parameter arguments as in token_sample_rows).
     A greedy row (temperature 0) is ranked at temperature 1, unfiltered; a row with invalid device-side parameters gives -1 / -inf in
-    every slot, entropy NaN and kept 0. Returns (tokens int64 [rows, n], logprobs fp32 [rows, n], entropy fp32 [rows])."""
+    every slot, entropy NaN and kept 0. Returns (tokens int64 [rows, n], logprobs fp32 [rows, n], entropy fp32 [rows]). allow = TokenAllow:
+    cover_token_topn_rows_allowed, only the allowed columns of each row's set are ranked and the entropy is that of the restricted kept set."""
     if hi <= lo or lo < 0:
         raise L.CoverError(f"token_topn_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
     if not 1 <= int(n) <= 64:
@@ -899,22 +976,30 @@ def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_
     a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
     a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
     a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    if allow is not None:
+        al = _allow_arg("token_topn_rows", allow, rows, hi, logits)
+        L.check(L.lib().cover_token_topn_rows_allowed(C.byref(a), C.byref(al), _stream()), "token_topn_rows_allowed")
+        return tok, lp, ent
     L.check(L.lib().cover_token_topn_rows(C.byref(a), _stream()), "token_topn_rows")
     return tok, lp, ent
 
 
 def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None,
-               row_params=None):
+               row_params=None, allow=None):
     """One decode step's pick over columns [lo, hi), the three-way choice of every token head. Returns (token, its logit, kept or None).
     uniform None: greedy token_select (temperature and filt are unused); uniform with filt None: token_select's unfiltered inverse-CDF
     sample; uniform with filt = (top_k, top_p): ONE token_sample call, whose kept count is returned. out_logprob fp32 [rows]: filled with
     the log-probability of each pick under the distribution it came from (greedy: temperature 1, unfiltered), by token_sample itself or
     by one token_logprob launch behind token_select. The out_* rows are the wrappers' own; no arithmetic or allocation of its own.
     row_params = (temperature, top_k, top_p) device tensors [rows]: ONE token_sample_rows call with the parameters of every row its own
-    (uniform is required, temperature and filt are unused; a row with temperature 0 is greedy); its kept count is returned."""
+    (uniform is required, temperature and filt are unused; a row with temperature 0 is greedy); its kept count is returned.
+    allow = TokenAllow (with row_params only): that call restricted to each row's allowed-token set."""
+    if allow is not None and row_params is None:
+        raise L.CoverError("pick_token: allow needs row_params (the allowed-token sets belong to the per-row call)")
     if row_params is not None:
+        extra = {} if allow is None else dict(allow=allow)      # None: exactly the call made before the argument existed
         return token_sample_rows(logits, lo, hi, uniform, row_params[0], row_params[1], row_params[2], out_tok=out_tok, out_logit=out_logit,
-                                 out_kept=out_kept, out_logprob=out_logprob)
+                                 out_kept=out_kept, out_logprob=out_logprob, **extra)
     if uniform is not None and filt is not None:
         return token_sample(logits, lo, hi, uniform, temperature=temperature, top_k=filt[0], top_p=filt[1], out_tok=out_tok,
                             out_logit=out_logit, out_kept=out_kept, out_logprob=out_logprob)

@@ -95,7 +95,8 @@ class PI0FASTTokens:
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, top_k: RowParam = 0,
-                        top_p: RowParam = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0):
+                        top_p: RowParam = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0,
+                        allowed_tokens: Optional[ops.TokenAllow] = None):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -123,7 +124,15 @@ class PI0FASTTokens:
         ONE ops.token_sample_rows launch over the vocabulary (ops.pick_token(row_params=)): uniforms is then required, a row with
         temperature 0 is greedy (the arg-max, scored at temperature 1 unfiltered; its uniforms are not read), return_logprobs is that
         launch's log-probability and top_logprobs is ops.token_topn_rows. Rows are decoded on their own, as in sampling (no greedy
-        de-duplication); share_prefix works as before."""
+        de-duplication); share_prefix works as before.
+        allowed_tokens = ops.TokenAllow (bits over the vocabulary's ids, optionally set_of_row int32 [B]): every row draws from its set
+        only -- each step's pick is ONE cover_token_sample_rows_allowed launch (scalar parameters are broadcast through
+        ops.row_param_tensors; uniforms None = temperature 0 for every row, and rows are decoded on their own: no greedy
+        de-duplication), return_logprobs and top_logprobs are taken under the restricted distribution (the allowed scorer and ranker).
+        The sets are validated on the host once (one read-back), CoverError otherwise: set_of_row has B entries inside [0, n_sets) and
+        every set a row names holds an id below the vocabulary size, so no pick is the -1 of an invalid row. share_prefix,
+        force_tokens, the EOS / pad bookkeeping (a finished row's pad is not a draw and need not be allowed) and the fused feedback are
+        untouched. None launches exactly what it launched before."""
         dev = self.dev
         if not 0 <= int(top_logprobs) <= 64:
             raise ValueError("top_logprobs must be in 0..64")
@@ -137,9 +146,13 @@ class PI0FASTTokens:
             if uniforms is None:
                 raise ValueError("per-row temperature / top_k / top_p need uniforms (a greedy row is a temperature of 0)")
             rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
+        if allowed_tokens is not None:
+            self._check_allowed(allowed_tokens, tokens.shape[0])
+            if rp is None:     # the allowed pick is the per-row call: scalars are broadcast, no uniforms = every row greedy
+                rp = ops.row_param_tensors(tokens.shape[0], *((0.0, 0, 1.0) if uniforms is None else (temperature, top_k, top_p)), dev)
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
-        if (not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
+        if (allowed_tokens is None and not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
                 and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images)):
             first, slot = prefix_groups(tokens, pad_mask)
             if first.shape[0] < tokens.shape[0]:
@@ -152,10 +165,30 @@ class PI0FASTTokens:
                     return sub_out[back]
                 return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
         return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp)
+                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens)
+
+    def _check_allowed(self, allow, B):
+        """generate_tokens' host check of its allowed-token sets (one read-back of the bits and the row indices)."""
+        if not isinstance(allow, ops.TokenAllow):
+            raise ops.L.CoverError("allowed_tokens must be an ops.TokenAllow")
+        vocab = self.c["vocab"]
+        if allow.bits.shape[1] * 32 < vocab:
+            raise ops.L.CoverError(f"allowed_tokens: {allow.bits.shape[1]} words per set do not cover the {vocab} ids of the vocabulary")
+        used = np.zeros(1, dtype=np.int64)
+        if allow.set_of_row is not None:
+            if allow.set_of_row.numel() != B:
+                raise ops.L.CoverError(f"allowed_tokens: set_of_row must have one entry per row ({B})")
+            used = np.unique(allow.set_of_row.detach().cpu().numpy().astype(np.int64))
+            if used[0] < 0 or used[-1] >= allow.n_sets:
+                raise ops.L.CoverError(f"allowed_tokens: set_of_row must lie in [0, {allow.n_sets})")
+        words = allow.bits.detach().cpu().view(torch.int32).numpy().view(np.uint32)[used, :(vocab + 31) // 32].copy()
+        if vocab & 31:
+            words[:, -1] &= np.uint32((1 << (vocab & 31)) - 1)
+        if not np.all(words.any(axis=1)):
+            raise ops.L.CoverError(f"allowed_tokens: a set that a row uses allows no id below the vocabulary size {vocab}")
 
     def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None):
+                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None):
         """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
@@ -163,7 +196,8 @@ class PI0FASTTokens:
         prompt's through segment 0's slot_of_batch; between two steps ONE ops.decode_feedback launch settles the token, the
         log-probability, the done flag, the live count and the next step's embedding row. COVER_FAST_FEEDBACK=0 (read per call) issues
         the torch statements of the other path instead.
-        rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused)."""
+        rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused).
+        allow ops.TokenAllow or None (rp is then set): the pick, the score and the ranks over each row's allowed ids only."""
         dev, c = self.dev, self.c
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
@@ -230,6 +264,8 @@ class PI0FASTTokens:
         head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
         tsel = torch.empty(B, dtype=torch.int64, device=dev)
         xd = torch.empty(B, D, dtype=BF, device=dev)
+        u_none = torch.zeros(B, dtype=torch.float32, device=dev) if allow is not None and u_t is None else None   # greedy rows read no uniform
+        akw = {} if allow is None else dict(allow=allow)      # None: the calls made before the argument existed
 
         def pick(hidden, i):
             hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
@@ -238,16 +274,16 @@ class PI0FASTTokens:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
             # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
             if rp is not None:     # one ops.token_sample_rows launch; ops.token_topn_rows ranks under each row's own distribution
-                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp)
+                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_none if u_t is None else u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp, **akw)
                 if n_top:
-                    ops.token_topn_rows(lg, 0, c["vocab"], n_top, rp[0], rp[1], rp[2], out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
+                    ops.token_topn_rows(lg, 0, c["vocab"], n_top, rp[0], rp[1], rp[2], out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i], **akw)
             else:
                 t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
                                             out_logprob=lp)
                 if n_top:     # the distribution out_logprob scores the pick under (greedy: temperature 1, unfiltered)
                     ops.token_topn(lg, 0, c["vocab"], n_top, 1.0 if u_t is None else temperature, 0 if u_t is None else top_k,
                                    1.0 if u_t is None else top_p, out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
-            if u_t is not None and trace is not None:
+            if (u_t is not None or allow is not None) and trace is not None:
                 trace.setdefault("picks", []).append(t.clone())
                 trace.setdefault("kept", []).append(kept)
             if fused:      # the statements below and the next step's embed_gather, one launch
@@ -314,6 +350,9 @@ class PI0FASTConfig:
     return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
     top_logprobs: int = 0               # keep the n most probable tokens / log-probabilities / entropy of every step (last_top_logprobs)
     share_prefix: bool = False          # candidates with equal frames and prompt share one prefill (generate_tokens(share_prefix=True))
+    # half-open (a, b) ranges of PaliGemma ids every row may draw (generate_tokens(allowed_tokens=)): the FAST band from
+    # fast_action_token_range plus (b = a + 1) the format tokens; the EOS id is always added. None = the whole vocabulary
+    allowed_token_ranges: Optional[Sequence[Tuple[int, int]]] = None
 
 
 class PI0FASTPolicy:
@@ -331,6 +370,11 @@ class PI0FASTPolicy:
         self._gen = None if config.sample_seed is None else torch.Generator().manual_seed(int(config.sample_seed))
         self.last_sequence_logprobs = None        # fp32 [B] on the device, set by a generation that ran with config.return_logprobs
         self.last_top_logprobs = None             # host.TopLogprobs on the device, set by a generation that ran with config.top_logprobs > 0
+        self.allowed_tokens = None                # one set for every row, built once; EOS is always in it, otherwise a row can never finish
+        if config.allowed_token_ranges is not None:
+            ranges = [(int(a), int(b)) for a, b in config.allowed_token_ranges]
+            bits = ops.token_allow_sets(model.c["vocab"], [ranges + [int(paligemma_tokenizer.eos_token_id)]], model.dev)
+            self.allowed_tokens = ops.TokenAllow(bits)
         self.reset()
 
     def reset(self):
@@ -403,6 +447,8 @@ class PI0FASTPolicy:
                 sampling.update(top_logprobs=self.config.top_logprobs)
             if self.config.share_prefix:
                 sampling.update(share_prefix=True)
+            if self.allowed_tokens is not None:
+                sampling.update(allowed_tokens=self.allowed_tokens)
             if self._gen is not None:
                 u = torch.rand(B, self.config.max_decoding_steps, generator=self._gen, dtype=torch.float32)
                 sampling.update(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)
@@ -453,3 +499,13 @@ def fast_coefficients_to_actions(token_lists: Sequence[Sequence[int]], bpe_decod
 def fast_tokens_to_paligemma_tokens(tokens: np.ndarray, vocab_size: int, fast_skip_tokens: int = 128) -> np.ndarray:
     """_act_tokens_to_paligemma_tokens (:538-540): FAST ids live at the top of PaliGemma's vocabulary, mirrored (an involution)."""
     return vocab_size - 1 - fast_skip_tokens - np.asarray(tokens)
+
+
+def fast_action_token_range(vocab_size: int, fast_vocab_size: int, fast_skip_tokens: int = 128) -> Tuple[int, int]:
+    """The half-open band (a, b) of PaliGemma ids that fast_tokens_to_paligemma_tokens maps the FAST ids 0 .. fast_vocab_size - 1 onto:
+    what PI0FASTConfig.allowed_token_ranges takes for the action tokens, next to the ids of the format tokens ("Action", ":", "|")."""
+    b = int(vocab_size) - int(fast_skip_tokens)
+    a = b - int(fast_vocab_size)
+    if fast_vocab_size < 1 or a < 0:
+        raise ValueError("fast_action_token_range: 1 <= fast_vocab_size <= vocab_size - fast_skip_tokens is required")
+    return a, b

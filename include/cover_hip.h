@@ -609,6 +609,42 @@ typedef struct cover_token_topn_rows_args {
 } cover_token_topn_rows_args;
 int cover_token_topn_rows(const cover_token_topn_rows_args* args, void* stream);
 
+/* Allowed-token sets per row: cover_token_sample_rows, cover_token_logprob_rows and cover_token_topn_rows restricted to the columns a
+ * row may draw (Hugging Face's prefix_allowed_tokens_fn / suppress_tokens / bad_words_ids for single ids), inside the kernels: no
+ * masked copy of the [rows, vocabulary] slab is written or read. The argument structs are the unmasked calls', unchanged.
+ * An allow set is a bitmask over ABSOLUTE column ids: bit (c & 31) of word (c >> 5) is 1 when column c may be drawn. A launch carries
+ * n_sets sets, ld_words words apart, and set_of_row[rows] (NULL: every row uses set 0). For a row with set A each call computes what
+ * the unmasked _rows call computes on the row restricted to the columns of [lo, hi) that are in A, column ids unchanged:
+ *   disallowed columns    never reach the arithmetic: they may hold NaN, +-inf or 3e38 without changing one output bit.
+ *   sampled row           maximum, top-k (ties with the k-th value stay), top-p cut and the inverse-CDF pick run over the allowed columns
+ *                         only, on the same Q43 integer masses. kept_out counts allowed columns only, so top_k >= |A n [lo, hi)| keeps
+ *                         every allowed column. logprob_out = lp(pick) under that restricted distribution. If no allowed column has
+ *                         mass (all NaN or -inf), the pick is the first allowed column.
+ *   greedy row            the first arg-max among the allowed columns, scored at temperature 1, unfiltered, over the allowed columns;
+ *                         kept_out = |A n [lo, hi)|.
+ *   scorer                a token outside [lo, hi) or not in A gets -inf and nothing is read for it.
+ *   top-n                 only allowed columns are ranked; slots beyond min(n, kept) are -1 / -inf; the entropy is that of the
+ *                         restricted kept set.
+ *   invalid               additionally to the unmasked calls' conditions: set_of_row[r] outside [0, n_sets), or a set without a column
+ *                         in [lo, hi) (both live on the device). Reported as an invalid row is there: token -1, logit_out = logprob_out =
+ *                         NaN, kept_out = 0 (topn: every slot -1 / -inf, entropy NaN, kept 0). No trap; the other rows are unaffected.
+ * What a row computes depends on its logits, uniform, parameters and the CONTENTS of its set alone -- never on the set's index, the
+ * other rows or the row's position. Token, selected logit and log-probability equal the unmasked call's on a copy of the row with -inf
+ * in the disallowed columns, bit for bit; an all-ones set gives the unmasked call's outputs, bit for bit.
+ * One 1024-thread block per row, one launch, no workspace, recordable: a replay follows the current contents of bits and set_of_row.
+ * COVER_EINVAL, and nothing launched: everything the unmasked call refuses; a null allow or null bits; n_sets < 1; ld_words <
+ * ceil(hi / 32); bits not 4-byte aligned. */
+typedef struct cover_token_allow {
+    const uint32_t* bits;   /* [n_sets][ld_words], 4-byte aligned */
+    long long ld_words;     /* words between two sets, >= ceil(hi / 32) */
+    int n_sets;             /* >= 1 */
+    int _pad;
+    const int* set_of_row;  /* [rows] or NULL = set 0 for every row */
+} cover_token_allow;
+int cover_token_sample_rows_allowed(const cover_token_sample_rows_args* args, const cover_token_allow* allow, void* stream);
+int cover_token_logprob_rows_allowed(const cover_token_logprob_rows_args* args, const cover_token_allow* allow, void* stream);
+int cover_token_topn_rows_allowed(const cover_token_topn_rows_args* args, const cover_token_allow* allow, void* stream);
+
 /* The bookkeeping between two steps of an autoregressive decode loop (pi0-FAST generate_tokens), one launch, one block per
  * candidate row, no workspace: recordable into a hipGraph. Per row b, in this order:
  *   t = force ? force[b * force_stride] : pick[b];  lp_out[b * ld_lp] = done[b] ? 0.0f : lp[b];  if (done[b]) t = pad;
