@@ -154,6 +154,10 @@ class TokenAllow(C.Structure):
     _fields_ = [("bits", c_p), ("ld_words", c_ll), ("n_sets", c_i), ("_pad", c_i), ("set_of_row", c_p)]
 
 
+class TokenRef(C.Structure):
+    _fields_ = [("temperature", c_f), ("_pad", c_i), ("logprob_out", c_p)]
+
+
 class DecodeFeedbackArgs(C.Structure):
     _fields_ = [("pick", c_p), ("force", c_p), ("force_stride", c_ll), ("lp", c_p), ("lp_out", c_p), ("ld_lp", c_ll),
                 ("done", c_p), ("tok_out", c_p), ("ld_tok", c_ll), ("eos", c_ll), ("pad", c_ll),
@@ -226,7 +230,7 @@ _STRUCTS = {
     "cover_token_sample_args": TokenSampleArgs, "cover_token_sample_scored_args": TokenSampleScoredArgs,
     "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs,
     "cover_token_sample_rows_args": TokenSampleRowsArgs, "cover_token_logprob_rows_args": TokenLogprobRowsArgs,
-    "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_decode_feedback_args": DecodeFeedbackArgs,
+    "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
@@ -293,7 +297,9 @@ SYMBOLS = {
     "cover_token_sample_rows_allowed": (c_i, [_P(TokenSampleRowsArgs), _P(TokenAllow), c_p]),
     "cover_token_logprob_rows_allowed": (c_i, [_P(TokenLogprobRowsArgs), _P(TokenAllow), c_p]),
     "cover_token_topn_rows_allowed": (c_i, [_P(TokenTopnRowsArgs), _P(TokenAllow), c_p]),
+    "cover_token_sample_rows_ref": (c_i, [_P(TokenSampleRowsArgs), _P(TokenAllow), _P(TokenRef), c_p]),
     "cover_decode_feedback": (c_i, [_P(DecodeFeedbackArgs), c_p]),
+    "cover_decode_feedback_lp2": (c_i, [_P(DecodeFeedbackArgs), c_p, c_p, c_ll, c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),

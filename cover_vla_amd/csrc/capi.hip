@@ -340,6 +340,17 @@ int cover_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cov
            "token_topn_rows_allowed (as token_topn_rows; allow and bits required, bits 4-byte aligned, n_sets >= 1, ld_words >= ceil(hi / 32))");
     return COVER_OK;
 }
+int cover_token_sample_rows_ref(const cover_token_sample_rows_args* a, const cover_token_allow* al, const cover_token_ref* ref, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_token_sample_rows_ref: null args");
+    HIPCHK(launch_token_sample_rows_ref(a, al, ref, ST(stream)),
+           "token_sample_rows_ref (as token_sample_rows, with allow as token_sample_rows_allowed; ref and ref->logprob_out required, ref->temperature > 0 and finite)");
+    return COVER_OK;
+}
+int cover_decode_feedback_lp2(const cover_decode_feedback_args* a, const float* lp2, float* lp2_out, long long ld_lp2, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_decode_feedback_lp2: null args");
+    HIPCHK(launch_decode_feedback_lp2(a, lp2, lp2_out, ld_lp2, ST(stream)), "decode_feedback_lp2 (as decode_feedback; lp2 and lp2_out required)");
+    return COVER_OK;
+}
 int cover_decode_feedback(const cover_decode_feedback_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_decode_feedback: null args");
     HIPCHK(launch_decode_feedback(a, ST(stream)),
@@ -892,7 +903,7 @@ size_t cover_sizeof(const char* n) {
 #define SZ(T) if (!strcmp(n, #T)) return sizeof(T)
     SZ(cover_gemm_epi); SZ(cover_kv_segment); SZ(cover_attn_args); SZ(cover_rope_args); SZ(cover_patchify_args);
     SZ(cover_gemm_f32_args); SZ(cover_mha_f32_args); SZ(cover_token_select_args); SZ(cover_token_sample_args); SZ(cover_score_select_args);
-    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_decode_feedback_args);
+    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_token_ref); SZ(cover_decode_feedback_args);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
 #undef SZ

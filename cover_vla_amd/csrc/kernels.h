@@ -49,6 +49,7 @@ hipError_t launch_rope_kv_write_pair(const cover_rope_args* a0, const cover_rope
 hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids, int n, float scale, bf16_t* out,
                                int ldo, hipStream_t st);
 hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st);
+hipError_t launch_decode_feedback_lp2(const cover_decode_feedback_args* a, const float* lp2, float* lp2_out, long long ld_lp2, hipStream_t st);
 hipError_t launch_patchify(const cover_patchify_args* a, hipStream_t st);
 hipError_t launch_copy_rows_bf16(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int rows, int cols,
                                  const int* src_row_idx, const int* dst_row_idx, hipStream_t st);
@@ -85,6 +86,8 @@ hipError_t launch_token_topn_rows(const cover_token_topn_rows_args* a, hipStream
 hipError_t launch_token_sample_rows_allowed(const cover_token_sample_rows_args* a, const cover_token_allow* al, hipStream_t st);
 hipError_t launch_token_logprob_rows_allowed(const cover_token_logprob_rows_args* a, const cover_token_allow* al, hipStream_t st);
 hipError_t launch_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, hipStream_t st);
+hipError_t launch_token_sample_rows_ref(const cover_token_sample_rows_args* a, const cover_token_allow* al /* nullptr: unmasked */,
+                                        const cover_token_ref* ref, hipStream_t st);
 // ---- select.hip ----------------------------------------------------------------------------------
 hipError_t launch_token_select(const cover_token_select_args* a, hipStream_t st);
 hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st);

@@ -416,13 +416,16 @@ hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids,
 // Thread 0 settles the row's token (forced token, pad after EOS), stores it and the step's log-probability, updates the row's done
 // byte and the step's live counter; the block then gathers the token's embedding row for the next step (embed_gather_k's arithmetic).
 // A row touches only its own done byte, token and log-probability cells: no ordering between blocks is needed.
-__global__ __launch_bounds__(128) void decode_feedback_k(cover_decode_feedback_args a) {
+// LP2 (cover_decode_feedback_lp2): a second log-probability column, settled exactly as the first.
+template <bool LP2>
+__device__ __forceinline__ void decode_feedback_row(const cover_decode_feedback_args& a, const float* lp2, float* lp2_out, long long ld_lp2) {
     __shared__ long long s_tok;
     const int b = blockIdx.x;
     if (threadIdx.x == 0) {
         const bool was_done = a.done[b] != 0;
         long long t = a.force ? a.force[(long long)b * a.force_stride] : a.pick[b];
         if (a.lp_out) a.lp_out[(long long)b * a.ld_lp] = was_done ? 0.0f : a.lp[b];
+        if constexpr (LP2) lp2_out[(long long)b * ld_lp2] = was_done ? 0.0f : lp2[b];
         if (was_done) t = a.pad;
         a.tok_out[(long long)b * a.ld_tok] = t;
         const bool now_done = was_done || t == a.eos;
@@ -436,13 +439,27 @@ __global__ __launch_bounds__(128) void decode_feedback_k(cover_decode_feedback_a
     const bf16_t* src = (t >= 0 && t < a.vocab) ? (const bf16_t*)a.table + (size_t)t * a.dim : nullptr;   // outside the table: a zero row, nothing read
     embed_row<true>(src, a.dim, a.scale, (bf16_t*)a.x_out, (size_t)b * a.ldo);
 }
-hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st) {
-    if (a->rows < 0 || !a->pick || !a->done || !a->tok_out || (a->lp == nullptr) != (a->lp_out == nullptr)) return hipErrorInvalidValue;
+__global__ __launch_bounds__(128) void decode_feedback_k(cover_decode_feedback_args a) { decode_feedback_row<false>(a, nullptr, nullptr, 0); }
+__global__ __launch_bounds__(128) void decode_feedback_lp2_k(cover_decode_feedback_args a, const float* lp2, float* lp2_out, long long ld_lp2) {
+    decode_feedback_row<true>(a, lp2, lp2_out, ld_lp2);
+}
+static bool decode_feedback_ok(const cover_decode_feedback_args* a) {
+    if (a->rows < 0 || !a->pick || !a->done || !a->tok_out || (a->lp == nullptr) != (a->lp_out == nullptr)) return false;
     if (a->x_out && (!a->table || a->dim <= 0 || (a->dim & 7) || a->vocab <= 0 || a->ldo < a->dim || (a->ldo & 7) ||
                      ((((uintptr_t)a->table) | ((uintptr_t)a->x_out)) & 15)))
-        return hipErrorInvalidValue;
+        return false;
+    return true;
+}
+hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st) {
+    if (!decode_feedback_ok(a)) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     hipLaunchKernelGGL(decode_feedback_k, dim3(a->rows), dim3(128), 0, st, *a);
+    return hipGetLastError();
+}
+hipError_t launch_decode_feedback_lp2(const cover_decode_feedback_args* a, const float* lp2, float* lp2_out, long long ld_lp2, hipStream_t st) {
+    if (!decode_feedback_ok(a) || !lp2 || !lp2_out) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(decode_feedback_lp2_k, dim3(a->rows), dim3(128), 0, st, *a, lp2, lp2_out, ld_lp2);
     return hipGetLastError();
 }
 

@@ -546,16 +546,36 @@ __device__ __forceinline__ float kept_logprob(const KeptSet& ks, float l, int re
     return (float)((double)x - (log((double)mass) - 43.0 * 0.693147180559945309417232121458));
 }
 
+// The reference score of a pick (cover_token_sample_rows_ref): lp of column `pick` (logit l, both held by thread 0) under temperature
+// t_ref with both filters off, over the columns of row_src. The calls are logprob_row's at (t_ref, 0, 1) -- kept_tiles and scan_bins with
+// the KeptSet that kept_set returns for those parameters (the row maximum does not depend on them) -- so the value is that kernel's, bit
+// for bit. A row whose own kept set already is the reference's (unfiltered at t_ref) reuses its mass: no pass. Every thread of the
+// block calls this after the row's own outputs are stored; block-uniform.
+template <class Src>
+__device__ __forceinline__ void ref_logprob(SampleShared& s, const Src& row_src, const KeptSet& ks, u64 mass, float t_ref, float l, int pick,
+                                            int row, float* ref_out) {
+    const KeptSet kr{ks.m, t_ref, 0u, 0u, 0x7fffffff};
+    if (!(ks.T == t_ref && ks.tk == 0u && ks.wstar == 0u && ks.idx_cut == 0x7fffffff)) {
+        kept_tiles(s, row_src, kr);
+        scan_bins<false, true>(s, SMP_BINS, 1ull);
+        mass = s.r_mass_total;
+    }
+    if (threadIdx.x == 0) ref_out[row] = kept_logprob(kr, l, pick, mass);
+}
+
 // One row of the sampler: steps 1-4 of cover_token_sample over columns [lo, hi) of lg with the uniform u. Every thread of the block calls
 // this; thread 0 stores. logprob_out == nullptr: no score. token_sample_k and token_sample_rows_k are this function with the launch's and
 // the row's parameters respectively, so a row means the same in both.
-template <bool ALLOW = false>
+// REF (cover_token_sample_rows_ref): ref_out[row] = the log-probability of the same pick under the reference distribution -- temperature
+// t_ref, both filters off, over the same columns -- i.e. logprob_row at (t_ref, 0, 1) on the pick, bit for bit (ref_logprob below).
+template <bool ALLOW = false, bool REF = false>
 __device__ __forceinline__ void sample_row(SampleShared& s, const float* lg, int lo, int hi, float temperature, int top_k, float top_p, float u,
                                            int row, int64_t* token_out, float* logit_out, int* kept_out, float* logprob_out,
-                                           const AllowRow<ALLOW>& ar = AllowRow<ALLOW>{}) {
+                                           const AllowRow<ALLOW>& ar = AllowRow<ALLOW>{}, float t_ref = 1.0f, float* ref_out = nullptr) {
     const int tid = threadIdx.x;
     const int n = hi - lo;
     SampleSrcT<ALLOW> src = make_src<ALLOW>(lg + lo, n, lo, ar);
+    const SampleSrcT<ALLOW> row_src = src;   // kept_set may switch src to the compacted list; the reference mass needs the whole row
     const KeptSet ks = kept_set(s, src, top_k, top_p, temperature);
 
     // ---- pick: running mass of the kept tokens in index order; tiles of 1024 columns first, then the columns of the crossing tile
@@ -572,17 +592,20 @@ __device__ __forceinline__ void sample_row(SampleShared& s, const float* lg, int
         if (ks.kept(l, rel, q)) hist_add(s, (rel + shift) & 1023, q);
     });
     scan_bins<false, true>(s, 1024, need2);
+    int pick = 0;
+    float l = 0.f;
     if (tid == 0) {
-        int pick = t0 + s.r_bin;
+        pick = t0 + s.r_bin;
         pick = pick < 0 ? 0 : (pick < n ? pick : n - 1);
         if constexpr (ALLOW)   // a row without mass (its allowed columns all NaN or -inf) crosses nowhere: the first allowed column
             if (!allow1(src, pick)) pick = src.first;
         token_out[row] = lo + pick;
-        const float l = lg[lo + pick];
+        l = lg[lo + pick];
         if (logit_out) logit_out[row] = l;
         if (kept_out) kept_out[row] = (int)kept;
         if (logprob_out) logprob_out[row] = kept_logprob(ks, l, pick, mass);
     }
+    if constexpr (REF) ref_logprob(s, row_src, ks, mass, t_ref, l, pick, row, ref_out);
 }
 
 template <bool SCORED>
@@ -954,6 +977,63 @@ __global__ __launch_bounds__(SMP_T) void token_sample_rows_allowed_k(cover_token
     }
 }
 
+// cover_token_sample_rows_ref: token_sample_rows_k (ALLOW: token_sample_rows_allowed_k; al is then the launch's sets, otherwise unused) with
+// one more store per row, ref.logprob_out[row] = lp(pick) at ref.temperature, unfiltered (ref_logprob). Kernels of their own, so the two
+// above compile to what they compiled to before this one existed; every other output is theirs, from the same row functions.
+template <bool ALLOW>
+__global__ __launch_bounds__(SMP_T) void token_sample_rows_ref_k(cover_token_sample_rows_args a, cover_token_allow al, cover_token_ref ref) {
+    __shared__ SampleShared s;
+    __shared__ int first;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<ALLOW> ar;
+    bool valid = rp.mode != 2;
+    if constexpr (ALLOW) valid = valid && allow_row(s, al, a.lo, a.hi, row, ar);
+    if (!valid) {   // block-uniform
+        if (tid == 0) {
+            a.token_out[row] = -1;
+            if (a.logit_out) a.logit_out[row] = NAN;
+            if (a.kept_out) a.kept_out[row] = 0;
+            if (a.logprob_out) a.logprob_out[row] = NAN;
+            ref.logprob_out[row] = NAN;
+        }
+        return;
+    }
+    const float* lg = a.logits + (size_t)row * a.ld;
+    if (rp.mode == 0) {
+        sample_row<ALLOW, true>(s, lg, a.lo, a.hi, rp.T, rp.k, rp.p, a.uniform[row], row, a.token_out, a.logit_out, a.kept_out, a.logprob_out, ar,
+                                ref.temperature, ref.logprob_out);
+        return;
+    }
+    // greedy: as in the kernels above; the pick's own score is taken at temperature 1, unfiltered, which is the reference's when ref.temperature == 1
+    const int n = a.hi - a.lo;
+    SampleSrcT<ALLOW> src = make_src<ALLOW>(lg + a.lo, n, a.lo, ar);
+    if (tid == 0) first = 0x7fffffff;
+    const KeptSet ks = kept_set(s, src, 0, 1.0f, 1.0f);
+    kept_tiles(s, src, ks);
+    scan_bins<false, true>(s, SMP_BINS, 1ull);
+    const u64 mass = s.r_mass_total;
+    int mine = 0x7fffffff;
+    for_each(s, src, [&](float l, int rel) {
+        if (l == ks.m && rel < mine) mine = rel;
+    });
+    if (mine != 0x7fffffff) atomicMin(&first, mine);
+    __syncthreads();
+    int pick = 0;
+    float l = 0.f;
+    if (tid == 0) {
+        pick = first;
+        if constexpr (ALLOW) pick = pick < n ? pick : src.first;
+        else pick = pick < n ? pick : 0;
+        a.token_out[row] = a.lo + pick;
+        l = lg[a.lo + pick];
+        if (a.logit_out) a.logit_out[row] = l;
+        if (a.kept_out) a.kept_out[row] = src_count(src);
+        if (a.logprob_out) a.logprob_out[row] = kept_logprob(ks, l, pick, mass);
+    }
+    ref_logprob(s, src, ks, mass, ref.temperature, l, pick, row, ref.logprob_out);
+}
+
 __global__ __launch_bounds__(SMP_T) void token_logprob_rows_allowed_k(cover_token_logprob_rows_args a, cover_token_allow al) {
     __shared__ SampleShared s;
     const int row = blockIdx.x;
@@ -1088,6 +1168,18 @@ hipError_t launch_token_sample_rows_allowed(const cover_token_sample_rows_args* 
     if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     hipLaunchKernelGGL(token_sample_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
+    return hipGetLastError();
+}
+
+// al == nullptr: the unmasked kernel. The reference temperature travels by value: a captured launch keeps the one it was recorded with.
+hipError_t launch_token_sample_rows_ref(const cover_token_sample_rows_args* a, const cover_token_allow* al, const cover_token_ref* ref,
+                                        hipStream_t st) {
+    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a->lo, a->hi, a->rows) || (al && !allow_ok(al, a->hi))) return hipErrorInvalidValue;
+    if (!ref || !ref->logprob_out || !(ref->temperature > 0.f) || !(ref->temperature < INFINITY)) return hipErrorInvalidValue;
+    if (a->rows == 0) return hipSuccess;
+    if (al) hipLaunchKernelGGL(token_sample_rows_ref_k<true>, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al, *ref);
+    else hipLaunchKernelGGL(token_sample_rows_ref_k<false>, dim3(a->rows), dim3(SMP_T), 0, st, *a, cover_token_allow{}, *ref);
     return hipGetLastError();
 }
 

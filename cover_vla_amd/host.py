@@ -65,7 +65,11 @@ def sampling_ladder(n_prompts: int, n_samples: int, temperature, top_k=0, top_p=
     or a length-n_samples sequence; returns (temperature float32, top_k int32, top_p float32) numpy arrays [n_prompts * n_samples] in
     which candidate i carries entry i % n_samples -- the "candidate i belongs to prompt i // n_samples" order of OpenVLA.sample, whose
     temperature / top_k / top_p arguments take these arrays. Values must be finite with temperature >= 0, top_k >= 0 (an integer) and
-    top_p > 0. Index bookkeeping only."""
+    top_p > 0. Index bookkeeping only.
+    The return_logprobs of a ladder are each taken under their own rung's distribution and do not compare across rungs (a greedy rung is
+    scored at temperature 1, a top_k = 1 rung scores every pick 0.0, a hot rung is penalised for its own flatness): a candidate_prior for
+    verify_and_select / cover_prior_select under a ladder should be the prior_temperature tensor of OpenVLA.sample /
+    PI0FASTTokens.generate_tokens (PI0FASTPolicy.last_sequence_prior_logprobs), every pick scored at one reference temperature, unfiltered."""
     if int(n_prompts) < 1 or int(n_samples) < 1:
         raise ValueError("sampling_ladder: n_prompts and n_samples must be >= 1")
     out = []
@@ -173,7 +177,11 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     candidate_prior ([B] sequence log-probabilities of the candidates under the policy, e.g. PI0FASTPolicy.last_sequence_logprobs, or
     [B, steps] per-step values) with prior_beta > 0: stage 2 selects on score + prior_beta * prior (stage 1 scores one candidate: a
     prior cannot change it). The two keywords reach the verifier only then, so a verifier that does not know them keeps working;
-    max_score is then the winner's combined score and the dict also carries the winner's `prior`."""
+    max_score is then the winner's combined score and the dict also carries the winner's `prior`.
+    When the candidates were drawn with per-candidate sampling parameters (sampling_ladder), candidate_prior should be the reference
+    log-probabilities -- the tensor OpenVLA.sample / generate_tokens return with prior_temperature, or
+    PI0FASTPolicy.last_sequence_prior_logprobs -- which score every candidate at ONE temperature, unfiltered; the return_logprobs values
+    are taken under each candidate's own rung and do not compare across rungs. No reference temperature or prior_beta is chosen here."""
     if not (prior_beta >= 0.0 and math.isfinite(prior_beta)):
         raise ValueError(f"verify_and_select: prior_beta must be finite and >= 0 (got {prior_beta})")
     use_prior = candidate_prior is not None and prior_beta > 0

@@ -198,7 +198,8 @@ class OpenVLA:
     def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
                uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, trace: Optional[dict] = None,
                force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
-               top_k: RowParam = 0, top_p: RowParam = 1.0, return_logprobs: bool = False, top_logprobs: int = 0):
+               top_k: RowParam = 0, top_p: RowParam = 1.0, return_logprobs: bool = False, top_logprobs: int = 0,
+               prior_temperature: Optional[float] = None):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
         uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
@@ -224,11 +225,24 @@ class OpenVLA:
         over the action bins [action_lo, action_hi), the launch's range: a candidate with temperature 0 is greedy and takes the arg-max
         over the 256 action bins (its log-probability: temperature 1, unfiltered, over those bins), whereas an all-greedy call
         (uniforms=None) keeps its arg-max over the tokenizer vocabulary. The decode graph is keyed on the fact "per-row parameters", not
-        on their values: the three tensors are static buffers filled before each replay, so a new ladder is not a new capture."""
+        on their values: the three tensors are static buffers filled before each replay, so a new ladder is not a new capture.
+        prior_temperature = T_ref (> 0, finite): the return gains a fp32 [N, n_gen] tensor (after the return_logprobs tensor if that is
+        present, before TopLogprobs): the log-probability of each pick under ONE reference distribution for every candidate -- temperature
+        T_ref, unfiltered, over the action bins -- written by the pick's own launch (cover_token_sample_rows_ref; ops.token_logprob_rows at
+        (T_ref, 0, 1) on the pick, bit for bit). It is the prior that compares across the rungs of a ladder: return_logprobs scores every
+        candidate under its own rung. Scalar parameters are broadcast and the per-row path is taken (the only one that carries the
+        reference); uniforms is required: a greedy candidate is a row with temperature 0. The decode graph's key carries the value of
+        T_ref, which travels by value in the launch. None launches exactly what it launched before."""
         c, dev = self.c, self.dev
         n_top = int(top_logprobs)
         if not 0 <= n_top <= 64:
             raise ValueError("top_logprobs must be in 0..64")
+        t_ref = None
+        if prior_temperature is not None:
+            t_ref = ops.ref_temperature_value("sample: prior_temperature", prior_temperature)
+            if uniforms is None:
+                raise ValueError("prior_temperature needs uniforms: the reference score comes from the per-row sampler, in which a greedy "
+                                 "candidate is a row with temperature=0 (pass uniforms and temperature=0 rows instead of uniforms=None)")
         P, Lt = prompt_tokens.shape
         N = P * n_samples
 
@@ -269,7 +283,7 @@ class OpenVLA:
         pos_all = ((T0 + cand_len)[None, :] + torch.arange(self.n_gen, dtype=torch.int32, device=dev)[:, None]).contiguous()
         u_t = None if uniforms is None else uniforms.to(torch.float32).t().contiguous()
         rp = None
-        if any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
+        if t_ref is not None or any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
             if uniforms is None:
                 raise ValueError("per-candidate temperature / top_k / top_p need uniforms (a greedy candidate is a temperature of 0)")
             rp = ops.row_param_tensors(N, temperature, top_k, top_p, dev)
@@ -279,7 +293,7 @@ class OpenVLA:
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
             # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
             # per-row parameters: the key carries the fact, the values live in static buffers (st["rp"]) like the uniforms
-            key = (P, n_samples, Lt, uniforms is None, "rows" if rp is not None else float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ())
+            key = (P, n_samples, Lt, uniforms is None, "rows" if rp is not None else float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ()) + ((("prior", t_ref),) if t_ref is not None else ())
             st = self._dec.get(key)
             if st is None:
                 st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
@@ -287,6 +301,7 @@ class OpenVLA:
                           sel=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev),
                           u=None if u_t is None else torch.empty_like(u_t),
                           lps=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None,
+                          prior=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if t_ref is not None else None,
                           top=self._top_bufs(N, n_top), rp=None if rp is None else tuple(torch.empty_like(t) for t in rp),
                           prompt_slots=torch.arange(P, dtype=torch.int32, device=dev), prompt_lens=torch.empty(P, dtype=torch.int32, device=dev))
                 self._dec[key] = st
@@ -298,7 +313,8 @@ class OpenVLA:
                 for dst, src in zip(st["rp"], rp):
                     dst.copy_(src)
             body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"], rp=st["rp"])
+                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"], rp=st["rp"],
+                                             prior=None if t_ref is None else (t_ref, st["prior"]))
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -316,16 +332,18 @@ class OpenVLA:
             else:
                 st["graph"].launch()
             # the eager pass before a capture has filled the same buffers
-            return self._sample_result(st["tokens"], st["sel"], st["lps"], st["top"])
+            return self._sample_result(st["tokens"], st["sel"], st["lps"], st["top"], st["prior"])
         # step-major buffers: row i of each is contiguous, so the kernels of step i read / write them in place (no per-step slice copies)
         tokens = torch.empty(self.n_gen, N, dtype=torch.int64, device=dev)
         sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
         lps = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None
         top = self._top_bufs(N, n_top)
+        prior = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if t_ref is not None else None
         fed = tokens if force_tokens is None else force_tokens.t().contiguous()
         self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top, rp=rp)
-        return self._sample_result(tokens, sel, lps, top)
+                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top, rp=rp,
+                          prior=None if t_ref is None else (t_ref, prior))
+        return self._sample_result(tokens, sel, lps, top, prior)
 
     def _top_bufs(self, N, n_top):
         """Step-major buffers of sample(top_logprobs=n): (tokens [n_gen, N, n], logprobs [n_gen, N, n], entropy [n_gen, N]), None for n = 0."""
@@ -336,21 +354,23 @@ class OpenVLA:
                 torch.empty(self.n_gen, N, dtype=torch.float32, device=self.dev))
 
     @staticmethod
-    def _sample_result(tokens, sel, lps, top):
+    def _sample_result(tokens, sel, lps, top, prior=None):
         """Candidate-major copies of the step-major buffers: what sample returns."""
         out = (tokens.t().contiguous(), sel.t().contiguous())
         if lps is not None:
             out += (lps.t().contiguous(),)
+        if prior is not None:
+            out += (prior.t().contiguous(),)
         if top is not None:
             out += (TopLogprobs(top[0].transpose(0, 1).contiguous(), top[1].transpose(0, 1).contiguous(), top[2].t().contiguous()),)
         return out
 
     def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None, rp=None):
+                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None, rp=None, prior=None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
         ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top, rp)
+        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top, rp, prior)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
@@ -362,20 +382,23 @@ class OpenVLA:
                                 dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top, rp)
+            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top, rp, prior)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None, rp=None):
+    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None, rp=None, prior=None):
         """Norm, head GEMM, one ops.pick_token. filt: None = the unfiltered ops.token_select pick; (top_k, top_p) = ops.token_sample over
         the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks.
         top (tokens, logprobs, entropy) or None: slab i receives ops.token_topn of the distribution the pick came from.
-        rp (temperature, top_k, top_p) device tensors [N] or None: the pick is ops.token_sample_rows, the top-n ops.token_topn_rows."""
+        rp (temperature, top_k, top_p) device tensors [N] or None: the pick is ops.token_sample_rows, the top-n ops.token_topn_rows.
+        prior (T_ref, fp32 [n_gen, N]) or None (rp is then set): row i receives the picks' log-probability at temperature T_ref, unfiltered."""
         N = h.shape[0]
         u = None if uniforms is None else uniforms[i]
         # out_kept: written by the filtered pick (ops.token_sample) only
         out = dict(out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=None if lps is None else lps[i])
         if rp is not None:
             out["row_params"] = rp
+        if prior is not None:
+            out["ref"] = (prior[0], prior[1][i])
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
         if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)

@@ -6,6 +6,7 @@ libcover_hip.so. Nothing in this module computes on the CPU or through torch ker
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -869,8 +870,19 @@ def _allow_arg(what, allow, rows, hi, logits):
     return al
 
 
+def ref_temperature_value(what, v) -> float:
+    """A reference temperature (token_sample_rows' ref_temperature, the models' prior_temperature) as a float: one finite number > 0, else CoverError."""
+    try:
+        v = float(v)
+    except (TypeError, ValueError) as e:
+        raise L.CoverError(f"{what} must be one number") from e
+    if not (v > 0.0 and math.isfinite(v)):
+        raise L.CoverError(f"{what} must be finite and > 0 (got {v})")
+    return v
+
+
 def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=None, out_tok=None, out_logit=None, out_kept=None,
-                      out_logprob=None, allow=None):
+                      out_logprob=None, allow=None, ref_temperature=None, out_ref_logprob=None):
     """token_sample with the parameters of every row its own (cover_token_sample_rows): temperature fp32 / top_k int32 / top_p fp32 device
     tensors [rows] (top_k None = 0, top_p None = 1 for every row); a Python sequence or CPU tensor is validated on the host
     (temperature >= 0, top_p > 0, top_k >= 0, all finite) and uploaded. temperature[r] > 0: row r is token_sample's row with its
@@ -881,9 +893,18 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
     deterministic: a row's result does not depend on the other rows of the launch.
     allow = TokenAllow: cover_token_sample_rows_allowed, the same on each row restricted to the columns of its set (max, top-k, top-p, pick,
     kept and log-probability over the allowed columns only; disallowed columns are never looked at); a row whose set index is out of
-    range or whose set has no column in [lo, hi) is an invalid row. None issues exactly the unmasked call."""
+    range or whose set has no column in [lo, hi) is an invalid row. None issues exactly the unmasked call.
+    ref_temperature = T_ref with out_ref_logprob fp32 [rows] (given together): cover_token_sample_rows_ref, the same launch also writes the
+    log-probability of each pick under ONE reference distribution shared by every row -- temperature T_ref, both filters off, over the same
+    range and the same allowed set -- which is token_logprob_rows(logits, lo, hi, token, T_ref, None, None, allow=) bit for bit (NaN on an
+    invalid row). The common yardstick of a ladder: out_logprob is taken under each row's own distribution and does not compare across
+    rungs. Both None issues exactly the call made without them."""
     if uniform is None:
         raise L.CoverError("token_sample_rows needs uniforms [rows] (a greedy row ignores its entry)")
+    if (ref_temperature is None) != (out_ref_logprob is None):
+        raise L.CoverError("token_sample_rows: ref_temperature and out_ref_logprob are given together")
+    if ref_temperature is not None:
+        ref_temperature = ref_temperature_value("token_sample_rows: ref_temperature", ref_temperature)
     if hi <= lo or lo < 0:
         raise L.CoverError(f"token_sample_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
@@ -896,7 +917,10 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
                         ("out_logprob", out_logprob, torch.float32)):
         if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
             raise L.CoverError(f"token_sample_rows: {name} must be contiguous {dt} [rows]")
-    _chk_dev(logits, uniform, out_tok, out_logit, out_kept, out_logprob)
+    if out_ref_logprob is not None and (not isinstance(out_ref_logprob, torch.Tensor) or out_ref_logprob.dtype != torch.float32
+                                        or out_ref_logprob.dim() != 1 or out_ref_logprob.numel() != rows or not out_ref_logprob.is_contiguous()):
+        raise L.CoverError("token_sample_rows: out_ref_logprob must be contiguous torch.float32 [rows]")
+    _chk_dev(logits, uniform, out_tok, out_logit, out_kept, out_logprob, out_ref_logprob)
     T, k, p = _upload_row_params(params, logits.device)
     tok = torch.empty(rows, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
     lg = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_logit is None else out_logit
@@ -905,6 +929,12 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
     a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
     a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), T.data_ptr(), _ptr(k), _ptr(p)
     a.token_out, a.logit_out, a.kept_out, a.logprob_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr(), _ptr(out_logprob)
+    if out_ref_logprob is not None:
+        al = None if allow is None else C.byref(_allow_arg("token_sample_rows", allow, rows, hi, logits))
+        ref = L.TokenRef()
+        ref.temperature, ref.logprob_out = ref_temperature, out_ref_logprob.data_ptr()
+        L.check(L.lib().cover_token_sample_rows_ref(C.byref(a), al, C.byref(ref), _stream()), "token_sample_rows_ref")
+        return tok, lg, kept
     if allow is not None:
         al = _allow_arg("token_sample_rows", allow, rows, hi, logits)
         L.check(L.lib().cover_token_sample_rows_allowed(C.byref(a), C.byref(al), _stream()), "token_sample_rows_allowed")
@@ -985,7 +1015,7 @@ def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_
 
 
 def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok=None, out_logit=None, out_kept=None, out_logprob=None,
-               row_params=None, allow=None):
+               row_params=None, allow=None, ref=None):
     """One decode step's pick over columns [lo, hi), the three-way choice of every token head. Returns (token, its logit, kept or None).
     uniform None: greedy token_select (temperature and filt are unused); uniform with filt None: token_select's unfiltered inverse-CDF
     sample; uniform with filt = (top_k, top_p): ONE token_sample call, whose kept count is returned. out_logprob fp32 [rows]: filled with
@@ -993,11 +1023,17 @@ def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok
     by one token_logprob launch behind token_select. The out_* rows are the wrappers' own; no arithmetic or allocation of its own.
     row_params = (temperature, top_k, top_p) device tensors [rows]: ONE token_sample_rows call with the parameters of every row its own
     (uniform is required, temperature and filt are unused; a row with temperature 0 is greedy); its kept count is returned.
-    allow = TokenAllow (with row_params only): that call restricted to each row's allowed-token set."""
+    allow = TokenAllow (with row_params only): that call restricted to each row's allowed-token set.
+    ref = (T_ref, out fp32 [rows]) (with row_params only): that call also scores each pick at the reference temperature T_ref, unfiltered,
+    into out (token_sample_rows' ref_temperature / out_ref_logprob)."""
     if allow is not None and row_params is None:
         raise L.CoverError("pick_token: allow needs row_params (the allowed-token sets belong to the per-row call)")
+    if ref is not None and row_params is None:
+        raise L.CoverError("pick_token: ref needs row_params (the reference score belongs to the per-row call)")
     if row_params is not None:
         extra = {} if allow is None else dict(allow=allow)      # None: exactly the call made before the argument existed
+        if ref is not None:
+            extra.update(ref_temperature=ref[0], out_ref_logprob=ref[1])
         return token_sample_rows(logits, lo, hi, uniform, row_params[0], row_params[1], row_params[2], out_tok=out_tok, out_logit=out_logit,
                                  out_kept=out_kept, out_logprob=out_logprob, **extra)
     if uniform is not None and filt is not None:
@@ -1012,14 +1048,18 @@ def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok
 
 
 def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp_out=None, table=None, scale=1.0, x_out=None,
-                    live=None):
+                    live=None, lp2=None, lp2_out=None):
     """The bookkeeping between two decode steps in one launch (cover_decode_feedback). Per row b: t = force[b] if given else pick[b];
     lp_out[b, step] = 0.0 if done[b] else lp[b]; t = pad if done[b]; tok_out[b, step] = t; done[b] |= t == eos;
     x_out[b] = bf16(table[t] * scale) (embed_gather on the emitted ids; an id outside the table gives a zero row); live[step] += not done[b].
     pick int64 [rows] contiguous; done torch.bool [rows], in place; tok_out int64 / lp_out fp32 [rows, >= step + 1] with unit column
     stride (any row stride); force int64 [rows] with any stride (a column view); live int32 [>= step + 1], zeroed by the caller.
-    x_out bf16 [rows, dim] or None (no embedding: the last step). Recordable, no workspace. Returns x_out."""
-    _chk_dev(pick, done, tok_out, force, lp, lp_out, table, x_out, live)
+    x_out bf16 [rows, dim] or None (no embedding: the last step). Recordable, no workspace. Returns x_out.
+    lp2 / lp2_out (together; shapes as lp / lp_out): a second log-probability column settled the same way in the same launch
+    (cover_decode_feedback_lp2), lp2_out[b, step] = 0.0 if done[b] else lp2[b]; both None issues exactly cover_decode_feedback."""
+    if (lp2 is None) != (lp2_out is None):
+        raise L.CoverError("decode_feedback: lp2 and lp2_out are given together")
+    _chk_dev(pick, done, tok_out, force, lp, lp_out, table, x_out, live, lp2, lp2_out)
     rows = pick.numel()
     assert pick.dtype == torch.int64 and pick.is_contiguous() and done.dtype == torch.bool and done.is_contiguous() and done.numel() == rows
     assert tok_out.dtype == torch.int64 and tok_out.dim() == 2 and tok_out.shape[0] == rows and 0 <= step < tok_out.shape[1]
@@ -1048,6 +1088,13 @@ def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp
     if live is not None:
         assert live.dtype == torch.int32 and live.dim() == 1 and live.is_contiguous() and step < live.numel()
         a.live = live.data_ptr() + 4 * step
+    if lp2 is not None:
+        assert lp2.dtype == torch.float32 and lp2.is_contiguous() and lp2.numel() == rows
+        assert lp2_out.dtype == torch.float32 and lp2_out.dim() == 2 and lp2_out.shape[0] == rows and step < lp2_out.shape[1]
+        assert lp2_out.stride(1) == 1 or lp2_out.shape[1] == 1
+        L.check(L.lib().cover_decode_feedback_lp2(C.byref(a), lp2.data_ptr(), lp2_out.data_ptr() + 4 * step, lp2_out.stride(0), _stream()),
+                "decode_feedback_lp2")
+        return x_out
     L.check(L.lib().cover_decode_feedback(C.byref(a), _stream()), "decode_feedback")
     return x_out
 

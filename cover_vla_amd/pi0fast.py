@@ -96,7 +96,7 @@ class PI0FASTTokens:
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, top_k: RowParam = 0,
                         top_p: RowParam = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0,
-                        allowed_tokens: Optional[ops.TokenAllow] = None):
+                        allowed_tokens: Optional[ops.TokenAllow] = None, prior_temperature: Optional[float] = None):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -132,10 +132,23 @@ class PI0FASTTokens:
         The sets are validated on the host once (one read-back), CoverError otherwise: set_of_row has B entries inside [0, n_sets) and
         every set a row names holds an id below the vocabulary size, so no pick is the -1 of an invalid row. share_prefix,
         force_tokens, the EOS / pad bookkeeping (a finished row's pad is not a draw and need not be allowed) and the fused feedback are
-        untouched. None launches exactly what it launched before."""
+        untouched. None launches exactly what it launched before.
+        prior_temperature = T_ref (> 0, finite): the return gains a fp32 [B, max_new_tokens] tensor (after the return_logprobs tensor if
+        that is present, before TopLogprobs): the log-probability of each step's own pick under ONE reference distribution for every
+        row -- temperature T_ref, unfiltered, over the vocabulary (over the row's allowed set with allowed_tokens) -- written by the
+        pick's own launch (cover_token_sample_rows_ref; ops.token_logprob_rows at (T_ref, 0, 1) on the pick, bit for bit). 0.0 on pads
+        after EOS and on skipped steps, so host.sequence_logprob applies. It is the prior that compares across the rungs of a ladder
+        (host.sampling_ladder): return_logprobs scores every row under its own rung. Scalar parameters are broadcast and the per-row
+        path is taken (the only one that carries the reference); uniforms is required: a greedy candidate is a row with temperature 0.
+        None launches exactly what it launched before."""
         dev = self.dev
         if not 0 <= int(top_logprobs) <= 64:
             raise ValueError("top_logprobs must be in 0..64")
+        if prior_temperature is not None:
+            prior_temperature = ops.ref_temperature_value("generate_tokens: prior_temperature", prior_temperature)
+            if uniforms is None:
+                raise ValueError("prior_temperature needs uniforms: the reference score comes from the per-row sampler, in which a greedy "
+                                 "candidate is a row with temperature=0 (pass uniforms and temperature=0 rows instead of uniforms=None)")
         u_t = None
         if uniforms is not None:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
@@ -145,6 +158,8 @@ class PI0FASTTokens:
         if any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
             if uniforms is None:
                 raise ValueError("per-row temperature / top_k / top_p need uniforms (a greedy row is a temperature of 0)")
+            rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
+        if prior_temperature is not None and rp is None:     # the reference score is the per-row call's: scalars are broadcast
             rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
         if allowed_tokens is not None:
             self._check_allowed(allowed_tokens, tokens.shape[0])
@@ -165,7 +180,7 @@ class PI0FASTTokens:
                     return sub_out[back]
                 return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
         return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens)
+                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens, prior_temperature)
 
     def _check_allowed(self, allow, B):
         """generate_tokens' host check of its allowed-token sets (one read-back of the bits and the row indices)."""
@@ -188,7 +203,7 @@ class PI0FASTTokens:
             raise ops.L.CoverError(f"allowed_tokens: a set that a row uses allows no id below the vocabulary size {vocab}")
 
     def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None):
+                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None, t_ref=None):
         """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
@@ -197,7 +212,9 @@ class PI0FASTTokens:
         log-probability, the done flag, the live count and the next step's embedding row. COVER_FAST_FEEDBACK=0 (read per call) issues
         the torch statements of the other path instead.
         rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused).
-        allow ops.TokenAllow or None (rp is then set): the pick, the score and the ranks over each row's allowed ids only."""
+        allow ops.TokenAllow or None (rp is then set): the pick, the score and the ranks over each row's allowed ids only.
+        t_ref float or None (rp is then set): the pick's launch also scores it at temperature t_ref, unfiltered; that column is settled
+        like the log-probabilities (fused: decode_feedback's lp2) and returned after them."""
         dev, c = self.dev, self.c
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
@@ -253,6 +270,8 @@ class PI0FASTTokens:
         live = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev) if fused else None   # live[i]: rows still running after step i
         lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
         lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
+        rls = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if t_ref is not None else None
+        rl = torch.empty(B, dtype=torch.float32, device=dev) if t_ref is not None else None
         # step-major [steps, B, n]: slab i is what step i's ops.token_topn writes; steps that never run keep the padding
         top_tok = torch.full((max_new_tokens, B, n_top), -1, dtype=torch.int64, device=dev) if n_top else None
         top_lp = torch.full((max_new_tokens, B, n_top), float("-inf"), dtype=torch.float32, device=dev) if n_top else None
@@ -266,6 +285,8 @@ class PI0FASTTokens:
         xd = torch.empty(B, D, dtype=BF, device=dev)
         u_none = torch.zeros(B, dtype=torch.float32, device=dev) if allow is not None and u_t is None else None   # greedy rows read no uniform
         akw = {} if allow is None else dict(allow=allow)      # None: the calls made before the argument existed
+        rkw = {} if t_ref is None else dict(ref=(t_ref, rl))
+        fkw = {} if t_ref is None else dict(lp2=rl, lp2_out=rls)
 
         def pick(hidden, i):
             hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
@@ -274,7 +295,7 @@ class PI0FASTTokens:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
             # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
             if rp is not None:     # one ops.token_sample_rows launch; ops.token_topn_rows ranks under each row's own distribution
-                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_none if u_t is None else u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp, **akw)
+                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_none if u_t is None else u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp, **akw, **rkw)
                 if n_top:
                     ops.token_topn_rows(lg, 0, c["vocab"], n_top, rp[0], rp[1], rp[2], out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i], **akw)
             else:
@@ -289,8 +310,10 @@ class PI0FASTTokens:
             if fused:      # the statements below and the next step's embed_gather, one launch
                 ops.decode_feedback(t, done, out, i, eos_token_id, pad_token_id, force=None if force is None else force[:, i], lp=lp,
                                     lp_out=lps, table=self.embed, scale=self.emb_scale, x_out=xd if i + 1 < max_new_tokens else None,
-                                    live=live)
+                                    live=live, **fkw)
                 return
+            if rl is not None:
+                rls[:, i].copy_(torch.where(done, torch.zeros_like(rl), rl))
             if lp is not None:
                 lps[:, i].copy_(torch.where(done, torch.zeros_like(lp), lp))          # a finished row's pad is not a choice: 0
             if force is not None:
@@ -313,9 +336,11 @@ class PI0FASTTokens:
             g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
             self.lm.forward(xd, [g], final_norm=False)
             pick(xd, i)
-        if not return_logprobs and not n_top:
+        if not return_logprobs and not n_top and rls is None:
             return out
         res = (out, lps) if return_logprobs else (out,)
+        if rls is not None:
+            res += (rls,)
         if n_top:
             # a row is finished at step i once an earlier step emitted EOS: its pad is not a choice (index bookkeeping on the emitted tokens)
             eos = out == eos_token_id
@@ -349,6 +374,9 @@ class PI0FASTConfig:
     sample_seed: Optional[int] = None
     return_logprobs: bool = False       # keep each row's sequence log-probability of the last generation (last_sequence_logprobs)
     top_logprobs: int = 0               # keep the n most probable tokens / log-probabilities / entropy of every step (last_top_logprobs)
+    # T_ref: keep each row's sequence log-probability under ONE reference temperature, unfiltered (last_sequence_prior_logprobs): the prior
+    # that compares across rows with different (temperature, top_k, top_p); needs sample_seed. None = not computed
+    prior_temperature: Optional[float] = None
     share_prefix: bool = False          # candidates with equal frames and prompt share one prefill (generate_tokens(share_prefix=True))
     # half-open (a, b) ranges of PaliGemma ids every row may draw (generate_tokens(allowed_tokens=)): the FAST band from
     # fast_action_token_range plus (b = a + 1) the format tokens; the EOS id is always added. None = the whole vocabulary
@@ -369,6 +397,7 @@ class PI0FASTPolicy:
         # the source of randomness of sampled decoding: a host generator seeded ONCE, so a seed and an observation sequence fix the actions
         self._gen = None if config.sample_seed is None else torch.Generator().manual_seed(int(config.sample_seed))
         self.last_sequence_logprobs = None        # fp32 [B] on the device, set by a generation that ran with config.return_logprobs
+        self.last_sequence_prior_logprobs = None  # fp32 [B] on the device, set by a generation that ran with config.prior_temperature
         self.last_top_logprobs = None             # host.TopLogprobs on the device, set by a generation that ran with config.top_logprobs > 0
         self.allowed_tokens = None                # one set for every row, built once; EOS is always in it, otherwise a row can never finish
         if config.allowed_token_ranges is not None:
@@ -449,6 +478,8 @@ class PI0FASTPolicy:
                 sampling.update(share_prefix=True)
             if self.allowed_tokens is not None:
                 sampling.update(allowed_tokens=self.allowed_tokens)
+            if self.config.prior_temperature is not None:
+                sampling.update(prior_temperature=self.config.prior_temperature)
             if self._gen is not None:
                 u = torch.rand(B, self.config.max_decoding_steps, generator=self._gen, dtype=torch.float32)
                 sampling.update(uniforms=u.to(dev), temperature=self.config.temperature, top_k=self.config.top_k, top_p=self.config.top_p)
@@ -457,6 +488,11 @@ class PI0FASTPolicy:
                                               pad_token_id=self.pad_token_id, **sampling)
             if self.config.top_logprobs:
                 toks, self.last_top_logprobs = toks[:-1], toks[-1]
+                toks = toks if self.config.return_logprobs or self.config.prior_temperature is not None else toks[0]
+            if self.config.prior_temperature is not None:
+                from .host import sequence_logprob
+                toks, prior = toks[:-1], toks[-1]
+                self.last_sequence_prior_logprobs = sequence_logprob(prior)
                 toks = toks if self.config.return_logprobs else toks[0]
             if self.config.return_logprobs:
                 from .host import sequence_logprob

@@ -645,6 +645,32 @@ int cover_token_sample_rows_allowed(const cover_token_sample_rows_args* args, co
 int cover_token_logprob_rows_allowed(const cover_token_logprob_rows_args* args, const cover_token_allow* allow, void* stream);
 int cover_token_topn_rows_allowed(const cover_token_topn_rows_args* args, const cover_token_allow* allow, void* stream);
 
+/* A common yardstick for a ladder of proposal distributions: cover_token_sample_rows (allow == NULL) or cover_token_sample_rows_allowed
+ * with one more output per row, the log-probability of the SAME pick under one reference distribution shared by every row of the
+ * launch: temperature ref->temperature, both filters off, over the same range [lo, hi) and the same allowed-token set. For a valid
+ * row with pick t, logit l_t and row maximum m (over the allowed columns):
+ *     ref->logprob_out[r] = x_ref(t) - log(M_ref),   x_ref = (l_t - m) / T_ref,   M_ref = sum of q43(w(l, m, T_ref)) over every (allowed)
+ *     column of [lo, hi), an exact uint64 sum of the Q43 weights like every other mass of these calls; logarithm and difference in double,
+ *     one rounding to fp32.
+ * That is cover_token_logprob_rows (cover_token_logprob_rows_allowed) of the pick at (T_ref, top_k 0, top_p 1), bit for bit: the sums are
+ * integers, so the summation order cannot matter. The per-step log-probabilities of a ladder (logprob_out) are each taken under
+ * their own row's distribution and do not compare across rungs; this column does, and is what cover_prior_select should be fed
+ * under a ladder. The reference is unfiltered on purpose: a filtered one would score the picks of looser rungs -inf.
+ * Every other output (token_out, logit_out, kept_out, logprob_out) is the underlying call's, bit for bit. A row whose own distribution
+ * already is the reference (unfiltered with temperature[r] == T_ref; a greedy row when T_ref == 1) reuses its mass, every other row makes
+ * one more pass over its columns. An invalid row (bad parameters, bad set index, empty set) writes NaN; a row without mass writes what
+ * cover_token_logprob_rows(_allowed) writes for that pick. One launch, no workspace, recordable; T_ref travels by value, so a
+ * captured launch keeps the one it was recorded with.
+ * COVER_EINVAL, and nothing launched: everything the underlying call refuses; a null ref or ref->logprob_out; ref->temperature <= 0,
+ * NaN or infinite. */
+typedef struct cover_token_ref {
+    float temperature;    /* > 0, finite: the reference temperature */
+    int _pad;
+    float* logprob_out;   /* [rows], required */
+} cover_token_ref;
+int cover_token_sample_rows_ref(const cover_token_sample_rows_args* args, const cover_token_allow* allow /* NULL: unmasked */,
+                                const cover_token_ref* ref, void* stream);
+
 /* The bookkeeping between two steps of an autoregressive decode loop (pi0-FAST generate_tokens), one launch, one block per
  * candidate row, no workspace: recordable into a hipGraph. Per row b, in this order:
  *   t = force ? force[b * force_stride] : pick[b];  lp_out[b * ld_lp] = done[b] ? 0.0f : lp[b];  if (done[b]) t = pad;
@@ -668,6 +694,10 @@ typedef struct cover_decode_feedback_args {
     int rows;
 } cover_decode_feedback_args;
 int cover_decode_feedback(const cover_decode_feedback_args* args, void* stream);
+/* cover_decode_feedback with a second log-probability column (the reference score of cover_token_sample_rows_ref): the same kernel,
+ * and additionally lp2_out[b * ld_lp2] = done[b] ? 0.0f : lp2[b], with done as it was before this step's update, exactly as lp_out.
+ * lp2 [rows] and lp2_out are required; every other rule is cover_decode_feedback's. */
+int cover_decode_feedback_lp2(const cover_decode_feedback_args* args, const float* lp2, float* lp2_out, long long ld_lp2, void* stream);
 
 /* K20: fuse + score + grouped arg-max (efficient_ensemble_merged.py:404-448). it: [n_members][512] image-text
  * embeddings (unit rows), act: [n_members][N][512]; scores_out [N]; result_out int32 [4] =
