@@ -165,6 +165,11 @@ class DecodeFeedbackArgs(C.Structure):
                 ("live", c_p), ("rows", c_i)]
 
 
+class TokenFsm(C.Structure):
+    _fields_ = [("class_of_token", c_p), ("trans", c_p), ("set_of_state", c_p), ("n_states", c_i), ("n_classes", c_i),
+                ("state", c_p), ("set_of_row", c_p)]
+
+
 class ScoreSelectArgs(C.Structure):
     _fields_ = [("it", c_p), ("act", c_p), ("n_members", c_i), ("N", c_i), ("dim", c_i), ("group_size", c_i),
                 ("scores_out", c_p), ("result_out", c_p), ("best_out", c_p), ("fused_it_out", c_p),
@@ -231,6 +236,7 @@ _STRUCTS = {
     "cover_token_logprob_args": TokenLogprobArgs, "cover_token_topn_args": TokenTopnArgs,
     "cover_token_sample_rows_args": TokenSampleRowsArgs, "cover_token_logprob_rows_args": TokenLogprobRowsArgs,
     "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
+    "cover_token_fsm": TokenFsm,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
@@ -300,6 +306,7 @@ SYMBOLS = {
     "cover_token_sample_rows_ref": (c_i, [_P(TokenSampleRowsArgs), _P(TokenAllow), _P(TokenRef), c_p]),
     "cover_decode_feedback": (c_i, [_P(DecodeFeedbackArgs), c_p]),
     "cover_decode_feedback_lp2": (c_i, [_P(DecodeFeedbackArgs), c_p, c_p, c_ll, c_p]),
+    "cover_decode_feedback_fsm": (c_i, [_P(DecodeFeedbackArgs), _P(TokenFsm), c_p, c_p, c_ll, c_p]),
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),

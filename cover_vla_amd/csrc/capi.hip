@@ -351,6 +351,13 @@ int cover_decode_feedback_lp2(const cover_decode_feedback_args* a, const float* 
     HIPCHK(launch_decode_feedback_lp2(a, lp2, lp2_out, ld_lp2, ST(stream)), "decode_feedback_lp2 (as decode_feedback; lp2 and lp2_out required)");
     return COVER_OK;
 }
+int cover_decode_feedback_fsm(const cover_decode_feedback_args* a, const cover_token_fsm* fsm, const float* lp2, float* lp2_out, long long ld_lp2,
+                              void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_decode_feedback_fsm: null args");
+    HIPCHK(launch_decode_feedback_fsm(a, fsm, lp2, lp2_out, ld_lp2, ST(stream)),
+           "decode_feedback_fsm (as decode_feedback; fsm and every member required, n_states >= 1, 1 <= n_classes <= 256, vocab > 0, lp2 and lp2_out together)");
+    return COVER_OK;
+}
 int cover_decode_feedback(const cover_decode_feedback_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_decode_feedback: null args");
     HIPCHK(launch_decode_feedback(a, ST(stream)),
@@ -903,7 +910,7 @@ size_t cover_sizeof(const char* n) {
 #define SZ(T) if (!strcmp(n, #T)) return sizeof(T)
     SZ(cover_gemm_epi); SZ(cover_kv_segment); SZ(cover_attn_args); SZ(cover_rope_args); SZ(cover_patchify_args);
     SZ(cover_gemm_f32_args); SZ(cover_mha_f32_args); SZ(cover_token_select_args); SZ(cover_token_sample_args); SZ(cover_score_select_args);
-    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_token_ref); SZ(cover_decode_feedback_args);
+    SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_token_ref); SZ(cover_decode_feedback_args); SZ(cover_token_fsm);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
 #undef SZ

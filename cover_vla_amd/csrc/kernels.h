@@ -50,6 +50,8 @@ hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids,
                                int ldo, hipStream_t st);
 hipError_t launch_decode_feedback(const cover_decode_feedback_args* a, hipStream_t st);
 hipError_t launch_decode_feedback_lp2(const cover_decode_feedback_args* a, const float* lp2, float* lp2_out, long long ld_lp2, hipStream_t st);
+hipError_t launch_decode_feedback_fsm(const cover_decode_feedback_args* a, const cover_token_fsm* f, const float* lp2, float* lp2_out,
+                                      long long ld_lp2, hipStream_t st);
 hipError_t launch_patchify(const cover_patchify_args* a, hipStream_t st);
 hipError_t launch_copy_rows_bf16(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int rows, int cols,
                                  const int* src_row_idx, const int* dst_row_idx, hipStream_t st);

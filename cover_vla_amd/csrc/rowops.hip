@@ -417,8 +417,14 @@ hipError_t launch_embed_gather(const bf16_t* table, int dim, const int64_t* ids,
 // byte and the step's live counter; the block then gathers the token's embedding row for the next step (embed_gather_k's arithmetic).
 // A row touches only its own done byte, token and log-probability cells: no ordering between blocks is needed.
 // LP2 (cover_decode_feedback_lp2): a second log-probability column, settled exactly as the first.
-template <bool LP2>
-__device__ __forceinline__ void decode_feedback_row(const cover_decode_feedback_args& a, const float* lp2, float* lp2_out, long long ld_lp2) {
+// FSM (cover_decode_feedback_fsm): thread 0 also advances the row's token-class automaton on the emitted token and stores the index
+// of the allowed-token set the row's next pick draws from. A live row with an id inside the vocabulary moves; a finished row, an id
+// outside the vocabulary or a class outside the table leaves the state alone; a state outside [0, n_states) reads no table and
+// names set -1, which the _allowed kernels report as an invalid row.
+struct no_fsm {};
+template <bool LP2, bool FSM = false, class F = no_fsm>
+__device__ __forceinline__ void decode_feedback_row(const cover_decode_feedback_args& a, const float* lp2, float* lp2_out, long long ld_lp2,
+                                                    const F& f = F()) {
     __shared__ long long s_tok;
     const int b = blockIdx.x;
     if (threadIdx.x == 0) {
@@ -427,6 +433,20 @@ __device__ __forceinline__ void decode_feedback_row(const cover_decode_feedback_
         if (a.lp_out) a.lp_out[(long long)b * a.ld_lp] = was_done ? 0.0f : a.lp[b];
         if constexpr (LP2) lp2_out[(long long)b * ld_lp2] = was_done ? 0.0f : lp2[b];
         if (was_done) t = a.pad;
+        if constexpr (FSM) {
+            int s = f.state[b], set = -1;
+            if (s >= 0 && s < f.n_states) {
+                if (!was_done && t >= 0 && t < a.vocab) {
+                    const int cls = f.class_of_token[t];
+                    if (cls < f.n_classes) {
+                        s = f.trans[(long long)s * f.n_classes + cls];
+                        f.state[b] = s;
+                    }
+                }
+                if (s >= 0 && s < f.n_states) set = f.set_of_state[s];
+            }
+            f.set_of_row[b] = set;
+        }
         a.tok_out[(long long)b * a.ld_tok] = t;
         const bool now_done = was_done || t == a.eos;
         a.done[b] = now_done ? 1 : 0;
@@ -442,6 +462,11 @@ __device__ __forceinline__ void decode_feedback_row(const cover_decode_feedback_
 __global__ __launch_bounds__(128) void decode_feedback_k(cover_decode_feedback_args a) { decode_feedback_row<false>(a, nullptr, nullptr, 0); }
 __global__ __launch_bounds__(128) void decode_feedback_lp2_k(cover_decode_feedback_args a, const float* lp2, float* lp2_out, long long ld_lp2) {
     decode_feedback_row<true>(a, lp2, lp2_out, ld_lp2);
+}
+template <bool LP2>
+__global__ __launch_bounds__(128) void decode_feedback_fsm_k(cover_decode_feedback_args a, cover_token_fsm f, const float* lp2, float* lp2_out,
+                                                             long long ld_lp2) {
+    decode_feedback_row<LP2, true>(a, lp2, lp2_out, ld_lp2, f);
 }
 static bool decode_feedback_ok(const cover_decode_feedback_args* a) {
     if (a->rows < 0 || !a->pick || !a->done || !a->tok_out || (a->lp == nullptr) != (a->lp_out == nullptr)) return false;
@@ -460,6 +485,16 @@ hipError_t launch_decode_feedback_lp2(const cover_decode_feedback_args* a, const
     if (!decode_feedback_ok(a) || !lp2 || !lp2_out) return hipErrorInvalidValue;
     if (a->rows == 0) return hipSuccess;
     hipLaunchKernelGGL(decode_feedback_lp2_k, dim3(a->rows), dim3(128), 0, st, *a, lp2, lp2_out, ld_lp2);
+    return hipGetLastError();
+}
+hipError_t launch_decode_feedback_fsm(const cover_decode_feedback_args* a, const cover_token_fsm* f, const float* lp2, float* lp2_out,
+                                      long long ld_lp2, hipStream_t st) {
+    if (!decode_feedback_ok(a) || !f || (lp2 == nullptr) != (lp2_out == nullptr)) return hipErrorInvalidValue;
+    if (!f->class_of_token || !f->trans || !f->set_of_state || !f->state || !f->set_of_row) return hipErrorInvalidValue;
+    if (f->n_states < 1 || f->n_classes < 1 || f->n_classes > 256 || a->vocab <= 0) return hipErrorInvalidValue;   // class_of_token is [vocab]
+    if (a->rows == 0) return hipSuccess;
+    if (lp2) hipLaunchKernelGGL(decode_feedback_fsm_k<true>, dim3(a->rows), dim3(128), 0, st, *a, *f, lp2, lp2_out, ld_lp2);
+    else hipLaunchKernelGGL(decode_feedback_fsm_k<false>, dim3(a->rows), dim3(128), 0, st, *a, *f, nullptr, nullptr, 0);
     return hipGetLastError();
 }
 

@@ -86,6 +86,72 @@ def sampling_ladder(n_prompts: int, n_samples: int, temperature, top_k=0, top_p=
     return tuple(out)
 
 
+class TokenGrammar(NamedTuple):
+    """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
+    allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)
+    fsm: Any           # ops.TokenFsm
+
+
+def _id_mask(vocab, ids, what):
+    """bool [vocab] of an id list or one half-open (lo, hi) range."""
+    on = np.zeros(vocab, dtype=bool)
+    if isinstance(ids, tuple) and len(ids) == 2:
+        a, b = int(ids[0]), int(ids[1])
+        if not 0 <= a < b <= vocab:
+            raise ValueError(f"length_grammar: {what} range ({a}, {b}) must be non-empty inside [0, {vocab})")
+        on[a:b] = True
+        return on
+    ids = [int(t) for t in (ids if isinstance(ids, (list, set, frozenset, np.ndarray)) else [ids])]
+    if not ids or min(ids) < 0 or max(ids) >= vocab:
+        raise ValueError(f"length_grammar: {what} needs at least one id, all inside [0, {vocab})")
+    on[ids] = True
+    return on
+
+
+def length_grammar(vocab, body, end, eos, min_len, max_len, extra_sets=None, device=None):
+    """The grammar "min_len..max_len body tokens, one end token, then EOS" as a token-class automaton for generate_tokens(grammar=) /
+    ops.decode_feedback(fsm=). body, end and eos are id lists (or one id) or a half-open (lo, hi) tuple, pairwise disjoint.
+    States 0..max_len count the body tokens emitted so far, then ENDED = max_len + 1 (after an end token) and FINISHED = max_len + 2
+    (after EOS). Classes: 0 body, 1 end, 2 eos, 3 every other id. A state allows
+        n < min_len: body        min_len <= n < max_len: body or end        n == max_len: end        ENDED, FINISHED: eos
+    and a token of an allowed class moves (body: n + 1, end: ENDED, eos: FINISHED); a token whose class the state does not allow (only a
+    teacher-forced one can be) leaves the state where it is. The bit sets are the distinct rows of that table in order of first use
+    (at most four, however large max_len is: the states share them through set_of_state); extra_sets (token_allow_sets' format) are
+    appended after them for the caller's own use. Returns TokenGrammar(ops.TokenAllow, ops.TokenFsm), the bits on device if given."""
+    from . import ops
+    vocab, min_len, max_len = int(vocab), int(min_len), int(max_len)
+    if not 0 <= min_len <= max_len:
+        raise ValueError("length_grammar: 0 <= min_len <= max_len is required")
+    m_body, m_end, m_eos = _id_mask(vocab, body, "body"), _id_mask(vocab, end, "end"), _id_mask(vocab, eos, "eos")
+    if (m_body & m_end).any() or (m_body & m_eos).any() or (m_end & m_eos).any():
+        raise ValueError("length_grammar: body, end and eos must be pairwise disjoint")
+    BODY, END, EOS, OTHER = 0, 1, 2, 3
+    cls = np.full(vocab, OTHER, dtype=np.uint8)
+    cls[m_body], cls[m_end], cls[m_eos] = BODY, END, EOS
+    ended, finished = max_len + 1, max_len + 2
+    n_states = max_len + 3
+    allowed = [(n < max_len, n >= min_len, False) for n in range(max_len + 1)] + [(False, False, True)] * 2    # (body, end, eos) per state
+    trans = np.repeat(np.arange(n_states, dtype=np.int32)[:, None], 4, axis=1)                                   # default: stay
+    for s, (b, e, z) in enumerate(allowed):
+        if b:
+            trans[s, BODY] = s + 1
+        if e:
+            trans[s, END] = ended
+        if z:
+            trans[s, EOS] = finished
+    kinds, set_of_state = [], np.zeros(n_states, dtype=np.int32)
+    for s, k in enumerate(allowed):
+        if k not in kinds:
+            kinds.append(k)
+        set_of_state[s] = kinds.index(k)
+    masks = [(m_body & b) | (m_end & e) | (m_eos & z) for b, e, z in kinds]
+    sets = [list(np.nonzero(m)[0]) for m in masks] + list(extra_sets or [])
+    allow = ops.TokenAllow(ops.token_allow_sets(vocab, sets, device))
+    fsm = ops.TokenFsm(cls, trans, set_of_state, start_state=0)
+    fsm.check_sets(allow)
+    return TokenGrammar(allow, fsm)
+
+
 def step_entropy_summary(entropy, tokens=None, pad_id=None):
     """Per-candidate (mean, max) of the per-step entropies over the steps the candidate was live: entropy [N, steps] (torch tensor on
     any device, or numpy) -> two [N] of the same kind. With tokens [N, steps] and pad_id the steps whose emitted token is the pad are

@@ -1047,8 +1047,103 @@ def pick_token(logits, lo, hi, uniform=None, temperature=1.0, filt=None, out_tok
     return tok, lg, None
 
 
+class TokenFsm:
+    """A token-class automaton per row (cover_token_fsm), validated once on the host: class_of_token [vocab] integers in [0, n_classes),
+    trans [n_states, n_classes] integers in [0, n_states), set_of_state [n_states] integers >= 0 (the allowed-set index a row in that
+    state draws from; checked against a TokenAllow's n_sets by check_sets / token_fsm_check), start_state in [0, n_states). n_classes
+    <= 256. Arrays, sequences or tensors; the host copies are kept as numpy (class_of_token_np, trans_np, set_of_state_np), the device
+    copies are made by to(device) once. Regular grammars only: no stack, nothing across rows."""
+
+    def __init__(self, class_of_token, trans, set_of_state, start_state=0):
+        def host(v, what):
+            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            if v.dtype.kind not in "iub" or v.size == 0:
+                raise L.CoverError(f"TokenFsm: {what} must be a non-empty integer array")
+            return v.astype(np.int64)
+        cls, tr, sos = host(class_of_token, "class_of_token"), host(trans, "trans"), host(set_of_state, "set_of_state")
+        if cls.ndim != 1 or tr.ndim != 2 or sos.ndim != 1 or sos.shape[0] != tr.shape[0]:
+            raise L.CoverError("TokenFsm: class_of_token is [vocab], trans [n_states, n_classes] and set_of_state [n_states]")
+        n_states, n_classes = tr.shape
+        if not 1 <= n_classes <= 256:
+            raise L.CoverError(f"TokenFsm: 1 <= n_classes <= 256 is required (got {n_classes})")
+        if cls.min() < 0 or cls.max() >= n_classes:
+            raise L.CoverError(f"TokenFsm: every class_of_token entry must lie in [0, {n_classes})")
+        if tr.min() < 0 or tr.max() >= n_states:
+            raise L.CoverError(f"TokenFsm: every trans entry must lie in [0, {n_states})")
+        if sos.min() < 0:
+            raise L.CoverError("TokenFsm: every set_of_state entry must be >= 0")
+        if not 0 <= int(start_state) < n_states:
+            raise L.CoverError(f"TokenFsm: start_state must lie in [0, {n_states})")
+        self.class_of_token_np, self.trans_np, self.set_of_state_np = cls.astype(np.uint8), tr.astype(np.int32), sos.astype(np.int32)
+        self.n_states, self.n_classes, self.vocab, self.start_state = int(n_states), int(n_classes), int(cls.shape[0]), int(start_state)
+        self.class_of_token = self.trans = self.set_of_state = None      # device tensors, made by to()
+
+    def to(self, device):
+        """Upload the three tables to device (once per device); returns self."""
+        device = torch.device(device)
+        if self.trans is None or self.trans.device != device:
+            self.class_of_token = torch.from_numpy(self.class_of_token_np).to(device)
+            self.trans = torch.from_numpy(self.trans_np).to(device)
+            self.set_of_state = torch.from_numpy(self.set_of_state_np).to(device)
+        return self
+
+    def check_sets(self, allow):
+        """Every set_of_state entry names a set of allow (a TokenAllow): CoverError otherwise."""
+        if not isinstance(allow, TokenAllow):
+            raise L.CoverError("TokenFsm: allow must be an ops.TokenAllow")
+        if int(self.set_of_state_np.max()) >= allow.n_sets:
+            raise L.CoverError(f"TokenFsm: every set_of_state entry must lie in [0, {allow.n_sets}) (the TokenAllow's n_sets)")
+
+    def rows(self, n, device):
+        """(state int32 [n] = start_state, set_of_row int32 [n] = set_of_state[start_state]) on device: the two per-row tensors of a decode.
+        set_of_row is what the TokenAllow of the picks takes; decode_feedback(fsm=) rewrites both every step."""
+        self.to(device)
+        state = torch.full((int(n),), self.start_state, dtype=torch.int32, device=device)
+        return state, torch.full((int(n),), int(self.set_of_state_np[self.start_state]), dtype=torch.int32, device=device)
+
+    def step_torch(self, state, set_of_row, tokens, live):
+        """The update of cover_decode_feedback_fsm in device tensors, in place (the models' unfused path and the fused kernel's in-repo
+        reference): state = where(live & valid, trans[state, class_of_token[t]], state); set_of_row = set_of_state[state] (-1 for a state
+        outside [0, n_states)). tokens int64 [rows] the emitted ids, live bool [rows] = not done before the step. No host round trip."""
+        ok_s = (state >= 0) & (state < self.n_states)
+        move = live & ok_s & (tokens >= 0) & (tokens < self.vocab)
+        cls = self.class_of_token[tokens.clamp(0, self.vocab - 1)].to(torch.int64)
+        s64 = state.clamp(0, self.n_states - 1).to(torch.int64)
+        state.copy_(torch.where(move, self.trans[s64, cls], state))
+        ok_s = (state >= 0) & (state < self.n_states)
+        set_of_row.copy_(torch.where(ok_s, self.set_of_state[state.clamp(0, self.n_states - 1).to(torch.int64)], torch.full_like(set_of_row, -1)))
+
+
+def token_fsm_check(fsm, allow, lo, hi):
+    """Host check of a grammar before it drives a decode: every state reachable from fsm.start_state must have at least one allowed
+    column in [lo, hi) in its set, walking only along classes that have an allowed token (in [lo, hi)) in the state's set. CoverError
+    naming the dead state otherwise: a row that reached it would be the invalid row (-1 / NaN) of the _allowed kernels. One read-back
+    of allow.bits; returns the sorted list of reachable states."""
+    if not isinstance(fsm, TokenFsm):
+        raise L.CoverError("token_fsm_check: fsm must be an ops.TokenFsm")
+    fsm.check_sets(allow)
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi or hi > fsm.vocab or hi > allow.bits.shape[1] * 32:
+        raise L.CoverError(f"token_fsm_check: 0 <= lo < hi <= vocab ({fsm.vocab}) within the words of allow.bits is required (got lo={lo}, hi={hi})")
+    words = np.ascontiguousarray(allow.bits.detach().cpu().view(torch.int32).numpy()).view(np.uint32)
+    on = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, lo:hi].astype(bool)       # [n_sets, hi - lo]
+    cls = fsm.class_of_token_np[lo:hi]
+    seen, todo = {fsm.start_state}, [fsm.start_state]
+    while todo:
+        s = todo.pop()
+        live = np.unique(cls[on[fsm.set_of_state_np[s]]])
+        if live.size == 0:
+            raise L.CoverError(f"token_fsm_check: state {s} is reachable from state {fsm.start_state} and its set "
+                               f"{int(fsm.set_of_state_np[s])} allows no column in [{lo}, {hi})")
+        for n in fsm.trans_np[s, live]:
+            if int(n) not in seen:
+                seen.add(int(n))
+                todo.append(int(n))
+    return sorted(seen)
+
+
 def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp_out=None, table=None, scale=1.0, x_out=None,
-                    live=None, lp2=None, lp2_out=None):
+                    live=None, lp2=None, lp2_out=None, fsm=None, fsm_state=None, fsm_set_of_row=None):
     """The bookkeeping between two decode steps in one launch (cover_decode_feedback). Per row b: t = force[b] if given else pick[b];
     lp_out[b, step] = 0.0 if done[b] else lp[b]; t = pad if done[b]; tok_out[b, step] = t; done[b] |= t == eos;
     x_out[b] = bf16(table[t] * scale) (embed_gather on the emitted ids; an id outside the table gives a zero row); live[step] += not done[b].
@@ -1056,10 +1151,16 @@ def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp
     stride (any row stride); force int64 [rows] with any stride (a column view); live int32 [>= step + 1], zeroed by the caller.
     x_out bf16 [rows, dim] or None (no embedding: the last step). Recordable, no workspace. Returns x_out.
     lp2 / lp2_out (together; shapes as lp / lp_out): a second log-probability column settled the same way in the same launch
-    (cover_decode_feedback_lp2), lp2_out[b, step] = 0.0 if done[b] else lp2[b]; both None issues exactly cover_decode_feedback."""
+    (cover_decode_feedback_lp2), lp2_out[b, step] = 0.0 if done[b] else lp2[b]; both None issues exactly cover_decode_feedback.
+    fsm = TokenFsm with fsm_state / fsm_set_of_row int32 [rows] (all three together; TokenFsm.rows makes the two tensors): the launch is
+    cover_decode_feedback_fsm, which also advances each live row's automaton on its emitted token (fsm_state, in place) and writes
+    fsm_set_of_row[b] = set_of_state[state[b]] -- the set_of_row of the next pick's TokenAllow. A table, if given, has fsm.vocab rows.
+    Without the three it launches exactly what it launched before."""
     if (lp2 is None) != (lp2_out is None):
         raise L.CoverError("decode_feedback: lp2 and lp2_out are given together")
-    _chk_dev(pick, done, tok_out, force, lp, lp_out, table, x_out, live, lp2, lp2_out)
+    if (fsm is None) != (fsm_state is None) or (fsm is None) != (fsm_set_of_row is None):
+        raise L.CoverError("decode_feedback: fsm, fsm_state and fsm_set_of_row are given together")
+    _chk_dev(pick, done, tok_out, force, lp, lp_out, table, x_out, live, lp2, lp2_out, fsm_state, fsm_set_of_row)
     rows = pick.numel()
     assert pick.dtype == torch.int64 and pick.is_contiguous() and done.dtype == torch.bool and done.is_contiguous() and done.numel() == rows
     assert tok_out.dtype == torch.int64 and tok_out.dim() == 2 and tok_out.shape[0] == rows and 0 <= step < tok_out.shape[1]
@@ -1092,6 +1193,23 @@ def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp
         assert lp2.dtype == torch.float32 and lp2.is_contiguous() and lp2.numel() == rows
         assert lp2_out.dtype == torch.float32 and lp2_out.dim() == 2 and lp2_out.shape[0] == rows and step < lp2_out.shape[1]
         assert lp2_out.stride(1) == 1 or lp2_out.shape[1] == 1
+    if fsm is not None:
+        if not isinstance(fsm, TokenFsm):
+            raise L.CoverError("decode_feedback: fsm must be an ops.TokenFsm")
+        for name, t in (("fsm_state", fsm_state), ("fsm_set_of_row", fsm_set_of_row)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != rows or not t.is_contiguous():
+                raise L.CoverError(f"decode_feedback: {name} must be a contiguous int32 tensor [rows]")
+        if table is not None and x_out is not None and table.shape[0] != fsm.vocab:
+            raise L.CoverError(f"decode_feedback: the table has {table.shape[0]} rows, fsm.class_of_token {fsm.vocab} entries")
+        fsm.to(pick.device)
+        a.vocab = fsm.vocab
+        f = L.TokenFsm()
+        f.class_of_token, f.trans, f.set_of_state = fsm.class_of_token.data_ptr(), fsm.trans.data_ptr(), fsm.set_of_state.data_ptr()
+        f.n_states, f.n_classes, f.state, f.set_of_row = fsm.n_states, fsm.n_classes, fsm_state.data_ptr(), fsm_set_of_row.data_ptr()
+        l2 = (None, None, 0) if lp2 is None else (lp2.data_ptr(), lp2_out.data_ptr() + 4 * step, lp2_out.stride(0))
+        L.check(L.lib().cover_decode_feedback_fsm(C.byref(a), C.byref(f), l2[0], l2[1], l2[2], _stream()), "decode_feedback_fsm")
+        return x_out
+    if lp2 is not None:
         L.check(L.lib().cover_decode_feedback_lp2(C.byref(a), lp2.data_ptr(), lp2_out.data_ptr() + 4 * step, lp2_out.stride(0), _stream()),
                 "decode_feedback_lp2")
         return x_out

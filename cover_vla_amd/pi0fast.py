@@ -96,7 +96,7 @@ class PI0FASTTokens:
                         force_tokens: Optional[torch.Tensor] = None, trace: Optional[dict] = None,
                         uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, top_k: RowParam = 0,
                         top_p: RowParam = 1.0, return_logprobs: bool = False, share_prefix: bool = False, top_logprobs: int = 0,
-                        allowed_tokens: Optional[ops.TokenAllow] = None, prior_temperature: Optional[float] = None):
+                        allowed_tokens: Optional[ops.TokenAllow] = None, prior_temperature: Optional[float] = None, grammar=None):
         """images: list (cameras) of [B,3,H,W]; tokens int64 [B,L] RIGHT padded with pad_mask [B,L] (the reference pads left for
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
@@ -140,8 +140,33 @@ class PI0FASTTokens:
         after EOS and on skipped steps, so host.sequence_logprob applies. It is the prior that compares across the rungs of a ladder
         (host.sampling_ladder): return_logprobs scores every row under its own rung. Scalar parameters are broadcast and the per-row
         path is taken (the only one that carries the reference); uniforms is required: a greedy candidate is a row with temperature 0.
+        None launches exactly what it launched before.
+        grammar = host.TokenGrammar(allow, fsm) (host.length_grammar builds one; exclusive with allowed_tokens, it carries its own sets):
+        a token-class automaton per candidate row chooses the set every step's pick draws from. Each row starts in fsm.start_state, so
+        the first pick reads that state's set; between two steps the row's automaton advances on the token it emitted (sampled, greedy
+        and teacher-forced alike; a finished row stops moving) and the next pick -- the same cover_token_sample_rows_allowed launch as
+        with allowed_tokens -- reads the new state's set. With share_prefix the step's feedback launch is cover_decode_feedback_fsm
+        and nothing returns to the host; otherwise (and with COVER_FAST_FEEDBACK=0) the same update runs in device tensors
+        (ops.TokenFsm.step_torch). return_logprobs, prior_temperature and top_logprobs are taken under each step's own set; a forced
+        token outside the current set scores -inf. ops.token_fsm_check runs once before the loop (CoverError names a reachable state
+        whose set is empty), so no pick is the -1 of an invalid row. The state is per candidate row, never per prompt slot.
         None launches exactly what it launched before."""
         dev = self.dev
+        fsm = None
+        if grammar is not None:
+            if allowed_tokens is not None:
+                raise ValueError("grammar and allowed_tokens are mutually exclusive: a grammar carries its own sets")
+            g_allow, g_fsm = grammar
+            if not isinstance(g_allow, ops.TokenAllow) or not isinstance(g_fsm, ops.TokenFsm):
+                raise ops.L.CoverError("grammar must hold an ops.TokenAllow and an ops.TokenFsm (host.TokenGrammar)")
+            if g_fsm.vocab != self.c["vocab"]:
+                raise ops.L.CoverError(f"grammar: class_of_token has {g_fsm.vocab} entries, the vocabulary {self.c['vocab']}")
+            if g_allow.bits.device != dev:
+                raise ops.L.CoverError(f"grammar: the allowed-token bits must be on {dev}")
+            ops.token_fsm_check(g_fsm, g_allow, 0, self.c["vocab"])
+            state, set_of_row = g_fsm.rows(tokens.shape[0], dev)
+            allowed_tokens = ops.TokenAllow(g_allow.bits, set_of_row)     # the picks read the tensor the feedback step rewrites
+            fsm = (g_fsm, state, set_of_row)
         if not 0 <= int(top_logprobs) <= 64:
             raise ValueError("top_logprobs must be in 0..64")
         if prior_temperature is not None:
@@ -162,7 +187,8 @@ class PI0FASTTokens:
         if prior_temperature is not None and rp is None:     # the reference score is the per-row call's: scalars are broadcast
             rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
         if allowed_tokens is not None:
-            self._check_allowed(allowed_tokens, tokens.shape[0])
+            if fsm is None:
+                self._check_allowed(allowed_tokens, tokens.shape[0])
             if rp is None:     # the allowed pick is the per-row call: scalars are broadcast, no uniforms = every row greedy
                 rp = ops.row_param_tensors(tokens.shape[0], *((0.0, 0, 1.0) if uniforms is None else (temperature, top_k, top_p)), dev)
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
@@ -180,7 +206,7 @@ class PI0FASTTokens:
                     return sub_out[back]
                 return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
         return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens, prior_temperature)
+                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens, prior_temperature, fsm)
 
     def _check_allowed(self, allow, B):
         """generate_tokens' host check of its allowed-token sets (one read-back of the bits and the row indices)."""
@@ -203,7 +229,7 @@ class PI0FASTTokens:
             raise ops.L.CoverError(f"allowed_tokens: a set that a row uses allows no id below the vocabulary size {vocab}")
 
     def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None, t_ref=None):
+                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None, t_ref=None, fsm=None):
         """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
@@ -214,7 +240,10 @@ class PI0FASTTokens:
         rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused).
         allow ops.TokenAllow or None (rp is then set): the pick, the score and the ranks over each row's allowed ids only.
         t_ref float or None (rp is then set): the pick's launch also scores it at temperature t_ref, unfiltered; that column is settled
-        like the log-probabilities (fused: decode_feedback's lp2) and returned after them."""
+        like the log-probabilities (fused: decode_feedback's lp2) and returned after them.
+        fsm (ops.TokenFsm, state int32 [B], set_of_row int32 [B]) or None (allow.set_of_row is then that set_of_row): every step advances
+        each row's automaton on its emitted token and rewrites set_of_row for the next pick -- fused: in decode_feedback's launch,
+        otherwise TokenFsm.step_torch on device tensors."""
         dev, c = self.dev, self.c
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
@@ -287,6 +316,8 @@ class PI0FASTTokens:
         akw = {} if allow is None else dict(allow=allow)      # None: the calls made before the argument existed
         rkw = {} if t_ref is None else dict(ref=(t_ref, rl))
         fkw = {} if t_ref is None else dict(lp2=rl, lp2_out=rls)
+        if fsm is not None:
+            fkw.update(fsm=fsm[0], fsm_state=fsm[1], fsm_set_of_row=fsm[2])
 
         def pick(hidden, i):
             hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
@@ -320,6 +351,8 @@ class PI0FASTTokens:
                 t = force[:, i].to(dev)
             t = torch.where(done, torch.full_like(t, pad_token_id), t)               # index bookkeeping: finished rows emit pad
             out[:, i].copy_(t)
+            if fsm is not None:
+                fsm[0].step_torch(fsm[1], fsm[2], t, ~done)                          # done as it was before this step
             done.logical_or_(t == eos_token_id)
 
         pick(h, 0)
@@ -381,6 +414,9 @@ class PI0FASTConfig:
     # half-open (a, b) ranges of PaliGemma ids every row may draw (generate_tokens(allowed_tokens=)): the FAST band from
     # fast_action_token_range plus (b = a + 1) the format tokens; the EOS id is always added. None = the whole vocabulary
     allowed_token_ranges: Optional[Sequence[Tuple[int, int]]] = None
+    # host.TokenGrammar (fast_chunk_grammar / host.length_grammar): a per-row automaton picks each step's allowed set
+    # (generate_tokens(grammar=)); exclusive with allowed_token_ranges. None = no grammar
+    token_grammar: Optional[object] = None
 
 
 class PI0FASTPolicy:
@@ -404,6 +440,8 @@ class PI0FASTPolicy:
             ranges = [(int(a), int(b)) for a, b in config.allowed_token_ranges]
             bits = ops.token_allow_sets(model.c["vocab"], [ranges + [int(paligemma_tokenizer.eos_token_id)]], model.dev)
             self.allowed_tokens = ops.TokenAllow(bits)
+        if config.token_grammar is not None and config.allowed_token_ranges is not None:
+            raise ValueError("token_grammar and allowed_token_ranges are mutually exclusive: a grammar carries its own sets")
         self.reset()
 
     def reset(self):
@@ -478,6 +516,8 @@ class PI0FASTPolicy:
                 sampling.update(share_prefix=True)
             if self.allowed_tokens is not None:
                 sampling.update(allowed_tokens=self.allowed_tokens)
+            if self.config.token_grammar is not None:
+                sampling.update(grammar=self.config.token_grammar)
             if self.config.prior_temperature is not None:
                 sampling.update(prior_temperature=self.config.prior_temperature)
             if self._gen is not None:
@@ -545,3 +585,15 @@ def fast_action_token_range(vocab_size: int, fast_vocab_size: int, fast_skip_tok
     if fast_vocab_size < 1 or a < 0:
         raise ValueError("fast_action_token_range: 1 <= fast_vocab_size <= vocab_size - fast_skip_tokens is required")
     return a, b
+
+
+def fast_chunk_grammar(config: PI0FASTConfig, min_len: int, max_len: int, *, vocab_size: int, fast_vocab_size: int, end_token_id: int,
+                       eos_token_id: int, device=None):
+    """host.length_grammar for one FAST action chunk: min_len..max_len ids of the action band (fast_action_token_range with
+    config.fast_skip_tokens), then the terminator extract_actions splits at (the PaliGemma id of "|", end_token_id), then the
+    tokenizer's EOS. The ids are the caller's tokenizers', as for allowed_token_ranges; "Action" and ":" are outside this grammar, so it
+    fits a model that is to emit the band directly. Returns the host.TokenGrammar that PI0FASTConfig.token_grammar and
+    generate_tokens(grammar=) take. Nothing uses it by default."""
+    from .host import length_grammar
+    band = fast_action_token_range(vocab_size, fast_vocab_size, config.fast_skip_tokens)
+    return length_grammar(vocab_size, band, [int(end_token_id)], [int(eos_token_id)], min_len, max_len, device=device)

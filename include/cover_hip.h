@@ -698,6 +698,33 @@ int cover_decode_feedback(const cover_decode_feedback_args* args, void* stream);
  * and additionally lp2_out[b * ld_lp2] = done[b] ? 0.0f : lp2[b], with done as it was before this step's update, exactly as lp_out.
  * lp2 [rows] and lp2_out are required; every other rule is cover_decode_feedback's. */
 int cover_decode_feedback_lp2(const cover_decode_feedback_args* args, const float* lp2, float* lp2_out, long long ld_lp2, void* stream);
+/* Token grammars on the device: cover_decode_feedback that also advances one finite automaton per row on the emitted token and writes the
+ * index of the allowed-token set the row's NEXT pick draws from, so a cover_token_*_rows_allowed launch whose allow->set_of_row is
+ * fsm->set_of_row follows a per-step grammar with no host round trip ("at least m action tokens, then the terminator, then EOS only").
+ * The automaton is regular and per row: states, token classes, one transition table; no stack, nothing across rows.
+ * Per row b, with t the token cover_decode_feedback emits (forced token and pad after EOS included) and done[b] as it was before the step:
+ *   if (!done[b] && 0 <= t < args->vocab)  state[b] = trans[state[b] * n_classes + class_of_token[t]];
+ *   otherwise the state is unchanged: a finished row stops moving, an id outside the vocabulary (the -1 of an invalid row) reads nothing
+ *   from class_of_token; a class id >= n_classes (outside the contract) leaves the state unchanged too;
+ *   set_of_row[b] = set_of_state[state[b]], always.
+ * A state[b] outside [0, n_states) lives on the device and cannot be refused on the host: it is left unchanged, no table is read for it and
+ * set_of_row[b] = -1, which the _allowed kernels report as an invalid row. No trap; the other rows are unaffected.
+ * args->vocab is the length of class_of_token and is required here with or without x_out. Every other output (tok_out, lp_out, done,
+ * x_out, live) is cover_decode_feedback's, bit for bit; with lp2 / lp2_out (optional, together) the second column is
+ * cover_decode_feedback_lp2's. One launch, one block per row, no workspace, recordable: a replay follows the current contents of the tables.
+ * COVER_EINVAL, and nothing launched: everything cover_decode_feedback refuses; a null fsm or any null member; n_states < 1; n_classes < 1
+ * or > 256; vocab < 1; lp2 without lp2_out or the reverse. */
+typedef struct cover_token_fsm {
+    const uint8_t* class_of_token;  /* [vocab] class id of every token, < n_classes */
+    const int*     trans;           /* [n_states][n_classes] next state, each in [0, n_states) */
+    const int*     set_of_state;    /* [n_states] allowed-set index that a row in this state draws from */
+    int n_states, n_classes;
+    int* state;                     /* [rows] in/out: current state of each row */
+    int* set_of_row;                /* [rows] out: set_of_state[state[b]] after the update;
+                                       the array the next cover_token_*_rows_allowed launch reads */
+} cover_token_fsm;
+int cover_decode_feedback_fsm(const cover_decode_feedback_args* args, const cover_token_fsm* fsm,
+                              const float* lp2 /* optional */, float* lp2_out, long long ld_lp2, void* stream);
 
 /* K20: fuse + score + grouped arg-max (efficient_ensemble_merged.py:404-448). it: [n_members][512] image-text
  * embeddings (unit rows), act: [n_members][N][512]; scores_out [N]; result_out int32 [4] =
