@@ -73,6 +73,17 @@ __device__ __forceinline__ u64 shfl64(u64 v, int l) {
     hi = __shfl(hi, l);
     return ((u64)hi << 32) | lo;
 }
+// the sum of v over the 64 lanes of a wave, in every lane (exact: integers)
+__device__ __forceinline__ u64 wave_sum64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+        lo = __shfl_xor(lo, o);
+        hi = __shfl_xor(hi, o);
+        v += ((u64)hi << 32) | lo;
+    }
+    return v;
+}
 
 // The elements a stage iterates: columns [0, n) of the row (rel = column - lo), or the compacted candidates in LDS.
 template <bool ALLOW>
@@ -145,7 +156,8 @@ __device__ __forceinline__ SampleSrcT<ALLOW> make_src(const float* p, int n, int
 }
 
 // f(logit, rel) for every element. Row: scalar head up to the first 16-byte boundary, float4 body (four loads in flight per lane),
-// scalar tail -- any lo / ld works, aligned rows take the vector path.
+// scalar tail -- any lo / ld works, aligned rows take the vector path. One walk for both sources: without a set allow1 / allow4 are the
+// constants true / 15, so the unmasked instantiation carries no test.
 template <class Src, class F>
 __device__ __forceinline__ void for_each(const SampleShared& s, const Src& src, F f) {
     const int tid = threadIdx.x;
@@ -158,47 +170,30 @@ __device__ __forceinline__ void for_each(const SampleShared& s, const Src& src, 
     const int n = src.n;
     int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
     head = head < n ? head : n;
-    if constexpr (Src::allow) {   // the same walk; the mask words of a group are loaded with its float4, all in flight together
-        for (int c = tid; c < head; c += SMP_T)
-            if (allow1(src, c)) f(p[c], c);
-        const int n4 = (n - head) >> 2;
-        const float4* v = (const float4*)(p + head);
-        auto take = [&](const float4& x, unsigned m, int c) {
-            const int i0 = head + 4 * c;
-            if (m & 1u) f(x.x, i0);
-            if (m & 2u) f(x.y, i0 + 1);
-            if (m & 4u) f(x.z, i0 + 2);
-            if (m & 8u) f(x.w, i0 + 3);
-        };
-        int c = tid;
-        for (; c + 3 * SMP_T < n4; c += 4 * SMP_T) {
-            const unsigned m0 = allow4(src, head + 4 * c), m1 = allow4(src, head + 4 * (c + SMP_T)),
-                           m2 = allow4(src, head + 4 * (c + 2 * SMP_T)), m3 = allow4(src, head + 4 * (c + 3 * SMP_T));
-            const float4 x0 = v[c], x1 = v[c + SMP_T], x2 = v[c + 2 * SMP_T], x3 = v[c + 3 * SMP_T];
-            take(x0, m0, c); take(x1, m1, c + SMP_T); take(x2, m2, c + 2 * SMP_T); take(x3, m3, c + 3 * SMP_T);
-        }
-        for (; c < n4; c += SMP_T) {
-            const unsigned m = allow4(src, head + 4 * c);
-            take(v[c], m, c);
-        }
-        for (int t = head + 4 * n4 + tid; t < n; t += SMP_T)
-            if (allow1(src, t)) f(p[t], t);
-        return;
-    }
-    for (int c = tid; c < head; c += SMP_T) f(p[c], c);
+    for (int c = tid; c < head; c += SMP_T)
+        if (allow1(src, c)) f(p[c], c);
     const int n4 = (n - head) >> 2;
     const float4* v = (const float4*)(p + head);
-    auto take = [&](const float4& x, int c) {
+    auto take = [&](const float4& x, unsigned m, int c) {
         const int i0 = head + 4 * c;
-        f(x.x, i0); f(x.y, i0 + 1); f(x.z, i0 + 2); f(x.w, i0 + 3);
+        if (m & 1u) f(x.x, i0);
+        if (m & 2u) f(x.y, i0 + 1);
+        if (m & 4u) f(x.z, i0 + 2);
+        if (m & 8u) f(x.w, i0 + 3);
     };
     int c = tid;
-    for (; c + 3 * SMP_T < n4; c += 4 * SMP_T) {
+    for (; c + 3 * SMP_T < n4; c += 4 * SMP_T) {   // the mask words of a group are loaded with its float4, all in flight together
+        const unsigned m0 = allow4(src, head + 4 * c), m1 = allow4(src, head + 4 * (c + SMP_T)),
+                       m2 = allow4(src, head + 4 * (c + 2 * SMP_T)), m3 = allow4(src, head + 4 * (c + 3 * SMP_T));
         const float4 x0 = v[c], x1 = v[c + SMP_T], x2 = v[c + 2 * SMP_T], x3 = v[c + 3 * SMP_T];
-        take(x0, c); take(x1, c + SMP_T); take(x2, c + 2 * SMP_T); take(x3, c + 3 * SMP_T);
+        take(x0, m0, c); take(x1, m1, c + SMP_T); take(x2, m2, c + 2 * SMP_T); take(x3, m3, c + 3 * SMP_T);
     }
-    for (; c < n4; c += SMP_T) take(v[c], c);
-    for (int t = head + 4 * n4 + tid; t < n; t += SMP_T) f(p[t], t);
+    for (; c < n4; c += SMP_T) {
+        const unsigned m = allow4(src, head + 4 * c);
+        take(v[c], m, c);
+    }
+    for (int t = head + 4 * n4 + tid; t < n; t += SMP_T)
+        if (allow1(src, t)) f(p[t], t);
 }
 // the same for rel in [r0, r1) only
 template <class Src, class F>
@@ -303,6 +298,44 @@ __device__ __forceinline__ bool key_in_prefix(unsigned key, unsigned prefix, int
 }
 __device__ __forceinline__ int key_digit(unsigned key, int lev) { return (int)((key >> key_shift(lev)) & (unsigned)(key_bins(lev) - 1)); }
 
+// Compacts the elements with pred(l, rel) into LDS, in whatever order the atomics grant, and switches src to that list. The caller has
+// counted them (a first-digit histogram): at most SMP_CAP, the slot guard only keeps a miscount inside the arrays. s.n_list is 0 on
+// entry (kept_set zeroes it, and a row is compacted at most once). Every thread of the block calls this; block-uniform.
+template <class Src, class P>
+__device__ __forceinline__ void compact_to_list(SampleShared& s, Src& src, P pred) {
+    for_each(s, src, [&](float l, int rel) {
+        if (pred(l, rel)) {
+            const unsigned slot = atomicAdd(&s.n_list, 1u);
+            if (slot < SMP_CAP) {
+                s.list_l[slot] = l;
+                s.list_i[slot] = rel;
+            }
+        }
+    });
+    __syncthreads();
+    src.list = true;
+}
+
+// The r-th smallest rel (r >= 1) among the elements with pred(l, rel): a count selection over two 10-bit digits of rel. Every thread
+// of the block calls this; block-uniform.
+template <class Src, class P>
+__device__ __forceinline__ int nth_index(SampleShared& s, const Src& src, u64 r, P pred) {
+    int ip = 0;
+    for (int lev = 0; lev < 2; ++lev) {
+        const int sh = lev == 0 ? 10 : 0;
+        hist_zero(s);
+        for_each(s, src, [&](float l, int rel) {
+            if (!pred(l, rel)) return;
+            if (lev == 1 && (rel >> 10) != (ip >> 10)) return;
+            hist_add(s, (rel >> sh) & 1023, 0ull);
+        });
+        scan_bins<false, false>(s, 1024, r);
+        ip |= s.r_bin << sh;
+        r -= (u64)s.r_cnt_before;
+    }
+    return ip;
+}
+
 // The kept set of one row (steps 1-3 of cover_token_sample), as every entry point of this file sees it: column rel of [lo, hi) with logit l
 // is kept  <=>  lkey(l) >= tk  and  ( wkey(w) > wstar  or  (wkey(w) == wstar and rel <= idx_cut) ),  w = weight_of(l, m, T).
 // A pure function of (l, rel) and five block-uniform values, so the sampler (which walks the row or the compacted list) and the
@@ -350,19 +383,8 @@ __device__ __forceinline__ KeptSet kept_set(SampleShared& s, Src& src, int top_k
     if (use_k) {
         scan_bins<true, false>(s, key_bins(0), (u64)top_k);
         const int b0 = s.r_bin;
-        if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {   // block-uniform
-            for_each(s, src, [&](float l, int rel) {
-                if (key_digit(lkey(l), 0) >= b0) {
-                    const unsigned slot = atomicAdd(&s.n_list, 1u);
-                    if (slot < SMP_CAP) {
-                        s.list_l[slot] = l;
-                        s.list_i[slot] = rel;
-                    }
-                }
-            });
-            __syncthreads();
-            src.list = true;
-        }
+        if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP)   // block-uniform
+            compact_to_list(s, src, [&](float l, int rel) { return key_digit(lkey(l), 0) >= b0; });
         unsigned prefix = 0u;
         u64 need = (u64)top_k;
         for (int lev = 0; lev < 3; ++lev) {
@@ -394,21 +416,8 @@ __device__ __forceinline__ KeptSet kept_set(SampleShared& s, Src& src, int top_k
             scan_bins<true, true>(s, key_bins(0), 0ull, 1, (double)top_p);
             target = s.r_need;
             const int b0 = s.r_bin;
-            if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {
-                for_each(s, src, [&](float l, int rel) {
-                    if (lkey(l) < tk) return;
-                    const float w = weight_of(l, m, T);
-                    if (key_digit(wkey(w), 0) >= b0) {
-                        const unsigned slot = atomicAdd(&s.n_list, 1u);
-                        if (slot < SMP_CAP) {
-                            s.list_l[slot] = l;
-                            s.list_i[slot] = rel;
-                        }
-                    }
-                });
-                __syncthreads();
-                src.list = true;
-            }
+            if (s.r_cnt_before + s.r_cnt_bin <= SMP_CAP)
+                compact_to_list(s, src, [&](float l, int rel) { return lkey(l) >= tk && key_digit(wkey(weight_of(l, m, T)), 0) >= b0; });
         }
         unsigned prefix = 0u;
         u64 need = target, q_tie = 0ull;
@@ -433,23 +442,8 @@ __device__ __forceinline__ KeptSet kept_set(SampleShared& s, Src& src, int top_k
         // n_tie tokens share the weight at the cut; the first r of them in index order complete the prefix
         u64 r = q_tie ? (need + q_tie - 1ull) / q_tie : 1ull;
         r = r < 1ull ? 1ull : (r > (u64)n_tie ? (u64)n_tie : r);
-        if (r < (u64)n_tie) {   // block-uniform; idx* = the r-th smallest index among the tied tokens (two 10-bit digits of rel)
-            int ip = 0;
-            for (int lev = 0; lev < 2; ++lev) {
-                const int sh = lev == 0 ? 10 : 0;
-                hist_zero(s);
-                for_each(s, src, [&](float l, int rel) {
-                    if (lkey(l) < tk) return;
-                    if (wkey(weight_of(l, m, T)) != wstar) return;
-                    if (lev == 1 && (rel >> 10) != (ip >> 10)) return;
-                    hist_add(s, (rel >> sh) & 1023, 0ull);
-                });
-                scan_bins<false, false>(s, 1024, r);
-                ip |= s.r_bin << sh;
-                r -= (u64)s.r_cnt_before;
-            }
-            idx_cut = ip;
-        }
+        if (r < (u64)n_tie)   // block-uniform; idx* = the r-th smallest index among the tied tokens
+            idx_cut = nth_index(s, src, r, [&](float l, int rel) { return lkey(l) >= tk && wkey(weight_of(l, m, T)) == wstar; });
     }
     return KeptSet{m, T, tk, wstar, idx_cut};
 }
@@ -490,28 +484,15 @@ __device__ __forceinline__ int kept_tiles(SampleShared& s, const Src& src, const
         auto packed = [&](const float4& x, int c) -> u64 {
             const int i0 = head + 4 * c;
             u64 acc = 0ull, q;
-            if constexpr (Src::allow) {
-                const unsigned m = allow4(src, i0);
-                if ((m & 1u) && ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
-                if ((m & 2u) && ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
-                if ((m & 4u) && ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
-                if ((m & 8u) && ks.kept(x.w, i0 + 3, q)) acc += q + (1ull << 52);
-                return acc;
-            }
-            if (ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
-            if (ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
-            if (ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
-            if (ks.kept(x.w, i0 + 3, q)) acc += q + (1ull << 52);
+            const unsigned m = allow4(src, i0);
+            if ((m & 1u) && ks.kept(x.x, i0, q)) acc += q + (1ull << 52);
+            if ((m & 2u) && ks.kept(x.y, i0 + 1, q)) acc += q + (1ull << 52);
+            if ((m & 4u) && ks.kept(x.z, i0 + 2, q)) acc += q + (1ull << 52);
+            if ((m & 8u) && ks.kept(x.w, i0 + 3, q)) acc += q + (1ull << 52);
             return acc;
         };
         auto flush = [&](u64 acc, int cb) {   // cb: the wave's first float4 of this load
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                unsigned lo32 = (unsigned)acc, hi32 = (unsigned)(acc >> 32);
-                lo32 = __shfl_xor(lo32, o);
-                hi32 = __shfl_xor(hi32, o);
-                acc += ((u64)hi32 << 32) | lo32;
-            }
+            acc = wave_sum64(acc);
             if (lane == 0 && acc) {
                 const int bin = (head + 4 * cb + shift) >> 10;
                 atomicAdd(&s.cnt[bin], (unsigned)(acc >> 52));
@@ -686,13 +667,7 @@ __device__ __forceinline__ void topn_row(SampleShared& s, TopnShared& t, const c
             }
         });
         if (lev == 0) {   // per wave: integer shuffles, then one LDS atomic
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                unsigned lo32 = (unsigned)ent, hi32 = (unsigned)(ent >> 32);
-                lo32 = __shfl_xor(lo32, o);
-                hi32 = __shfl_xor(hi32, o);
-                ent += ((u64)hi32 << 32) | lo32;
-            }
+            ent = wave_sum64(ent);
             if (lane == 0 && ent) atomicAdd(&t.ent, ent);
         }
         scan_bins<true, false>(s, key_bins(lev), need);
@@ -701,42 +676,20 @@ __device__ __forceinline__ void topn_row(SampleShared& s, TopnShared& t, const c
         n_tie = s.r_cnt_bin;
         if (lev == 0 && !src.list && s.r_cnt_before + s.r_cnt_bin <= SMP_CAP) {   // block-uniform; the list is free: kept_set left the row in place
             const int b0 = s.r_bin;
-            for_each(s, src, [&](float l, int rel) {
+            compact_to_list(s, src, [&](float l, int rel) {
                 u64 q;
-                if (!ks.kept(l, rel, q)) return;
-                if (key_digit(lkey(l), 0) >= b0) {
-                    const unsigned slot = atomicAdd(&s.n_list, 1u);
-                    if (slot < SMP_CAP) {
-                        s.list_l[slot] = l;
-                        s.list_i[slot] = rel;
-                    }
-                }
+                return ks.kept(l, rel, q) && key_digit(lkey(l), 0) >= b0;
             });
-            __syncthreads();
-            src.list = true;
         }
     }
     const unsigned thr = prefix;
     // n_tie kept tokens share the logit at the threshold; the first `need` of them in index order complete the ranks
     int idx_cut = 0x7fffffff;
-    if (need < (u64)n_tie) {   // block-uniform; the need-th smallest index among them (two 10-bit digits of rel, as kept_set's idx_cut)
-        u64 r = need < 1ull ? 1ull : need;
-        int ip = 0;
-        for (int lev = 0; lev < 2; ++lev) {
-            const int sh = lev == 0 ? 10 : 0;
-            hist_zero(s);
-            for_each(s, src, [&](float l, int rel) {
-                u64 q;
-                if (lkey(l) != thr || !ks.kept(l, rel, q)) return;
-                if (lev == 1 && (rel >> 10) != (ip >> 10)) return;
-                hist_add(s, (rel >> sh) & 1023, 0ull);
-            });
-            scan_bins<false, false>(s, 1024, r);
-            ip |= s.r_bin << sh;
-            r -= (u64)s.r_cnt_before;
-        }
-        idx_cut = ip;
-    }
+    if (need < (u64)n_tie)   // block-uniform; the need-th smallest index among them (as kept_set's idx_cut)
+        idx_cut = nth_index(s, src, need < 1ull ? 1ull : need, [&](float l, int rel) {
+            u64 q;
+            return lkey(l) == thr && ks.kept(l, rel, q);
+        });
 
     // ---- exactly `want` entries reach LDS (in whatever order the atomics grant); one wave ranks them
     for_each(s, src, [&](float l, int rel) {
@@ -815,6 +768,100 @@ __device__ __forceinline__ RowParams row_params(const float* temperature, const 
     return r;
 }
 
+// ---- allowed-token sets per row (cover_token_*_rows_allowed) ------------------------------------------------------------------
+// The row's set: counts the allowed columns of [lo, hi) and finds the first of them (one pass over the words that cover the range, edge
+// words trimmed to it; integer LDS atomics). false: the row is invalid (set index outside [0, n_sets), or no allowed column in range).
+// Every thread of the block calls this; block-uniform.
+__device__ __forceinline__ bool allow_row(SampleShared& s, const cover_token_allow& al, int lo, int hi, int row, AllowRow<true>& ar) {
+    const int tid = threadIdx.x;
+    const int set = al.set_of_row ? al.set_of_row[row] : 0;
+    if (set < 0 || set >= al.n_sets) return false;
+    const unsigned* bits = al.bits + (size_t)set * (size_t)al.ld_words;
+    if (tid == 0) {
+        s.r_cnt_total = 0u;
+        s.r_bin = 0x7fffffff;
+    }
+    __syncthreads();
+    const int w0 = lo >> 5, w1 = (hi - 1) >> 5;
+    unsigned cnt = 0u;
+    int first = 0x7fffffff;
+    for (int w = w0 + tid; w <= w1; w += SMP_T) {   // ascending per thread: its first hit is its lowest
+        unsigned v = bits[w];
+        if (w == w0) v &= 0xffffffffu << (lo & 31);
+        if (w == w1 && (hi & 31)) v &= (1u << (hi & 31)) - 1u;
+        cnt += (unsigned)__popc(v);
+        if (v && first == 0x7fffffff) first = (w << 5) + (__ffs((int)v) - 1) - lo;
+    }
+    if (cnt) {
+        atomicAdd(&s.r_cnt_total, cnt);
+        atomicMin(&s.r_bin, first);
+    }
+    __syncthreads();
+    ar.bits = bits;
+    ar.cnt = (int)s.r_cnt_total;
+    ar.first = s.r_bin;
+    __syncthreads();   // the row functions write s.r_* again
+    return ar.cnt > 0;
+}
+
+// ---- one block of a *_rows launch ---------------------------------------------------------------------------------------------
+// What an invalid row (row_params' mode 2; with sets also a set index outside [0, n_sets) or no allowed column in range) stores in place
+// of a result. Thread 0 stores (top-n: the first n threads); block-uniform.
+__device__ __forceinline__ void invalid_logprob_row(const cover_token_logprob_rows_args& a, int row) {
+    if (threadIdx.x == 0) {
+        a.logprob_out[row] = NAN;
+        if (a.kept_out) a.kept_out[row] = 0;
+    }
+}
+__device__ __forceinline__ void invalid_topn_row(const cover_token_topn_rows_args& a, int row) {
+    const int tid = threadIdx.x;
+    if (tid < a.n) {
+        a.token_out[(size_t)row * a.ld_tok + tid] = -1;
+        a.logprob_out[(size_t)row * a.ld_lp + tid] = -INFINITY;
+    }
+    if (tid == 0) {
+        if (a.entropy_out) a.entropy_out[row] = NAN;
+        if (a.kept_out) a.kept_out[row] = 0;
+    }
+}
+
+// Row blockIdx.x of a launch with parameters per row: the row's parameters, with ALLOW its set, then the scalar kernels' row function on
+// them, so a row computes what the scalar kernel computes for it in every entry point. al is read only with ALLOW.
+template <bool ALLOW>
+__device__ __forceinline__ void logprob_rows_block(SampleShared& s, const cover_token_logprob_rows_args& a, const cover_token_allow& al) {
+    const int row = blockIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<ALLOW> ar;
+    bool valid = rp.mode != 2;
+    if constexpr (ALLOW) valid = valid && allow_row(s, al, a.lo, a.hi, row, ar);
+    if (!valid) {
+        invalid_logprob_row(a, row);
+        return;
+    }
+    logprob_row<ALLOW>(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, rp.T, rp.k, rp.p, row, a.token, a.logprob_out, a.kept_out, ar);
+}
+template <bool ALLOW>
+__device__ __forceinline__ void topn_rows_block(SampleShared& s, TopnShared& t, const cover_token_topn_rows_args& a,
+                                                const cover_token_allow& al) {
+    const int row = blockIdx.x;
+    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
+    AllowRow<ALLOW> ar;
+    bool valid = rp.mode != 2;
+    if constexpr (ALLOW) valid = valid && allow_row(s, al, a.lo, a.hi, row, ar);
+    if (!valid) {
+        invalid_topn_row(a, row);
+        return;
+    }
+    cover_token_topn_args b;
+    b.logits = a.logits; b.ld = a.ld; b.rows = a.rows; b.lo = a.lo; b.hi = a.hi;
+    b.temperature = rp.T; b.top_k = rp.k; b.top_p = rp.p; b.n = a.n;
+    b.token_out = a.token_out; b.ld_tok = a.ld_tok; b.logprob_out = a.logprob_out; b.ld_lp = a.ld_lp;
+    b.entropy_out = a.entropy_out; b.kept_out = a.kept_out;
+    topn_row<ALLOW>(s, t, b, row, ar);
+}
+
+// The kernels: one per entry point, each the block function above at its <ALLOW, REF>. Kernels of their own (not one kernel with run-time
+// flags), so adding an entry point leaves the instructions of the others as they were.
 __global__ __launch_bounds__(SMP_T) void token_sample_rows_k(cover_token_sample_rows_args a) {
     __shared__ SampleShared s;
     __shared__ int first;
@@ -857,82 +904,15 @@ __global__ __launch_bounds__(SMP_T) void token_sample_rows_k(cover_token_sample_
         if (a.logprob_out) a.logprob_out[row] = kept_logprob(ks, l, pick, s.r_mass_total);
     }
 }
-
 __global__ __launch_bounds__(SMP_T) void token_logprob_rows_k(cover_token_logprob_rows_args a) {
     __shared__ SampleShared s;
-    const int row = blockIdx.x;
-    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
-    if (rp.mode == 2) {
-        if (threadIdx.x == 0) {
-            a.logprob_out[row] = NAN;
-            if (a.kept_out) a.kept_out[row] = 0;
-        }
-        return;
-    }
-    logprob_row(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, rp.T, rp.k, rp.p, row, a.token, a.logprob_out, a.kept_out);
+    logprob_rows_block<false>(s, a, cover_token_allow{});
 }
-
 __global__ __launch_bounds__(SMP_T) void token_topn_rows_k(cover_token_topn_rows_args a) {
     __shared__ SampleShared s;
     __shared__ TopnShared t;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
-    if (rp.mode == 2) {
-        if (tid < a.n) {
-            a.token_out[(size_t)row * a.ld_tok + tid] = -1;
-            a.logprob_out[(size_t)row * a.ld_lp + tid] = -INFINITY;
-        }
-        if (tid == 0) {
-            if (a.entropy_out) a.entropy_out[row] = NAN;
-            if (a.kept_out) a.kept_out[row] = 0;
-        }
-        return;
-    }
-    cover_token_topn_args b;
-    b.logits = a.logits; b.ld = a.ld; b.rows = a.rows; b.lo = a.lo; b.hi = a.hi;
-    b.temperature = rp.T; b.top_k = rp.k; b.top_p = rp.p; b.n = a.n;
-    b.token_out = a.token_out; b.ld_tok = a.ld_tok; b.logprob_out = a.logprob_out; b.ld_lp = a.ld_lp;
-    b.entropy_out = a.entropy_out; b.kept_out = a.kept_out;
-    topn_row(s, t, b, row);
+    topn_rows_block<false>(s, t, a, cover_token_allow{});
 }
-
-// ---- allowed-token sets per row (cover_token_*_rows_allowed) ------------------------------------------------------------------
-// The row's set: counts the allowed columns of [lo, hi) and finds the first of them (one pass over the words that cover the range, edge
-// words trimmed to it; integer LDS atomics). false: the row is invalid (set index outside [0, n_sets), or no allowed column in range).
-// Every thread of the block calls this; block-uniform.
-__device__ __forceinline__ bool allow_row(SampleShared& s, const cover_token_allow& al, int lo, int hi, int row, AllowRow<true>& ar) {
-    const int tid = threadIdx.x;
-    const int set = al.set_of_row ? al.set_of_row[row] : 0;
-    if (set < 0 || set >= al.n_sets) return false;
-    const unsigned* bits = al.bits + (size_t)set * (size_t)al.ld_words;
-    if (tid == 0) {
-        s.r_cnt_total = 0u;
-        s.r_bin = 0x7fffffff;
-    }
-    __syncthreads();
-    const int w0 = lo >> 5, w1 = (hi - 1) >> 5;
-    unsigned cnt = 0u;
-    int first = 0x7fffffff;
-    for (int w = w0 + tid; w <= w1; w += SMP_T) {   // ascending per thread: its first hit is its lowest
-        unsigned v = bits[w];
-        if (w == w0) v &= 0xffffffffu << (lo & 31);
-        if (w == w1 && (hi & 31)) v &= (1u << (hi & 31)) - 1u;
-        cnt += (unsigned)__popc(v);
-        if (v && first == 0x7fffffff) first = (w << 5) + (__ffs((int)v) - 1) - lo;
-    }
-    if (cnt) {
-        atomicAdd(&s.r_cnt_total, cnt);
-        atomicMin(&s.r_bin, first);
-    }
-    __syncthreads();
-    ar.bits = bits;
-    ar.cnt = (int)s.r_cnt_total;
-    ar.first = s.r_bin;
-    __syncthreads();   // the row functions write s.r_* again
-    return ar.cnt > 0;
-}
-
-// The three kernels below are token_*_rows_k above with the row's set looked up first and handed to the same row functions.
 __global__ __launch_bounds__(SMP_T) void token_sample_rows_allowed_k(cover_token_sample_rows_args a, cover_token_allow al) {
     __shared__ SampleShared s;
     __shared__ int first;
@@ -1033,45 +1013,14 @@ __global__ __launch_bounds__(SMP_T) void token_sample_rows_ref_k(cover_token_sam
     }
     ref_logprob(s, src, ks, mass, ref.temperature, l, pick, row, ref.logprob_out);
 }
-
 __global__ __launch_bounds__(SMP_T) void token_logprob_rows_allowed_k(cover_token_logprob_rows_args a, cover_token_allow al) {
     __shared__ SampleShared s;
-    const int row = blockIdx.x;
-    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
-    AllowRow<true> ar;
-    if (rp.mode == 2 || !allow_row(s, al, a.lo, a.hi, row, ar)) {
-        if (threadIdx.x == 0) {
-            a.logprob_out[row] = NAN;
-            if (a.kept_out) a.kept_out[row] = 0;
-        }
-        return;
-    }
-    logprob_row<true>(s, a.logits + (size_t)row * a.ld, a.lo, a.hi, rp.T, rp.k, rp.p, row, a.token, a.logprob_out, a.kept_out, ar);
+    logprob_rows_block<true>(s, a, al);
 }
-
 __global__ __launch_bounds__(SMP_T) void token_topn_rows_allowed_k(cover_token_topn_rows_args a, cover_token_allow al) {
     __shared__ SampleShared s;
     __shared__ TopnShared t;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const RowParams rp = row_params(a.temperature, a.top_k, a.top_p, row);
-    AllowRow<true> ar;
-    if (rp.mode == 2 || !allow_row(s, al, a.lo, a.hi, row, ar)) {
-        if (tid < a.n) {
-            a.token_out[(size_t)row * a.ld_tok + tid] = -1;
-            a.logprob_out[(size_t)row * a.ld_lp + tid] = -INFINITY;
-        }
-        if (tid == 0) {
-            if (a.entropy_out) a.entropy_out[row] = NAN;
-            if (a.kept_out) a.kept_out[row] = 0;
-        }
-        return;
-    }
-    cover_token_topn_args b;
-    b.logits = a.logits; b.ld = a.ld; b.rows = a.rows; b.lo = a.lo; b.hi = a.hi;
-    b.temperature = rp.T; b.top_k = rp.k; b.top_p = rp.p; b.n = a.n;
-    b.token_out = a.token_out; b.ld_tok = a.ld_tok; b.logprob_out = a.logprob_out; b.ld_lp = a.ld_lp;
-    b.entropy_out = a.entropy_out; b.kept_out = a.kept_out;
-    topn_row<true>(s, t, b, row, ar);
+    topn_rows_block<true>(s, t, a, al);
 }
 
 __global__ void fill_i32_k(int* p, int n, int v) {
@@ -1079,26 +1028,48 @@ __global__ void fill_i32_k(int* p, int n, int v) {
     if (i < n) p[i] = v;
 }
 
+// ---- launches: every check fails with hipErrorInvalidValue ------------------------------------------------------------------------
+static bool range_ok(int lo, int hi, int rows) { return hi > lo && lo >= 0 && hi - lo <= (1 << 20) && rows >= 0; }
 static bool sample_params_ok(int lo, int hi, int rows, float temperature, int top_k, float top_p) {
-    if (hi <= lo || lo < 0 || hi - lo > (1 << 20) || rows < 0) return false;
-    return temperature > 0.f && top_p > 0.f && top_k >= 0;
+    return range_ok(lo, hi, rows) && temperature > 0.f && top_p > 0.f && top_k >= 0;
+}
+static bool topn_shape_ok(int n, int ld_tok, int ld_lp) { return n >= 1 && n <= 64 && ld_tok >= n && ld_lp >= n; }
+// The *_rows families. The per-row parameters live on the device: only the pointers and the launch's own shape are checked here, a bad
+// row reports itself (see row_params).
+static bool sample_rows_ok(const cover_token_sample_rows_args* a) {
+    return a->logits && a->uniform && a->temperature && a->token_out && range_ok(a->lo, a->hi, a->rows);
+}
+static bool logprob_rows_ok(const cover_token_logprob_rows_args* a) {
+    return a->logits && a->temperature && a->token && a->logprob_out && range_ok(a->lo, a->hi, a->rows);
+}
+static bool topn_rows_ok(const cover_token_topn_rows_args* a) {
+    return a->logits && a->temperature && a->token_out && a->logprob_out && range_ok(a->lo, a->hi, a->rows) &&
+           topn_shape_ok(a->n, a->ld_tok, a->ld_lp);
+}
+// the set itself lives on the device as well: the launch checks its shape, a row whose set index or set is unusable reports itself
+static bool allow_ok(const cover_token_allow* al, int hi) {
+    if (!al || !al->bits || ((uintptr_t)al->bits & 3u)) return false;
+    return al->n_sets >= 1 && al->ld_words >= (long long)((hi + 31) / 32);
+}
+// one 1024-thread block per row; no rows: nothing is launched
+template <class K, class... A>
+static hipError_t launch_rows(K kernel, int rows, hipStream_t st, const A&... args) {
+    if (rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3(rows), dim3(SMP_T), 0, st, args...);
+    return hipGetLastError();
 }
 
 hipError_t launch_token_logprob(const cover_token_logprob_args* a, hipStream_t st) {
     if (!a->logits || !a->token || !a->logprob_out) return hipErrorInvalidValue;
     if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_logprob_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
-    return hipGetLastError();
+    return launch_rows(token_logprob_k, a->rows, st, *a);
 }
 
 hipError_t launch_token_topn(const cover_token_topn_args* a, hipStream_t st) {
     if (!a->logits || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
     if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, a->top_k, a->top_p)) return hipErrorInvalidValue;
-    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_topn_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
-    return hipGetLastError();
+    if (!topn_shape_ok(a->n, a->ld_tok, a->ld_lp)) return hipErrorInvalidValue;
+    return launch_rows(token_topn_k, a->rows, st, *a);
 }
 
 // logprob_out == nullptr: cover_token_sample; otherwise cover_token_sample_scored (the same launch with one more store per row)
@@ -1124,80 +1095,47 @@ static hipError_t launch_token_sample_impl(const cover_token_sample_args* a, flo
         if (a->kept_out) hipLaunchKernelGGL(fill_i32_k, dim3((a->rows + 255) / 256), dim3(256), 0, st, a->kept_out, a->rows, n);
         return hipGetLastError();
     }
-    if (logprob_out) hipLaunchKernelGGL(token_sample_k<true>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
-    else hipLaunchKernelGGL(token_sample_k<false>, dim3(a->rows), dim3(SMP_T), 0, st, *a, logprob_out);
-    return hipGetLastError();
+    if (logprob_out) return launch_rows(token_sample_k<true>, a->rows, st, *a, logprob_out);
+    return launch_rows(token_sample_k<false>, a->rows, st, *a, logprob_out);
 }
 
-// the per-row parameters live on the device: only the launch's own shape is checked here, a bad row reports itself (see row_params)
-static bool sample_rows_ok(int lo, int hi, int rows) { return hi > lo && lo >= 0 && hi - lo <= (1 << 20) && rows >= 0; }
-
 hipError_t launch_token_sample_rows(const cover_token_sample_rows_args* a, hipStream_t st) {
-    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_sample_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
-    return hipGetLastError();
+    if (!sample_rows_ok(a)) return hipErrorInvalidValue;
+    return launch_rows(token_sample_rows_k, a->rows, st, *a);
 }
 
 hipError_t launch_token_logprob_rows(const cover_token_logprob_rows_args* a, hipStream_t st) {
-    if (!a->logits || !a->temperature || !a->token || !a->logprob_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_logprob_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
-    return hipGetLastError();
+    if (!logprob_rows_ok(a)) return hipErrorInvalidValue;
+    return launch_rows(token_logprob_rows_k, a->rows, st, *a);
 }
 
 hipError_t launch_token_topn_rows(const cover_token_topn_rows_args* a, hipStream_t st) {
-    if (!a->logits || !a->temperature || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows)) return hipErrorInvalidValue;
-    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_topn_rows_k, dim3(a->rows), dim3(SMP_T), 0, st, *a);
-    return hipGetLastError();
-}
-
-// the set itself lives on the device as well: the launch checks its shape, a row whose set index or set is unusable reports itself
-static bool allow_ok(const cover_token_allow* al, int hi) {
-    if (!al || !al->bits || ((uintptr_t)al->bits & 3u)) return false;
-    return al->n_sets >= 1 && al->ld_words >= (long long)((hi + 31) / 32);
+    if (!topn_rows_ok(a)) return hipErrorInvalidValue;
+    return launch_rows(token_topn_rows_k, a->rows, st, *a);
 }
 
 hipError_t launch_token_sample_rows_allowed(const cover_token_sample_rows_args* a, const cover_token_allow* al, hipStream_t st) {
-    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_sample_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
-    return hipGetLastError();
+    if (!sample_rows_ok(a) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    return launch_rows(token_sample_rows_allowed_k, a->rows, st, *a, *al);
 }
 
 // al == nullptr: the unmasked kernel. The reference temperature travels by value: a captured launch keeps the one it was recorded with.
 hipError_t launch_token_sample_rows_ref(const cover_token_sample_rows_args* a, const cover_token_allow* al, const cover_token_ref* ref,
                                         hipStream_t st) {
-    if (!a->logits || !a->uniform || !a->temperature || !a->token_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows) || (al && !allow_ok(al, a->hi))) return hipErrorInvalidValue;
+    if (!sample_rows_ok(a) || (al && !allow_ok(al, a->hi))) return hipErrorInvalidValue;
     if (!ref || !ref->logprob_out || !(ref->temperature > 0.f) || !(ref->temperature < INFINITY)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    if (al) hipLaunchKernelGGL(token_sample_rows_ref_k<true>, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al, *ref);
-    else hipLaunchKernelGGL(token_sample_rows_ref_k<false>, dim3(a->rows), dim3(SMP_T), 0, st, *a, cover_token_allow{}, *ref);
-    return hipGetLastError();
+    if (al) return launch_rows(token_sample_rows_ref_k<true>, a->rows, st, *a, *al, *ref);
+    return launch_rows(token_sample_rows_ref_k<false>, a->rows, st, *a, cover_token_allow{}, *ref);
 }
 
 hipError_t launch_token_logprob_rows_allowed(const cover_token_logprob_rows_args* a, const cover_token_allow* al, hipStream_t st) {
-    if (!a->logits || !a->temperature || !a->token || !a->logprob_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_logprob_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
-    return hipGetLastError();
+    if (!logprob_rows_ok(a) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    return launch_rows(token_logprob_rows_allowed_k, a->rows, st, *a, *al);
 }
 
 hipError_t launch_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, hipStream_t st) {
-    if (!a->logits || !a->temperature || !a->token_out || !a->logprob_out) return hipErrorInvalidValue;
-    if (!sample_rows_ok(a->lo, a->hi, a->rows) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
-    if (a->n < 1 || a->n > 64 || a->ld_tok < a->n || a->ld_lp < a->n) return hipErrorInvalidValue;
-    if (a->rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_topn_rows_allowed_k, dim3(a->rows), dim3(SMP_T), 0, st, *a, *al);
-    return hipGetLastError();
+    if (!topn_rows_ok(a) || !allow_ok(al, a->hi)) return hipErrorInvalidValue;
+    return launch_rows(token_topn_rows_allowed_k, a->rows, st, *a, *al);
 }
 
 hipError_t launch_token_sample(const cover_token_sample_args* a, hipStream_t st) { return launch_token_sample_impl(a, nullptr, st); }

@@ -713,6 +713,58 @@ def token_logprob(logits, lo, hi, tokens, temperature=1.0, top_k=0, top_p=1.0, o
     return lp
 
 
+# ---- checks and struct fields the CoverError-raising token wrappers share (what = the wrapper's name in the message) ----
+def _chk_range(what, lo, hi):
+    if hi <= lo or lo < 0:
+        raise L.CoverError(f"{what}: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
+
+
+def _chk_logits(what, logits, hi) -> int:
+    """logits fp32 [rows, >= hi] with unit column stride; returns rows."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
+        raise L.CoverError(f"{what}: logits must be fp32 [rows, >= hi] with unit column stride")
+    return logits.shape[0]
+
+
+def _chk_topn_n(what, n) -> int:
+    if not 1 <= int(n) <= 64:
+        raise L.CoverError(f"{what}: 1 <= n <= 64 is required (got n={n})")
+    return int(n)
+
+
+def _chk_rows_out(what, rows, *outs):
+    """Each (name, tensor or None, dtype): contiguous [rows]."""
+    for name, t, dt in outs:
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise L.CoverError(f"{what}: {name} must be contiguous {dt} [rows]")
+
+
+def _chk_rows_n_out(what, rows, n, *outs):
+    """Each (name, tensor or None, dtype): [rows, n], unit column stride, any row stride >= n."""
+    for name, t, dt in outs:
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, n) or (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n)):
+            raise L.CoverError(f"{what}: {name} must be {dt} [rows, n] with unit column stride and a row stride >= n")
+
+
+def _fill_rows(a, logits, rows, lo, hi):
+    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+
+
+def _topn_outputs(a, what, logits, rows, n, out_tok, out_logprob, out_entropy, out_kept):
+    """Checks the four outputs of a top-n call, allocates the missing ones and fills a's output fields; returns (tok, lp, ent)."""
+    _chk_rows_n_out(what, rows, n, ("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32))
+    _chk_rows_out(what, rows, ("out_entropy", out_entropy, torch.float32), ("out_kept", out_kept, torch.int32))
+    _chk_dev(logits, out_tok, out_logprob, out_entropy, out_kept)
+    tok = torch.empty(rows, n, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
+    lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if out_logprob is None else out_logprob
+    ent = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_entropy is None else out_entropy
+    a.n = n
+    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
+    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
+    a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    return tok, lp, ent
+
+
 def token_topn(logits, lo, hi, n, temperature=1.0, top_k=0, top_p=1.0, out_tok=None, out_logprob=None, out_entropy=None, out_kept=None):
     """The n (1..64) most probable tokens of every row under the distribution token_sample draws from with the same parameters over
     columns [lo, hi), their log-probabilities and the entropy of that distribution (cover_token_topn). Returns (tokens int64 [rows, n],
@@ -724,28 +776,12 @@ def token_topn(logits, lo, hi, n, temperature=1.0, top_k=0, top_p=1.0, out_tok=N
     if not temperature > 0 or not top_p > 0 or top_k < 0 or hi <= lo or lo < 0:
         raise L.CoverError(f"token_topn: temperature > 0, top_p > 0, top_k >= 0 and 0 <= lo < hi are required "
                            f"(got temperature={temperature}, top_k={top_k}, top_p={top_p}, lo={lo}, hi={hi})")
-    if not 1 <= int(n) <= 64:
-        raise L.CoverError(f"token_topn: 1 <= n <= 64 is required (got n={n})")
-    n = int(n)
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
-        raise L.CoverError("token_topn: logits must be fp32 [rows, >= hi] with unit column stride")
-    rows = logits.shape[0]
-    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, n) or (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n)):
-            raise L.CoverError(f"token_topn: {name} must be {dt} [rows, n] with unit column stride and a row stride >= n")
-    for name, t, dt in (("out_entropy", out_entropy, torch.float32), ("out_kept", out_kept, torch.int32)):
-        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
-            raise L.CoverError(f"token_topn: {name} must be contiguous {dt} [rows]")
-    _chk_dev(logits, out_tok, out_logprob, out_entropy, out_kept)
-    tok = torch.empty(rows, n, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
-    lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if out_logprob is None else out_logprob
-    ent = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_entropy is None else out_entropy
+    n = _chk_topn_n("token_topn", n)
+    rows = _chk_logits("token_topn", logits, hi)
     a = L.TokenTopnArgs()
-    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
-    a.temperature, a.top_k, a.top_p, a.n = temperature, int(top_k), top_p, n
-    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
-    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
-    a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    tok, lp, ent = _topn_outputs(a, "token_topn", logits, rows, n, out_tok, out_logprob, out_entropy, out_kept)
+    _fill_rows(a, logits, rows, lo, hi)
+    a.temperature, a.top_k, a.top_p = temperature, int(top_k), top_p
     L.check(L.lib().cover_token_topn(C.byref(a), _stream()), "token_topn")
     return tok, lp, ent
 
@@ -905,18 +941,13 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
         raise L.CoverError("token_sample_rows: ref_temperature and out_ref_logprob are given together")
     if ref_temperature is not None:
         ref_temperature = ref_temperature_value("token_sample_rows: ref_temperature", ref_temperature)
-    if hi <= lo or lo < 0:
-        raise L.CoverError(f"token_sample_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
-        raise L.CoverError("token_sample_rows: logits must be fp32 [rows, >= hi] with unit column stride")
-    rows = logits.shape[0]
+    _chk_range("token_sample_rows", lo, hi)
+    rows = _chk_logits("token_sample_rows", logits, hi)
     params = _row_params("token_sample_rows", rows, temperature, top_k, top_p)
     if uniform.dtype != torch.float32 or uniform.numel() != rows or not uniform.is_contiguous():
         raise L.CoverError("token_sample_rows: uniform must be contiguous fp32 [rows]")
-    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logit", out_logit, torch.float32), ("out_kept", out_kept, torch.int32),
-                        ("out_logprob", out_logprob, torch.float32)):
-        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
-            raise L.CoverError(f"token_sample_rows: {name} must be contiguous {dt} [rows]")
+    _chk_rows_out("token_sample_rows", rows, ("out_tok", out_tok, torch.int64), ("out_logit", out_logit, torch.float32),
+                  ("out_kept", out_kept, torch.int32), ("out_logprob", out_logprob, torch.float32))
     if out_ref_logprob is not None and (not isinstance(out_ref_logprob, torch.Tensor) or out_ref_logprob.dtype != torch.float32
                                         or out_ref_logprob.dim() != 1 or out_ref_logprob.numel() != rows or not out_ref_logprob.is_contiguous()):
         raise L.CoverError("token_sample_rows: out_ref_logprob must be contiguous torch.float32 [rows]")
@@ -926,7 +957,7 @@ def token_sample_rows(logits, lo, hi, uniform, temperature, top_k=None, top_p=No
     lg = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_logit is None else out_logit
     kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if out_kept is None else out_kept
     a = L.TokenSampleRowsArgs()
-    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    _fill_rows(a, logits, rows, lo, hi)
     a.uniform, a.temperature, a.top_k, a.top_p = uniform.data_ptr(), T.data_ptr(), _ptr(k), _ptr(p)
     a.token_out, a.logit_out, a.kept_out, a.logprob_out = tok.data_ptr(), lg.data_ptr(), kept.data_ptr(), _ptr(out_logprob)
     if out_ref_logprob is not None:
@@ -948,22 +979,17 @@ def token_logprob_rows(logits, lo, hi, tokens, temperature, top_k=None, top_p=No
     token_sample_rows). A greedy row (temperature 0) is scored at temperature 1, unfiltered; a row with invalid device-side parameters
     gives NaN and kept 0. On token_sample_rows' own picks it equals that call's out_logprob bit for bit. allow = TokenAllow:
     cover_token_logprob_rows_allowed, scored under the row restricted to its set; a token that is not allowed gets -inf."""
-    if hi <= lo or lo < 0:
-        raise L.CoverError(f"token_logprob_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
-        raise L.CoverError("token_logprob_rows: logits must be fp32 [rows, >= hi] with unit column stride")
-    rows = logits.shape[0]
+    _chk_range("token_logprob_rows", lo, hi)
+    rows = _chk_logits("token_logprob_rows", logits, hi)
     params = _row_params("token_logprob_rows", rows, temperature, top_k, top_p)
     if tokens.dtype != torch.int64 or tokens.numel() != rows or not tokens.is_contiguous():
         raise L.CoverError("token_logprob_rows: tokens must be contiguous int64 [rows]")
-    for name, t, dt in (("out", out, torch.float32), ("out_kept", out_kept, torch.int32)):
-        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
-            raise L.CoverError(f"token_logprob_rows: {name} must be contiguous {dt} [rows]")
+    _chk_rows_out("token_logprob_rows", rows, ("out", out, torch.float32), ("out_kept", out_kept, torch.int32))
     _chk_dev(logits, tokens, out, out_kept)
     T, k, p = _upload_row_params(params, logits.device)
     lp = torch.empty(rows, dtype=torch.float32, device=logits.device) if out is None else out
     a = L.TokenLogprobRowsArgs()
-    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
+    _fill_rows(a, logits, rows, lo, hi)
     a.temperature, a.top_k, a.top_p = T.data_ptr(), _ptr(k), _ptr(p)
     a.token, a.logprob_out, a.kept_out = tokens.data_ptr(), lp.data_ptr(), _ptr(out_kept)
     if allow is not None:
@@ -980,32 +1006,15 @@ def token_topn_rows(logits, lo, hi, n, temperature, top_k=None, top_p=None, out_
     A greedy row (temperature 0) is ranked at temperature 1, unfiltered; a row with invalid device-side parameters gives -1 / -inf in
     every slot, entropy NaN and kept 0. Returns (tokens int64 [rows, n], logprobs fp32 [rows, n], entropy fp32 [rows]). allow = TokenAllow:
     cover_token_topn_rows_allowed, only the allowed columns of each row's set are ranked and the entropy is that of the restricted kept set."""
-    if hi <= lo or lo < 0:
-        raise L.CoverError(f"token_topn_rows: 0 <= lo < hi is required (got lo={lo}, hi={hi})")
-    if not 1 <= int(n) <= 64:
-        raise L.CoverError(f"token_topn_rows: 1 <= n <= 64 is required (got n={n})")
-    n = int(n)
-    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or hi > logits.shape[1]:
-        raise L.CoverError("token_topn_rows: logits must be fp32 [rows, >= hi] with unit column stride")
-    rows = logits.shape[0]
+    _chk_range("token_topn_rows", lo, hi)
+    n = _chk_topn_n("token_topn_rows", n)
+    rows = _chk_logits("token_topn_rows", logits, hi)
     params = _row_params("token_topn_rows", rows, temperature, top_k, top_p)
-    for name, t, dt in (("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, n) or (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < n)):
-            raise L.CoverError(f"token_topn_rows: {name} must be {dt} [rows, n] with unit column stride and a row stride >= n")
-    for name, t, dt in (("out_entropy", out_entropy, torch.float32), ("out_kept", out_kept, torch.int32)):
-        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
-            raise L.CoverError(f"token_topn_rows: {name} must be contiguous {dt} [rows]")
-    _chk_dev(logits, out_tok, out_logprob, out_entropy, out_kept)
-    T, k, p = _upload_row_params(params, logits.device)
-    tok = torch.empty(rows, n, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
-    lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if out_logprob is None else out_logprob
-    ent = torch.empty(rows, dtype=torch.float32, device=logits.device) if out_entropy is None else out_entropy
     a = L.TokenTopnRowsArgs()
-    a.logits, a.ld, a.rows, a.lo, a.hi = logits.data_ptr(), logits.stride(0), rows, lo, hi
-    a.temperature, a.top_k, a.top_p, a.n = T.data_ptr(), _ptr(k), _ptr(p), n
-    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
-    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
-    a.entropy_out, a.kept_out = ent.data_ptr(), _ptr(out_kept)
+    tok, lp, ent = _topn_outputs(a, "token_topn_rows", logits, rows, n, out_tok, out_logprob, out_entropy, out_kept)
+    T, k, p = _upload_row_params(params, logits.device)
+    _fill_rows(a, logits, rows, lo, hi)
+    a.temperature, a.top_k, a.top_p = T.data_ptr(), _ptr(k), _ptr(p)
     if allow is not None:
         al = _allow_arg("token_topn_rows", allow, rows, hi, logits)
         L.check(L.lib().cover_token_topn_rows_allowed(C.byref(a), C.byref(al), _stream()), "token_topn_rows_allowed")

@@ -224,6 +224,20 @@ def test_constructed_rows(dev):
         for t, fin in ((33, False), (lo, False), (hi, False), (0, False), (64, True)):
             s = ops.token_logprob_rows(xd, lo, hi, torch.full((8,), t, dtype=torch.int64, device=DEV), Td, None, None, allow=al)
             assert bool(torch.isfinite(s).all()) if fin else bool(torch.isneginf(s).all()), (lo, t)
+    # rows without a maximum (the kernels' stated fallbacks): allowed columns all NaN -> the first allowed column, greedy and sampled
+    # alike; an unmasked greedy row of NaNs -> column lo
+    ld, lo, hi = 300, 5, 261
+    x = torch.randn(3, ld, generator=g)
+    cols = [lo + 7, lo + 40, hi - 1]
+    on = np.zeros((3, ld), dtype=bool)
+    on[:, cols] = True
+    x[:, cols] = float("nan")
+    x[2, lo:hi] = float("nan")
+    xd, ud, Td = _dev(x, torch.full((3,), 0.37), torch.tensor([0.0, 0.8, 0.0]))
+    tok, lg, kept, lp = _rows(xd, lo, hi, ud, Td, None, None, allow=_allow(on, np.arange(3)))
+    assert tok.tolist() == [lo + 7] * 3 and torch.isnan(lg).all() and kept[[0, 2]].tolist() == [3, 3]
+    tok, lg, kept, lp = _rows(xd[2:3], lo, hi, ud[2:3], Td[2:3], None, None)
+    assert tok.tolist() == [lo] and torch.isnan(lg).all() and kept.tolist() == [hi - lo]
     torch.cuda.synchronize()
 
 

@@ -209,6 +209,26 @@ def test_invalid_rows_and_rows_without_mass(dev):
         torch.cuda.synchronize()
         assert torch.isnan(got[4][bad_rows]).all() and (got[0][bad_rows] == -1).all()
         assert all(same(a[ok_rows], b[ok_rows]) for a, b in zip(got, ref_good)), t_ref
+    # rows without a maximum through both _ref kernels: allowed columns all NaN -> the first allowed column (row 0 sampled, row 3 greedy:
+    # set 0; row 5 greedy: set 1, columns 0, 3, 6, ...); unmasked, the greedy row 5 of NaNs -> column lo. The reference score is the scorer's.
+    x3 = x.clone()
+    x3[0, lo + 50:lo + 90] = nan
+    x3[3, lo + 50:lo + 90] = nan
+    x3[5, lo:hi] = nan
+    x3d = _dev(x3)[0]
+    Tg = good[0].clone()
+    Tg[3] = 0.0
+    par = _dev(Tg, good[1], good[2])
+    al = ops.TokenAllow(words, sor_good)
+    for t_ref in T_REFS:
+        got = _ref(x3d, lo, hi, ud, *par, t_ref, allow=al)
+        assert [int(got[0][r]) for r in (0, 3, 5)] == [lo + 50, lo + 50, 6] and torch.isnan(got[1][[0, 3, 5]]).all()
+        assert same(got[4], _score(x3d, lo, hi, got[0], t_ref, allow=al))
+        assert all(same(a, b) for a, b in zip(got[:4], _plain(x3d, lo, hi, ud, *par, allow=al)))
+        got = _ref(x3d, lo, hi, ud, *par, t_ref)
+        assert int(got[0][5]) == lo and bool(torch.isnan(got[1][5])) and int(got[2][5]) == hi - lo
+        assert same(got[4], _score(x3d, lo, hi, got[0], t_ref))
+        assert all(same(a, b) for a, b in zip(got[:4], _plain(x3d, lo, hi, ud, *par)))
     torch.cuda.synchronize()
 
 
