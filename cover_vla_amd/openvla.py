@@ -16,7 +16,7 @@ Work that is provably identical across candidates is done once:
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import os
 
@@ -25,11 +25,18 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .host import TopLogprobs
 from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower, _f32
+from .sampling import PickPlan, StepOutputs
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+# What the decode loop of one decision reads and writes, the decision's own tensors (eager) or a shape's static buffers (graph):
+# prompt_of_cand / cand_len / last_row int32 [N], pos_all int32 [n_gen, N], u step-major uniforms fp32 [n_gen, N] or None, prompt_slots /
+# prompt_lens int32 [P], outs the StepOutputs, fed int64 [n_gen, N] the tokens fed back (outs.tokens, or the forced ones)
+_DecodeState = NamedTuple("_DecodeState", [(f, object) for f in ("prompt_of_cand", "cand_len", "last_row", "pos_all", "u", "prompt_slots",
+                                                                  "prompt_lens", "outs", "fed")])
 
 
 class OpenVLA:
@@ -202,49 +209,23 @@ class OpenVLA:
                prior_temperature: Optional[float] = None):
         """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
         n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
-        uniforms fp32 [N, n_gen] in [0,1) for inverse-CDF sampling over the 256 action tokens, None = greedy over the
-        tokenizer vocabulary; top_k / top_p filter the sampled distribution after the temperature, in the order and with the
-        meaning of Hugging Face's `generate(do_sample=True, top_k, top_p)` (ops.token_sample; 0 / 1.0 = off, the unfiltered
-        ops.token_select path; greedy ignores them). force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
+        uniforms fp32 [N, n_gen], temperature / top_k / top_p (scalars or length-N sequences / tensors), return_logprobs, top_logprobs and
+        prior_temperature: the sampling arguments cover_vla_amd.sampling documents (S = n_gen steps). Their range here: a sampled or
+        per-candidate call picks over the 256 action tokens [action_lo, action_hi); an all-greedy call (uniforms=None) takes its arg-max
+        over the tokenizer vocabulary and is scored over it, whereas a temperature-0 candidate of a per-candidate call takes the arg-max
+        over the action bins, the range of its ops.token_sample_rows launch. Scalar top_k <= 0 and top_p >= 1 is the unfiltered ops.token_select path.
+        force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
         returning this path's own picks. on_prefill_enqueued: optional callable invoked once the prefill launches are
         queued -- the point where a caller should queue independent side-stream work (the verifier towers): the
-        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not. Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen]).
-        return_logprobs: a third tensor fp32 [N, n_gen], the log-probability of each pick under the distribution it was drawn from
-        (sampled: temperature, top_k, top_p over the action bins, cover_token_sample_scored / cover_token_logprob; greedy: temperature 1,
-        no filters, over the tokenizer vocabulary the arg-max runs over). With force_tokens it is still this path's own picks that are
-        scored. The default launches exactly what it launched without the argument.
-        top_logprobs = n in 1..64: appends host.TopLogprobs(tokens int64 [N, n_gen, n], logprobs fp32 [N, n_gen, n], entropy fp32
-        [N, n_gen]) to the return: per step the n most probable tokens of the distribution return_logprobs documents (descending logit,
-        equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities (cover_token_logprob's, bit for
-        bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used. 0: today's launches.
-        Parameters per candidate: temperature, top_k and top_p each accept a scalar or a length-N sequence / tensor (host.sampling_ladder
-        builds them). All scalars is the path above, untouched. As soon as one of the three is per candidate, all three are validated on
-        the host (temperature >= 0, top_k >= 0, top_p > 0, all finite, else CoverError; a device tensor of any numeric dtype is read back
-        once for it, so no pick is ever the -1 of an invalid row), broadcast to fp32 / int32 / fp32 [N] device tensors and every step's pick is ONE ops.token_sample_rows launch (ops.pick_token(row_params=)); uniforms is then
-        required, return_logprobs is that launch's log-probability and top_logprobs is ops.token_topn_rows. In this mode EVERY row picks
-        over the action bins [action_lo, action_hi), the launch's range: a candidate with temperature 0 is greedy and takes the arg-max
-        over the 256 action bins (its log-probability: temperature 1, unfiltered, over those bins), whereas an all-greedy call
-        (uniforms=None) keeps its arg-max over the tokenizer vocabulary. The decode graph is keyed on the fact "per-row parameters", not
-        on their values: the three tensors are static buffers filled before each replay, so a new ladder is not a new capture.
-        prior_temperature = T_ref (> 0, finite): the return gains a fp32 [N, n_gen] tensor (after the return_logprobs tensor if that is
-        present, before TopLogprobs): the log-probability of each pick under ONE reference distribution for every candidate -- temperature
-        T_ref, unfiltered, over the action bins -- written by the pick's own launch (cover_token_sample_rows_ref; ops.token_logprob_rows at
-        (T_ref, 0, 1) on the pick, bit for bit). It is the prior that compares across the rungs of a ladder: return_logprobs scores every
-        candidate under its own rung. Scalar parameters are broadcast and the per-row path is taken (the only one that carries the
-        reference); uniforms is required: a greedy candidate is a row with temperature 0. The decode graph's key carries the value of
-        T_ref, which travels by value in the launch. None launches exactly what it launched before."""
+        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not.
+        Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen][, logprobs][, prior][, TopLogprobs]).
+        The decode graph is keyed on PickPlan.graph_key: on the fact "per-row parameters", not on their values (the three tensors are
+        static buffers filled before each replay, so a new ladder is not a new capture), and on the value of prior_temperature."""
         c, dev = self.c, self.dev
-        n_top = int(top_logprobs)
-        if not 0 <= n_top <= 64:
-            raise ValueError("top_logprobs must be in 0..64")
-        t_ref = None
-        if prior_temperature is not None:
-            t_ref = ops.ref_temperature_value("sample: prior_temperature", prior_temperature)
-            if uniforms is None:
-                raise ValueError("prior_temperature needs uniforms: the reference score comes from the per-row sampler, in which a greedy "
-                                 "candidate is a row with temperature=0 (pass uniforms and temperature=0 rows instead of uniforms=None)")
         P, Lt = prompt_tokens.shape
         N = P * n_samples
+        plan = PickPlan.resolve("sample", "candidate", N, dev, has_uniforms=uniforms is not None, params=(temperature, top_k, top_p),
+                                top_logprobs=top_logprobs, prior_temperature=prior_temperature, filter_always=False)
 
         def mark(name):   # optional phase timing (tools/phases.py): trace["events"] collects (name, event) pairs
             if trace is not None and "events" in trace:
@@ -282,39 +263,26 @@ class OpenVLA:
         last_row = (Tp + prompt_of_cand * Lt + cand_len - 1).to(torch.int32)
         pos_all = ((T0 + cand_len)[None, :] + torch.arange(self.n_gen, dtype=torch.int32, device=dev)[:, None]).contiguous()
         u_t = None if uniforms is None else uniforms.to(torch.float32).t().contiguous()
-        rp = None
-        if t_ref is not None or any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
-            if uniforms is None:
-                raise ValueError("per-candidate temperature / top_k / top_p need uniforms (a greedy candidate is a temperature of 0)")
-            rp = ops.row_param_tensors(N, temperature, top_k, top_p, dev)
-            temperature, filt = None, None
-        else:
-            filt = None if uniforms is None or (top_k <= 0 and top_p >= 1.0) else (int(top_k), float(top_p))
+        new_outs = lambda: StepOutputs.alloc(self.n_gen, N, dev, logit=True, logprob=return_logprobs, ref=plan.t_ref is not None, n_top=plan.n_top, fill=None)
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
-            # static buffers per batch shape; the per-decision values (prompt lengths -> rows / positions, uniforms) are copied in
-            # per-row parameters: the key carries the fact, the values live in static buffers (st["rp"]) like the uniforms
-            key = (P, n_samples, Lt, uniforms is None, "rows" if rp is not None else float(temperature), self.slice_action_head, filt) + ((True,) if return_logprobs else ()) + ((("top", n_top),) if n_top else ()) + ((("prior", t_ref),) if t_ref is not None else ())
+            # static buffers per batch shape and mode; the per-decision values (prompt lengths -> rows / positions, uniforms, per-row parameters) are copied in
+            key = (P, n_samples, Lt) + plan.graph_key(return_logprobs)
             st = self._dec.get(key)
             if st is None:
-                st = dict(graph=None, prompt_of_cand=prompt_of_cand.clone(), cand_len=torch.empty_like(cand_len), last_row=torch.empty_like(last_row),
-                          pos_all=torch.empty_like(pos_all), tokens=torch.empty(self.n_gen, N, dtype=torch.int64, device=dev),
-                          sel=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev),
-                          u=None if u_t is None else torch.empty_like(u_t),
-                          lps=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None,
-                          prior=torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if t_ref is not None else None,
-                          top=self._top_bufs(N, n_top), rp=None if rp is None else tuple(torch.empty_like(t) for t in rp),
-                          prompt_slots=torch.arange(P, dtype=torch.int32, device=dev), prompt_lens=torch.empty(P, dtype=torch.int32, device=dev))
+                outs = new_outs()
+                st = dict(graph=None, plan=plan._replace(rp=None if plan.rp is None else tuple(torch.empty_like(t) for t in plan.rp)),
+                          state=_DecodeState(prompt_of_cand.clone(), torch.empty_like(cand_len), torch.empty_like(last_row), torch.empty_like(pos_all),
+                                             None if u_t is None else torch.empty_like(u_t), torch.arange(P, dtype=torch.int32, device=dev),
+                                             torch.empty(P, dtype=torch.int32, device=dev), outs, outs.tokens))
                 self._dec[key] = st
-            st["cand_len"].copy_(cand_len); st["last_row"].copy_(last_row); st["pos_all"].copy_(pos_all)
-            st["prompt_lens"].copy_(prompt_lens.to(torch.int32))
+            s = st["state"]
+            s.cand_len.copy_(cand_len); s.last_row.copy_(last_row); s.pos_all.copy_(pos_all)
+            s.prompt_lens.copy_(prompt_lens.to(torch.int32))
             if u_t is not None:
-                st["u"].copy_(u_t)
-            if rp is not None:
-                for dst, src in zip(st["rp"], rp):
-                    dst.copy_(src)
-            body = lambda: self._decode_body(x, N, n_samples, Lt, st["prompt_of_cand"], st["cand_len"], st["last_row"], st["pos_all"], st["u"], temperature,
-                                             st["tokens"], st["sel"], st["tokens"], None, st["prompt_slots"], st["prompt_lens"], filt=filt, lps=st["lps"], top=st["top"], rp=st["rp"],
-                                             prior=None if t_ref is None else (t_ref, st["prior"]))
+                s.u.copy_(u_t)
+            for dst, src in zip(st["plan"].rp or (), plan.rp or ()):
+                dst.copy_(src)
+            body = lambda: self._decode_body(x, st["plan"], s)
             if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
                 st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
             if st["graph"] is None:
@@ -332,100 +300,54 @@ class OpenVLA:
             else:
                 st["graph"].launch()
             # the eager pass before a capture has filled the same buffers
-            return self._sample_result(st["tokens"], st["sel"], st["lps"], st["top"], st["prior"])
-        # step-major buffers: row i of each is contiguous, so the kernels of step i read / write them in place (no per-step slice copies)
-        tokens = torch.empty(self.n_gen, N, dtype=torch.int64, device=dev)
-        sel = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev)
-        lps = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if return_logprobs else None
-        top = self._top_bufs(N, n_top)
-        prior = torch.empty(self.n_gen, N, dtype=torch.float32, device=dev) if t_ref is not None else None
-        fed = tokens if force_tokens is None else force_tokens.t().contiguous()
-        self._decode_body(x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, u_t, temperature, tokens, sel, fed, trace,
-                          torch.arange(P, dtype=torch.int32, device=dev), prompt_lens.to(torch.int32).contiguous(), mark, filt=filt, lps=lps, top=top, rp=rp,
-                          prior=None if t_ref is None else (t_ref, prior))
-        return self._sample_result(tokens, sel, lps, top, prior)
+            return s.outs.result()
+        outs = new_outs()
+        state = _DecodeState(prompt_of_cand, cand_len, last_row, pos_all, u_t, torch.arange(P, dtype=torch.int32, device=dev),
+                             prompt_lens.to(torch.int32).contiguous(), outs, outs.tokens if force_tokens is None else force_tokens.t().contiguous())
+        self._decode_body(x, plan, state, trace, mark)
+        return outs.result()
 
-    def _top_bufs(self, N, n_top):
-        """Step-major buffers of sample(top_logprobs=n): (tokens [n_gen, N, n], logprobs [n_gen, N, n], entropy [n_gen, N]), None for n = 0."""
-        if not n_top:
-            return None
-        return (torch.empty(self.n_gen, N, n_top, dtype=torch.int64, device=self.dev),
-                torch.empty(self.n_gen, N, n_top, dtype=torch.float32, device=self.dev),
-                torch.empty(self.n_gen, N, dtype=torch.float32, device=self.dev))
-
-    @staticmethod
-    def _sample_result(tokens, sel, lps, top, prior=None):
-        """Candidate-major copies of the step-major buffers: what sample returns."""
-        out = (tokens.t().contiguous(), sel.t().contiguous())
-        if lps is not None:
-            out += (lps.t().contiguous(),)
-        if prior is not None:
-            out += (prior.t().contiguous(),)
-        if top is not None:
-            out += (TopLogprobs(top[0].transpose(0, 1).contiguous(), top[1].transpose(0, 1).contiguous(), top[2].t().contiguous()),)
-        return out
-
-    def _decode_body(self, x, N, n_samples, Lt, prompt_of_cand, cand_len, last_row, pos_all, uniforms, temperature, tokens, sel, fed, trace,
-                     prompt_slots, prompt_lens_i32, mark=lambda name: None, filt=None, lps=None, top=None, rp=None, prior=None):
+    def _decode_body(self, x, plan, s, trace=None, mark=lambda name: None):
         """Head on the last prompt rows, then n_gen - 1 decode passes + heads. Launches only (no allocation, no host read): recordable."""
         D, T0 = self.c["llm_dim"], self.T0
-        ops.copy_rows(x, self.h_sel, N, D, last_row, None)
-        self._head_select(self.h_sel[:N], uniforms, 0, temperature, tokens, sel, trace, filt, lps, top, rp, prior)
+        N, P = s.cand_len.shape[0], s.prompt_slots.shape[0]
+        Lt = (x.shape[0] - (T0 - 1)) // P             # x: the patch rows, then P x Lt text rows
+        ops.copy_rows(x, self.h_sel, N, D, s.last_row, None)
+        self._head_pick(self.h_sel[:N], 0, plan, s, trace)
         xd = self.x_dec[:N]
         own = {}
         if self.own_kv is not None:   # regular structure of the batch: the n_samples candidates of prompt p are rows [p S, (p + 1) S)
-            own = dict(own_kv=self.own_kv, seg1_group=n_samples, seg1_slot_of_group=prompt_slots, seg1_len_of_group=prompt_lens_i32)
+            own = dict(own_kv=self.own_kv, seg1_group=N // P, seg1_slot_of_group=s.prompt_slots, seg1_len_of_group=s.prompt_lens)
         for i in range(1, self.n_gen):
-            ops.embed_gather(self.embed, fed[i - 1], out=xd)
-            g = self.llm.group(N, 1, pos_all[i - 1],
+            ops.embed_gather(self.embed, s.fed[i - 1], out=xd)
+            g = self.llm.group(N, 1, s.pos_all[i - 1],
                                [dict(region=0, length=T0, slot_of_batch=self.zero_slots),
-                                dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
+                                dict(region=1, length=Lt, len_of_batch=s.cand_len, slot_of_batch=s.prompt_of_cand),
                                 dict(region=2, length=i)], 2, write_t_off=i - 1, seg0_shared=True, **own)
             self.llm.forward(xd, [g], final_norm=False)
-            self._head_select(xd, uniforms, i, temperature, tokens, sel, trace, filt, lps, top, rp, prior)
+            self._head_pick(xd, i, plan, s, trace)
             mark(f"decode{i}")
 
-    def _head_select(self, h, uniforms, i, temperature, tokens, sel, trace, filt=None, lps=None, top=None, rp=None, prior=None):
-        """Norm, head GEMM, one ops.pick_token. filt: None = the unfiltered ops.token_select pick; (top_k, top_p) = ops.token_sample over
-        the same columns. lps fp32 [n_gen, N] or None: row i receives the log-probability of step i's picks.
-        top (tokens, logprobs, entropy) or None: slab i receives ops.token_topn of the distribution the pick came from.
-        rp (temperature, top_k, top_p) device tensors [N] or None: the pick is ops.token_sample_rows, the top-n ops.token_topn_rows.
-        prior (T_ref, fp32 [n_gen, N]) or None (rp is then set): row i receives the picks' log-probability at temperature T_ref, unfiltered."""
-        N = h.shape[0]
-        u = None if uniforms is None else uniforms[i]
+    def _head_pick(self, h, i, plan, s, trace):
+        """Norm, head GEMM and step i's plan.pick into row i of the state's output buffers (the top-n slab i with it)."""
+        N, o = h.shape[0], s.outs
+        u = None if s.u is None else s.u[i]
         # out_kept: written by the filtered pick (ops.token_sample) only
-        out = dict(out_logit=sel[i], out_kept=self.kept_sel[:N], out_logprob=None if lps is None else lps[i])
-        if rp is not None:
-            out["row_params"] = rp
-        if prior is not None:
-            out["ref"] = (prior[0], prior[1][i])
+        out = dict(out_logit=o.sel[i], out_kept=self.kept_sel[:N], out_logprob=None if o.lps is None else o.lps[i],
+                   out_ref=None if o.prior is None else o.prior[i], top=o.top_at(i))
         hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
-        if uniforms is not None and (trace is None or "events" in trace) and self.slice_action_head:
+        if not plan.greedy and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
-            t, _, _ = ops.pick_token(lg, 0, self.c["n_bins"], u, temperature, filt, **out)
-            torch.add(t, self.action_lo, out=tokens[i])
-            if top is not None:
-                self._head_topn(lg, 0, self.c["n_bins"], uniforms is None, temperature, filt, top, i, rp)
-                top[0][i].add_((top[0][i] >= 0) * self.action_lo)          # ids as the tokens are; the -1 padding stays
+            t, _, _ = plan.pick(lg, 0, self.c["n_bins"], u, **out)
+            torch.add(t, self.action_lo, out=o.tokens[i])
+            if o.top is not None:
+                o.top[0][i].add_((o.top[0][i] >= 0) * self.action_lo)      # ids as the tokens are; the -1 padding stays
             return
         lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
         if trace is not None and "events" not in trace:
             trace.setdefault("logits", []).append(lg.clone())
-        lo, hi = (0, self.c["tok_vocab"]) if uniforms is None else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
-        ops.pick_token(lg, lo, hi, u, temperature, filt, out_tok=tokens[i], **out)
-        if top is not None:
-            self._head_topn(lg, lo, hi, uniforms is None, temperature, filt, top, i, rp)
-
-    @staticmethod
-    def _head_topn(lg, lo, hi, greedy, temperature, filt, top, i, rp=None):
-        """One ops.token_topn launch on step i's logits; greedy: temperature 1, unfiltered (what return_logprobs scores a greedy pick under).
-        rp: ops.token_topn_rows with the parameters of every row its own."""
-        if rp is not None:
-            ops.token_topn_rows(lg, lo, hi, top[0].shape[2], rp[0], rp[1], rp[2], out_tok=top[0][i], out_logprob=top[1][i], out_entropy=top[2][i])
-            return
-        k, p = (0, 1.0) if greedy or filt is None else filt
-        ops.token_topn(lg, lo, hi, top[0].shape[2], 1.0 if greedy else temperature, k, p, out_tok=top[0][i], out_logprob=top[1][i],
-                       out_entropy=top[2][i])
+        lo, hi = (0, self.c["tok_vocab"]) if plan.greedy else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
+        plan.pick(lg, lo, hi, u, out_tok=o.tokens[i], **out)
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

@@ -6,6 +6,7 @@ libcover_hip.so. Nothing in this module computes on the CPU or through torch ker
 from __future__ import annotations
 
 import ctypes as C
+import gc
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
@@ -1346,11 +1347,21 @@ class Graph:
 
     def __enter__(self):
         self.stream = _stream()
-        L.check(L.lib().cover_graph_begin(self.stream), "graph_begin")
+        # no cyclic collection inside the capture: garbage that owns device memory (a torch.cuda.MemPool behind a reference cycle, as
+        # PooledGraph's in the verifier) frees it in its destructor, and a hipFree on the capturing thread aborts the process
+        self._gc = gc.isenabled()
+        gc.disable()
+        try:
+            L.check(L.lib().cover_graph_begin(self.stream), "graph_begin")
+        except BaseException:
+            self._gc and gc.enable()
+            raise
         return self
 
     def __exit__(self, et, ev, tb):
         rc = L.lib().cover_graph_end(self.stream, C.byref(self.handle))
+        if self._gc:
+            gc.enable()
         if et is None:
             L.check(rc, "graph_end")
         return False

@@ -33,6 +33,7 @@ from . import ops
 from .host import TopLogprobs
 from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower
+from .sampling import PickPlan, StepOutputs
 
 
 def prefix_groups(tokens, pad_mask) -> Tuple[np.ndarray, np.ndarray]:
@@ -101,30 +102,16 @@ class PI0FASTTokens:
         generation: positions come from the cumulative pad mask and padded keys are masked, so the side does not enter the
         arithmetic). Returns int64 [B, max_new_tokens] on the device: the greedy continuation, `pad_token_id` after a row's EOS
         (what `generate(do_sample=False)` returns after the prompt). force_tokens (tests): teacher-force the fed-back tokens.
-        uniforms fp32 [B, max_new_tokens] in [0, 1) on the device: sample instead (`generate(do_sample=True, temperature, top_k,
-        top_p)`: ops.token_sample over the vocabulary, column i drives step i); every row is decoded on its own, rows that share
-        frames and prompt diverge with their uniforms. None = greedy; temperature / top_k / top_p are then unused.
-        return_logprobs: returns (tokens, logprobs fp32 [B, max_new_tokens]): the log-probability of each step's own pick under the
-        distribution it came from (sampled: temperature, top_k, top_p over the vocabulary; greedy: temperature 1, unfiltered). Steps
-        at which a row emits `pad_token_id` because it has finished, and steps the early stop skips, carry 0.0: a row sum is the
-        sequence log-probability. The default launches exactly what it launched without the argument.
+        uniforms fp32 [B, max_new_tokens] on the device, temperature / top_k / top_p (scalars or length-B sequences / tensors), return_logprobs,
+        top_logprobs and prior_temperature: the sampling arguments cover_vla_amd.sampling documents (S = max_new_tokens steps, the range is the
+        vocabulary; a sampled scalar call is always ops.token_sample, a per-row one ops.token_sample_rows). Sampled and per-row calls decode every row
+        on its own (no greedy de-duplication): rows that share frames and prompt diverge with their uniforms. With return_logprobs / prior_temperature
+        the return is a tuple; steps at which a row emits `pad_token_id` because it has finished, and steps the early stop skips, carry
+        0.0 in both (a row sum is the sequence log-probability, host.sequence_logprob) and -1 / -inf / 0.0 in TopLogprobs.
         share_prefix: rows with equal (frames, prompt) share ONE prefilled prefix (greedy, sampled and forced alike): the prefill
         runs over the P distinct rows, every candidate row still decodes and picks on its own, reading its prompt's prefix K/V through
         the segment's slot_of_batch. Needs P <= max_prompts and B <= max_batch. GEMM row counts differ from the per-row path, so
         results agree with it to bf16 rounding (bit for bit when P == B). The default launches exactly what it launched before.
-        top_logprobs = n in 1..64: appends host.TopLogprobs(tokens int64 [B, max_new_tokens, n], logprobs fp32 [B, max_new_tokens, n],
-        entropy fp32 [B, max_new_tokens]) to the return: per step the n most probable tokens of the distribution return_logprobs
-        documents (descending logit, equal logits by ascending id; -1 / -inf where it keeps fewer than n), their log-probabilities
-        (cover_token_logprob's, bit for bit) and its entropy in nats -- one ops.token_topn launch per step on the logits the pick used.
-        Steps after a row's EOS, and steps the early stop skips, carry -1 / -inf / 0.0. 0: today's launches.
-        Parameters per row: temperature, top_k and top_p each accept a scalar or a length-B sequence / tensor. All scalars is the path
-        above, untouched. As soon as one of the three is per row, all three are validated on the host (temperature >= 0, top_k >= 0,
-        top_p > 0, all finite, else CoverError; a device tensor of any numeric dtype is read back once for it, so no pick is ever the -1
-        of an invalid row), broadcast to fp32 / int32 / fp32 [B] device tensors and every step's pick is
-        ONE ops.token_sample_rows launch over the vocabulary (ops.pick_token(row_params=)): uniforms is then required, a row with
-        temperature 0 is greedy (the arg-max, scored at temperature 1 unfiltered; its uniforms are not read), return_logprobs is that
-        launch's log-probability and top_logprobs is ops.token_topn_rows. Rows are decoded on their own, as in sampling (no greedy
-        de-duplication); share_prefix works as before.
         allowed_tokens = ops.TokenAllow (bits over the vocabulary's ids, optionally set_of_row int32 [B]): every row draws from its set
         only -- each step's pick is ONE cover_token_sample_rows_allowed launch (scalar parameters are broadcast through
         ops.row_param_tensors; uniforms None = temperature 0 for every row, and rows are decoded on their own: no greedy
@@ -133,14 +120,6 @@ class PI0FASTTokens:
         every set a row names holds an id below the vocabulary size, so no pick is the -1 of an invalid row. share_prefix,
         force_tokens, the EOS / pad bookkeeping (a finished row's pad is not a draw and need not be allowed) and the fused feedback are
         untouched. None launches exactly what it launched before.
-        prior_temperature = T_ref (> 0, finite): the return gains a fp32 [B, max_new_tokens] tensor (after the return_logprobs tensor if
-        that is present, before TopLogprobs): the log-probability of each step's own pick under ONE reference distribution for every
-        row -- temperature T_ref, unfiltered, over the vocabulary (over the row's allowed set with allowed_tokens) -- written by the
-        pick's own launch (cover_token_sample_rows_ref; ops.token_logprob_rows at (T_ref, 0, 1) on the pick, bit for bit). 0.0 on pads
-        after EOS and on skipped steps, so host.sequence_logprob applies. It is the prior that compares across the rungs of a ladder
-        (host.sampling_ladder): return_logprobs scores every row under its own rung. Scalar parameters are broadcast and the per-row
-        path is taken (the only one that carries the reference); uniforms is required: a greedy candidate is a row with temperature 0.
-        None launches exactly what it launched before.
         grammar = host.TokenGrammar(allow, fsm) (host.length_grammar builds one; exclusive with allowed_tokens, it carries its own sets):
         a token-class automaton per candidate row chooses the set every step's pick draws from. Each row starts in fsm.start_state, so
         the first pick reads that state's set; between two steps the row's automaton advances on the token it emitted (sampled, greedy
@@ -167,30 +146,15 @@ class PI0FASTTokens:
             state, set_of_row = g_fsm.rows(tokens.shape[0], dev)
             allowed_tokens = ops.TokenAllow(g_allow.bits, set_of_row)     # the picks read the tensor the feedback step rewrites
             fsm = (g_fsm, state, set_of_row)
-        if not 0 <= int(top_logprobs) <= 64:
-            raise ValueError("top_logprobs must be in 0..64")
-        if prior_temperature is not None:
-            prior_temperature = ops.ref_temperature_value("generate_tokens: prior_temperature", prior_temperature)
-            if uniforms is None:
-                raise ValueError("prior_temperature needs uniforms: the reference score comes from the per-row sampler, in which a greedy "
-                                 "candidate is a row with temperature=0 (pass uniforms and temperature=0 rows instead of uniforms=None)")
+        plan = PickPlan.resolve("generate_tokens", "row", tokens.shape[0], dev, has_uniforms=uniforms is not None, params=(temperature, top_k, top_p),
+                                top_logprobs=top_logprobs, prior_temperature=prior_temperature, allow=allowed_tokens, filter_always=True)
         u_t = None
         if uniforms is not None:
             if tuple(uniforms.shape) != (tokens.shape[0], max_new_tokens):
                 raise ValueError("uniforms must be [B, max_new_tokens]")
             u_t = uniforms.to(device=dev, dtype=torch.float32).t().contiguous()       # step-major: row i is step i's [B]
-        rp = None
-        if any(ops.is_per_row(v) for v in (temperature, top_k, top_p)):
-            if uniforms is None:
-                raise ValueError("per-row temperature / top_k / top_p need uniforms (a greedy row is a temperature of 0)")
-            rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
-        if prior_temperature is not None and rp is None:     # the reference score is the per-row call's: scalars are broadcast
-            rp = ops.row_param_tensors(tokens.shape[0], temperature, top_k, top_p, dev)
-        if allowed_tokens is not None:
-            if fsm is None:
-                self._check_allowed(allowed_tokens, tokens.shape[0])
-            if rp is None:     # the allowed pick is the per-row call: scalars are broadcast, no uniforms = every row greedy
-                rp = ops.row_param_tensors(tokens.shape[0], *((0.0, 0, 1.0) if uniforms is None else (temperature, top_k, top_p)), dev)
+        if allowed_tokens is not None and fsm is None:
+            self._check_allowed(allowed_tokens, tokens.shape[0])
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
         if (allowed_tokens is None and not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
@@ -205,8 +169,9 @@ class PI0FASTTokens:
                 if not isinstance(sub_out, tuple):
                     return sub_out[back]
                 return tuple(TopLogprobs(*(t[back] for t in o)) if isinstance(o, TopLogprobs) else o[back] for o in sub_out)
-        return self._generate(images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                              temperature, top_k, top_p, return_logprobs, share_prefix, int(top_logprobs), rp, allowed_tokens, prior_temperature, fsm)
+        res = self._generate((images, img_masks, tokens, pad_mask), max_new_tokens, (eos_token_id, pad_token_id), force_tokens, trace, u_t,
+                             plan, return_logprobs, share_prefix, fsm)
+        return res if len(res) > 1 else res[0]
 
     def _check_allowed(self, allow, B):
         """generate_tokens' host check of its allowed-token sets (one read-back of the bits and the row indices)."""
@@ -228,23 +193,22 @@ class PI0FASTTokens:
         if not np.all(words.any(axis=1)):
             raise ops.L.CoverError(f"allowed_tokens: a set that a row uses allows no id below the vocabulary size {vocab}")
 
-    def _generate(self, images, img_masks, tokens, pad_mask, max_new_tokens, eos_token_id, pad_token_id, force_tokens, trace, u_t,
-                  temperature, top_k, top_p, return_logprobs, share, n_top=0, rp=None, allow=None, t_ref=None, fsm=None):
-        """The one prefill + decode loop. Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
+    def _generate(self, inputs, max_new_tokens, stop_ids, force_tokens, trace, u_t, plan, return_logprobs, share, fsm=None):
+        """The one prefill + decode loop; returns StepOutputs.result(): (tokens[, logprobs][, prior][, TopLogprobs]).
+        inputs = (images, img_masks, tokens, pad_mask), stop_ids = (eos_token_id, pad_token_id), plan the call's sampling.PickPlan.
+        Region 0 of the cache holds P prefixes, region 1 every row's own tokens (slot b).
         share False: P = B, every row prefills its own prefix; between two steps the torch statements, one ops.embed_gather and, every
         `eos_check_every` steps, the `done.all()` read-back.
         share True: the P distinct prefixes (slots 0..P-1, in order of first occurrence) are prefilled once and every row reads its
         prompt's through segment 0's slot_of_batch; between two steps ONE ops.decode_feedback launch settles the token, the
         log-probability, the done flag, the live count and the next step's embedding row. COVER_FAST_FEEDBACK=0 (read per call) issues
         the torch statements of the other path instead.
-        rp (temperature, top_k, top_p) device tensors [B] or None: the parameters of every row its own (temperature, top_k, top_p unused).
-        allow ops.TokenAllow or None (rp is then set): the pick, the score and the ranks over each row's allowed ids only.
-        t_ref float or None (rp is then set): the pick's launch also scores it at temperature t_ref, unfiltered; that column is settled
-        like the log-probabilities (fused: decode_feedback's lp2) and returned after them.
-        fsm (ops.TokenFsm, state int32 [B], set_of_row int32 [B]) or None (allow.set_of_row is then that set_of_row): every step advances
-        each row's automaton on its emitted token and rewrites set_of_row for the next pick -- fused: in decode_feedback's launch,
-        otherwise TokenFsm.step_torch on device tensors."""
+        plan.t_ref: the reference score of each pick is settled like the log-probabilities (fused: decode_feedback's lp2).
+        fsm (ops.TokenFsm, state int32 [B], set_of_row int32 [B]) or None (plan.allow.set_of_row is then that set_of_row): every step
+        advances each row's automaton on its emitted token and rewrites set_of_row for the next pick -- fused: in decode_feedback's
+        launch, otherwise TokenFsm.step_torch on device tensors."""
         dev, c = self.dev, self.c
+        (images, img_masks, tokens, pad_mask), (eos_token_id, pad_token_id) = inputs, stop_ids
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
                 or max_new_tokens > self.max_new or len(images) > self.n_cams):
@@ -294,17 +258,12 @@ class PI0FASTTokens:
         # HF generate(do_sample=False) stops once every row has emitted EOS (modeling_pi0fast.py:861-946 runs it with
         # max_new_tokens = max_decoding_steps = 256, a FAST sequence is a few dozen tokens): every `eos_check_every` steps `done.all()`
         # (fused: live[i - 1]) is read back, and the rest of `out` is the pad the finished rows would have emitted anyway
-        out = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int64, device=dev)
+        outs = StepOutputs.alloc(max_new_tokens, B, dev, logit=False, logprob=return_logprobs, ref=plan.t_ref is not None, n_top=plan.n_top, fill=pad_token_id)
+        out, lps, rls = outs.tokens, outs.lps, outs.prior
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         live = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev) if fused else None   # live[i]: rows still running after step i
-        lps = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if return_logprobs else None
-        lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None
-        rls = torch.zeros(B, max_new_tokens, dtype=torch.float32, device=dev) if t_ref is not None else None
-        rl = torch.empty(B, dtype=torch.float32, device=dev) if t_ref is not None else None
-        # step-major [steps, B, n]: slab i is what step i's ops.token_topn writes; steps that never run keep the padding
-        top_tok = torch.full((max_new_tokens, B, n_top), -1, dtype=torch.int64, device=dev) if n_top else None
-        top_lp = torch.full((max_new_tokens, B, n_top), float("-inf"), dtype=torch.float32, device=dev) if n_top else None
-        top_ent = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev) if n_top else None
+        lp = torch.empty(B, dtype=torch.float32, device=dev) if return_logprobs else None      # each step's scores, settled by the feedback
+        rl = torch.empty(B, dtype=torch.float32, device=dev) if rls is not None else None
         force = force_tokens
         if share and force is not None:
             force = force.to(device=dev, dtype=torch.int64)                          # the per-row form moves one column per step
@@ -312,10 +271,8 @@ class PI0FASTTokens:
         head_ws = ops.gemm_workspace(B, self.lm_head.N, self.lm_head.K, dev)
         tsel = torch.empty(B, dtype=torch.int64, device=dev)
         xd = torch.empty(B, D, dtype=BF, device=dev)
-        u_none = torch.zeros(B, dtype=torch.float32, device=dev) if allow is not None and u_t is None else None   # greedy rows read no uniform
-        akw = {} if allow is None else dict(allow=allow)      # None: the calls made before the argument existed
-        rkw = {} if t_ref is None else dict(ref=(t_ref, rl))
-        fkw = {} if t_ref is None else dict(lp2=rl, lp2_out=rls)
+        u_none = torch.zeros(B, dtype=torch.float32, device=dev) if plan.rp is not None and u_t is None else None   # greedy rows read no uniform
+        fkw = {} if rls is None else dict(lp2=rl, lp2_out=rls)
         if fsm is not None:
             fkw.update(fsm=fsm[0], fsm_state=fsm[1], fsm_set_of_row=fsm[2])
 
@@ -324,18 +281,9 @@ class PI0FASTTokens:
             lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
             if trace is not None:
                 trace.setdefault("logits", []).append(lg[:, :c["vocab"]].clone())
-            # greedy over the vocabulary, or always ops.token_sample (also with top_k = 0, top_p = 1.0)
-            if rp is not None:     # one ops.token_sample_rows launch; ops.token_topn_rows ranks under each row's own distribution
-                t, _, kept = ops.pick_token(lg, 0, c["vocab"], u_none if u_t is None else u_t[i], out_tok=tsel, out_logprob=lp, row_params=rp, **akw, **rkw)
-                if n_top:
-                    ops.token_topn_rows(lg, 0, c["vocab"], n_top, rp[0], rp[1], rp[2], out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i], **akw)
-            else:
-                t, _, kept = ops.pick_token(lg, 0, c["vocab"], None if u_t is None else u_t[i], temperature, (top_k, top_p), out_tok=tsel,
-                                            out_logprob=lp)
-                if n_top:     # the distribution out_logprob scores the pick under (greedy: temperature 1, unfiltered)
-                    ops.token_topn(lg, 0, c["vocab"], n_top, 1.0 if u_t is None else temperature, 0 if u_t is None else top_k,
-                                   1.0 if u_t is None else top_p, out_tok=top_tok[i], out_logprob=top_lp[i], out_entropy=top_ent[i])
-            if (u_t is not None or allow is not None) and trace is not None:
+            t, _, kept = plan.pick(lg, 0, c["vocab"], u_none if u_t is None else u_t[i], out_tok=tsel, out_logprob=lp, out_ref=rl,
+                                   top=outs.top_at(i))
+            if (u_t is not None or plan.allow is not None) and trace is not None:
                 trace.setdefault("picks", []).append(t.clone())
                 trace.setdefault("kept", []).append(kept)
             if fused:      # the statements below and the next step's embed_gather, one launch
@@ -369,20 +317,11 @@ class PI0FASTTokens:
             g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
             self.lm.forward(xd, [g], final_norm=False)
             pick(xd, i)
-        if not return_logprobs and not n_top and rls is None:
-            return out
-        res = (out, lps) if return_logprobs else (out,)
-        if rls is not None:
-            res += (rls,)
-        if n_top:
-            # a row is finished at step i once an earlier step emitted EOS: its pad is not a choice (index bookkeeping on the emitted tokens)
-            eos = out == eos_token_id
-            fin = (eos.cumsum(dim=1) - eos.to(torch.int64)) > 0                      # [B, steps]
-            tt, tl, te = top_tok.transpose(0, 1), top_lp.transpose(0, 1), top_ent.t()
-            res += (TopLogprobs(torch.where(fin[:, :, None], torch.full_like(tt, -1), tt),
-                                torch.where(fin[:, :, None], torch.full_like(tl, float("-inf")), tl),
-                                torch.where(fin, torch.zeros_like(te), te)),)
-        return res
+        if outs.top is None:
+            return outs.result()
+        # a row is finished at step i once an earlier step emitted EOS: its pad is not a choice (index bookkeeping on the emitted tokens)
+        eos = out == eos_token_id
+        return outs.result(fin=(eos.cumsum(dim=1) - eos.to(torch.int64)) > 0)        # [B, steps]
 
 
 @dataclass
