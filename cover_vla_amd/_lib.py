@@ -184,6 +184,23 @@ class PriorSelectArgs(C.Structure):
                 ("ranked_out", c_p)]
 
 
+class BeamMergeArgs(C.Structure):
+    _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("feed_pad", c_ll),
+                ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p), ("cum_out", c_p),
+                ("step_lp_out", c_p)]
+
+
+class KvGatherSlotsArgs(C.Structure):
+    _fields_ = [("k_base", c_p), ("vt_base", c_p), ("k_offset", c_ll), ("vt_offset", c_ll), ("k_slot_stride", c_ll),
+                ("vt_slot_stride", c_ll), ("src_slot", c_p), ("dst_slot", c_p),
+                ("n_layers", c_i), ("rows", c_i), ("n_slots", c_i), ("cap", c_i), ("Hkv", c_i), ("D", c_i), ("n_t", c_i), ("_pad", c_i)]
+
+
+class BeamBacktrackArgs(C.Structure):
+    _fields_ = [("parent", c_p), ("token", c_p), ("step_lp", c_p), ("steps", c_i), ("rows", c_i), ("B", c_i), ("_pad", c_i),
+                ("tokens_out", c_p), ("logprobs_out", c_p)]
+
+
 class Workspace(C.Structure):
     _fields_ = [("ptr", c_p), ("bytes", C.c_size_t)]
 
@@ -237,7 +254,8 @@ _STRUCTS = {
     "cover_token_sample_rows_args": TokenSampleRowsArgs, "cover_token_logprob_rows_args": TokenLogprobRowsArgs,
     "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_token_fsm": TokenFsm,
-    "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
+    "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_beam_merge_args": BeamMergeArgs,
+    "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
 }
@@ -310,6 +328,9 @@ SYMBOLS = {
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),
+    "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
+    "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
+    "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),
     "cover_tokens_to_histories": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_f, c_p, c_p, c_p]),
     "cover_tokens_to_histories_steps": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
     "cover_actions_to_histories": (c_i, [c_p, c_ll, c_ll, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_p, c_p]),

@@ -402,6 +402,25 @@ int cover_prior_select(const cover_prior_select_args* a, void* stream) {
     return COVER_OK;
 }
 
+int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
+    HIPCHK(launch_beam_merge(a, ST(stream)),
+           "beam_merge (groups >= 0, 1 <= B <= 64, ld_tok >= B, ld_lp >= B, feed_pad >= 0, every pointer required, cum_out != cum)");
+    return COVER_OK;
+}
+int cover_kv_gather_slots(const cover_kv_gather_slots_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_kv_gather_slots: null args");
+    HIPCHK(launch_kv_gather_slots(a, ST(stream)),
+           "kv_gather_slots (tables and slot arrays required, 1 <= n_layers <= 65535, n_slots >= 1, cap and Hkv * D multiples of 8, "
+           "Hkv * D * cap < 2^31, 0 <= n_t <= cap, offsets >= 0, offsets and slot strides multiples of 8, slot strides >= Hkv * D * cap)");
+    return COVER_OK;
+}
+int cover_beam_backtrack(const cover_beam_backtrack_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_beam_backtrack: null args");
+    HIPCHK(launch_beam_backtrack(a, ST(stream)), "beam_backtrack (every pointer required, steps >= 1, B >= 1, rows >= 0, rows % B == 0)");
+    return COVER_OK;
+}
+
 int cover_resample_axis(const void* in, int in_is_f32, void* out, int out_is_f32, int Hin, int Win, int C, int Hout, int Wout,
                         int axis, const int* bounds, const void* coefs, int ksize, int fixed_point, void* stream) {
     if (!in || !out || !bounds || !coefs || ksize <= 0 || (axis != 0 && axis != 1)) return fail(COVER_EINVAL, "cover_resample_axis: bad arguments");
@@ -913,6 +932,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_prior_select_args); SZ(cover_token_sample_scored_args); SZ(cover_token_logprob_args); SZ(cover_token_topn_args); SZ(cover_token_sample_rows_args); SZ(cover_token_logprob_rows_args); SZ(cover_token_topn_rows_args); SZ(cover_token_allow); SZ(cover_token_ref); SZ(cover_decode_feedback_args); SZ(cover_token_fsm);
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
+    SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
 #undef SZ
     return 0;
 }

@@ -102,6 +102,10 @@ hipError_t launch_actions_to_histories(const float* actions, long long n_stride,
 hipError_t launch_group_argmax(const float* scores, int N, int gs, int* result, float* best, hipStream_t st);
 hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st);
 size_t gemm_workspace_bytes(int M, int N, int K);
+// ---- beam.hip ------------------------------------------------------------------------------------
+hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
+hipError_t launch_kv_gather_slots(const cover_kv_gather_slots_args* a, hipStream_t st);
+hipError_t launch_beam_backtrack(const cover_beam_backtrack_args* a, hipStream_t st);
 
 // ---- image.hip -----------------------------------------------------------------------------------
 hipError_t launch_resample_axis(const void* in, int in_kind, void* out, int out_kind, int Hin, int Win, int C, int Hout, int Wout,

@@ -318,6 +318,20 @@ class Decoder:
         g._keep = keep
         return g
 
+    def kv_tables(self):
+        """(k_base, vt_base): int64 device tensors [n_layers] of k_cache[i].data_ptr() / vt_cache[i].data_ptr(), built once -- the per-layer
+        pointer tables ops.kv_gather_slots reads on the device."""
+        if getattr(self, "_kv_tables", None) is None:
+            self._kv_tables = tuple(torch.tensor([t.data_ptr() for t in cache], dtype=torch.int64, device=self.dev)
+                                    for cache in (self.k_cache, self.vt_cache))
+        return self._kv_tables
+
+    def kv_region(self, r: int) -> dict:
+        """Region r of the cache geometry as ops.kv_gather_slots' keyword arguments (element offsets and slot strides)."""
+        g = self.geom
+        return dict(k_offset=g.k_off[r], vt_offset=g.vt_off[r], k_slot_stride=g.k_strides(r)[0], vt_slot_stride=g.vt_strides(r)[0],
+                    n_slots=g.slots[r], cap=g.caps[r], Hkv=g.Hkv, D=g.D)
+
     def workspace(self, rows: int) -> torch.Tensor:
         """A pass workspace of its own for up to `rows` rows: independent passes of one decoder that run CONCURRENTLY on different streams
         (row-group chains of the pi0 denoise loop) must not share the decoder's."""

@@ -202,40 +202,12 @@ class OpenVLA:
         return out
 
     # ---------------------------------------------------------------------------------------------- sampler
-    def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
-               uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, trace: Optional[dict] = None,
-               force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
-               top_k: RowParam = 0, top_p: RowParam = 1.0, return_logprobs: bool = False, top_logprobs: int = 0,
-               prior_temperature: Optional[float] = None):
-        """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
-        n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
-        uniforms fp32 [N, n_gen], temperature / top_k / top_p (scalars or length-N sequences / tensors), return_logprobs, top_logprobs and
-        prior_temperature: the sampling arguments cover_vla_amd.sampling documents (S = n_gen steps). Their range here: a sampled or
-        per-candidate call picks over the 256 action tokens [action_lo, action_hi); an all-greedy call (uniforms=None) takes its arg-max
-        over the tokenizer vocabulary and is scored over it, whereas a temperature-0 candidate of a per-candidate call takes the arg-max
-        over the action bins, the range of its ops.token_sample_rows launch. Scalar top_k <= 0 and top_p >= 1 is the unfiltered ops.token_select path.
-        force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
-        returning this path's own picks. on_prefill_enqueued: optional callable invoked once the prefill launches are
-        queued -- the point where a caller should queue independent side-stream work (the verifier towers): the
-        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not.
-        Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen][, logprobs][, prior][, TopLogprobs]).
-        The decode graph is keyed on PickPlan.graph_key: on the fact "per-row parameters", not on their values (the three tensors are
-        static buffers filled before each replay, so a new ladder is not a new capture), and on the value of prior_temperature."""
-        c, dev = self.c, self.dev
+    def _prefill(self, frame_u8, prompt_tokens, mark=lambda name: None, on_vision_enqueued=None, on_prefill_enqueued=None):
+        """Vision pass and prefill of one decision (sample and beam_search): the patch rows and the P x Lt text rows through the decoder
+        in one pass, their K/V left in regions 0 and 1. Returns the pass's rows x (hidden states: the patch rows, then P x Lt text rows)."""
+        dev = self.dev
         P, Lt = prompt_tokens.shape
-        N = P * n_samples
-        plan = PickPlan.resolve("sample", "candidate", N, dev, has_uniforms=uniforms is not None, params=(temperature, top_k, top_p),
-                                top_logprobs=top_logprobs, prior_temperature=prior_temperature, filter_always=False)
-
-        def mark(name):   # optional phase timing (tools/phases.py): trace["events"] collects (name, event) pairs
-            if trace is not None and "events" in trace:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                trace["events"].append((name, ev))
-
-        if P > self.max_prompts or N > self.max_candidates or Lt > self.max_text:
-            raise ValueError("prompts/candidates/text length exceed the sizes this model was built for")
-        D, T0 = c["llm_dim"], self.T0
+        T0 = self.T0
         Tp = T0 - 1                                   # patch rows; the BOS row is input-independent (see _ensure_bos_kv)
         self._ensure_bos_kv()
         # ---- prefill input rows: the patches (positions 1..Tp) then P x Lt text rows
@@ -257,11 +229,54 @@ class OpenVLA:
         mark("prefill")
         if on_prefill_enqueued is not None:
             on_prefill_enqueued()
-        # ---- first action token: last valid text position of each candidate's prompt
-        prompt_of_cand = (torch.arange(N, device=dev) // n_samples).to(torch.int32)
+        return x
+
+    def _cand_rows(self, prompt_lens, P, Lt, per_prompt):
+        """Row bookkeeping of N = P * per_prompt candidates, candidate i of prompt i // per_prompt: (prompt_of_cand, cand_len, last_row --
+        the prefill row of the last valid text position, where the first action token is read -- and pos_all [n_gen, N])."""
+        dev, T0 = self.dev, self.T0
+        N = P * per_prompt
+        prompt_of_cand = (torch.arange(N, device=dev) // per_prompt).to(torch.int32)
         cand_len = prompt_lens.to(torch.int32)[prompt_of_cand.long()].contiguous()
-        last_row = (Tp + prompt_of_cand * Lt + cand_len - 1).to(torch.int32)
+        last_row = (T0 - 1 + prompt_of_cand * Lt + cand_len - 1).to(torch.int32)
         pos_all = ((T0 + cand_len)[None, :] + torch.arange(self.n_gen, dtype=torch.int32, device=dev)[:, None]).contiguous()
+        return prompt_of_cand, cand_len, last_row, pos_all
+
+    def sample(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_samples: int,
+               uniforms: Optional[torch.Tensor] = None, temperature: RowParam = 1.0, trace: Optional[dict] = None,
+               force_tokens: Optional[torch.Tensor] = None, on_prefill_enqueued=None, on_vision_enqueued=None,
+               top_k: RowParam = 0, top_p: RowParam = 1.0, return_logprobs: bool = False, top_logprobs: int = 0,
+               prior_temperature: Optional[float] = None):
+        """frame_u8 [n_cams,H,W,3] uint8; prompt_tokens int64 [P, Lt] right padded, prompt_lens int32 [P] (device);
+        n_samples candidates per prompt (N = P*n_samples, candidate i belongs to prompt i // n_samples);
+        uniforms fp32 [N, n_gen], temperature / top_k / top_p (scalars or length-N sequences / tensors), return_logprobs, top_logprobs and
+        prior_temperature: the sampling arguments cover_vla_amd.sampling documents (S = n_gen steps). Their range here: a sampled or
+        per-candidate call picks over the 256 action tokens [action_lo, action_hi); an all-greedy call (uniforms=None) takes its arg-max
+        over the tokenizer vocabulary and is scored over it, whereas a temperature-0 candidate of a per-candidate call takes the arg-max
+        over the action bins, the range of its ops.token_sample_rows launch. Scalar top_k <= 0 and top_p >= 1 is the unfiltered ops.token_select path.
+        force_tokens int64 [N, n_gen] (tests): teacher-force the fed-back tokens while still
+        returning this path's own picks. on_prefill_enqueued: optional callable invoked once the prefill launches are
+        queued -- the point where a caller should queue independent side-stream work (the verifier towers): the
+        HBM-bound decode passes that follow tolerate concurrent kernels, the MFMA-bound prefill does not.
+        Returns (tokens int64 [N, n_gen], selected-logit fp32 [N, n_gen][, logprobs][, prior][, TopLogprobs]).
+        The decode graph is keyed on PickPlan.graph_key: on the fact "per-row parameters", not on their values (the three tensors are
+        static buffers filled before each replay, so a new ladder is not a new capture), and on the value of prior_temperature."""
+        dev = self.dev
+        P, Lt = prompt_tokens.shape
+        N = P * n_samples
+        plan = PickPlan.resolve("sample", "candidate", N, dev, has_uniforms=uniforms is not None, params=(temperature, top_k, top_p),
+                                top_logprobs=top_logprobs, prior_temperature=prior_temperature, filter_always=False)
+
+        def mark(name):   # optional phase timing (tools/phases.py): trace["events"] collects (name, event) pairs
+            if trace is not None and "events" in trace:
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record()
+                trace["events"].append((name, ev))
+
+        if P > self.max_prompts or N > self.max_candidates or Lt > self.max_text:
+            raise ValueError("prompts/candidates/text length exceed the sizes this model was built for")
+        x = self._prefill(frame_u8, prompt_tokens, mark, on_vision_enqueued, on_prefill_enqueued)
+        prompt_of_cand, cand_len, last_row, pos_all = self._cand_rows(prompt_lens, P, Lt, n_samples)
         u_t = None if uniforms is None else uniforms.to(torch.float32).t().contiguous()
         new_outs = lambda: StepOutputs.alloc(self.n_gen, N, dev, logit=True, logprob=return_logprobs, ref=plan.t_ref is not None, n_top=plan.n_top, fill=None)
         if self.decode_graph and trace is None and force_tokens is None and not self.slice_action_head:
@@ -335,7 +350,7 @@ class OpenVLA:
         # out_kept: written by the filtered pick (ops.token_sample) only
         out = dict(out_logit=o.sel[i], out_kept=self.kept_sel[:N], out_logprob=None if o.lps is None else o.lps[i],
                    out_ref=None if o.prior is None else o.prior[i], top=o.top_at(i))
-        hn = ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:N])
+        hn = self._final_norm(h)
         if not plan.greedy and (trace is None or "events" in trace) and self.slice_action_head:
             lg = ops.gemm(hn, self.lm_head_actions, out=self.logits_actions[:N], ws=self.head_ws_actions)
             t, _, _ = plan.pick(lg, 0, self.c["n_bins"], u, **out)
@@ -343,11 +358,101 @@ class OpenVLA:
             if o.top is not None:
                 o.top[0][i].add_((o.top[0][i] >= 0) * self.action_lo)      # ids as the tokens are; the -1 padding stays
             return
-        lg = ops.gemm(hn, self.lm_head, out=self.logits[:N], ws=self.head_ws)
-        if trace is not None and "events" not in trace:
-            trace.setdefault("logits", []).append(lg.clone())
+        lg = self._full_head(hn, trace)
         lo, hi = (0, self.c["tok_vocab"]) if plan.greedy else (self.action_lo, self.action_hi)   # greedy: the tokenizer vocabulary
         plan.pick(lg, lo, hi, u, out_tok=o.tokens[i], **out)
+
+    def _final_norm(self, h):
+        return ops.rmsnorm(h, self.llm.final_norm, 1e-5, w_offset=0.0, style=1, out=self.hn[:h.shape[0]])
+
+    def _full_head(self, hn, trace):
+        """The full lm_head on normed rows, into the static logits buffer; a trace (not a phase-timing one) keeps a clone."""
+        lg = ops.gemm(hn, self.lm_head, out=self.logits[:hn.shape[0]], ws=self.head_ws)
+        if trace is not None and "events" not in trace:
+            trace.setdefault("logits", []).append(lg.clone())
+        return lg
+
+    # ---------------------------------------------------------------------------------------------- beam search
+    def beam_search(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_beams: int, *,
+                    trace: Optional[dict] = None):
+        """The n_beams most probable DISTINCT action chunks of every prompt found by step-synchronous beam search, each with its exact
+        sequence log-probability: the deterministic alternative to n_samples i.i.d. draws of sample(), whose candidates of one prompt
+        often coincide under a peaked head. Inputs as sample(); N = P * n_beams, candidate i belongs to prompt i // n_beams.
+        Ranking distribution: softmax at temperature 1, unfiltered, over the action bins [action_lo, action_hi) -- the range of a
+        per-candidate sample(). Every step is the final norm and the full lm_head, ops.token_topn(n_beams) per row, ops.beam_merge per
+        prompt (higher score, then lower beam, then lower rank), and before the next decode pass ops.kv_gather_slots brings each parent's
+        own-token K/V into its child's slot; ops.beam_backtrack follows the parents at the end.
+        Returns (tokens int64 [N, n_gen], logprobs fp32 [N, n_gen], scores fp32 [N]): scores is the beams' final cumulative
+        log-probability, the fp32 left-to-right sum of logprobs; within a prompt the candidates are pairwise distinct and come in
+        descending score. (tokens, logprobs) are what ops.prior_select and host.verify_and_select(candidate_prior=...) take.
+        The own-token K/V ping-pong between slots [0, N) and [N, 2 N) of the candidates' cache region, so the model must be BUILT WITH
+        TWICE THE CANDIDATES: ValueError when 2 * N > max_candidates, when n_beams is outside 1..64, and when own_kv is not None (the
+        head-major own-token cache has no gather). The loop is launches only (no host read, no allocation) and runs eagerly.
+        trace={}: trace["logits"] gets every step's logits clone, trace["beam"] a dict per step of the raw parent / token / cum of the
+        merge (and its inputs cand_tok / cand_lp).
+        Out of scope: pi0-FAST, EOS / length handling, allowed sets and grammars, Gumbel (stochastic) beams, slice_action_head (the
+        full head is used whatever that switch says) and hipGraph capture of the loop."""
+        dev = self.dev
+        P, Lt = prompt_tokens.shape
+        B = int(n_beams)
+        if not 1 <= B <= 64:
+            raise ValueError(f"beam_search: 1 <= n_beams <= 64 is required (got {n_beams})")
+        N = P * B
+        if self.own_kv is not None:
+            raise ValueError("beam_search: the head-major own-token cache (own_kv) is not supported; build the model with own_kv=None")
+        if 2 * N > self.max_candidates:
+            raise ValueError(f"beam_search: the own-token K/V ping-pong between two sets of N = {N} slots: build the model with "
+                             f"max_candidates >= {2 * N} (twice the candidates; it has {self.max_candidates})")
+        if P > self.max_prompts or Lt > self.max_text:
+            raise ValueError("prompts/text length exceed the sizes this model was built for")
+        S, T0, lo, hi = self.n_gen, self.T0, self.action_lo, self.action_hi
+        x = self._prefill(frame_u8, prompt_tokens)
+        prompt_of_cand, cand_len, last_row, pos_all = self._cand_rows(prompt_lens, P, Lt, B)
+        # ---- everything the loop touches, allocated here
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        parent = torch.empty(S, N, **i32)
+        token, feed = torch.empty(S, N, dtype=torch.int64, device=dev), torch.empty(S, N, dtype=torch.int64, device=dev)
+        step_lp = torch.empty(S, N, **f32)
+        cum = torch.full((S + 1, N), float("-inf"), **f32)            # row i: the scores step i starts from; row S: the final ones
+        cum[0, ::B] = 0.0                                             # the B rows of a prompt carry identical logits at step 0
+        cand_tok, cand_lp = torch.empty(N, B, dtype=torch.int64, device=dev), torch.empty(N, B, **f32)
+        ent = torch.empty(N, **f32)
+        rows = torch.arange(N, **i32)
+        slots = (rows, rows + N)                                      # the candidates' slots of pass parity h
+        src_base = tuple(s - s % B for s in (rows + N, rows))         # parity h reads parity 1 - h: (1 - h) N + g B, the parent is added per step
+        src, dead = torch.empty(N, **i32), torch.empty(N, dtype=torch.bool, device=dev)
+        k_tab, vt_tab = self.llm.kv_tables()
+        region = self.llm.kv_region(2)
+        out_tokens, out_lps = torch.empty(N, S, dtype=torch.int64, device=dev), torch.empty(N, S, **f32)
+        xd = self.x_dec[:N]
+
+        def head_merge(h, i):
+            lg = self._full_head(self._final_norm(h), trace)
+            ops.token_topn(lg, lo, hi, B, 1.0, 0, 1.0, out_tok=cand_tok, out_logprob=cand_lp, out_entropy=ent)
+            ops.beam_merge(cum[i], cand_tok, cand_lp, B, lo, out_parent=parent[i], out_token=token[i], out_feed=feed[i], out_cum=cum[i + 1],
+                           out_step_lp=step_lp[i])
+            if trace is not None:
+                trace.setdefault("beam", []).append(dict(parent=parent[i].clone(), token=token[i].clone(), cum=cum[i + 1].clone(),
+                                                         cand_tok=cand_tok.clone(), cand_lp=cand_lp.clone()))
+
+        ops.copy_rows(x, self.h_sel, N, self.c["llm_dim"], last_row, None)
+        head_merge(self.h_sel[:N], 0)
+        for i in range(1, S):
+            h = i & 1
+            ops.embed_gather(self.embed, feed[i - 1], out=xd)
+            # the child's slot of this parity takes tokens t < i - 1 of its parent's slot of the other parity (dead beam: no copy)
+            torch.lt(parent[i - 1], 0, out=dead)
+            torch.add(src_base[h], parent[i - 1], out=src)
+            src.masked_fill_(dead, -1)
+            ops.kv_gather_slots(k_tab, vt_tab, src, slots[h], i - 1, **region)
+            g = self.llm.group(N, 1, pos_all[i - 1],
+                               [dict(region=0, length=T0, slot_of_batch=self.zero_slots),
+                                dict(region=1, length=Lt, len_of_batch=cand_len, slot_of_batch=prompt_of_cand),
+                                dict(region=2, length=i, slot_of_batch=slots[h])], 2, write_slot=slots[h], write_t_off=i - 1, seg0_shared=True)
+            self.llm.forward(xd, [g], final_norm=False)               # writes t = i - 1 itself
+            head_merge(xd, i)
+        ops.beam_backtrack(parent, token, step_lp, B, out_tokens=out_tokens, out_logprobs=out_lps)
+        return out_tokens, out_lps, cum[S]
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

@@ -1337,6 +1337,91 @@ def prior_select(scores, logprobs, group_size, beta, *, tokens=None, pad_token_i
     return out
 
 
+# ------------------------------------------------------------------------------------------------ beam search
+def beam_merge(cum, cand_tok, cand_lp, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None, out_step_lp=None):
+    """One beam-search step over G = rows / n_beams prompt groups (cover_beam_merge; row g * n_beams + b is beam b of group g).
+    cum fp32 [rows] contiguous: the beams' scores so far, -inf / NaN = dead; cand_tok int64 / cand_lp fp32 [rows, n_beams] (unit column
+    stride, any row stride >= n_beams): each row's top-n_beams list as token_topn writes it. Candidate (b, j) scores cum[b] +
+    cand_lp[b][j] (one fp32 add) and is live iff cum[b] is finite, cand_tok[b][j] >= 0 and cand_lp[b][j] is finite; output beam r is
+    the r-th live candidate by higher score, then lower b, then lower j. Returns (parent int32, token int64, feed int64, cum fp32,
+    step_lp fp32), each [rows]: parent is the row index inside the group, feed is token or, for a dead output, feed_pad (a valid
+    token id for the next embed_gather); dead outputs are -1 / -1 / feed_pad / -inf / -inf. out_cum must not be cum.
+    Deterministic, one launch, recordable."""
+    B = _chk_topn_n("beam_merge", n_beams)
+    if cum.dtype != torch.float32 or cum.dim() != 1 or not cum.is_contiguous() or cum.numel() % B != 0:
+        raise L.CoverError("beam_merge: cum must be contiguous fp32 [rows], rows a multiple of n_beams")
+    rows = cum.numel()
+    if int(feed_pad) < 0:
+        raise L.CoverError(f"beam_merge: feed_pad must be a valid token id (got {feed_pad})")
+    _chk_rows_n_out("beam_merge", rows, B, ("cand_tok", cand_tok, torch.int64), ("cand_lp", cand_lp, torch.float32))
+    outs = (("out_parent", out_parent, torch.int32), ("out_token", out_token, torch.int64), ("out_feed", out_feed, torch.int64),
+            ("out_cum", out_cum, torch.float32), ("out_step_lp", out_step_lp, torch.float32))
+    _chk_rows_out("beam_merge", rows, *outs)
+    _chk_dev(cum, cand_tok, cand_lp, out_parent, out_token, out_feed, out_cum, out_step_lp)
+    if out_cum is not None and out_cum.data_ptr() == cum.data_ptr():
+        raise L.CoverError("beam_merge: out_cum must not alias cum")
+    parent, token, feed, cum_o, step_lp = (torch.empty(rows, dtype=dt, device=cum.device) if t is None else t for _, t, dt in outs)
+    a = L.BeamMergeArgs()
+    a.cum, a.feed_pad, a.groups, a.B = cum.data_ptr(), int(feed_pad), rows // B, B
+    a.cand_tok, a.ld_tok = cand_tok.data_ptr(), max(cand_tok.stride(0), B)
+    a.cand_lp, a.ld_lp = cand_lp.data_ptr(), max(cand_lp.stride(0), B)
+    a.parent_out, a.token_out, a.feed_out = parent.data_ptr(), token.data_ptr(), feed.data_ptr()
+    a.cum_out, a.step_lp_out = cum_o.data_ptr(), step_lp.data_ptr()
+    L.check(L.lib().cover_beam_merge(C.byref(a), _stream()), "beam_merge")
+    return parent, token, feed, cum_o, step_lp
+
+
+def kv_gather_slots(k_base, vt_base, src_slot, dst_slot, n_t, *, k_offset, vt_offset, k_slot_stride, vt_slot_stride, n_slots, cap, Hkv, D):
+    """Slot-to-slot copies inside one region of the per-layer bf16 K / V^T caches, every layer in one launch (cover_kv_gather_slots).
+    k_base / vt_base: int64 device tensors [n_layers] of the layers' cache data_ptr() (models.Decoder.kv_tables()); the keyword
+    arguments describe the region (models.Decoder.kv_region(r)): K [slot][t][Hkv][D], V^T [slot][Hkv][D][cap], offsets and slot strides
+    in elements. src_slot / dst_slot int32 [rows] on the device: K rows and V^T columns t < n_t of slot dst_slot[i] become those of slot
+    src_slot[i]; a row with either slot outside [0, n_slots) is skipped; several rows may share a source. THE CALLER GUARANTEES that no
+    destination is also a source and that destinations are distinct. V^T is copied in 16-byte runs: up to 7 columns past n_t of a
+    destination slot may be overwritten. n_t == 0 is a no-op. One launch, recordable."""
+    for name, t in (("k_base", k_base), ("vt_base", vt_base)):
+        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise L.CoverError(f"kv_gather_slots: {name} must be a contiguous int64 [n_layers] tensor of device pointers")
+    if vt_base.numel() != k_base.numel() or k_base.numel() < 1:
+        raise L.CoverError("kv_gather_slots: k_base and vt_base must have one entry per layer")
+    if src_slot.dtype != torch.int32 or src_slot.dim() != 1 or not src_slot.is_contiguous():
+        raise L.CoverError("kv_gather_slots: src_slot must be contiguous int32 [rows]")
+    _chk_rows_out("kv_gather_slots", src_slot.numel(), ("dst_slot", dst_slot, torch.int32))
+    _chk_dev(k_base, vt_base, src_slot, dst_slot)
+    if not 0 <= int(n_t) <= int(cap):
+        raise L.CoverError(f"kv_gather_slots: 0 <= n_t <= cap is required (got n_t={n_t}, cap={cap})")
+    a = L.KvGatherSlotsArgs()
+    a.k_base, a.vt_base, a.src_slot, a.dst_slot = k_base.data_ptr(), vt_base.data_ptr(), src_slot.data_ptr(), dst_slot.data_ptr()
+    a.k_offset, a.vt_offset, a.k_slot_stride, a.vt_slot_stride = int(k_offset), int(vt_offset), int(k_slot_stride), int(vt_slot_stride)
+    a.n_layers, a.rows, a.n_slots, a.cap, a.Hkv, a.D, a.n_t = k_base.numel(), src_slot.numel(), int(n_slots), int(cap), int(Hkv), int(D), int(n_t)
+    L.check(L.lib().cover_kv_gather_slots(C.byref(a), _stream()), "kv_gather_slots")
+
+
+def beam_backtrack(parent, token, step_lp, n_beams, out_tokens=None, out_logprobs=None):
+    """The sequences that end in each final beam (cover_beam_backtrack). parent int32, token int64, step_lp fp32, all contiguous
+    step-major [steps, rows] as beam_merge wrote them step by step; rows a multiple of n_beams. Returns candidate-major (tokens int64
+    [rows, steps], logprobs fp32 [rows, steps]): final beam r's last-step entries are its own, parent then names the beam of the step
+    before inside the group; a parent outside [0, n_beams) leaves the remaining earlier steps -1 / -inf. One launch, recordable."""
+    if parent.dtype != torch.int32 or parent.dim() != 2 or not parent.is_contiguous() or parent.shape[0] < 1 or int(n_beams) < 1 or \
+            parent.shape[1] % int(n_beams) != 0:
+        raise L.CoverError("beam_backtrack: parent must be contiguous int32 [steps >= 1, rows], rows a multiple of n_beams >= 1")
+    steps, rows = parent.shape
+    for name, t, dt in (("token", token, torch.int64), ("step_lp", step_lp, torch.float32)):
+        if t.dtype != dt or t.shape != parent.shape or not t.is_contiguous():
+            raise L.CoverError(f"beam_backtrack: {name} must be contiguous {dt} of parent's shape")
+    for name, t, dt in (("out_tokens", out_tokens, torch.int64), ("out_logprobs", out_logprobs, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, steps) or not t.is_contiguous()):
+            raise L.CoverError(f"beam_backtrack: {name} must be contiguous {dt} [rows, steps]")
+    _chk_dev(parent, token, step_lp, out_tokens, out_logprobs)
+    tokens = torch.empty(rows, steps, dtype=torch.int64, device=parent.device) if out_tokens is None else out_tokens
+    lps = torch.empty(rows, steps, dtype=torch.float32, device=parent.device) if out_logprobs is None else out_logprobs
+    a = L.BeamBacktrackArgs()
+    a.parent, a.token, a.step_lp, a.steps, a.rows, a.B = parent.data_ptr(), token.data_ptr(), step_lp.data_ptr(), steps, rows, int(n_beams)
+    a.tokens_out, a.logprobs_out = tokens.data_ptr(), lps.data_ptr()
+    L.check(L.lib().cover_beam_backtrack(C.byref(a), _stream()), "beam_backtrack")
+    return tokens, lps
+
+
 # ------------------------------------------------------------------------------------------------ graphs / timers
 class Graph:
     """hipGraph captured from whatever runs on the current stream inside the `with` block."""

@@ -23,6 +23,7 @@ range (over the row's allowed set where there is one) -- written by the pick's o
 ops.token_logprob_rows at (T_ref, 0, 1) on the pick, bit for bit). It is the prior that compares across the rungs of a ladder:
 return_logprobs scores every row under its own rung. Scalar parameters are broadcast and the per-row path is taken (the only one that carries
 the reference); uniforms is required: a greedy candidate is a row with temperature 0. None launches exactly what it launched before.
+The deterministic alternative to drawing -- the B most probable distinct sequences per prompt -- is OpenVLA.beam_search; it takes none of the above.
 """
 from __future__ import annotations
 

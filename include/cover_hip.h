@@ -797,6 +797,62 @@ typedef struct cover_prior_select_args {
 } cover_prior_select_args;
 int cover_prior_select(const cover_prior_select_args* args, void* stream);
 
+/* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
+ * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
+ *
+ * cover_beam_merge: one step of `groups` prompt groups x B beams (1 <= B <= 64); row g * B + b is beam b of group g.
+ *   cum[row]               the beam's score so far; -inf or NaN marks a dead beam
+ *   cand_tok / cand_lp     [groups * B, >= B] with row strides ld_tok / ld_lp: the row's top-B list exactly as cover_token_topn writes it
+ *                          (descending logit, equal logits by ascending id, padded with -1 / -inf)
+ *   candidate (b, j)       score = cum[b] + cand_lp[b][j], ONE fp32 add; live iff cum[b] is finite, cand_tok[b][j] >= 0 and
+ *                          cand_lp[b][j] is finite
+ *   output beam r          the r-th live candidate of the group in the order: higher score first (-0 == +0), then lower b, then lower j
+ *   parent_out[row]        b of the chosen candidate (the row index INSIDE the group)        -1   when fewer than r + 1 are live
+ *   token_out[row]         its cand_tok                                                      -1
+ *   feed_out[row]          token_out, what the next embedding gather may safely read         feed_pad (a valid token id, >= 0)
+ *   cum_out[row]           its score                                                         -inf
+ *   step_lp_out[row]       its cand_lp                                                       -inf
+ * cum and cum_out must not alias (COVER_EINVAL when they are the same pointer). One block per group: a bitonic sort of the B * B
+ * 64-bit keys (score image, b * B + j) in LDS; the keys are unique, so the order is the rule above whatever the schedule. */
+typedef struct cover_beam_merge_args {
+    const float* cum;                          /* [groups * B] */
+    const int64_t* cand_tok; long long ld_tok; /* [groups * B, B] */
+    const float* cand_lp; long long ld_lp;     /* [groups * B, B] */
+    long long feed_pad;
+    int groups, B;
+    int* parent_out; int64_t* token_out; int64_t* feed_out; float* cum_out; float* step_lp_out;   /* [groups * B] each */
+} cover_beam_merge_args;
+int cover_beam_merge(const cover_beam_merge_args* args, void* stream);
+
+/* cover_kv_gather_slots: rows x n_layers slot-to-slot copies inside ONE region of the per-layer bf16 K / V^T caches, one launch.
+ * k_base / vt_base are DEVICE tables [n_layers] of the layers' cache allocations (16-byte aligned); the region starts k_offset /
+ * vt_offset elements into each and holds n_slots slots, K [slot][t][Hkv][D] and V^T [slot][Hkv][D][cap] (dense inside a slot, slot
+ * strides in elements). For every row, K rows t < n_t and V^T columns t < n_t of slot dst_slot[row] become those of slot
+ * src_slot[row], in every layer. A row whose src_slot or dst_slot is outside [0, n_slots) is skipped; several rows may name one source.
+ * THE CALLER GUARANTEES that no destination slot is also a source and that the destinations are distinct (the copies of a launch run
+ * in no order). K is copied exactly; V^T in whole 16-byte runs, so up to 7 columns past n_t of a DESTINATION slot may be overwritten
+ * with the source's -- nothing outside destination slots is written. n_t == 0 and rows == 0 are legal no-ops.
+ * COVER_EINVAL unless 1 <= n_layers <= 65535, n_slots >= 1, cap a positive multiple of 8, Hkv * D a multiple of 8,
+ * Hkv * D * cap < 2^31, 0 <= n_t <= cap, offsets >= 0, offsets and slot strides multiples of 8 and slot strides >= Hkv * D * cap. */
+typedef struct cover_kv_gather_slots_args {
+    const void* const* k_base; const void* const* vt_base;   /* device tables [n_layers] */
+    long long k_offset, vt_offset, k_slot_stride, vt_slot_stride;
+    const int* src_slot; const int* dst_slot;                /* device int32 [rows] */
+    int n_layers, rows, n_slots, cap, Hkv, D, n_t, _pad;
+} cover_kv_gather_slots_args;
+int cover_kv_gather_slots(const cover_kv_gather_slots_args* args, void* stream);
+
+/* cover_beam_backtrack: parent int32, token int64, step_lp fp32, all step-major [steps, rows] as cover_beam_merge wrote them step by
+ * step (rows = groups * B) -> candidate-major tokens_out int64 [rows, steps] and logprobs_out fp32 [rows, steps]: the sequence that ends
+ * in each final beam. Final beam r's entries of the last step are its own; parent[s][.] then names the beam of step s - 1 inside the
+ * group. A parent outside [0, B) anywhere leaves the candidate's remaining EARLIER steps as -1 / -inf. rows % B == 0, steps >= 1. */
+typedef struct cover_beam_backtrack_args {
+    const int* parent; const int64_t* token; const float* step_lp;   /* [steps, rows] */
+    int steps, rows, B, _pad;
+    int64_t* tokens_out; float* logprobs_out;                        /* [rows, steps] */
+} cover_beam_backtrack_args;
+int cover_beam_backtrack(const cover_beam_backtrack_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Composite forwards: the per-layer Python loops of the reference (18-layer loop in
  * paligemma_with_expert.py:258-349, HF/timm encoder loops) run here in C++ so that a whole tower / prefill /
