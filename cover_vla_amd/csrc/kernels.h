@@ -115,6 +115,14 @@ hipError_t launch_u8_to_chw_norm(const uint8_t* in, float* out, int H, int W, in
 hipError_t launch_bilinear_pad(const float* in, float* out, int NC, int Hin, int Win, int Hr, int Wr, int Hout, int Wout, int pad_top,
                                int pad_left, float pad_value, hipStream_t st);
 
+// ---- capi.hip: the string cover_last_error() returns (thread-local); fail() records it and hands `code` back
+int fail(int code, const char* what, hipError_t e = hipSuccess);
+#define HIPCHK(call, what)                                  \
+    do {                                                    \
+        hipError_t _e = (call);                             \
+        if (_e != hipSuccess) return fail(_e == hipErrorInvalidValue ? COVER_EINVAL : COVER_EHIP, what, _e); \
+    } while (0)
+
 // ---- prof.hip: optional per-launch hipEvent timing (classes: 0 skinny GEMM, 1 tiled GEMM, 2 attention) ----------
 bool prof_enabled();
 int prof_open(hipStream_t st, int cls, double work);

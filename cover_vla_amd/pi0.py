@@ -267,7 +267,7 @@ class PI0FlowMatching:
                 g = self.expert.group(b1 - b0, S, st["spos"][b0:b1].view(-1),
                                       [dict(region=0, length=Tp, len_of_batch=st["row_plen"][b0:b1], slot_of_batch=st["row_prompt"][b0:b1]),
                                        dict(region=1, length=S, mask=ops.MASK_VISLEN, vis_len=self.vis_len, slot_of_batch=sl)], 1,
-                                      write_slot=sl, write_scratch=True)   # suffix K/V: per-step temporaries in the rows' own slots
+                                      write_slot=sl)   # suffix K/V: per-step temporaries in the rows' own slots
                 st["chains"].append(dict(b0=b0, b1=b1, g=g, ws=self.expert.workspace((b1 - b0) * S),
                                          stream=torch.cuda.Stream(device=dev) if ci > 0 else None))
             self._den[(B, n_ch, knobs)] = st

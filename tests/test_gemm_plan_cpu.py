@@ -83,7 +83,7 @@ def ws_of(M, shapes):
 
 def model_cases():
     """(label, M, N, K, kind, variant, ws_bytes, f8_off): the GEMMs of the shipped profiles as the layer code issues them
-    (cover_vla_amd/synth.py sizes; the decoder / tower workspace = the largest over the layer's four GEMMs, as capi.hip sizes it)"""
+    (cover_vla_amd/synth.py sizes; the decoder / tower workspace = the largest over the layer's four GEMMs, as forward.hip sizes it)"""
     cases = []
 
     def decoder(tag, M, dim, Hq, Hkv, D, mlp, act, fp8=False, f8_off=False):
@@ -244,6 +244,36 @@ def test_gemm_workspace_bytes_unchanged():
     h = _lib.lib()
     got = [h.cover_gemm_workspace_bytes(M, N, K) for M, N, K in WORKSPACE_SHAPES]
     assert got == WORKSPACE_BYTES
+
+
+# ---- the pass workspaces (forward.hip: dec_ws / vit_ws). The tables were recorded from the library as it was when both layouts were still carved
+# through out-parameters in capi.hip, so they pin the parent's sizes. Only the scalar geometry of a desc is read: no device, no layer array.
+DEC_WS_ROWS = (1, 16, 64, 65, 200, 512)   # 65 crosses the rows > 64 boundary behind which the fp8 buffers are used
+DEC_WS_BYTES = {   # (dim, Hq, Hkv, D, mlp): synth.OPENVLA_SMALL, the tests' TINY pi0 (prefix, expert), synth.OPENVLA_7B, synth.PI0_FULL (prefix, expert)
+    (256, 4, 4, 64, 512): [14336, 214272, 855552, 2467072, 7588608, 19425536],
+    (256, 4, 1, 64, 512): [13568, 201984, 806400, 2417152, 7435008, 19032320],
+    (128, 4, 1, 64, 256): [6400, 87296, 347136, 1285120, 3951872, 10115328],
+    (4096, 32, 32, 128, 11008): [620032, 9910272, 50911232, 51707136, 159097344, 113686784],
+    (2048, 8, 1, 256, 16384): [596224, 9528832, 38113792, 9955840, 30631680, 78416128],
+    (1024, 8, 1, 256, 4096): [294912, 4705792, 18821632, 19116288, 58817280, 58296576],
+}
+VIT_WS_SHAPES = ((1, 32), (2, 33), (4, 256))   # (n_seq, T); T = 33: the V^T scratch is padded to tcap = 64 != T
+VIT_WS_BYTES = {   # (dim, heads, head_dim_p, mlp_p): the SigLIP tower of synth.OPENVLA_SMALL, SigLIP-So400m (synth.OPENVLA_7B / PI0_FULL)
+    (128, 2, 64, 256): [114944, 962304, 14680320],
+    (1152, 16, 96, 4352): [6152448, 11663104, 177996032],
+}
+
+
+def test_pass_workspace_bytes_unchanged():
+    h = _lib.lib()
+    for (dim, Hq, Hkv, D, mlp), want in DEC_WS_BYTES.items():
+        d = _lib.DecDesc()
+        d.dim, d.Hq, d.Hkv, d.D, d.mlp = dim, Hq, Hkv, D, mlp
+        assert [h.cover_decoder_workspace_bytes(C.byref(d), r) for r in DEC_WS_ROWS] == want, (dim, Hq, Hkv, D, mlp)
+    for (dim, heads, dp, mlp_p), want in VIT_WS_BYTES.items():
+        d = _lib.VitDesc()
+        d.dim, d.heads, d.head_dim_p, d.mlp_p = dim, heads, dp, mlp_p
+        assert [h.cover_vit_workspace_bytes(C.byref(d), n, T) for n, T in VIT_WS_SHAPES] == want, (dim, heads, dp, mlp_p)
 
 
 # ---- recorded from the planner before it was split from the launch code: (label, plan or None for COVER_EINVAL)

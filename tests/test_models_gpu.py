@@ -507,7 +507,7 @@ def test_full_width_gemma_layers_match_reference_g2(dev):
 
 def test_expert_layer_200_rows_qkv_slabs_folded_by_rope_equals_reduction_launch(dev):
     """The pi0 action expert at its real shapes and the P1 batch (40 candidates x 5 suffix tokens = 200 rows over 8 prompts' cached
-    prefixes): the split-K slabs of the tiled QKV GEMM are folded by rope_kv_write (capi.hip, COVER_QKV_FOLD) -- bit-identical layer
+    prefixes): the split-K slabs of the tiled QKV GEMM are folded by rope_kv_write (forward.hip, COVER_QKV_FOLD) -- bit-identical layer
     output and suffix K / V to the path with the separate reduction launch."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_oracle_golden import _g2_case

@@ -37,25 +37,38 @@ def _case(seed=3, P=3, Lt=9, n_samples=2, n_cams=1, n_gen=7, peaked=False):
                                                                  (False, 1, 8, "bf16", None), (False, 1, 2, "fp8", None), (True, 1, 8, "fp8", None),
                                                                  (False, 1, 2, "bf16", "bf16"), (True, 1, 8, "bf16", "bf16"), (False, 2, 1, "bf16", "bf16"),
                                                                  (False, 1, 2, "bf16", "fp8"), (False, 1, 8, "fp8", "fp8"),
-                                                                 (True, 1, 1, "bf16", "peaked"), (False, 1, 1, "bf16", "peaked"), (True, 1, 8, "bf16", "peaked")])
+                                                                 (True, 1, 1, "bf16", "peaked"), (False, 1, 1, "bf16", "peaked"), (True, 1, 8, "bf16", "peaked"),
+                                                                 (False, 1, 2, "bf16", "three_launch")])
 def test_openvla_small_matches_oracle(dev, greedy, n_cams, horizon, wdtype, own_kv):
     """n_cams = 2 is BASELINE config 4's observation (two 224^2 cameras -> 512 patch rows in the shared prefix); horizon > 1 is
     config 5's action chunk (7 x horizon action tokens per candidate: the own-token KV segment grows to 56 keys); wdtype "fp8" =
     config 5's e4m3 decoder / lm_head weights, compared with the oracle on the DE-QUANTISED weights; own_kv = the large-N
     decode path (head-major own-token cache: own-token VALU pass + one MFMA pass over [shared | text]), "fp8" = config 5's fp8 KV,
-    compared with the oracle that quantises the own tokens' K / V rows the same way."""
+    compared with the oracle that quantises the own tokens' K / V rows the same way; "three_launch" = the default cache layout with a per-row
+    length table on the own-token segment (every entry the segment's length: the same attention), which the fused decode launch does not take, so
+    cover_decoder_forward attends the shared segment once for all candidates and then each candidate's own segments (its SHARED_THEN_OWN route, which
+    the models themselves only reach at config 5's sizes)."""
     from cover_ref import blocks as Bk, openvla as OR
     from cover_vla_amd.openvla import OpenVLA
     n_gen = 7 * horizon
     # own_kv == "peaked": the checkpoint with decision margins (synth.openvla_state(peaked=True)) on the default cache layout -- there the
     # data decide (nearly) every pick, so "equal wherever decided" becomes "equal", greedy and sampled
-    peaked = own_kv == "peaked"
-    own_kv = None if peaked else own_kv
+    peaked, three_launch = own_kv == "peaked", own_kv == "three_launch"
+    own_kv = None if peaked or three_launch else own_kv
     c, sd, frame, toks, lens, u = _case(n_cams=n_cams, n_gen=n_gen, peaked=peaked)
     n_samples = 1 if greedy else 2
     P = toks.shape[0]
     model = OpenVLA(sd, c, device="cuda:0", max_prompts=4, max_candidates=8, max_text=toks.shape[1], n_cams=n_cams, horizon=horizon,
                     weight_dtype=wdtype, own_kv=own_kv)
+    if three_launch:
+        group = model.llm.group
+
+        def group_with_own_lengths(B, T, positions, segs, write_seg, **kw):
+            if kw.get("seg0_shared"):
+                own_len = torch.full((B,), segs[2]["length"], dtype=torch.int32, device=positions.device)
+                segs = segs[:2] + [dict(segs[2], len_of_batch=own_len)]
+            return group(B, T, positions, segs, write_seg, **kw)
+        model.llm.group = group_with_own_lengths
     un = None if greedy else u[: P * n_samples]
     otr = {}
     if wdtype == "fp8":
