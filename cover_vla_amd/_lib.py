@@ -201,6 +201,18 @@ class BeamBacktrackArgs(C.Structure):
                 ("tokens_out", c_p), ("logprobs_out", c_p)]
 
 
+class GumbelTopnArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_ll), ("rows", c_i), ("lo", c_i), ("hi", c_i), ("temperature", c_f),
+                ("phi", c_p), ("g_parent", c_p), ("uniform", c_p), ("ld_u", c_ll), ("n", c_i), ("_pad", c_i),
+                ("token_out", c_p), ("ld_tok", c_ll), ("logprob_out", c_p), ("ld_lp", c_ll), ("perturbed_out", c_p), ("ld_g", c_ll)]
+
+
+class BeamMergeGumbelArgs(C.Structure):
+    _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("cand_g", c_p), ("ld_g", c_ll),
+                ("feed_pad", c_ll), ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p),
+                ("cum_out", c_p), ("step_lp_out", c_p), ("g_out", c_p), ("kappa_out", c_p)]
+
+
 class Workspace(C.Structure):
     _fields_ = [("ptr", c_p), ("bytes", C.c_size_t)]
 
@@ -255,7 +267,8 @@ _STRUCTS = {
     "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_token_fsm": TokenFsm,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_beam_merge_args": BeamMergeArgs,
-    "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
+    "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
+    "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
     "cover_dec_pass": DecPass, "cover_decode_attn_args": DecodeAttnArgs, "cover_own_attn_args": OwnAttnArgs,
 }
@@ -331,6 +344,8 @@ SYMBOLS = {
     "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
     "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
     "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),
+    "cover_gumbel_topn": (c_i, [_P(GumbelTopnArgs), c_p]),
+    "cover_beam_merge_gumbel": (c_i, [_P(BeamMergeGumbelArgs), c_p]),
     "cover_tokens_to_histories": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_f, c_p, c_p, c_p]),
     "cover_tokens_to_histories_steps": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
     "cover_actions_to_histories": (c_i, [c_p, c_ll, c_ll, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_p, c_p]),

@@ -1,26 +1,22 @@
-// Beam search pieces (cover_beam_merge, cover_kv_gather_slots, cover_beam_backtrack): the merge of the B x B continuations of a prompt
+// Beam search pieces (cover_beam_merge, cover_beam_merge_gumbel, cover_kv_gather_slots, cover_beam_backtrack): the merge of the B x B continuations of a prompt
 // group, the slot-to-slot copy of each parent's own-token K/V into its child's slot, and the walk back through the parents.
 // Conventions of sample.hip / select.hip: a bad host argument is hipErrorInvalidValue; nothing a device buffer holds can take a load or a
 // store out of bounds (a bad slot or parent skips its row); every result is a fixed function of the inputs -- no atomics, the one sort has
 // unique keys; every store is a per-lane vector store.
 #include "common.h"
 #include "kernels.h"
+#include "keysort.h"
 
 // ---------------------------------------------------------------------------------------------------
 // merge: one block per group, a bitonic sort of the B * B candidates (padded to a power of two n2 <= 4096) in LDS on 64-bit keys
 //   key = (descending-order image of the fp32 score) << 32 | (b * B + j)        a dead candidate: all ones
 // The low half makes every key unique and IS the tie rule (lower b, then lower j), so the network's result does not depend on how it is
 // scheduled. 78 compare-exchange stages at n2 = 4096 against B * B * B * B comparisons for a rank by counting (16.7 M at B = 64).
+// KEYED (cover_beam_merge_gumbel): the score is the stored cand_g in place of cum + cand_lp, it is written to g_out, and the key behind
+// the B kept ones is the group's kappa. cover_beam_merge runs the same kernel on its own fields, cand_g / g_out / kappa_out unset.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t desc_key(float s) {
-    if (s == 0.0f) s = 0.0f;                                   // -0 and +0 are one score
-    const uint32_t u = __float_as_uint(s);
-    const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // larger float -> larger unsigned
-    return ~asc;
-}
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-__global__ __launch_bounds__(1024) void beam_merge_k(cover_beam_merge_args a, int n2) {
+template <bool KEYED>
+__global__ __launch_bounds__(1024) void beam_merge_k(cover_beam_merge_gumbel_args a, int n2) {
     __shared__ unsigned long long key[4096];
     const int B = a.B, g = blockIdx.x;
     const long long row0 = (long long)g * B;
@@ -31,29 +27,23 @@ __global__ __launch_bounds__(1024) void beam_merge_k(cover_beam_merge_args a, in
             const float cum = a.cum[row0 + b];
             const float lp = a.cand_lp[(row0 + b) * a.ld_lp + j];
             const long long tk = a.cand_tok[(row0 + b) * a.ld_tok + j];
-            if (finite_f(cum) && finite_f(lp) && tk >= 0) k = ((unsigned long long)desc_key(cum + lp) << 32) | (unsigned)c;
+            float score = cum + lp;
+            bool live = finite_f(cum) && finite_f(lp) && tk >= 0;
+            if constexpr (KEYED) {
+                score = a.cand_g[(row0 + b) * a.ld_g + j];
+                live = live && finite_f(score);
+            }
+            if (live) k = ((unsigned long long)desc_key(score) << 32) | (unsigned)c;
         }
         key[c] = k;
     }
     __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (n2 >> 1); t += blockDim.x) {
-                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), p = i | stride;
-                const bool up = (i & size) == 0;
-                const unsigned long long x = key[i], y = key[p];
-                if ((x > y) == up) {
-                    key[i] = y;
-                    key[p] = x;
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_lds(key, n2);
     for (int r = threadIdx.x; r < B; r += blockDim.x) {
         const unsigned long long k = key[r];
         int parent = -1;
         long long tok = -1, feed = a.feed_pad;
-        float cum = -INFINITY, lp = -INFINITY;
+        float cum = -INFINITY, lp = -INFINITY, gk = -INFINITY;
         if (k != ~0ull) {
             const int c = (int)(unsigned)k;            // < B * B: written above from a live candidate
             parent = c / B;
@@ -62,26 +52,49 @@ __global__ __launch_bounds__(1024) void beam_merge_k(cover_beam_merge_args a, in
             tok = a.cand_tok[(row0 + parent) * a.ld_tok + j];
             cum = a.cum[row0 + parent] + lp;
             feed = tok;
+            if constexpr (KEYED) gk = a.cand_g[(row0 + parent) * a.ld_g + j];
         }
         a.parent_out[row0 + r] = parent;
         a.token_out[row0 + r] = tok;
         a.feed_out[row0 + r] = feed;
         a.cum_out[row0 + r] = cum;
         a.step_lp_out[row0 + r] = lp;
+        if constexpr (KEYED) a.g_out[row0 + r] = gk;
+    }
+    if constexpr (KEYED) {
+        if (threadIdx.x == 0 && a.kappa_out) {         // n2 > B: n2 >= 2 and n2 >= B * B
+            const unsigned long long k = key[B];
+            float kappa = -INFINITY;
+            if (k != ~0ull) {
+                const int c = (int)(unsigned)k, b = c / B;
+                kappa = a.cand_g[(row0 + b) * a.ld_g + (c - b * B)];
+            }
+            a.kappa_out[g] = kappa;
+        }
     }
 }
-hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st) {
-    if (a->groups < 0 || a->B < 1 || a->B > 64 || a->ld_tok < a->B || a->ld_lp < a->B || a->feed_pad < 0) return hipErrorInvalidValue;
-    if (!a->cum || !a->cand_tok || !a->cand_lp || !a->parent_out || !a->token_out || !a->feed_out || !a->cum_out || !a->step_lp_out)
+template <bool KEYED>
+static hipError_t launch_merge(const cover_beam_merge_gumbel_args& a, hipStream_t st) {
+    if (a.groups < 0 || a.B < 1 || a.B > 64 || a.ld_tok < a.B || a.ld_lp < a.B || a.feed_pad < 0) return hipErrorInvalidValue;
+    if (!a.cum || !a.cand_tok || !a.cand_lp || !a.parent_out || !a.token_out || !a.feed_out || !a.cum_out || !a.step_lp_out)
         return hipErrorInvalidValue;
-    if (a->cum == a->cum_out) return hipErrorInvalidValue;
-    if (a->groups == 0) return hipSuccess;
+    if (KEYED && (!a.cand_g || !a.g_out || a.ld_g < a.B)) return hipErrorInvalidValue;
+    if (a.cum == a.cum_out) return hipErrorInvalidValue;
+    if (a.groups == 0) return hipSuccess;
     int n2 = 2;
-    while (n2 < a->B * a->B) n2 <<= 1;
+    while (n2 < a.B * a.B) n2 <<= 1;
     const int threads = n2 / 2 < 64 ? 64 : (n2 / 2 > 1024 ? 1024 : n2 / 2);
-    hipLaunchKernelGGL(beam_merge_k, dim3(a->groups), dim3(threads), 0, st, *a, n2);
+    hipLaunchKernelGGL(beam_merge_k<KEYED>, dim3(a.groups), dim3(threads), 0, st, a, n2);
     return hipGetLastError();
 }
+hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st) {
+    cover_beam_merge_gumbel_args b{};
+    b.cum = a->cum; b.cand_tok = a->cand_tok; b.ld_tok = a->ld_tok; b.cand_lp = a->cand_lp; b.ld_lp = a->ld_lp;
+    b.feed_pad = a->feed_pad; b.groups = a->groups; b.B = a->B;
+    b.parent_out = a->parent_out; b.token_out = a->token_out; b.feed_out = a->feed_out; b.cum_out = a->cum_out; b.step_lp_out = a->step_lp_out;
+    return launch_merge<false>(b, st);
+}
+hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st) { return launch_merge<true>(*a, st); }
 
 // ---------------------------------------------------------------------------------------------------
 // gather: block (row, layer, part) copies 16-byte chunks of one slot of one layer. K [slot][t][Hkv][D]: the n_t token rows are ONE run of

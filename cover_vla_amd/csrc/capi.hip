@@ -403,6 +403,19 @@ int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
            "beam_merge (groups >= 0, 1 <= B <= 64, ld_tok >= B, ld_lp >= B, feed_pad >= 0, every pointer required, cum_out != cum)");
     return COVER_OK;
 }
+int cover_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_beam_merge_gumbel: null args");
+    HIPCHK(launch_beam_merge_gumbel(a, ST(stream)),
+           "beam_merge_gumbel (groups >= 0, 1 <= B <= 64, ld_tok >= B, ld_lp >= B, ld_g >= B, feed_pad >= 0, every pointer but kappa_out required, "
+           "cum_out != cum)");
+    return COVER_OK;
+}
+int cover_gumbel_topn(const cover_gumbel_topn_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_gumbel_topn: null args");
+    HIPCHK(launch_gumbel_topn(a, ST(stream)),
+           "gumbel_topn (every pointer required, 0 <= lo < hi, hi - lo <= 4096, temperature > 0, 1 <= n <= 64, ld_u >= hi - lo, ld_tok / ld_lp / ld_g >= n)");
+    return COVER_OK;
+}
 int cover_kv_gather_slots(const cover_kv_gather_slots_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_kv_gather_slots: null args");
     HIPCHK(launch_kv_gather_slots(a, ST(stream)),
@@ -507,6 +520,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
+    SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args);
 #undef SZ
     return 0;
 }

@@ -90,6 +90,7 @@ hipError_t launch_token_logprob_rows_allowed(const cover_token_logprob_rows_args
 hipError_t launch_token_topn_rows_allowed(const cover_token_topn_rows_args* a, const cover_token_allow* al, hipStream_t st);
 hipError_t launch_token_sample_rows_ref(const cover_token_sample_rows_args* a, const cover_token_allow* al /* nullptr: unmasked */,
                                         const cover_token_ref* ref, hipStream_t st);
+hipError_t launch_gumbel_topn(const cover_gumbel_topn_args* a, hipStream_t st);
 // ---- select.hip ----------------------------------------------------------------------------------
 hipError_t launch_token_select(const cover_token_select_args* a, hipStream_t st);
 hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st);
@@ -104,6 +105,7 @@ hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st)
 size_t gemm_workspace_bytes(int M, int N, int K);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
+hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);
 hipError_t launch_kv_gather_slots(const cover_kv_gather_slots_args* a, hipStream_t st);
 hipError_t launch_beam_backtrack(const cover_beam_backtrack_args* a, hipStream_t st);
 

@@ -28,6 +28,7 @@
 //   per row, M the Q43 kept mass. Error: M as above; each term of S carries the fp32 rounding of x (twice), of expf and of the product.
 #include "common.h"
 #include "kernels.h"
+#include "keysort.h"
 
 typedef unsigned long long u64;
 #define SMP_BINS 2048
@@ -1023,6 +1024,95 @@ __global__ __launch_bounds__(SMP_T) void token_topn_rows_allowed_k(cover_token_t
     topn_rows_block<true>(s, t, a, al);
 }
 
+// ---- cover_gumbel_topn: one step of stochastic beam search for one beam (the formula: include/cover_hip.h) ------------------------------
+// The log-probabilities are token_logprob_k's: kept_set / kept_tiles / scan_bins at (temperature, 0, 1) in that kernel's order, then
+// kept_logprob per column. Behind them the histogram and the candidate list are free, and the same LDS holds the columns' keys and
+// perturbed scores (at most SMP_CAP = 4 * SMP_T columns: four per thread, in registers between the two block reductions).
+union GumbelShared {
+    SampleShared s;
+    struct {
+        u64 key[SMP_CAP];     // (descending image of g~) << 32 | column; a dead child: all ones
+        float g[SMP_CAP];     // g~ by column
+    } t;
+};
+__global__ __launch_bounds__(SMP_T) void gumbel_topn_k(cover_gumbel_topn_args a, int n2) {
+    __shared__ GumbelShared sh;
+    __shared__ float red[16];
+    const int row = blockIdx.x, tid = threadIdx.x, n = a.hi - a.lo;
+    int64_t* tok_o = a.token_out + (size_t)row * a.ld_tok;
+    float* lp_o = a.logprob_out + (size_t)row * a.ld_lp;
+    float* g_o = a.perturbed_out + (size_t)row * a.ld_g;
+    const float phi = a.phi[row], G = a.g_parent[row];
+    if (!finite_f(phi) || !finite_f(G)) {   // a dead beam (block-uniform): nothing of the row is read
+        if (tid < a.n) {
+            tok_o[tid] = -1;
+            lp_o[tid] = -INFINITY;
+            g_o[tid] = -INFINITY;
+        }
+        return;
+    }
+    const float* lg = a.logits + (size_t)row * a.ld + a.lo;
+    SampleSrc src{lg, n, false};
+    const KeptSet ks = kept_set(sh.s, src, 0, 1.0f, a.temperature);
+    kept_tiles(sh.s, src, ks);
+    scan_bins<false, true>(sh.s, SMP_BINS, 1ull);
+    const u64 mass = sh.s.r_mass_total;
+    __syncthreads();   // every thread holds the mass: sh.s is dead from here, sh.t takes its place
+
+    const float* ur = a.uniform + (size_t)row * a.ld_u;
+    float gv[SMP_CAP / SMP_T];
+    float z = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < SMP_CAP / SMP_T; ++k) {
+        const int c = tid + k * SMP_T;
+        float g = -INFINITY;
+        if (c < n) {
+            const float lp = kept_logprob(ks, lg[c], c, mass);
+            if (finite_f(lp)) {
+                const float u = fminf(fmaxf(ur[c], 0x1p-24f), 1.0f - 0x1p-24f);   // fmaxf drops a NaN
+                g = (phi + lp) - logf(-logf(u));
+                if (!finite_f(g)) g = -INFINITY;
+            }
+        }
+        gv[k] = g;
+        z = fmaxf(z, g);
+    }
+    z = block_max(z, red);
+#pragma unroll
+    for (int k = 0; k < SMP_CAP / SMP_T; ++k) {
+        const int c = tid + k * SMP_T;
+        if (c >= n2) continue;
+        const float g = gv[k];
+        float gt = -INFINITY;
+        if (g > -INFINITY) {
+            gt = G;   // g == z: the maximum inherits its parent's score, whatever expf and log1pf make of the formula there
+            if (g != z) {
+                const float v = G - g + log1pf(-expf(g - z));
+                gt = G - fmaxf(0.0f, v) - log1pf(expf(-fabsf(v)));
+            }
+            if (!finite_f(gt)) gt = -INFINITY;
+        }
+        sh.t.key[c] = gt > -INFINITY ? ((u64)desc_key(gt) << 32) | (unsigned)c : ~0ull;
+        if (c < n) sh.t.g[c] = gt;
+    }
+    __syncthreads();
+    bitonic_sort_lds(sh.t.key, n2);
+    if (tid < a.n) {
+        const u64 k = tid < n2 ? sh.t.key[tid] : ~0ull;
+        long long tok = -1;
+        float lp = -INFINITY, gt = -INFINITY;
+        if (k != ~0ull) {
+            const int c = (int)(unsigned)k;   // < n: written above from a live column
+            tok = a.lo + c;
+            lp = kept_logprob(ks, lg[c], c, mass);
+            gt = sh.t.g[c];
+        }
+        tok_o[tid] = tok;
+        lp_o[tid] = lp;
+        g_o[tid] = gt;
+    }
+}
+
 __global__ void fill_i32_k(int* p, int n, int v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -1147,4 +1237,13 @@ hipError_t launch_token_sample_scored(const cover_token_sample_scored_args* a, h
     b.uniform = a->uniform; b.temperature = a->temperature; b.top_k = a->top_k; b.top_p = a->top_p;
     b.token_out = a->token_out; b.logit_out = a->logit_out; b.kept_out = a->kept_out;
     return launch_token_sample_impl(&b, a->logprob_out, st);
+}
+
+hipError_t launch_gumbel_topn(const cover_gumbel_topn_args* a, hipStream_t st) {
+    if (!a->logits || !a->phi || !a->g_parent || !a->uniform || !a->token_out || !a->logprob_out || !a->perturbed_out) return hipErrorInvalidValue;
+    if (!sample_params_ok(a->lo, a->hi, a->rows, a->temperature, 0, 1.0f) || a->hi - a->lo > SMP_CAP) return hipErrorInvalidValue;
+    if (!topn_shape_ok(a->n, a->ld_tok, a->ld_lp) || a->ld_g < a->n || a->ld_u < a->hi - a->lo) return hipErrorInvalidValue;
+    int n2 = 2;
+    while (n2 < a->hi - a->lo) n2 <<= 1;
+    return launch_rows(gumbel_topn_k, a->rows, st, *a, n2);
 }

@@ -390,22 +390,56 @@ class OpenVLA:
         head-major own-token cache has no gather). The loop is launches only (no host read, no allocation) and runs eagerly.
         trace={}: trace["logits"] gets every step's logits clone, trace["beam"] a dict per step of the raw parent / token / cum of the
         merge (and its inputs cand_tok / cand_lp).
-        Out of scope: pi0-FAST, EOS / length handling, allowed sets and grammars, Gumbel (stochastic) beams, slice_action_head (the
-        full head is used whatever that switch says) and hipGraph capture of the loop."""
+        Out of scope: pi0-FAST, EOS / length handling, allowed sets and grammars, slice_action_head (the full head is used whatever
+        that switch says) and hipGraph capture of the loop. stochastic_beam_search is the sampled counterpart."""
+        return self._beam_loop("beam_search", frame_u8, prompt_tokens, prompt_lens, n_beams, trace)[:3]
+
+    def stochastic_beam_search(self, frame_u8: torch.Tensor, prompt_tokens: torch.Tensor, prompt_lens: torch.Tensor, n_beams: int,
+                               uniforms: torch.Tensor, temperature: float = 1.0, *, trace: Optional[dict] = None):
+        """n_beams pairwise DISTINCT action chunks per prompt, an exact sample WITHOUT REPLACEMENT from the policy's sequence distribution
+        -- softmax at `temperature`, unfiltered, over the action bins -- by stochastic beam search (Kool, van Hoof and Welling, 2019), at
+        the cost of a beam search: sample()'s i.i.d. candidates repeat under a peaked head, beam_search()'s are distinct but no sample.
+        Inputs, sizes and ValueErrors as beam_search (the model is built with twice the candidates), plus ValueErrors for uniforms that
+        are not fp32 [n_gen, N, n_bins] on the model's device and for temperature <= 0. uniforms[i, r] perturbs the children of beam r
+        at step i, one number per action bin; at step 0 only the first row of each prompt is live and the other rows' are unused.
+        beam_search's loop with the other list and merge pair: ops.gumbel_topn(n_beams) per row -- each child's perturbed score, the row's
+        Gumbel-perturbed log-probabilities conditioned on their maximum being the beam's own -- and ops.beam_merge_gumbel per prompt, which
+        keeps the n_beams children with the largest perturbed score.
+        Returns (tokens int64 [N, n_gen], logprobs fp32 [N, n_gen], scores fp32 [N], perturbed fp32 [N], kappa fp32 [P]): logprobs under
+        the softmax at `temperature`, scores their fp32 left-to-right sum, perturbed the candidates' final perturbed scores (<= 0,
+        descending within a prompt), kappa the last step's threshold: the perturbed score of the best child that was not kept (-inf if
+        none). Candidate s was included with probability q(s) = 1 - exp(-exp(scores[s] - kappa)), so sum_s exp(scores[s]) / q(s) f(s)
+        over a prompt's candidates estimates the policy's expectation of f (the paper's importance weights).
+        trace={}: as beam_search, each step's dict also holding cand_g, g and kappa.
+        Out of scope: as beam_search."""
+        return self._beam_loop("stochastic_beam_search", frame_u8, prompt_tokens, prompt_lens, n_beams, trace, uniforms, temperature)
+
+    def _beam_loop(self, what, frame_u8, prompt_tokens, prompt_lens, n_beams, trace, uniforms=None, temperature=1.0):
+        """The loop of beam_search (uniforms None: ops.token_topn lists at temperature 1, merged by score) and stochastic_beam_search
+        (ops.gumbel_topn lists, merged by perturbed score): prefill, head, per-row lists, merge, kv_gather_slots, decode pass, back-track.
+        Returns (tokens, logprobs, scores, perturbed, kappa), the last two None without uniforms."""
         dev = self.dev
         P, Lt = prompt_tokens.shape
         B = int(n_beams)
         if not 1 <= B <= 64:
-            raise ValueError(f"beam_search: 1 <= n_beams <= 64 is required (got {n_beams})")
+            raise ValueError(f"{what}: 1 <= n_beams <= 64 is required (got {n_beams})")
         N = P * B
         if self.own_kv is not None:
-            raise ValueError("beam_search: the head-major own-token cache (own_kv) is not supported; build the model with own_kv=None")
+            raise ValueError(f"{what}: the head-major own-token cache (own_kv) is not supported; build the model with own_kv=None")
         if 2 * N > self.max_candidates:
-            raise ValueError(f"beam_search: the own-token K/V ping-pong between two sets of N = {N} slots: build the model with "
+            raise ValueError(f"{what}: the own-token K/V ping-pong between two sets of N = {N} slots: build the model with "
                              f"max_candidates >= {2 * N} (twice the candidates; it has {self.max_candidates})")
         if P > self.max_prompts or Lt > self.max_text:
             raise ValueError("prompts/text length exceed the sizes this model was built for")
         S, T0, lo, hi = self.n_gen, self.T0, self.action_lo, self.action_hi
+        keyed = uniforms is not None
+        if keyed:
+            if not temperature > 0:
+                raise ValueError(f"{what}: temperature > 0 is required (got {temperature})")
+            if uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (S, N, hi - lo) or uniforms.device != torch.device(dev):
+                raise ValueError(f"{what}: uniforms must be fp32 [n_gen, N, n_bins] = [{S}, {N}, {hi - lo}] on {dev} "
+                                 f"(got {uniforms.dtype} {tuple(uniforms.shape)} on {uniforms.device})")
+            uniforms = uniforms.contiguous()
         x = self._prefill(frame_u8, prompt_tokens)
         prompt_of_cand, cand_len, last_row, pos_all = self._cand_rows(prompt_lens, P, Lt, B)
         # ---- everything the loop touches, allocated here
@@ -417,6 +451,10 @@ class OpenVLA:
         cum[0, ::B] = 0.0                                             # the B rows of a prompt carry identical logits at step 0
         cand_tok, cand_lp = torch.empty(N, B, dtype=torch.int64, device=dev), torch.empty(N, B, **f32)
         ent = torch.empty(N, **f32)
+        if keyed:                                                     # the perturbed scores, laid out as cum; a root's is 0
+            pert = torch.full((S + 1, N), float("-inf"), **f32)
+            pert[0, ::B] = 0.0
+            cand_g, kappa = torch.empty(N, B, **f32), torch.empty(P, **f32)
         rows = torch.arange(N, **i32)
         slots = (rows, rows + N)                                      # the candidates' slots of pass parity h
         src_base = tuple(s - s % B for s in (rows + N, rows))         # parity h reads parity 1 - h: (1 - h) N + g B, the parent is added per step
@@ -428,12 +466,20 @@ class OpenVLA:
 
         def head_merge(h, i):
             lg = self._full_head(self._final_norm(h), trace)
-            ops.token_topn(lg, lo, hi, B, 1.0, 0, 1.0, out_tok=cand_tok, out_logprob=cand_lp, out_entropy=ent)
-            ops.beam_merge(cum[i], cand_tok, cand_lp, B, lo, out_parent=parent[i], out_token=token[i], out_feed=feed[i], out_cum=cum[i + 1],
-                           out_step_lp=step_lp[i])
+            outs = dict(out_parent=parent[i], out_token=token[i], out_feed=feed[i], out_cum=cum[i + 1], out_step_lp=step_lp[i])
+            if keyed:
+                ops.gumbel_topn(lg, lo, hi, B, cum[i], pert[i], uniforms[i], temperature, out_tok=cand_tok, out_logprob=cand_lp,
+                                out_perturbed=cand_g)
+                ops.beam_merge_gumbel(cum[i], cand_tok, cand_lp, cand_g, B, lo, out_g=pert[i + 1], out_kappa=kappa, **outs)
+            else:
+                ops.token_topn(lg, lo, hi, B, 1.0, 0, 1.0, out_tok=cand_tok, out_logprob=cand_lp, out_entropy=ent)
+                ops.beam_merge(cum[i], cand_tok, cand_lp, B, lo, **outs)
             if trace is not None:
-                trace.setdefault("beam", []).append(dict(parent=parent[i].clone(), token=token[i].clone(), cum=cum[i + 1].clone(),
-                                                         cand_tok=cand_tok.clone(), cand_lp=cand_lp.clone()))
+                step = dict(parent=parent[i].clone(), token=token[i].clone(), cum=cum[i + 1].clone(),
+                            cand_tok=cand_tok.clone(), cand_lp=cand_lp.clone())
+                if keyed:
+                    step.update(cand_g=cand_g.clone(), g=pert[i + 1].clone(), kappa=kappa.clone())
+                trace.setdefault("beam", []).append(step)
 
         ops.copy_rows(x, self.h_sel, N, self.c["llm_dim"], last_row, None)
         head_merge(self.h_sel[:N], 0)
@@ -452,7 +498,7 @@ class OpenVLA:
             self.llm.forward(xd, [g], final_norm=False)               # writes t = i - 1 itself
             head_merge(xd, i)
         ops.beam_backtrack(parent, token, step_lp, B, out_tokens=out_tokens, out_logprobs=out_lps)
-        return out_tokens, out_lps, cum[S]
+        return out_tokens, out_lps, cum[S], (pert[S] if keyed else None), (kappa if keyed else None)
 
     # ---------------------------------------------------------------------------------------------- de-tokeniser
     def tokens_to_actions(self, tokens: np.ndarray) -> np.ndarray:

@@ -1422,6 +1422,82 @@ def beam_backtrack(parent, token, step_lp, n_beams, out_tokens=None, out_logprob
     return tokens, lps
 
 
+def gumbel_topn(logits, lo, hi, n, phi, g_parent, uniform, temperature=1.0, out_tok=None, out_logprob=None, out_perturbed=None):
+    """One stochastic-beam-search step of every row (cover_gumbel_topn; a row is one beam): its n (1..64) children with the largest
+    perturbed score over columns [lo, hi), hi - lo <= 4096. phi / g_parent fp32 [rows] contiguous: the beam's cumulative log-probability
+    and its own perturbed score (a row where either is not finite is a dead beam: all padding, nothing of it is read); uniform fp32
+    [rows, hi - lo] (unit column stride, any row stride): one number per column, clamped to [2^-24, 1 - 2^-24], NaN counting as 2^-24.
+    Child v has lp = log softmax(logits / temperature) over [lo, hi) (token_logprob's value at (temperature, 0, 1.0), bit for bit),
+    g = (phi + lp) - log(-log(u)) and the perturbed score g~ = G - max(0, v) - log1p(exp(-|v|)), v = G - g + log1p(-exp(g - max g)):
+    the row's Gumbels conditioned on their maximum being g_parent, which the arg-max child inherits exactly. Returns (tokens int64
+    [rows, n] absolute ids, logprobs fp32 [rows, n], perturbed fp32 [rows, n]) ordered by descending g~, equal g~ by ascending column;
+    children whose lp is not finite are left out and the remaining slots are -1 / -inf / -inf. The three out_* ([rows, n], unit column
+    stride, any row stride >= n) are written in place. Deterministic, one launch, recordable."""
+    if not temperature > 0:
+        raise L.CoverError(f"gumbel_topn: temperature > 0 is required (got {temperature})")
+    _chk_range("gumbel_topn", lo, hi)
+    if hi - lo > 4096:
+        raise L.CoverError(f"gumbel_topn: hi - lo <= 4096 is required (got lo={lo}, hi={hi})")
+    n = _chk_topn_n("gumbel_topn", n)
+    rows = _chk_logits("gumbel_topn", logits, hi)
+    if phi is None or g_parent is None or uniform is None:
+        raise L.CoverError("gumbel_topn: phi, g_parent and uniform are required")
+    _chk_rows_out("gumbel_topn", rows, ("phi", phi, torch.float32), ("g_parent", g_parent, torch.float32))
+    if uniform.dtype != torch.float32 or tuple(uniform.shape) != (rows, hi - lo) or (hi - lo > 1 and uniform.stride(1) != 1) or \
+            (rows > 1 and uniform.stride(0) < hi - lo):
+        raise L.CoverError("gumbel_topn: uniform must be fp32 [rows, hi - lo] with unit column stride and a row stride >= hi - lo")
+    outs = (("out_tok", out_tok, torch.int64), ("out_logprob", out_logprob, torch.float32), ("out_perturbed", out_perturbed, torch.float32))
+    _chk_rows_n_out("gumbel_topn", rows, n, *outs)
+    _chk_dev(logits, phi, g_parent, uniform, out_tok, out_logprob, out_perturbed)
+    tok, lp, g = (torch.empty(rows, n, dtype=dt, device=logits.device) if t is None else t for _, t, dt in outs)
+    a = L.GumbelTopnArgs()
+    _fill_rows(a, logits, rows, lo, hi)
+    a.temperature, a.phi, a.g_parent, a.n = temperature, phi.data_ptr(), g_parent.data_ptr(), n
+    a.uniform, a.ld_u = uniform.data_ptr(), max(uniform.stride(0), hi - lo)
+    a.token_out, a.ld_tok = tok.data_ptr(), max(tok.stride(0), n)
+    a.logprob_out, a.ld_lp = lp.data_ptr(), max(lp.stride(0), n)
+    a.perturbed_out, a.ld_g = g.data_ptr(), max(g.stride(0), n)
+    L.check(L.lib().cover_gumbel_topn(C.byref(a), _stream()), "gumbel_topn")
+    return tok, lp, g
+
+
+def beam_merge_gumbel(cum, cand_tok, cand_lp, cand_g, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None,
+                      out_step_lp=None, out_g=None, out_kappa=None):
+    """beam_merge ordered by a stored key (cover_beam_merge_gumbel): cand_g fp32 [rows, n_beams] is gumbel_topn's perturbed list next to
+    its tokens and logprobs. Candidate (b, j) is live iff cum[b] is finite, cand_tok[b][j] >= 0 and cand_lp[b][j] and cand_g[b][j] are
+    finite; output beam r is the r-th live candidate by higher cand_g (the stored float), then lower b, then lower j. Returns (parent,
+    token, feed, cum, step_lp, g, kappa): the first five as beam_merge (cum = cum[b] + cand_lp, one fp32 add), g fp32 [rows] the chosen
+    cand_g (-inf for a dead output), kappa fp32 [rows / n_beams] the cand_g of the group's (n_beams + 1)-th candidate in that order, -inf
+    when there is none: a kept sequence s was included with probability 1 - exp(-exp(cum_s - kappa)). out_cum must not be cum.
+    Deterministic, one launch, recordable."""
+    B = _chk_topn_n("beam_merge_gumbel", n_beams)
+    if cum.dtype != torch.float32 or cum.dim() != 1 or not cum.is_contiguous() or cum.numel() % B != 0:
+        raise L.CoverError("beam_merge_gumbel: cum must be contiguous fp32 [rows], rows a multiple of n_beams")
+    rows = cum.numel()
+    if int(feed_pad) < 0:
+        raise L.CoverError(f"beam_merge_gumbel: feed_pad must be a valid token id (got {feed_pad})")
+    _chk_rows_n_out("beam_merge_gumbel", rows, B, ("cand_tok", cand_tok, torch.int64), ("cand_lp", cand_lp, torch.float32),
+                    ("cand_g", cand_g, torch.float32))
+    outs = (("out_parent", out_parent, torch.int32), ("out_token", out_token, torch.int64), ("out_feed", out_feed, torch.int64),
+            ("out_cum", out_cum, torch.float32), ("out_step_lp", out_step_lp, torch.float32), ("out_g", out_g, torch.float32))
+    _chk_rows_out("beam_merge_gumbel", rows, *outs)
+    _chk_rows_out("beam_merge_gumbel", rows // B, ("out_kappa", out_kappa, torch.float32))
+    _chk_dev(cum, cand_tok, cand_lp, cand_g, out_parent, out_token, out_feed, out_cum, out_step_lp, out_g, out_kappa)
+    if out_cum is not None and out_cum.data_ptr() == cum.data_ptr():
+        raise L.CoverError("beam_merge_gumbel: out_cum must not alias cum")
+    parent, token, feed, cum_o, step_lp, g = (torch.empty(rows, dtype=dt, device=cum.device) if t is None else t for _, t, dt in outs)
+    kappa = torch.empty(rows // B, dtype=torch.float32, device=cum.device) if out_kappa is None else out_kappa
+    a = L.BeamMergeGumbelArgs()
+    a.cum, a.feed_pad, a.groups, a.B = cum.data_ptr(), int(feed_pad), rows // B, B
+    a.cand_tok, a.ld_tok = cand_tok.data_ptr(), max(cand_tok.stride(0), B)
+    a.cand_lp, a.ld_lp = cand_lp.data_ptr(), max(cand_lp.stride(0), B)
+    a.cand_g, a.ld_g = cand_g.data_ptr(), max(cand_g.stride(0), B)
+    a.parent_out, a.token_out, a.feed_out = parent.data_ptr(), token.data_ptr(), feed.data_ptr()
+    a.cum_out, a.step_lp_out, a.g_out, a.kappa_out = cum_o.data_ptr(), step_lp.data_ptr(), g.data_ptr(), kappa.data_ptr()
+    L.check(L.lib().cover_beam_merge_gumbel(C.byref(a), _stream()), "beam_merge_gumbel")
+    return parent, token, feed, cum_o, step_lp, g, kappa
+
+
 # ------------------------------------------------------------------------------------------------ graphs / timers
 class Graph:
     """hipGraph captured from whatever runs on the current stream inside the `with` block."""

@@ -853,6 +853,60 @@ typedef struct cover_beam_backtrack_args {
 } cover_beam_backtrack_args;
 int cover_beam_backtrack(const cover_beam_backtrack_args* args, void* stream);
 
+/* Stochastic beam search (Kool, van Hoof and Welling, 2019): the two launches that turn the beam search above into a sample of B distinct
+ * sequences WITHOUT REPLACEMENT from the policy's sequence distribution at a temperature. A beam carries phi, its cumulative
+ * log-probability, and G, its perturbed score (the root of a group: phi = 0, G = 0). cover_kv_gather_slots and cover_beam_backtrack are
+ * used as they are. No workspace, nothing data-dependent in a launch (recordable), no atomic decides a result.
+ *
+ * cover_gumbel_topn: per row (one beam) the n children with the largest perturbed score. Over columns [lo, hi), hi - lo <= 4096, with
+ * one uniform u_v per column (uniform[row * ld_u + v - lo]), all fp32:
+ *   lp_v = log softmax(logits / temperature)_v over [lo, hi): cover_token_logprob's value at (temperature, top_k 0, top_p 1), bit for bit
+ *   u'_v = fminf(fmaxf(u_v, 2^-24), 1 - 2^-24)                          (a NaN uniform is 2^-24)
+ *   g_v  = (phi + lp_v) - logf(-logf(u'_v))                             a column whose lp_v or g_v is not finite is a dead child
+ *   Z    = max_v g_v
+ *   v_v  = G - g_v + log1pf(-expf(g_v - Z))                             -inf at g_v == Z
+ *   g~_v = G - fmaxf(0, v_v) - log1pf(expf(-|v_v|))                     every column with g_v == Z gets g~_v == G, bit for bit
+ * token_out (absolute ids) / logprob_out (lp_v) / perturbed_out (g~_v), each [rows, n] with its row stride, hold the live children in the
+ * order (g~ descending, column ascending) on the fp32 g~ values of the launch itself (-0 == +0); slots past them are -1 / -inf / -inf.
+ * A row whose phi or g_parent is not finite is a dead beam: no logit and no uniform of it is read, its outputs are all padding.
+ * One 1024-thread block per row; the order is a bitonic sort of unique 64-bit keys (g~ image, column) in LDS.
+ * COVER_EINVAL unless every pointer is set, 0 <= lo < hi, hi - lo <= 4096, rows >= 0, temperature > 0, 1 <= n <= 64,
+ * ld_u >= hi - lo and ld_tok, ld_lp, ld_g >= n. */
+typedef struct cover_gumbel_topn_args {
+    const float* logits; long long ld;           /* fp32 [rows, >= hi] */
+    int rows, lo, hi;
+    float temperature;
+    const float* phi; const float* g_parent;     /* [rows] */
+    const float* uniform; long long ld_u;        /* [rows, hi - lo] */
+    int n, _pad;
+    int64_t* token_out; long long ld_tok;        /* [rows, n] */
+    float* logprob_out; long long ld_lp;         /* [rows, n] */
+    float* perturbed_out; long long ld_g;        /* [rows, n] */
+} cover_gumbel_topn_args;
+int cover_gumbel_topn(const cover_gumbel_topn_args* args, void* stream);
+
+/* cover_beam_merge_gumbel: cover_beam_merge ordered by a stored key in place of the score. cand_g [groups * B, >= B] (row stride ld_g)
+ * is the lists' perturbed_out. Candidate (b, j) is live iff cum[b] is finite, cand_tok[b][j] >= 0 and cand_lp[b][j] and cand_g[b][j]
+ * are finite. Output beam r is the r-th live candidate in the order: higher cand_g first (the stored float, -0 == +0; no arithmetic is
+ * done on it), then lower b, then lower j. parent_out / token_out / feed_out / cum_out (= cum[b] + cand_lp[b][j], ONE fp32 add) /
+ * step_lp_out and their padding are cover_beam_merge's;
+ *   g_out[row]       the chosen candidate's cand_g                                       -inf when fewer than r + 1 are live
+ *   kappa_out[g]     optional, [groups]: the cand_g of the (B + 1)-th candidate of the group in that order, -inf when fewer than B + 1 are
+ *                    live: the threshold of the paper's importance weights -- a returned sequence s was included with probability
+ *                    q(s) = 1 - exp(-exp(phi_s - kappa)), so sum_s p(s) / q(s) f(s) estimates E_p[f]. It falls out of the same sort.
+ * cum and cum_out must not alias. Errors as cover_beam_merge, and ld_g >= B. */
+typedef struct cover_beam_merge_gumbel_args {
+    const float* cum;                          /* [groups * B] */
+    const int64_t* cand_tok; long long ld_tok; /* [groups * B, B] */
+    const float* cand_lp; long long ld_lp;     /* [groups * B, B] */
+    const float* cand_g; long long ld_g;       /* [groups * B, B] */
+    long long feed_pad;
+    int groups, B;
+    int* parent_out; int64_t* token_out; int64_t* feed_out; float* cum_out; float* step_lp_out; float* g_out;   /* [groups * B] each */
+    float* kappa_out;                          /* [groups], optional */
+} cover_beam_merge_gumbel_args;
+int cover_beam_merge_gumbel(const cover_beam_merge_gumbel_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Composite forwards: the per-layer Python loops of the reference (18-layer loop in
  * paligemma_with_expert.py:258-349, HF/timm encoder loops) run here in C++ so that a whole tower / prefill /
