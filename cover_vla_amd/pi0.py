@@ -17,14 +17,57 @@ from __future__ import annotations
 import collections
 import math
 import os
-from typing import Callable, Dict, List, Optional
+from dataclasses import dataclass
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib as L
 from . import ops
-from .models import BF, Decoder, KvGeometry, VitTower, _f32
+from .models import BF, Decoder, KvGeometry, _f32
+from .paligemma import IDENTITY, PaliGemmaPrefix, frames_shared, normalize_state, row_groups, sub_state, unnormalize_action
+
+
+class PrefixPlan(NamedTuple):
+    """Which prefixes one call computes (_prefix_plan): index tensors on the model's device, counts and widths on the host."""
+    U: int                          # distinct (frames, prompt) pairs = prefix slots
+    prompt_of_row: torch.Tensor     # int64 [B]: the slot of each row
+    first_row: torch.Tensor         # int64 [U]: the first row of each slot
+    ic_first: torch.Tensor          # int64 [n_ic]: the first row of each class of camera frames
+    ic_of_group: torch.Tensor       # int64 [U]: the frame class of each slot
+    Lg: int                         # prompt columns the prefix pass runs over (trailing pad trimmed)
+    Lfull: int                      # prompt columns of the call
+
+
+@dataclass
+class _Chain:
+    """One contiguous row group [b0, b1) of the denoise loop: its decoder group and workspace, and (all but the first) its stream."""
+    b0: int
+    b1: int
+    g: object
+    ws: torch.Tensor
+    stream: Optional[torch.cuda.Stream]
+
+
+@dataclass
+class _DenoiseState:
+    """Static buffers of the denoise loop for one (batch size, chains, knobs), and the hipGraph captured over them."""
+    row_prompt: torch.Tensor
+    row_plen: torch.Tensor
+    spos: torch.Tensor
+    slots: torch.Tensor
+    suffix: torch.Tensor
+    x_t: torch.Tensor
+    cat: torch.Tensor
+    hid: torch.Tensor
+    xb: torch.Tensor
+    out32: torch.Tensor
+    tvec: torch.Tensor
+    temb: torch.Tensor
+    chains: List[_Chain]
+    calls: int = 0
+    graph: Optional[ops.Graph] = None
+    Tp: Optional[int] = None        # the prefix width baked into the chains' groups (and into a captured graph)
 
 
 class PI0FlowMatching:
@@ -35,21 +78,17 @@ class PI0FlowMatching:
         self.chunk, self.num_steps = c["chunk"], num_steps
         self.max_state_dim, self.max_action_dim = max_state_dim, max_action_dim
         self.W = c["ex_dim"]
-        self.n_img = (c["image"] // c["patch"]) ** 2
-        self.n_cams = n_cams
         dev = self.dev
-        sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
-        self.vit = VitTower(sub("vision."), dim=c["vit_dim"], layers=c["vit_layers"], heads=c["vit_heads"], mlp=c["vit_mlp"],
-                            patch=c["patch"], act="gelu_tanh", eps=1e-6, device=device)
-        self.projector = ops.pack_linear(sd["projector.weight"].to(dev), sd["projector.bias"])
-        self.embed = sd["lm.embed_tokens.weight"].to(BF).contiguous().to(dev)
+        self.pg = pg = PaliGemmaPrefix(sd, c, device=device, n_cams=n_cams)
+        self.vit, self.projector, self.embed, self.emb_scale = pg.vit, pg.projector, pg.embed, pg.emb_scale
+        self.n_img, self.n_cams = pg.n_img, n_cams
         self.Tp_cap = self.n_img * n_cams + max_lang
         S = 1 + self.chunk
         geom = KvGeometry(c["Hkv"], c["D"], [max_prompts, max_batch], [self.Tp_cap, S])
         n_pos = self.Tp_cap + S + 8
-        self.lm = Decoder(sub("lm."), dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"],
+        self.lm = Decoder(sub_state(sd, "lm."), dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"],
                           act="gelu_tanh", norm="gemma", eps=1e-6, rope="pi0", n_pos=n_pos, device=device, cache=geom)
-        self.expert = Decoder(sub("expert."), dim=c["ex_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"],
+        self.expert = Decoder(sub_state(sd, "expert."), dim=c["ex_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"],
                               mlp=c["ex_mlp"], act="gelu_tanh", norm="gemma", eps=1e-6, rope="pi0", n_pos=n_pos, device=device,
                               share_cache_with=self.lm, final_norm_bf16=False)
         # pi0's own projections stay fp32 (modeling_pi0.py:488-494)
@@ -58,24 +97,13 @@ class PI0FlowMatching:
         self.vis_len = torch.tensor([1] + [S] * self.chunk, dtype=torch.int32, device=dev)
         self.max_batch, self.max_prompts, self.max_lang = max_batch, max_prompts, max_lang
         self._den = {}     # static buffers (+ hipGraph) of the denoise loop per (batch size, chains)
-        # denoise loop: independent row-group chains on streams of their own, replayed as one hipGraph (see sample_actions)
+        # denoise loop: independent row-group chains on streams of their own, replayed as one hipGraph (see _denoise_state)
         self.n_chains = int(os.environ.get("COVER_PI0_CHAINS", "1"))
         self.denoise_graph = os.environ.get("COVER_PI0_GRAPH", "1") != "0"
         self._fold = {}    # folded suffix-embedding constants per step size (_suffix_fold)
         self._cap = None   # capture stream
 
     # ---------------------------------------------------------------------------------------------- prefix
-    def _image_tokens(self, img: torch.Tensor) -> torch.Tensor:
-        """img fp32 [n,3,H,W] in [-1,1] -> bf16 [n, n_img, lm_dim]: tower -> projector -> (/sqrt(D))*bf16(sqrt(D))
-        (modeling_pi0.py:529-538 with HF-4.48.3 get_image_features; Appendix A.3 double rounding)."""
-        x = self.vit.embed(img.float().contiguous())
-        x = self.vit.forward(x, post_ln=True)
-        n, T, _ = x.shape
-        D = self.c["lm_dim"]
-        y = ops.gemm(x.view(n * T, -1), self.projector)
-        ops.scale_bf16(y, D ** 0.5, float(torch.tensor(D ** 0.5, dtype=BF)))
-        return y.view(n, T, D)
-
     @staticmethod
     def _image_classes(cams: List[torch.Tensor], B: int) -> np.ndarray:
         """Equality classes of the rows' camera frames (all cameras together): int64 [B], class ids in order of first
@@ -83,7 +111,7 @@ class PI0FlowMatching:
         VERIFIED element-wise against its first row, so a collision can only split work, never merge different frames."""
         if B == 1:
             return np.zeros(1, dtype=np.int64)
-        if all(bool(torch.equal(im[:1].expand_as(im), im)) for im in cams):
+        if all(frames_shared(im) for im in cams):
             return np.zeros(B, dtype=np.int64)                                   # the evaluation driver's case: one frame
         fps = []
         for im in cams:
@@ -132,19 +160,49 @@ class PI0FlowMatching:
         self._fold[key] = f
         return f
 
+    # ---------------------------------------------------------------------------------------------- sample_actions and its steps
     def sample_actions(self, images: List[torch.Tensor], img_masks: List[torch.Tensor], lang_tokens: torch.Tensor,
                        lang_masks: torch.Tensor, state: torch.Tensor, noise: Optional[torch.Tensor] = None,
                        noise_std: float = 1.0, trace: Optional[dict] = None, on_prefix_enqueued: Optional[Callable] = None) -> torch.Tensor:
         """on_prefix_enqueued (optional): called once the vision tower + prefix pass are queued and before the Euler loop (bench.py's
         profiled decision splits its kernel timers there; not part of the reference's signature)."""
-        dev, c = self.dev, self.c
         B = state.shape[0]
         Lg = lang_tokens.shape[1]
         if B > self.max_batch or Lg > self.max_lang or len(images) != len(img_masks):
             raise ValueError(f"batch {B}/lang {Lg}/cams {len(images)} exceed the sizes this model was built for")
         if noise is None:
             noise = torch.normal(mean=0.0, std=noise_std, size=(B, self.chunk, self.max_action_dim), dtype=torch.float32,
-                                 device=dev)
+                                 device=self.dev)
+        cams, out = self._by_camera_pattern(images, img_masks, lang_tokens, lang_masks, state, noise, noise_std, trace)
+        if out is not None:
+            return out
+        plan = self._prefix_plan(cams, lang_tokens, lang_masks)
+        Tp, plen = self._prefill(plan, cams, lang_tokens, lang_masks, trace)
+        if on_prefix_enqueued is not None:
+            on_prefix_enqueued()
+        n_ch = 1 if trace is not None else max(1, min(self.n_chains, B))
+        # (the A/B knobs that are read per call are part of the key: a captured graph has their value baked in)
+        knobs = (os.environ.get("COVER_PI0_SUFFIX_FOLD", "1"), os.environ.get("COVER_QKV_FOLD", "1"))
+        st = self._denoise_state(B, n_ch, knobs, Tp)
+        return self._run_denoise(st, plan.prompt_of_row, plen, state, noise, knobs[0] != "0", trace)
+
+    @staticmethod
+    def _camera_parts(img_masks: List[torch.Tensor], B: int) -> List[Tuple[np.ndarray, List[int]]]:
+        """The rows of the batch partitioned by their camera pattern: [(rows int64, the cameras those rows have)], disjoint and
+        covering every row. ValueError for a row without any camera."""
+        mk_h = torch.stack([m.to(torch.bool).reshape(-1) for m in img_masks], dim=1).cpu().numpy()            # [B, cameras]
+        if mk_h.shape[0] != B:
+            raise ValueError("img_masks must have one entry per batch row")
+        parts = []
+        for pat in np.unique(mk_h, axis=0):
+            if not pat.any():
+                raise ValueError("every camera is masked out")
+            parts.append((np.nonzero((mk_h == pat[None]).all(axis=1))[0], [ci for ci in range(len(img_masks)) if pat[ci]]))
+        return parts
+
+    def _by_camera_pattern(self, images, img_masks, lang_tokens, lang_masks, state, noise, noise_std, trace):
+        """-> (cams, None): the cameras every row has; or (None, out): the rows differ, and out is the chunk of every row sampled
+        with the rows of its own pattern."""
         # ---- cameras: the reference marks an absent camera with an all-False mask over an all -1 image
         # (modeling_pi0.py:372-385); its tokens are padding -- never attended by a valid query, positions do not advance
         # over them (cumsum of the pad mask, :685), their own rows are never read back -- so dropping that camera from the
@@ -152,73 +210,74 @@ class PI0FlowMatching:
         # Masks that differ across the rows of one camera (embed_prefix carries them per row, :529-547; the CoVer driver never produces
         # them): the same argument row by row -- the rows are partitioned by their camera pattern and every part is sampled with
         # exactly its present cameras (its own prefix width; same noise rows, so the parts are what one call would have produced).
-        mk_h = torch.stack([m.to(torch.bool).reshape(-1) for m in img_masks], dim=1).cpu().numpy()            # [B, cameras]
-        if mk_h.shape[0] != B:
-            raise ValueError("img_masks must have one entry per batch row")
-        pats = np.unique(mk_h, axis=0)
-        if pats.shape[0] > 1:
+        dev = self.dev
+        parts = self._camera_parts(img_masks, state.shape[0])
+        if len(parts) > 1:
             if trace is not None:
                 raise NotImplementedError("trace with camera masks that differ across rows")
-            out = torch.empty(B, self.chunk, self.max_action_dim, dtype=torch.float32, device=dev)
-            for pat in pats:
-                if not pat.any():
-                    raise ValueError("every camera is masked out")
-                idx = torch.from_numpy(np.nonzero((mk_h == pat[None]).all(axis=1))[0]).to(dev)
-                on = [ci for ci in range(len(images)) if pat[ci]]
+            out = torch.empty(state.shape[0], self.chunk, self.max_action_dim, dtype=torch.float32, device=dev)
+            for rows, on in parts:
+                idx = torch.from_numpy(rows).to(dev)
                 ones = torch.ones(idx.numel(), dtype=torch.bool, device=dev)
                 out[idx] = self.sample_actions([images[ci][idx] for ci in on], [ones for _ in on], lang_tokens[idx], lang_masks[idx],
                                                state[idx], noise=noise[idx], noise_std=noise_std)
-            return out
-        cams = [im for ci, im in enumerate(images) if pats[0][ci]]
-        if not cams:
-            raise ValueError("every camera is masked out")
+            return None, out
+        cams = [images[ci] for ci in parts[0][1]]
         if len(cams) > self.n_cams:
             raise ValueError(f"{len(cams)} cameras > n_cams={self.n_cams} this model was built for")
+        return cams, None
+
+    def _prefix_plan(self, cams: List[torch.Tensor], lang_tokens: torch.Tensor, lang_masks: torch.Tensor) -> PrefixPlan:
+        """Host bookkeeping of one call: which (frames, prompt) pairs are distinct and how many prompt columns the prefix pass needs."""
+        dev = self.dev
+        B, Lfull = lang_tokens.shape
         # ---- dedup (index bookkeeping): a prefix is computed once per distinct (camera frames, prompt) pair, the SigLIP
         # tower once per distinct set of camera frames
         # (on the host: the count U is needed there anyway, and a device row-sort of B x 2Lg integers costs ~0.6 ms of
         # rocprim kernels against ~50 us for the round trip of a few tens of KB)
         img_class = self._image_classes(cams, B)                                   # host int64 [B], 0 for a shared frame
         key = torch.cat([lang_tokens, lang_masks.to(lang_tokens.dtype)], dim=1).cpu().numpy()
-        key = np.concatenate([img_class[:, None].astype(key.dtype), key], axis=1)
-        _, first_h, inv_h = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        first_h, slot_h = row_groups(img_class, key)
         U = int(first_h.shape[0])
         if U > self.max_prompts:
             raise ValueError(f"{U} distinct (frames, prompt) pairs > max_prompts={self.max_prompts}")
-        prompt_of_row = torch.from_numpy(np.ascontiguousarray(inv_h.reshape(-1)).astype(np.int64)).to(dev)
-        first_row = torch.from_numpy(np.ascontiguousarray(first_h).astype(np.int64)).to(dev)
+        prompt_of_row = torch.from_numpy(slot_h).to(dev)
+        first_row = torch.from_numpy(first_h).to(dev)
         n_ic = int(img_class.max()) + 1
         ic_first = torch.from_numpy(np.array([int(np.nonzero(img_class == k)[0][0]) for k in range(n_ic)], dtype=np.int64)).to(dev)
         ic_of_group = torch.from_numpy(img_class[first_h].astype(np.int64)).to(dev)
-        n_img_all = self.n_img * len(cams)
         # ---- trailing pad columns: the tokenizer pads every prompt on the right to max_length (modeling_pi0.py:398-407: L = 48..72 for
         # ~20 real tokens). A pad token is never a key (pad mask, :547-560 / :731-735), positions do not advance over it (:685) and its own
         # rows are never read back, so the prefix pass only needs the columns up to the longest real prompt of the batch: at P1 sizes
         # 8 x (256 + 23) = 2232 rows instead of 8 x 328 = 2624. Only when every mask row is a contiguous run from column 0 (checked
         # on the host copy that the dedup above already made); otherwise all L columns are kept.
-        Lfull = Lg
-        mh = key[:, 1 + Lg:] != 0
+        Lg = Lfull
+        mh = key[:, Lfull:] != 0
         lens_h = mh.sum(axis=1)
-        if os.environ.get("COVER_PI0_TRIM_PAD", "1") != "0" and bool(np.array_equal(mh, np.arange(Lg)[None, :] < lens_h[:, None])):
+        if os.environ.get("COVER_PI0_TRIM_PAD", "1") != "0" and bool(np.array_equal(mh, np.arange(Lfull)[None, :] < lens_h[:, None])):
             Lg = max(int(lens_h.max()), 1)
-            lang_tokens, lang_masks = lang_tokens[:, :Lg], lang_masks[:, :Lg]
+        return PrefixPlan(U, prompt_of_row, first_row, ic_first, ic_of_group, Lg, Lfull)
+
+    def _prefill(self, plan: PrefixPlan, cams, lang_tokens, lang_masks, trace) -> Tuple[int, torch.Tensor]:
+        """Assemble the plan's U prefixes (image tokens of every camera, then the prompt's embeddings) and run the prefix pass over them.
+        -> (Tp: the prefix width, plen int32 [U]: the valid keys of each prefix)."""
+        dev, pg = self.dev, self.pg
+        U, Lg = plan.U, plan.Lg
+        lang_tokens, lang_masks = lang_tokens[:, :Lg], lang_masks[:, :Lg]
+        n_img_all = self.n_img * len(cams)
         Tp = n_img_all + Lg
-        D = c["lm_dim"]
+        D = pg.D
         prefix = torch.empty(U, Tp, D, dtype=BF, device=dev)
         for ci, im in enumerate(cams):
-            tok = self._image_tokens(im[ic_first])  # [n_ic, n_img, D]
-            rows = torch.arange(self.n_img, device=dev)
-            sidx = (rows[None] + ic_of_group[:, None] * self.n_img).reshape(-1)
-            didx = (torch.arange(U, device=dev)[:, None] * Tp + ci * self.n_img + rows[None]).reshape(-1)
-            ops.copy_rows(tok.view(-1, D), prefix.view(-1, D), U * self.n_img, D, sidx.to(torch.int32), didx.to(torch.int32))
-        utok = lang_tokens[first_row].contiguous()
-        umask = lang_masks[first_row]
+            tok = pg.image_tokens(im[plan.ic_first])  # [n_ic, n_img, D]
+            pg.place(prefix, ci * self.n_img, tok, by_index=True, src_of_slot=plan.ic_of_group)
+        utok = lang_tokens[plan.first_row].contiguous()
+        umask = lang_masks[plan.first_row]
         lang = ops.embed_gather(self.embed, utok.view(-1), math.sqrt(D))
-        didx = (torch.arange(U, device=dev)[:, None] * Tp + n_img_all + torch.arange(Lg, device=dev)[None]).reshape(-1)
-        ops.copy_rows(lang, prefix.view(-1, D), U * Lg, D, None, didx.to(torch.int32))
+        pg.place(prefix, n_img_all, lang.view(U, Lg, D), by_index=True)
         if trace is not None:   # at the reference's full width (trimmed pad columns: zeros)
-            pe = torch.zeros(B, n_img_all + Lfull, D, dtype=BF, device=dev)
-            pe[:, :Tp] = prefix[prompt_of_row]
+            pe = torch.zeros(lang_tokens.shape[0], n_img_all + plan.Lfull, D, dtype=BF, device=dev)
+            pe[:, :Tp] = prefix[plan.prompt_of_row]
             trace["prefix_embs"] = pe
         # lengths / positions (prompts are right padded: valid keys are a contiguous prefix)
         plen = (n_img_all + umask.sum(dim=1)).to(torch.int32)
@@ -226,9 +285,11 @@ class PI0FlowMatching:
         ppos = (torch.cumsum(pad, dim=1) - 1).clamp(min=0).to(torch.int32).contiguous()
         g0 = self.lm.group(U, Tp, ppos.view(-1), [dict(region=0, length=Tp, len_of_batch=plen)], 0)
         self.lm.forward(prefix.view(U * Tp, D), [g0], final_norm=False)
-        if on_prefix_enqueued is not None:
-            on_prefix_enqueued()
+        return Tp, plen
 
+    def _denoise_state(self, B: int, n_ch: int, knobs: Tuple[str, str], Tp: int) -> _DenoiseState:
+        """The static buffers and chains of the denoise loop for this (batch size, chains, knobs): built on the first call, counted on
+        every call, and re-pointed (graph dropped) when the prefix width changes."""
         # ---- denoise loop (modeling_pi0.py:697-752). The rows of the batch never interact inside it (every row attends its own prompt's prefix
         # and its own suffix), and at B = 40 a layer-step is eight dependent launches of <= 224 workgroups that last 5-15 us each: the chip is
         # mostly fill and drain. The batch is therefore cut into `n_chains` contiguous row groups, each an independent chain of launches on a
@@ -240,123 +301,116 @@ class PI0FlowMatching:
         # 2 chains 29.7-30.3, 4 chains 40.4-41.5, 8 chains 54.6-55.1 -- the branches of the graph do not overlap: a launch at 100 rows lasts
         # nearly as long as one at 200 (it is fill / drain and a dependent round trip either way) and the branches overlap little, so the
         # decision grows with the number of launches. The default is therefore ONE chain, replayed.
-        S, W, A = 1 + self.chunk, self.W, self.max_action_dim
-        n_ch = max(1, min(self.n_chains, B))
-        if trace is not None:
-            n_ch = 1
-        # (the A/B knobs that are read per call are part of the key: a captured graph has their value baked in)
-        knobs = (os.environ.get("COVER_PI0_SUFFIX_FOLD", "1"), os.environ.get("COVER_QKV_FOLD", "1"))
+        dev = self.dev
+        S, W, A, chunk = 1 + self.chunk, self.W, self.max_action_dim, self.chunk
         st = self._den.get((B, n_ch, knobs))
         if st is None:
-            st = dict(calls=0, graph=None, ws_gen=-1,
-                      row_prompt=torch.empty(B, dtype=torch.int32, device=dev), row_plen=torch.empty(B, dtype=torch.int32, device=dev),
-                      spos=torch.empty(B, S, dtype=torch.int32, device=dev),
-                      slots=torch.arange(B, dtype=torch.int32, device=dev),
-                      suffix=torch.empty(B, S, W, dtype=torch.float32, device=dev),
-                      x_t=torch.empty(B, self.chunk, A, dtype=torch.float32, device=dev),
-                      cat=torch.empty(B * self.chunk, 2 * W, dtype=torch.float32, device=dev),
-                      hid=torch.empty(B * self.chunk, W, dtype=torch.float32, device=dev),
-                      xb=torch.empty(B * S, W, dtype=BF, device=dev), out32=torch.empty(B, S, W, dtype=torch.float32, device=dev),
-                      tvec=torch.empty(B * self.chunk, dtype=torch.float32, device=dev),
-                      temb=torch.empty(B * self.chunk, W, dtype=BF, device=dev))
+            f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+            i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+            st = _DenoiseState(row_prompt=i32(B), row_plen=i32(B), spos=i32(B, S), slots=torch.arange(B, dtype=torch.int32, device=dev),
+                               suffix=f32(B, S, W), x_t=f32(B, chunk, A), cat=f32(B * chunk, 2 * W), hid=f32(B * chunk, W),
+                               xb=torch.empty(B * S, W, dtype=BF, device=dev), out32=f32(B, S, W), tvec=f32(B * chunk),
+                               temb=torch.empty(B * chunk, W, dtype=BF, device=dev), chains=[])
             cuts = [(B * i) // n_ch for i in range(n_ch + 1)]
-            st["chains"] = []
             for ci in range(n_ch):
                 b0, b1 = cuts[ci], cuts[ci + 1]
-                sl = st["slots"][b0:b1]
-                g = self.expert.group(b1 - b0, S, st["spos"][b0:b1].view(-1),
-                                      [dict(region=0, length=Tp, len_of_batch=st["row_plen"][b0:b1], slot_of_batch=st["row_prompt"][b0:b1]),
+                sl = st.slots[b0:b1]
+                g = self.expert.group(b1 - b0, S, st.spos[b0:b1].view(-1),
+                                      [dict(region=0, length=Tp, len_of_batch=st.row_plen[b0:b1], slot_of_batch=st.row_prompt[b0:b1]),
                                        dict(region=1, length=S, mask=ops.MASK_VISLEN, vis_len=self.vis_len, slot_of_batch=sl)], 1,
                                       write_slot=sl)   # suffix K/V: per-step temporaries in the rows' own slots
-                st["chains"].append(dict(b0=b0, b1=b1, g=g, ws=self.expert.workspace((b1 - b0) * S),
-                                         stream=torch.cuda.Stream(device=dev) if ci > 0 else None))
+                st.chains.append(_Chain(b0, b1, g, self.expert.workspace((b1 - b0) * S), torch.cuda.Stream(device=dev) if ci > 0 else None))
             self._den[(B, n_ch, knobs)] = st
-        st["calls"] += 1
-        if st.get("Tp") != Tp:                      # the prefix width is baked into the groups (and into a captured graph)
-            for ch in st["chains"]:
-                ch["g"].segs[0].len = Tp
-            st["Tp"], st["graph"] = Tp, None
-        st["row_prompt"].copy_(prompt_of_row)
-        st["row_plen"].copy_(plen[prompt_of_row])
-        st["spos"].copy_(st["row_plen"][:, None] + torch.arange(S, device=dev, dtype=torch.int32)[None])
-        suffix, x_t, cat, hid, xb, out32, tvec, temb = (st[k] for k in ("suffix", "x_t", "cat", "hid", "xb", "out32", "tvec", "temb"))
+        st.calls += 1
+        if st.Tp != Tp:                             # the prefix width is baked into the groups (and into a captured graph)
+            for ch in st.chains:
+                ch.g.segs[0].len = Tp
+            st.Tp, st.graph = Tp, None
+        return st
+
+    def _euler_chain(self, st: _DenoiseState, ch: _Chain, fold, dt: float, trace, vs: list):
+        """The whole Euler loop for the rows [b0, b1) of the batch, queued on the current stream."""
+        S, W, A, ch_rows = 1 + self.chunk, self.W, self.max_action_dim, self.chunk
+        b0, b1 = ch.b0, ch.b1
+        n = b1 - b0
+        x_c, hid_c, suf_c = st.x_t[b0:b1], st.hid[b0 * ch_rows:b1 * ch_rows], st.suffix[b0:b1]
+        xb_c, out_c = st.xb[b0 * S:b1 * S], st.out32[b0:b1]
+        # the reference loops `while time >= -dt/2` on an fp32 tensor: exactly num_steps iterations (modeling_pi0.py:697-715)
+        time = torch.tensor(1.0, dtype=torch.float32)
+        dt32 = torch.tensor(dt, dtype=torch.float32)
+        step = 0
+        while time >= -dt32 / 2:
+            if fold is not None:
+                # embed_suffix (modeling_pi0.py:569-629) with its two linear maps in front of the SiLU folded (see _suffix_fold):
+                # hid = silu(x_t Wc^T + c_step): two launches per step instead of six
+                ops.gemm_f32(x_c.view(n * ch_rows, A), fold["Wc"], bias=fold["ctab"][step], act="silu", out=hid_c)
+            else:
+                rows = slice(b0 * ch_rows, b1 * ch_rows)
+                tv_c, te_c, cat_c = st.tvec[rows], st.temb[rows], st.cat[rows]
+                tv_c.fill_(float(time))
+                ops.sincos_time_embed(tv_c, W, 4e-3, 4.0, out=te_c)
+                ops.cast_bf16_to_f32(te_c, out=cat_c[:, W:])
+                ops.gemm_f32(x_c.view(n * ch_rows, A), self.p["action_in_proj"][0], bias=self.p["action_in_proj"][1], out=cat_c[:, :W])
+                ops.gemm_f32(cat_c, self.p["action_time_mlp_in"][0], bias=self.p["action_time_mlp_in"][1], act="silu", out=hid_c)
+            step += 1
+            wo, bo = self.p["action_time_mlp_out"]
+            ops.gemm_f32_raw(hid_c.data_ptr(), W, 1, wo.data_ptr(), W, 1, suf_c.data_ptr() + 4 * W, W, ch_rows, W, W,
+                             bias=bo, batch=n, a_bs=ch_rows * W, c_bs=S * W)  # rows 1..chunk of every suffix
+            if trace is not None and not vs:
+                trace["suffix_embs_t1"] = st.suffix.clone()
+            self.expert.forward(xb_c, [ch.g], final_norm=True, x_f32=suf_c.view(n * S, W), ws=ch.ws)
+            ops.cast_bf16_to_f32(xb_c, out=out_c.view(n * S, W))
+            # v_t = action_out_proj(suffix_out[:, -chunk:]) ; x_t += dt * v_t   (modeling_pi0.py:748-751, 713)
+            wp, bp = self.p["action_out_proj"]
+            ops.gemm_f32_raw(out_c.data_ptr() + 4 * W, W, 1, wp.data_ptr(), W, 1, x_c.data_ptr(), A, ch_rows, A, W,
+                             bias=bp, residual_ptr=x_c.data_ptr(), ld_res=A, alpha=float(dt32), batch=n, a_bs=S * W,
+                             c_bs=ch_rows * A)
+            if trace is not None:
+                vs.append(st.x_t.clone())
+            time = time + dt32
+
+    def _euler_fork_join(self, st: _DenoiseState, fold, dt: float, trace, vs: list):
+        """Every chain's Euler loop: chains 1.. on their own streams, forked from and joined to the current one."""
+        cur = torch.cuda.current_stream()
+        for ch in st.chains[1:]:
+            ch.stream.wait_stream(cur)
+            with torch.cuda.stream(ch.stream):
+                self._euler_chain(st, ch, fold, dt, trace, vs)
+        self._euler_chain(st, st.chains[0], fold, dt, trace, vs)
+        for ch in st.chains[1:]:
+            cur.wait_stream(ch.stream)
+
+    def _run_denoise(self, st: _DenoiseState, prompt_of_row, plen, state, noise, use_fold: bool, trace) -> torch.Tensor:
+        """Load this call's rows into the static buffers, then the Euler loop: eager on the state's first call (and always with a
+        trace or denoise_graph off), captured on the second, replayed from then on. -> x_0 fp32 [B, chunk, max_action_dim]."""
+        dev = self.dev
+        B, S, W = state.shape[0], 1 + self.chunk, self.W
+        st.row_prompt.copy_(prompt_of_row)
+        st.row_plen.copy_(plen[prompt_of_row])
+        st.spos.copy_(st.row_plen[:, None] + torch.arange(S, device=dev, dtype=torch.int32)[None])
         stp = ops.gemm_f32(state.float().contiguous(), self.p["state_proj"][0], bias=self.p["state_proj"][1])
-        ops.cast_bf16_to_f32(ops.cast_f32_to_bf16(stp), out=suffix.view(B, S * W)[:, :W])  # bf16-rounded state token
-        x_t.copy_(noise.to(torch.float32))
+        ops.cast_bf16_to_f32(ops.cast_f32_to_bf16(stp), out=st.suffix.view(B, S * W)[:, :W])  # bf16-rounded state token
+        st.x_t.copy_(noise.to(torch.float32))
         dt = -1.0 / self.num_steps
+        fold = self._suffix_fold(dt) if use_fold else None
         vs = []
-
-        fold = self._suffix_fold(dt) if os.environ.get("COVER_PI0_SUFFIX_FOLD", "1") != "0" else None
-        ch_rows = self.chunk
-
-        def euler_chain(ch):
-            """The whole Euler loop for the rows [b0, b1) of the batch, queued on the current stream."""
-            b0, b1 = ch["b0"], ch["b1"]
-            n = b1 - b0
-            x_c, hid_c, suf_c = x_t[b0:b1], hid[b0 * ch_rows:b1 * ch_rows], suffix[b0:b1]
-            xb_c, out_c = xb[b0 * S:b1 * S], out32[b0:b1]
-            # the reference loops `while time >= -dt/2` on an fp32 tensor: exactly num_steps iterations (modeling_pi0.py:697-715)
-            time = torch.tensor(1.0, dtype=torch.float32)
-            dt32 = torch.tensor(dt, dtype=torch.float32)
-            step = 0
-            while time >= -dt32 / 2:
-                if fold is not None:
-                    # embed_suffix (modeling_pi0.py:569-629) with its two linear maps in front of the SiLU folded (see _suffix_fold):
-                    # hid = silu(x_t Wc^T + c_step): two launches per step instead of six
-                    ops.gemm_f32(x_c.view(n * ch_rows, A), fold["Wc"], bias=fold["ctab"][step], act="silu", out=hid_c)
-                else:
-                    tv_c, te_c, cat_c = tvec[b0 * ch_rows:b1 * ch_rows], temb[b0 * ch_rows:b1 * ch_rows], cat[b0 * ch_rows:b1 * ch_rows]
-                    tv_c.fill_(float(time))
-                    ops.sincos_time_embed(tv_c, W, 4e-3, 4.0, out=te_c)
-                    ops.cast_bf16_to_f32(te_c, out=cat_c[:, W:])
-                    ops.gemm_f32(x_c.view(n * ch_rows, A), self.p["action_in_proj"][0], bias=self.p["action_in_proj"][1], out=cat_c[:, :W])
-                    ops.gemm_f32(cat_c, self.p["action_time_mlp_in"][0], bias=self.p["action_time_mlp_in"][1], act="silu", out=hid_c)
-                step += 1
-                wo, bo = self.p["action_time_mlp_out"]
-                ops.gemm_f32_raw(hid_c.data_ptr(), W, 1, wo.data_ptr(), W, 1, suf_c.data_ptr() + 4 * W, W, ch_rows, W, W,
-                                 bias=bo, batch=n, a_bs=ch_rows * W, c_bs=S * W)  # rows 1..chunk of every suffix
-                if trace is not None and not vs:
-                    trace["suffix_embs_t1"] = suffix.clone()
-                self.expert.forward(xb_c, [ch["g"]], final_norm=True, x_f32=suf_c.view(n * S, W), ws=ch["ws"])
-                ops.cast_bf16_to_f32(xb_c, out=out_c.view(n * S, W))
-                # v_t = action_out_proj(suffix_out[:, -chunk:]) ; x_t += dt * v_t   (modeling_pi0.py:748-751, 713)
-                wp, bp = self.p["action_out_proj"]
-                ops.gemm_f32_raw(out_c.data_ptr() + 4 * W, W, 1, wp.data_ptr(), W, 1, x_c.data_ptr(), A, ch_rows, A, W,
-                                 bias=bp, residual_ptr=x_c.data_ptr(), ld_res=A, alpha=float(dt32), batch=n, a_bs=S * W,
-                                 c_bs=ch_rows * A)
-                if trace is not None:
-                    vs.append(x_t.clone())
-                time = time + dt32
-
-        def euler_loop():
-            cur = torch.cuda.current_stream()
-            for ch in st["chains"][1:]:
-                ch["stream"].wait_stream(cur)
-                with torch.cuda.stream(ch["stream"]):
-                    euler_chain(ch)
-            euler_chain(st["chains"][0])
-            for ch in st["chains"][1:]:
-                cur.wait_stream(ch["stream"])
-
-        use_graph = trace is None and self.denoise_graph and st["calls"] >= 2
-        if not use_graph:
-            euler_loop()
+        if trace is not None or not self.denoise_graph or st.calls < 2:
+            self._euler_fork_join(st, fold, dt, trace, vs)
         else:
-            if st["graph"] is None:
+            if st.graph is None:
                 cur = torch.cuda.current_stream()
                 if self._cap is None:
                     self._cap = torch.cuda.Stream(device=dev)
                 self._cap.wait_stream(cur)
                 with torch.cuda.stream(self._cap):
                     with ops.Graph() as gr:
-                        euler_loop()
+                        self._euler_fork_join(st, fold, dt, trace, vs)
                 cur.wait_stream(self._cap)
-                st["graph"] = gr
-            st["graph"].launch()
-        x_t = x_t.clone()   # the static buffer is overwritten by the next decision
+                st.graph = gr
+            st.graph.launch()
         if trace is not None:
             trace["x_steps"] = vs
-        return x_t
+        return st.x_t.clone()   # the static buffer is overwritten by the next decision
 
 
 # --------------------------------------------------------------------------------------------------- policy wrapper
@@ -407,22 +461,6 @@ class PI0Policy:
         self._norm = {k: (m, mv(a), mv(b)) for k, (m, a, b) in norm.items()}
         self._preprocess_adapter = None
         self.reset()
-
-    def _normalize_state(self, x):
-        mode, a, b = self._norm.get("state", ("IDENTITY", None, None))
-        if mode == "MEAN_STD":
-            return (x - a) / (b + 1e-8)                       # normalize.py:169
-        if mode == "MIN_MAX":
-            return (x - a) / (b - a + 1e-8) * 2 - 1           # :177-179
-        return x
-
-    def _unnormalize_action(self, x):
-        mode, a, b = self._norm.get("action", ("IDENTITY", None, None))
-        if mode == "MEAN_STD":
-            return x * b + a                                  # :243
-        if mode == "MIN_MAX":
-            return (x + 1) / 2 * (b - a) + a                  # :250-251
-        return x
 
     @classmethod
     def from_pretrained(cls, pretrained_name_or_path: str, *, tokenizer: Callable, device="cuda:0", max_batch=64,
@@ -494,13 +532,13 @@ class PI0Policy:
     def select_action(self, batch: dict, noise: Optional[torch.Tensor] = None, noise_std: float = 1.0) -> collections.deque:
         """Returns the deque itself (the local modification of modeling_pi0.py:303-307); the caller copies and clears it."""
         if len(self._action_queue) == 0:
-            state = self._normalize_state(batch["observation.state"])
+            state = normalize_state(batch["observation.state"], self._norm.get("state", IDENTITY))
             images, img_masks = self.prepare_images(batch)
             state = pad_vector(state, self.config.max_state_dim)
             lang_tokens, lang_masks = self.prepare_language(batch)
             actions = self.model.sample_actions(images, img_masks, lang_tokens, lang_masks, state, noise=noise,
                                                 noise_std=noise_std)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
-            actions = self._unnormalize_action(actions)
+            actions = unnormalize_action(actions, self._norm.get("action", IDENTITY))
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue

@@ -24,7 +24,7 @@ from __future__ import annotations
 import os
 from collections import deque
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -32,24 +32,25 @@ import torch
 from . import ops
 from .host import TopLogprobs
 from .ops import RowParam
-from .models import BF, Decoder, KvGeometry, VitTower
+from .models import BF, Decoder, KvGeometry
+from .paligemma import PaliGemmaPrefix, frames_shared, normalize_state, row_groups, sub_state, unnormalize_action
 from .sampling import PickPlan, StepOutputs
 
 
 def prefix_groups(tokens, pad_mask) -> Tuple[np.ndarray, np.ndarray]:
-    """Rows of (tokens [B, L], pad_mask [B, L]) (integers; tensors or arrays) that are equal in both form a group; groups are numbered
-    in order of first occurrence. Returns (first int64 [P]: the first row of each group, slot int64 [B]: the group of each row), so
-    tokens[first][slot] == tokens. Host index bookkeeping on B x 2L integers: the ordering rule of greedy de-duplication below."""
-    tk = tokens.detach().cpu().numpy() if isinstance(tokens, torch.Tensor) else np.asarray(tokens)
-    pm = pad_mask.detach().cpu().numpy() if isinstance(pad_mask, torch.Tensor) else np.asarray(pad_mask)
-    if tk.ndim != 2 or pm.shape != tk.shape:
+    """paligemma.row_groups over (tokens [B, L], pad_mask [B, L]): rows that are equal in both form a group, numbered in order of
+    first occurrence; (first int64 [P], slot int64 [B]) with tokens[first][slot] == tokens."""
+    if len(tokens.shape) != 2 or tuple(pad_mask.shape) != tuple(tokens.shape):
         raise ValueError("prefix_groups: tokens and pad_mask must be [B, L] of one shape")
-    key = np.concatenate([tk.astype(np.int64), pm.astype(np.int64)], axis=1)
-    _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
-    order = np.argsort(first)                             # distinct rows in order of first occurrence
-    rank = np.empty_like(order)
-    rank[order] = np.arange(order.shape[0])
-    return first[order].astype(np.int64), rank[inv.reshape(-1)].astype(np.int64)
+    return row_groups(tokens, pad_mask)
+
+
+class _Prefilled(NamedTuple):
+    """What PI0FASTTokens._prefill hands to _decode."""
+    h: torch.Tensor           # bf16 [B, D]: the hidden row the first new token is picked from
+    plen: torch.Tensor        # int32 [B]: valid keys of each row's prefix
+    slot_t: torch.Tensor      # int32 [B]: the prefix slot each row reads
+    Tp: int                   # prefix width
 
 
 class PI0FASTTokens:
@@ -61,36 +62,18 @@ class PI0FASTTokens:
         prefix per DISTINCT (frames, prompt): a model for 8 prompts x 5 samples is built with max_prompts=8, max_batch=40. Calls
         without share_prefix prefill every row, so they need max_prompts >= their batch."""
         self.c, self.dev = dict(c), torch.device(device)
-        dev = self.dev
-        sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
-        self.n_img = (c["image"] // c["patch"]) ** 2
-        self.n_cams = n_cams
-        self.vit = VitTower(sub("vision."), dim=c["vit_dim"], layers=c["vit_layers"], heads=c["vit_heads"], mlp=c["vit_mlp"],
-                            patch=c["patch"], act="gelu_tanh", eps=1e-6, device=device)
-        self.projector = ops.pack_linear(sd["projector.weight"].to(dev), sd["projector.bias"])
-        self.embed = sd["lm.embed_tokens.weight"].to(BF).contiguous().to(dev)
+        self.pg = pg = PaliGemmaPrefix(sd, c, device=device, n_cams=n_cams)
+        self.vit, self.projector, self.embed, self.emb_scale = pg.vit, pg.projector, pg.embed, pg.emb_scale
+        self.n_img, self.n_cams = pg.n_img, n_cams
         self.lm_head = ops.pack_linear(self.embed)                       # tied (PaliGemma ties lm_head to embed_tokens)
         self.Tp_cap = self.n_img * n_cams + max_prompt
         self.max_prompts = max_batch if max_prompts is None else int(max_prompts)
         geom = KvGeometry(c["Hkv"], c["D"], [self.max_prompts, max_batch], [self.Tp_cap, max_new_tokens])
-        self.lm = Decoder(sub("lm."), dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"],
+        self.lm = Decoder(sub_state(sd, "lm."), dim=c["lm_dim"], layers=c["layers"], Hq=c["Hq"], Hkv=c["Hkv"], D=c["D"], mlp=c["lm_mlp"],
                           act="gelu_tanh", norm="gemma", eps=1e-6, rope="hf", n_pos=self.Tp_cap + max_new_tokens + 8, device=device,
                           cache=geom)
         self.max_batch, self.max_prompt, self.max_new = max_batch, max_prompt, max_new_tokens
         self.eos_check_every = 8          # decode steps between `done.all()` read-backs (0 = never stop early)
-        D = c["lm_dim"]
-        self.emb_scale = float(torch.tensor(D ** 0.5, dtype=BF))          # GemmaModel: normalizer in the embedding dtype
-
-    def _image_tokens(self, img: torch.Tensor) -> torch.Tensor:
-        """[n,3,H,W] in [-1,1] -> bf16 [n, n_img, dim]: tower -> projector -> / sqrt(dim) (get_image_features, HF 4.48.3), then
-        GemmaModel's * bf16(sqrt(dim)) on the embedded sequence -- two bf16 roundings, as the reference's dtype flow has them."""
-        x = self.vit.embed(img.float().contiguous())
-        x = self.vit.forward(x, post_ln=True)
-        n, T, _ = x.shape
-        D = self.c["lm_dim"]
-        y = ops.gemm(x.view(n * T, -1), self.projector)
-        ops.scale_bf16(y, D ** 0.5, self.emb_scale)
-        return y.view(n, T, D)
 
     def generate_tokens(self, images: List[torch.Tensor], img_masks: List[torch.Tensor], tokens: torch.Tensor, pad_mask: torch.Tensor,
                         max_new_tokens: int, eos_token_id: int = 1, pad_token_id: int = 0,
@@ -158,8 +141,8 @@ class PI0FASTTokens:
         # Greedy decoding is a function of (frames, prompt): candidates that share both (the samples of one rephrased prompt)
         # are generated once and the tokens broadcast -- index bookkeeping on the host, B x 2L integers
         if (allowed_tokens is None and not share_prefix and uniforms is None and force_tokens is None and tokens.shape[0] > 1
-                and all(bool(torch.equal(im[:1].expand_as(im), im)) for im in images)):
-            first, slot = prefix_groups(tokens, pad_mask)
+                and all(frames_shared(im) for im in images)):
+            first, slot = row_groups(tokens, pad_mask)
             if first.shape[0] < tokens.shape[0]:
                 fi = torch.from_numpy(first).to(dev)
                 sub_out = self.generate_tokens([im[fi] for im in images], [m[fi] for m in img_masks], tokens[fi], pad_mask[fi],
@@ -207,8 +190,13 @@ class PI0FASTTokens:
         fsm (ops.TokenFsm, state int32 [B], set_of_row int32 [B]) or None (plan.allow.set_of_row is then that set_of_row): every step
         advances each row's automaton on its emitted token and rewrites set_of_row for the next pick -- fused: in decode_feedback's
         launch, otherwise TokenFsm.step_torch on device tensors."""
-        dev, c = self.dev, self.c
-        (images, img_masks, tokens, pad_mask), (eos_token_id, pad_token_id) = inputs, stop_ids
+        pre = self._prefill(inputs, max_new_tokens, share, trace)
+        return self._decode(pre, max_new_tokens, stop_ids, force_tokens, trace, u_t, plan, return_logprobs, share, fsm)
+
+    def _prefill(self, inputs, max_new_tokens, share, trace) -> _Prefilled:
+        """Size checks, the grouping of share_prefix, the prefix of the P prefilled rows, the prefix pass and every row's first hidden row."""
+        dev, pg = self.dev, self.pg
+        images, img_masks, tokens, pad_mask = inputs
         B, L = tokens.shape
         if (B > (self.max_batch if share else min(self.max_batch, self.max_prompts)) or L > self.max_prompt
                 or max_new_tokens > self.max_new or len(images) > self.n_cams):
@@ -216,30 +204,29 @@ class PI0FASTTokens:
         if len(images) != len(img_masks) or not all(bool(m.to(torch.bool).all()) for m in img_masks):
             raise NotImplementedError("masked-out cameras are not supported on the pi0-FAST path (prepare_images :494-536 "
                                       "produces all-True masks for present cameras)")
-        same = [bool(torch.equal(im[:1].expand_as(im), im)) for im in images]      # the evaluation driver's case: one frame for all rows
+        same = [frames_shared(im) for im in images]                                  # the evaluation driver's case: one frame for all rows
         P = B
         take = lambda t: t                           # the rows that are prefilled: all of them, or (share) the first of each group
         slot_t = torch.arange(B, device=dev, dtype=torch.int32)
         if share:
             first = slot = np.arange(B, dtype=np.int64)                              # rows with frames of their own: every row is its own group
             if all(same):
-                first, slot = prefix_groups(tokens, pad_mask)
+                first, slot = row_groups(tokens, pad_mask)
             P = int(first.shape[0])
             if P > self.max_prompts:
                 raise ValueError(f"{P} distinct prompts exceed the {self.max_prompts} prefix slots this model was built for (max_prompts)")
             fi = torch.from_numpy(first).to(dev)
             take = lambda t: t[fi]
             slot_t = torch.from_numpy(slot).to(device=dev, dtype=torch.int32)
-        D = c["lm_dim"]
+        D = pg.D
         n_img_all = self.n_img * len(images)
         Tp = n_img_all + L
         # ---- prefill of the P prefix rows
         x = torch.empty(P, Tp, D, dtype=BF, device=dev)
         for ci, im in enumerate(images):
-            tok = self._image_tokens(im[:1] if same[ci] else take(im))
-            x[:, ci * self.n_img:(ci + 1) * self.n_img].copy_(tok.expand(P, -1, -1) if same[ci] else tok)   # device copy, no arithmetic
+            pg.place(x, ci * self.n_img, pg.image_tokens(im[:1] if same[ci] else take(im)))       # one frame: broadcast to the P slots
         te = ops.embed_gather(self.embed, take(tokens).reshape(-1).contiguous(), self.emb_scale)
-        x[:, n_img_all:].copy_(te.view(P, L, D))
+        pg.place(x, n_img_all, te.view(P, L, D))
         if trace is not None:
             trace["prefix_embs"] = x.clone()
             trace["prefill_rows"], trace["prefix_slots"] = P * Tp, P
@@ -254,6 +241,13 @@ class PI0FASTTokens:
         ops.copy_rows(xf, h, B, D, last, None)
         if trace is not None:
             trace["first_hidden"] = h.clone()
+        return _Prefilled(h, plen, slot_t, Tp)
+
+    def _decode(self, pre: _Prefilled, max_new_tokens, stop_ids, force_tokens, trace, u_t, plan, return_logprobs, share, fsm):
+        """The step loop: pick a token from the hidden row (final norm, lm_head, plan.pick), settle it (feedback), run the next pass."""
+        dev, c = self.dev, self.c
+        (h, plen, slot_t, Tp), (eos_token_id, pad_token_id) = pre, stop_ids
+        B, D = h.shape
         fused = share and os.environ.get("COVER_FAST_FEEDBACK", "1") != "0"
         # HF generate(do_sample=False) stops once every row has emitted EOS (modeling_pi0fast.py:861-946 runs it with
         # max_new_tokens = max_decoding_steps = 256, a FAST sequence is a few dozen tokens): every `eos_check_every` steps `done.all()`
@@ -275,8 +269,22 @@ class PI0FASTTokens:
         fkw = {} if rls is None else dict(lp2=rl, lp2_out=rls)
         if fsm is not None:
             fkw.update(fsm=fsm[0], fsm_state=fsm[1], fsm_set_of_row=fsm[2])
-
-        def pick(hidden, i):
+        seg0 = dict(region=0, length=Tp, len_of_batch=plen)
+        if share:
+            seg0["slot_of_batch"] = slot_t                                           # its prompt's prefix, wherever that was prefilled
+        hidden = h                                                                   # step 0 picks from the prefill's last valid row
+        for i in range(max_new_tokens):
+            if i > 0:
+                if force is None and self.eos_check_every > 0 and i % self.eos_check_every == 0:
+                    if (int(live[i - 1]) == 0) if fused else bool(done.all()):       # one 4-byte (1-byte) D2H
+                        break
+                if not fused:
+                    ops.embed_gather(self.embed, out[:, i - 1].contiguous(), self.emb_scale, out=xd)
+                pos_i = (plen + i).to(torch.int32).contiguous()                       # token i-1 sits at 1-indexed position plen + i
+                g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
+                self.lm.forward(xd, [g], final_norm=False)
+                hidden = xd
+            # ---- step i's pick
             hn = ops.rmsnorm(hidden, self.lm.final_norm, 1e-6, w_offset=1.0, style=0)
             lg = ops.gemm(hn, self.lm_head, out=logits, ws=head_ws)
             if trace is not None:
@@ -290,7 +298,7 @@ class PI0FASTTokens:
                 ops.decode_feedback(t, done, out, i, eos_token_id, pad_token_id, force=None if force is None else force[:, i], lp=lp,
                                     lp_out=lps, table=self.embed, scale=self.emb_scale, x_out=xd if i + 1 < max_new_tokens else None,
                                     live=live, **fkw)
-                return
+                continue
             if rl is not None:
                 rls[:, i].copy_(torch.where(done, torch.zeros_like(rl), rl))
             if lp is not None:
@@ -302,21 +310,6 @@ class PI0FASTTokens:
             if fsm is not None:
                 fsm[0].step_torch(fsm[1], fsm[2], t, ~done)                          # done as it was before this step
             done.logical_or_(t == eos_token_id)
-
-        pick(h, 0)
-        seg0 = dict(region=0, length=Tp, len_of_batch=plen)
-        if share:
-            seg0["slot_of_batch"] = slot_t                                           # its prompt's prefix, wherever that was prefilled
-        for i in range(1, max_new_tokens):
-            if force is None and self.eos_check_every > 0 and i % self.eos_check_every == 0:
-                if (int(live[i - 1]) == 0) if fused else bool(done.all()):           # one 4-byte (1-byte) D2H
-                    break
-            if not fused:
-                ops.embed_gather(self.embed, out[:, i - 1].contiguous(), self.emb_scale, out=xd)
-            pos_i = (plen + i).to(torch.int32).contiguous()                           # token i-1 sits at 1-indexed position plen + i
-            g = self.lm.group(B, 1, pos_i, [seg0, dict(region=1, length=i)], 1, write_t_off=i - 1)
-            self.lm.forward(xd, [g], final_norm=False)
-            pick(xd, i)
         if outs.top is None:
             return outs.result()
         # a row is finished at step i once an earlier step emitted EOS: its pad is not a choice (index bookkeeping on the emitted tokens)
@@ -402,20 +395,6 @@ class PI0FASTPolicy:
         order = torch.argsort((mask == 0).to(torch.int8), dim=1, stable=True)
         return torch.gather(ids, 1, order), torch.gather(mask, 1, order)
 
-    def _normalize_state(self, state):
-        mode, a, b = self.normalization["state"]
-        if mode == "IDENTITY":
-            return state
-        a, b = a.to(state.device), b.to(state.device)
-        return (state - a) / (b + 1e-8) if mode == "MEAN_STD" else (state - a) / (b - a + 1e-8) * 2 - 1
-
-    def _unnormalize_action(self, act):
-        mode, a, b = self.normalization["action"]
-        if mode == "IDENTITY":
-            return act
-        a, b = a.to(act.device), b.to(act.device)
-        return act * b + a if mode == "MEAN_STD" else (act + 1) / 2 * (b - a) + a
-
     # ---- extract_actions(tokens, action_horizon, action_dim) :794-859
     def extract_actions(self, tokens: torch.Tensor, action_horizon: int, action_dim: int) -> torch.Tensor:
         decoded = self.paligemma_tokenizer.batch_decode(tokens, skip_special_tokens=True)
@@ -435,7 +414,7 @@ class PI0FASTPolicy:
     def select_action(self, batch: dict) -> torch.Tensor:
         if len(self._action_queue) == 0:
             dev = self.model.dev
-            state = self._normalize_state(batch[self.config.state_key].to(torch.float32))
+            state = normalize_state(batch[self.config.state_key].to(torch.float32), self.normalization["state"])
             present = [k for k in self.config.image_keys if k in batch]
             if not present:
                 raise ValueError(f"All image features are missing from the batch. At least one expected. (batch: {batch.keys()})")
@@ -479,7 +458,7 @@ class PI0FASTPolicy:
                 self.last_sequence_logprobs = sequence_logprob(lps)
             actions = self.extract_actions(toks.cpu(), self.config.chunk_size, self.config.action_dim)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
-            actions = self._unnormalize_action(actions.to(torch.float32))
+            actions = unnormalize_action(actions.to(torch.float32), self.normalization["action"])
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue.popleft()
 

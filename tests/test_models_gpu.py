@@ -229,7 +229,7 @@ def test_pi0_sampler_matches_reference_golden(dev, name):
         x1 = model.sample_actions(*args, noise=noise.to(dev))
         x2 = model.sample_actions(*args, noise=noise.to(dev))
         st = [v for k, v in model._den.items() if k[:2] == (B, min(n_ch, B))][0]
-        assert st["graph"] is not None and len(st["chains"]) == min(n_ch, B)
+        assert st.graph is not None and len(st.chains) == min(n_ch, B)
         x3 = model.sample_actions(*args, noise=noise2.to(dev))
         assert torch.equal(x1, xe) and torch.equal(x2, xe) and torch.equal(x3, x3e), n_ch
         d = np.linalg.norm(xe.cpu().numpy() - x) / np.linalg.norm(upd)
