@@ -19,12 +19,14 @@ from __future__ import annotations
 from typing import Dict, NamedTuple, Optional
 
 import os
+import weakref
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops
+from .graphs import ReplayGraph
 from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower, _f32
 from .sampling import PickPlan, StepOutputs
@@ -106,7 +108,8 @@ class OpenVLA:
         self.zero_slots = torch.zeros(max(max_prompts, max_candidates), dtype=torch.int32, device=dev)
         self.bos = torch.tensor([1], dtype=torch.int64, device=dev)
         self._side = None
-        self._cap = None
+        # what the replayed bodies kept in _vis / _dec reach this model through: a strong reference would leave a dropped model to the cyclic collector
+        self._weak = weakref.proxy(self)
         self._vis = {}
         self._bos_ready = False
         # measurement switches (bench.py's profiled decision): hipGraph replay hides launches from the in-library kernel
@@ -141,12 +144,13 @@ class OpenVLA:
         st = self._vis.get(key)
         if st is None:
             c, P, dev = self.c, self.n_patches, self.dev
-            st = dict(frame=torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev),
-                      d=self.dino.static_bufs(n, H, W), s=self.siglip.static_bufs(n, H, W),
-                      fused=torch.empty(n * P, self.fused, dtype=BF, device=dev),
-                      h=[torch.empty(n * P, lin.n_out, dtype=BF, device=dev) for lin in self.proj],
-                      ws=[ops.gemm_workspace(n * P, lin.N, lin.K, dev) for lin in self.proj], graph=None)
-            self._vis[key] = st
+            bufs = dict(frame=torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev),
+                        d=self.dino.static_bufs(n, H, W), s=self.siglip.static_bufs(n, H, W),
+                        fused=torch.empty(n * P, self.fused, dtype=BF, device=dev),
+                        h=[torch.empty(n * P, lin.n_out, dtype=BF, device=dev) for lin in self.proj],
+                        ws=[ops.gemm_workspace(n * P, lin.N, lin.K, dev) for lin in self.proj])
+            me, dino, siglip = self._weak, self.dino, self.siglip
+            st = self._vis[key] = dict(bufs, graph=ReplayGraph(lambda: me._encode_static(bufs), dev, gen=lambda: (dino.ws_gen, siglip.ws_gen)))
         return st
 
     def _encode_static(self, st) -> torch.Tensor:
@@ -181,25 +185,10 @@ class OpenVLA:
         n, H, W, _ = frame_u8.shape
         st = self._vision_static(n, H, W)
         st["frame"].copy_(frame_u8)
-        gen = (self.dino.ws_gen, self.siglip.ws_gen)
-        if st["graph"] is not None and st.get("ws_gen") != gen:
-            st["graph"] = None                                           # a tower workspace moved (a larger frame batch ran since): re-capture
-        if st["graph"] is not None and self.vision_graph:
-            st["graph"].launch()
-            return st["h"][2]
-        out = self._encode_static(st)                                    # eager (also sizes the towers' workspaces)
-        if self.vision_graph and st["graph"] is None:
-            cur = torch.cuda.current_stream()
-            if self._cap is None:
-                self._cap = torch.cuda.Stream(device=self.dev)
-            self._cap.wait_stream(cur)
-            with torch.cuda.stream(self._cap):
-                with ops.Graph() as g:
-                    self._encode_static(st)
-            st["graph"] = g
-            st["ws_gen"] = (self.dino.ws_gen, self.siglip.ws_gen)
-            cur.wait_stream(self._cap)
-        return out
+        if not self.vision_graph:
+            return self._encode_static(st)
+        st["graph"].run()                                                # stale when a tower workspace moved (a larger frame batch ran since)
+        return st["h"][2]
 
     # ---------------------------------------------------------------------------------------------- sampler
     def _prefill(self, frame_u8, prompt_tokens, mark=lambda name: None, on_vision_enqueued=None, on_prefill_enqueued=None):
@@ -285,11 +274,13 @@ class OpenVLA:
             st = self._dec.get(key)
             if st is None:
                 outs = new_outs()
-                st = dict(graph=None, plan=plan._replace(rp=None if plan.rp is None else tuple(torch.empty_like(t) for t in plan.rp)),
-                          state=_DecodeState(prompt_of_cand.clone(), torch.empty_like(cand_len), torch.empty_like(last_row), torch.empty_like(pos_all),
-                                             None if u_t is None else torch.empty_like(u_t), torch.arange(P, dtype=torch.int32, device=dev),
-                                             torch.empty(P, dtype=torch.int32, device=dev), outs, outs.tokens))
-                self._dec[key] = st
+                st_plan = plan._replace(rp=None if plan.rp is None else tuple(torch.empty_like(t) for t in plan.rp))
+                st_state = _DecodeState(prompt_of_cand.clone(), torch.empty_like(cand_len), torch.empty_like(last_row), torch.empty_like(pos_all),
+                                        None if u_t is None else torch.empty_like(u_t), torch.arange(P, dtype=torch.int32, device=dev),
+                                        torch.empty(P, dtype=torch.int32, device=dev), outs, outs.tokens)
+                # x is the same rows of the static x_pre on every call of this key (P and Lt are part of it), so the body may keep it
+                me, llm = self._weak, self.llm
+                st = self._dec[key] = dict(graph=ReplayGraph(lambda: me._decode_body(x, st_plan, st_state), dev, gen=lambda: llm.ws_gen), plan=st_plan, state=st_state)
             s = st["state"]
             s.cand_len.copy_(cand_len); s.last_row.copy_(last_row); s.pos_all.copy_(pos_all)
             s.prompt_lens.copy_(prompt_lens.to(torch.int32))
@@ -297,24 +288,7 @@ class OpenVLA:
                 s.u.copy_(u_t)
             for dst, src in zip(st["plan"].rp or (), plan.rp or ()):
                 dst.copy_(src)
-            body = lambda: self._decode_body(x, st["plan"], s)
-            if st["graph"] is not None and st.get("ws_gen") != self.llm.ws_gen:
-                st["graph"] = None                                      # the decoder workspace moved under the captured pointer: re-capture
-            if st["graph"] is None:
-                body()                                                  # eager once (also sizes every workspace), then recorded
-                cur = torch.cuda.current_stream()
-                if self._cap is None:
-                    self._cap = torch.cuda.Stream(device=self.dev)
-                self._cap.wait_stream(cur)
-                with torch.cuda.stream(self._cap):
-                    with ops.Graph() as g:
-                        body()
-                st["graph"] = g
-                st["ws_gen"] = self.llm.ws_gen
-                cur.wait_stream(self._cap)
-            else:
-                st["graph"].launch()
-            # the eager pass before a capture has filled the same buffers
+            st["graph"].run()       # stale when the decoder workspace moved under the captured pointer; the eager pass before a capture fills the same buffers
             return s.outs.result()
         outs = new_outs()
         state = _DecodeState(prompt_of_cand, cand_len, last_row, pos_all, u_t, torch.arange(P, dtype=torch.int32, device=dev),

@@ -6,7 +6,6 @@ libcover_hip.so. Nothing in this module computes on the CPU or through torch ker
 from __future__ import annotations
 
 import ctypes as C
-import gc
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
@@ -15,13 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .graphs import Graph, PooledGraph, Timer, _stream  # noqa: F401  (ops.Graph / ops.PooledGraph / ops.Timer: their home is graphs.py)
 
 ACT = {"none": 0, "gelu_tanh": 1, "gelu_erf": 2, "silu": 3, "relu": 4}
 MASK_LEN, MASK_CAUSAL, MASK_VISLEN = 0, 1, 2
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -1496,91 +1492,3 @@ def beam_merge_gumbel(cum, cand_tok, cand_lp, cand_g, n_beams, feed_pad, out_par
     a.cum_out, a.step_lp_out, a.g_out, a.kappa_out = cum_o.data_ptr(), step_lp.data_ptr(), g.data_ptr(), kappa.data_ptr()
     L.check(L.lib().cover_beam_merge_gumbel(C.byref(a), _stream()), "beam_merge_gumbel")
     return parent, token, feed, cum_o, step_lp, g, kappa
-
-
-# ------------------------------------------------------------------------------------------------ graphs / timers
-class Graph:
-    """hipGraph captured from whatever runs on the current stream inside the `with` block."""
-
-    def __init__(self):
-        self.handle = C.c_void_p()
-        self.stream = None
-
-    def __enter__(self):
-        self.stream = _stream()
-        # no cyclic collection inside the capture: garbage that owns device memory (a torch.cuda.MemPool behind a reference cycle, as
-        # PooledGraph's in the verifier) frees it in its destructor, and a hipFree on the capturing thread aborts the process
-        self._gc = gc.isenabled()
-        gc.disable()
-        try:
-            L.check(L.lib().cover_graph_begin(self.stream), "graph_begin")
-        except BaseException:
-            self._gc and gc.enable()
-            raise
-        return self
-
-    def __exit__(self, et, ev, tb):
-        rc = L.lib().cover_graph_end(self.stream, C.byref(self.handle))
-        if self._gc:
-            gc.enable()
-        if et is None:
-            L.check(rc, "graph_end")
-        return False
-
-    def launch(self):
-        L.check(L.lib().cover_graph_launch(self.handle, _stream()), "graph_launch")
-
-
-class PooledGraph:
-    """A launch sequence that ALLOCATES its intermediates (ordinary op wrappers) as one replayable hipGraph.
-
-    call 1 runs `fn()` eagerly inside a private torch memory pool (this sizes every intermediate and leaves their blocks in the pool),
-    call 2 captures it inside the same pool (every allocation is served from the pool's cache: no hipMalloc under capture), later calls
-    replay. The pool belongs to this object alone, so the blocks the captured kernels write to are never handed to anybody else between
-    replays. `fn` takes no arguments: it reads static input tensors the caller refreshes before every call, and returns tensors that stay
-    valid (static) from the capture on. Streams that `fn` forks to and joins from become parallel branches of the graph."""
-
-    def __init__(self, fn, device):
-        self.fn, self.dev = fn, device
-        self.pool = torch.cuda.MemPool()
-        self.graph, self.out, self.calls = None, None, 0
-        self._cap = None
-
-    def __call__(self):
-        self.calls += 1
-        if self.graph is not None:
-            self.graph.launch()
-            return self.out
-        if self.calls == 1:
-            with torch.cuda.use_mem_pool(self.pool, device=self.dev):
-                out = self.fn()
-            # (this call's outputs live in the pool until the caller drops them; the capture below then allocates its own)
-            return out
-        cur = torch.cuda.current_stream()
-        if self._cap is None:
-            self._cap = torch.cuda.Stream(device=self.dev)
-        self._cap.wait_stream(cur)
-        with torch.cuda.use_mem_pool(self.pool, device=self.dev):
-            with torch.cuda.stream(self._cap):
-                with Graph() as g:
-                    self.out = self.fn()
-        cur.wait_stream(self._cap)
-        self.graph = g
-        self.graph.launch()          # the capture itself executed nothing
-        return self.out
-
-
-class Timer:
-    """hipEvent pair recorded on the current stream."""
-
-    def __init__(self):
-        self.h = C.c_void_p()
-        L.check(L.lib().cover_timer_create(C.byref(self.h)), "timer_create")
-
-    def start(self):
-        L.check(L.lib().cover_timer_start(self.h, _stream()), "timer_start")
-
-    def stop(self) -> float:
-        ms = C.c_float()
-        L.check(L.lib().cover_timer_stop(self.h, _stream(), C.byref(ms)), "timer_stop")
-        return ms.value

@@ -23,7 +23,7 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import graphs, ops
 from .models import BF, Decoder, KvGeometry, _f32
 from .paligemma import IDENTITY, PaliGemmaPrefix, frames_shared, normalize_state, row_groups, sub_state, unnormalize_action
 
@@ -66,7 +66,7 @@ class _DenoiseState:
     temb: torch.Tensor
     chains: List[_Chain]
     calls: int = 0
-    graph: Optional[ops.Graph] = None
+    graph: Optional[graphs.Graph] = None
     Tp: Optional[int] = None        # the prefix width baked into the chains' groups (and into a captured graph)
 
 
@@ -101,7 +101,6 @@ class PI0FlowMatching:
         self.n_chains = int(os.environ.get("COVER_PI0_CHAINS", "1"))
         self.denoise_graph = os.environ.get("COVER_PI0_GRAPH", "1") != "0"
         self._fold = {}    # folded suffix-embedding constants per step size (_suffix_fold)
-        self._cap = None   # capture stream
 
     # ---------------------------------------------------------------------------------------------- prefix
     @staticmethod
@@ -398,15 +397,7 @@ class PI0FlowMatching:
             self._euler_fork_join(st, fold, dt, trace, vs)
         else:
             if st.graph is None:
-                cur = torch.cuda.current_stream()
-                if self._cap is None:
-                    self._cap = torch.cuda.Stream(device=dev)
-                self._cap.wait_stream(cur)
-                with torch.cuda.stream(self._cap):
-                    with ops.Graph() as gr:
-                        self._euler_fork_join(st, fold, dt, trace, vs)
-                cur.wait_stream(self._cap)
-                st.graph = gr
+                st.graph, _ = graphs.capture(lambda: self._euler_fork_join(st, fold, dt, trace, vs), dev)
             st.graph.launch()
         if trace is not None:
             trace["x_steps"] = vs

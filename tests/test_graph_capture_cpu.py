@@ -18,10 +18,10 @@ class _FakeLib:
 
 
 def test_graph_capture_runs_with_the_collector_off_and_restores_it(monkeypatch):
-    from cover_vla_amd import ops
+    from cover_vla_amd import graphs, ops
     fake = _FakeLib()
-    monkeypatch.setattr(ops.L, "lib", lambda: fake)
-    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    monkeypatch.setattr(graphs.L, "lib", lambda: fake)
+    monkeypatch.setattr(graphs, "_stream", lambda: 0)       # ops.Graph is graphs.Graph: it reads its stream there
     assert gc.isenabled()
     with ops.Graph():
         assert not gc.isenabled()

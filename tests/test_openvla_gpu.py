@@ -262,7 +262,7 @@ def test_openvla_decode_graph_replay_equals_eager_loop(dev, own_kv, horizon):
         a_t, a_l = model.sample(f, tk, ln, 2, uu, 1.0)
         b_t, b_l = eager.sample(f, tk, ln, 2, uu, 1.0)
         assert torch.equal(a_t, b_t) and torch.equal(a_l, b_l)
-    assert all(st["graph"] is not None for st in model._dec.values()) and len(model._dec) == 2      # sampled and greedy shapes
+    assert all(st["graph"].captured for st in model._dec.values()) and len(model._dec) == 2      # sampled and greedy shapes
 
 
 def test_openvla_decode_graph_first_call_runs_the_body_twice(dev):
@@ -316,7 +316,7 @@ def test_openvla_decode_graph_survives_a_larger_prompt_batch(dev):
         b_t, b_l = eager.sample(f, tk, ln, 2, uu, 1.0)
         assert torch.equal(a_t, b_t) and torch.equal(a_l, b_l)
     assert model.llm.ws_gen == gen0, "the decoder workspace was re-allocated after __init__ sized it"
-    assert len(model._dec) == 2 and all(st["graph"] is not None and st["ws_gen"] == gen0 for st in model._dec.values())
+    assert len(model._dec) == 2 and all(st["graph"].captured and st["graph"].gen == gen0 for st in model._dec.values())
 
 
 def test_openvla_end_to_end_matches_hf_composition(dev):
