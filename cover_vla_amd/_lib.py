@@ -184,6 +184,13 @@ class PriorSelectArgs(C.Structure):
                 ("ranked_out", c_p)]
 
 
+class AugmentArgs(C.Structure):
+    _fields_ = [("src", c_p), ("n_stride", c_ll), ("t_stride", c_ll), ("normals", c_p), ("centers", c_p),
+                ("n_centers", c_i), ("tok_vocab", c_i), ("G", c_i), ("n", c_i), ("K", c_i), ("h", c_i),
+                ("sigma", c_f), ("sd_floor", c_f), ("clip_lo", c_f), ("clip_hi", c_f),
+                ("out", c_p), ("mean_out", c_p), ("sd_out", c_p), ("votes_out", c_p)]
+
+
 class BeamMergeArgs(C.Structure):
     _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("feed_pad", c_ll),
                 ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p), ("cum_out", c_p),
@@ -266,7 +273,8 @@ _STRUCTS = {
     "cover_token_sample_rows_args": TokenSampleRowsArgs, "cover_token_logprob_rows_args": TokenLogprobRowsArgs,
     "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_token_fsm": TokenFsm,
-    "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_beam_merge_args": BeamMergeArgs,
+    "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_augment_args": AugmentArgs,
+    "cover_beam_merge_args": BeamMergeArgs,
     "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
     "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
     "cover_vit_desc": VitDesc, "cover_dec_layer": DecLayer, "cover_dec_desc": DecDesc, "cover_dec_group": DecGroup,
@@ -341,6 +349,8 @@ SYMBOLS = {
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),
+    "cover_augment_tokens": (c_i, [_P(AugmentArgs), c_p]),
+    "cover_augment_actions": (c_i, [_P(AugmentArgs), c_p]),
     "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
     "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
     "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),

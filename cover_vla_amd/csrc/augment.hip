@@ -1,0 +1,126 @@
+// Gaussian proposal augmentation (cover_augment_tokens / cover_augment_actions): K verifier candidates per prompt from the prompt's n
+// policy samples -- per (step, dim) a diagonal Gaussian fitted to the samples, the gripper by majority vote. The results are compared
+// with a numpy restatement as bit patterns, so every value is a fixed sequence of fp32 roundings (the house rule of select.hip): plain
+// operators with contraction off for the whole file, because hipcc would otherwise fuse d * d + ss and mean + s * z into one v_fma_f32.
+#include "common.h"
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+// what a raw input element is worth, and what an augmented value is stored as: floats pass through, tokens go through the bin centres
+__device__ __forceinline__ float aug_value(const cover_augment_args& a, float raw) { return raw; }
+__device__ __forceinline__ float aug_value(const cover_augment_args& a, int64_t token) {
+    long long b = (long long)a.tok_vocab - token - 1;   // tokens_to_histories_k's rule
+    b = b < 0 ? 0 : (b > a.n_centers - 1 ? a.n_centers - 1 : b);
+    return a.centers[b];
+}
+__device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, float* o) { *o = v; }
+__device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, int64_t* o) {
+    // first index that minimises |v - centers[b]|: a plain scan (b is uniform over the wave: the table comes through scalar loads)
+    float best = fabsf(v - a.centers[0]);
+    int bi = 0;
+    for (int b = 1; b < a.n_centers; ++b) {
+        const float dist = fabsf(v - a.centers[b]);
+        if (dist < best) {
+            best = dist;
+            bi = b;
+        }
+    }
+    *o = (int64_t)a.tok_vocab - 1 - bi;
+}
+
+// The statistics of one prompt group, left in LDS: for item i = t * 6 + d < 6 h the mean and s = sigma * sd of (step t, dim d), for
+// step t the index of the sample whose gripper the augmented rows take. `in` is the group's first row; element (j, t, d) at
+// in[j * n_stride + t * t_stride + d]. One thread per item, the samples in index order.
+template <typename T>
+__device__ void augment_group_stats(const cover_augment_args& a, const T* in, long long t_stride, int g, float* s_mean, float* s_s,
+                                    int* s_jwin) {
+    const int n = a.n, h = a.h;
+    for (int i = threadIdx.x; i < 7 * h; i += blockDim.x) {
+        if (i < 6 * h) {
+            const int t = i / 6, d = i - t * 6;
+            const T* x = in + (long long)t * t_stride + d;
+            float sum = 0.0f;
+            for (int j = 0; j < n; ++j) sum = sum + aug_value(a, x[(long long)j * a.n_stride]);
+            const float mean = sum / (float)n;
+            float ss = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                const float dev = aug_value(a, x[(long long)j * a.n_stride]) - mean;
+                const float sq = dev * dev;
+                ss = ss + sq;
+            }
+            const float var = n > 1 ? ss / (float)(n - 1) : 0.0f;
+            const float sd = fmaxf(sqrtf(var), a.sd_floor);
+            s_mean[i] = mean;
+            s_s[i] = a.sigma * sd;
+            if (a.mean_out) a.mean_out[(size_t)g * 6 * h + i] = mean;
+            if (a.sd_out) a.sd_out[(size_t)g * 6 * h + i] = sd;
+        } else {
+            const int t = i - 6 * h;
+            const T* x = in + (long long)t * t_stride + 6;
+            int ones = 0, first0 = -1, first1 = -1;
+            for (int j = 0; j < n; ++j) {
+                const bool c1 = aug_value(a, x[(long long)j * a.n_stride]) >= 0.5f;
+                ones += c1 ? 1 : 0;
+                if (c1 && first1 < 0) first1 = j;
+                if (!c1 && first0 < 0) first0 = j;
+            }
+            const int zeros = n - ones;
+            const bool win1 = ones > zeros || (ones == zeros && first1 == 0);   // a tie goes to the class of sample 0
+            s_jwin[t] = win1 ? first1 : first0;
+            if (a.votes_out) {
+                a.votes_out[((size_t)g * h + t) * 2] = zeros;
+                a.votes_out[((size_t)g * h + t) * 2 + 1] = ones;
+            }
+        }
+    }
+}
+
+// one block per prompt group: statistics -> LDS, the n originals copied, then the block walks (k, t, d) of the K augmented rows in
+// output order (coalesced stores)
+template <typename T>
+__global__ __launch_bounds__(256) void augment_k(cover_augment_args a, long long t_stride) {
+    __shared__ float s_mean[6 * 64], s_s[6 * 64];
+    __shared__ int s_jwin[64];
+    const int g = blockIdx.x, n = a.n, K = a.K, h = a.h, w = 7 * h;
+    const T* in = (const T*)a.src + (long long)g * n * a.n_stride;
+    T* out = (T*)a.out + (size_t)g * (n + K) * w;
+    augment_group_stats<T>(a, in, t_stride, g, s_mean, s_s, s_jwin);
+    for (int i = threadIdx.x; i < n * w; i += blockDim.x) {
+        const int j = i / w, r = i - j * w, t = r / 7, d = r - t * 7;
+        out[i] = in[(long long)j * a.n_stride + (long long)t * t_stride + d];
+    }
+    __syncthreads();
+    out += (size_t)n * w;
+    const float* z = a.normals + (size_t)g * K * 6 * h;
+    for (int i = threadIdx.x; i < K * w; i += blockDim.x) {
+        const int k = i / w, r = i - k * w, t = r / 7, d = r - t * 7;
+        if (d == 6) {
+            out[i] = in[(long long)s_jwin[t] * a.n_stride + (long long)t * t_stride + 6];
+            continue;
+        }
+        const float p = s_s[t * 6 + d] * z[((size_t)k * h + t) * 6 + d];
+        float v = s_mean[t * 6 + d] + p;
+        v = fminf(fmaxf(v, a.clip_lo), a.clip_hi);
+        aug_store(a, v, out + i);
+    }
+}
+
+static bool augment_args_ok(const cover_augment_args* a) {
+    const float flt_max = 3.402823466e+38f;
+    if (a->G < 1 || a->n < 1 || a->n > 4096 || a->K < 0 || a->K > 4096 || a->h < 1 || a->h > 64) return false;
+    if ((long long)a->G * (a->n + a->K) > (1ll << 20)) return false;
+    if (!(a->sigma >= 0.0f) || !(a->sigma <= flt_max) || !(a->sd_floor >= 0.0f) || !(a->sd_floor <= flt_max)) return false;   // a NaN fails both
+    if (!(a->clip_lo <= a->clip_hi)) return false;
+    return a->src && a->out && (a->K == 0 || a->normals);
+}
+hipError_t launch_augment_tokens(const cover_augment_args* a, hipStream_t st) {
+    if (!augment_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(augment_k<int64_t>, dim3(a->G), dim3(256), 0, st, *a, 7ll);
+    return hipGetLastError();
+}
+hipError_t launch_augment_actions(const cover_augment_args* a, hipStream_t st) {
+    if (!augment_args_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(augment_k<float>, dim3(a->G), dim3(256), 0, st, *a, a->t_stride);
+    return hipGetLastError();
+}

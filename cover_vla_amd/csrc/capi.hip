@@ -396,6 +396,18 @@ int cover_prior_select(const cover_prior_select_args* a, void* stream) {
            "beta finite and >= 0, scores / logprobs / prior_out / combined_out / result_out / best_out required, ranked_out with top_m > 0)");
     return COVER_OK;
 }
+#define AUGMENT_LIMITS "G >= 1, 1 <= n <= 4096, 0 <= K <= 4096, 1 <= h <= 64, G * (n + K) <= 2^20, sigma and sd_floor finite and >= 0, " \
+                       "clip_lo <= clip_hi, src / out required, normals with K > 0"
+int cover_augment_tokens(const cover_augment_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_augment_tokens: null args");
+    HIPCHK(launch_augment_tokens(a, ST(stream)), "augment_tokens (" AUGMENT_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_augment_actions(const cover_augment_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_augment_actions: null args");
+    HIPCHK(launch_augment_actions(a, ST(stream)), "augment_actions (" AUGMENT_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -520,7 +532,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
-    SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args);
+    SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args);
 #undef SZ
     return 0;
 }

@@ -103,6 +103,9 @@ hipError_t launch_actions_to_histories(const float* actions, long long n_stride,
 hipError_t launch_group_argmax(const float* scores, int N, int gs, int* result, float* best, hipStream_t st);
 hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st);
 size_t gemm_workspace_bytes(int M, int N, int K);
+// ---- augment.hip ---------------------------------------------------------------------------------
+hipError_t launch_augment_tokens(const cover_augment_args* a, hipStream_t st);
+hipError_t launch_augment_actions(const cover_augment_args* a, hipStream_t st);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
 hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);

@@ -86,6 +86,57 @@ def sampling_ladder(n_prompts: int, n_samples: int, temperature, top_k=0, top_p=
     return tuple(out)
 
 
+def augmentation_normals(n_prompts: int, n_augmented: int, steps: int, seed: int):
+    """The standard normals of one Gaussian proposal augmentation (ops.augment_tokens / ops.augment_actions, OpenVLA.augment,
+    PI0Policy.select_action(augment=)): a host fp32 torch tensor [n_prompts, n_augmented, steps, 6] drawn from a CPU torch.Generator
+    seeded with `seed` -- element (g, k, t, d) perturbs dim d of step t of prompt g's k-th augmented candidate. The caller supplies them
+    as it supplies the samplers' uniforms: the same seed gives the same tensor and so the same augmented candidates, bit for bit; move it
+    to the policy's device once per decision. No seed schedule is chosen here."""
+    import torch
+    n_prompts, n_augmented, steps = int(n_prompts), int(n_augmented), int(steps)
+    if n_prompts < 1 or n_augmented < 0 or steps < 1:
+        raise ValueError("augmentation_normals: n_prompts >= 1, n_augmented >= 0 and steps >= 1 are required")
+    return torch.randn(n_prompts, n_augmented, steps, 6, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+
+
+class _AugmentFields(NamedTuple):
+    samples_per_prompt: int
+    n_augmented: int
+    normals: Any
+    sigma: float = 1.0
+    sd_floor: float = 0.0
+    clip: Any = (-1.0, 1.0)
+
+
+class Augment(_AugmentFields):
+    """What PI0Policy.select_action(augment=) takes: every prompt's samples_per_prompt policy samples (contiguous rows of the batch) are
+    followed by n_augmented candidates drawn from the diagonal Gaussian fitted to them in the policy's normalised action space
+    (ops.augment_actions: the arithmetic, the clip and the gripper vote -- on a gripper tie the augmented rows take the class of sample 0,
+    so the in-group vote of verify_and_select may then differ from the reference's "winner's sign" rule). normals: fp32
+    [prompts, n_augmented, n_action_steps, 6] on the policy's device (augmentation_normals). sigma scales the fitted standard deviation,
+    sd_floor is its lower bound, clip = (lo, hi) bounds the drawn values (+-inf = no clip). Values are checked here (CoverError), shapes
+    against the batch in ops.augment_actions. No default n_augmented, sigma or floor is recommended."""
+    __slots__ = ()
+
+    def __new__(cls, samples_per_prompt, n_augmented, normals, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0)):
+        import torch
+        from ._lib import CoverError
+        ints = (int, np.integer)
+        if not (isinstance(samples_per_prompt, ints) and isinstance(n_augmented, ints)) or not 1 <= samples_per_prompt <= 4096 \
+                or not 0 <= n_augmented <= 4096:
+            raise CoverError(f"Augment: integers 1 <= samples_per_prompt <= 4096 and 0 <= n_augmented <= 4096 are required "
+                             f"(got {samples_per_prompt!r}, {n_augmented!r})")
+        if not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.dim() != 4 or normals.shape[1] != n_augmented \
+                or normals.shape[3] != 6:
+            raise CoverError(f"Augment: normals must be an fp32 tensor [prompts, n_augmented = {n_augmented}, steps, 6]")
+        for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0):
+                raise CoverError(f"Augment: {name} must be a finite number >= 0 (got {v!r})")
+        if not isinstance(clip, (tuple, list)) or len(clip) != 2 or not all(isinstance(v, (int, float)) for v in clip) or not clip[0] <= clip[1]:
+            raise CoverError(f"Augment: clip must be a (lo, hi) pair of numbers with lo <= hi (got {clip!r})")
+        return super().__new__(cls, int(samples_per_prompt), int(n_augmented), normals, float(sigma), float(sd_floor), (float(clip[0]), float(clip[1])))
+
+
 class TokenGrammar(NamedTuple):
     """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
     allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)

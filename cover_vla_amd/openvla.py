@@ -483,3 +483,24 @@ class OpenVLA:
         d = self.c["tok_vocab"] - np.asarray(tokens)
         d = np.clip(d - 1, a_min=0, a_max=centers.shape[0] - 1)
         return centers[d]
+
+    # ---------------------------------------------------------------------------------------------- proposal augmentation
+    def bin_centers(self) -> torch.Tensor:
+        """The de-tokeniser's bin centres as the device kernels take them: tokens_to_actions' float64 arithmetic cast to fp32 [n_bins - 1],
+        built once per model."""
+        if getattr(self, "_centers", None) is None:
+            bins = np.linspace(-1, 1, self.c["n_bins"])
+            self._centers = torch.tensor((bins[:-1] + bins[1:]) / 2.0, dtype=torch.float32, device=self.dev)
+        return self._centers
+
+    def augment(self, tokens: torch.Tensor, n_samples: int, n_augmented: int, normals: torch.Tensor, *, sigma=1.0, sd_floor=0.0):
+        """Gaussian proposal augmentation of sampled chunks (ops.augment_tokens with this model's tok_vocab, bin centres and
+        steps = n_gen // 7): tokens int64 [P * n_samples, n_gen] as sample returns them -> int64 [P * S, n_gen], S = n_samples +
+        n_augmented; per prompt the n_samples policy rows verbatim, then n_augmented rows drawn from the diagonal Gaussian fitted to their
+        de-tokenised translation / rotation values (clipped to the bins' range [-1, 1], re-tokenised to the nearest bin centre) with the
+        gripper token of the samples' majority class; on a gripper tie the augmented rows take the class of sample 0. normals fp32
+        [P, n_augmented, n_gen // 7, 6] on the device (host.augmentation_normals). Every token of the result is an action token whenever
+        the sampled ones are; ops.tokens_to_histories, score_histories(group_size=S) and tokens_to_actions take it as they take sampled
+        tokens. One launch; the policy is not run. Off by default: nothing calls this."""
+        return ops.augment_tokens(tokens, n_samples, n_augmented, normals, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
+                                  sigma=sigma, sd_floor=sd_floor)

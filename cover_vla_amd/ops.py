@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -1331,6 +1331,101 @@ def prior_select(scores, logprobs, group_size, beta, *, tokens=None, pad_token_i
     a.result_out, a.best_out, a.ranked_out = out["result"].data_ptr(), out["best"].data_ptr(), (out["ranked"].data_ptr() if top_m else None)
     L.check(L.lib().cover_prior_select(C.byref(a), _stream()), "prior_select")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ proposal augmentation
+class AugmentStats(NamedTuple):
+    """What augment_tokens / augment_actions return beside the output with stats=True."""
+    mean: torch.Tensor     # fp32 [G, steps, 6]
+    sd: torch.Tensor       # fp32 [G, steps, 6], after the floor
+    votes: torch.Tensor    # int32 [G, steps, 2]: (class-0 count, class-1 count) of the gripper vote
+
+
+def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, out_shape,
+             stats, centers=None, tok_vocab=0):
+    """The checks and the launch both augment wrappers share. src: the input tensor; elem: its dtype; out_shape(G, S) -> the output's shape."""
+    n, K = int(n_samples), int(n_augmented)
+    if not 1 <= n <= 4096 or not 0 <= K <= 4096 or N < 1 or N % n != 0:
+        raise L.CoverError(f"{what}: 1 <= n_samples <= 4096, 0 <= n_augmented <= 4096 and rows % n_samples == 0 are required "
+                           f"(got rows={N}, n_samples={n}, n_augmented={K})")
+    G, S = N // n, n + K
+    if not 1 <= steps <= 64 or G * S > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and prompts * (n_samples + n_augmented) <= 2^20 are required (got steps={steps}, "
+                           f"prompts={G})")
+    if not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != (G, K, steps, 6) or not normals.is_contiguous():
+        raise L.CoverError(f"{what}: normals must be contiguous fp32 [prompts, n_augmented, steps, 6] = [{G}, {K}, {steps}, 6] "
+                           f"(got {tuple(normals.shape) if torch.is_tensor(normals) else type(normals).__name__})")
+    sigma, sd_floor = float(sigma), float(sd_floor)
+    for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
+        if not (math.isfinite(v) and v >= 0.0 and math.isfinite(C.c_float(v).value)):
+            raise L.CoverError(f"{what}: {name} must be finite and >= 0 (got {v})")
+    try:
+        lo, hi = (float(v) for v in clip)
+    except (TypeError, ValueError):
+        raise L.CoverError(f"{what}: clip must be a (lo, hi) pair") from None
+    if not lo <= hi:
+        raise L.CoverError(f"{what}: clip lo <= hi is required, +-inf = no clip (got {clip})")
+    shape = out_shape(G, S)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != elem or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise L.CoverError(f"{what}: out must be a contiguous {elem} tensor of shape {shape}")
+    _chk_dev(src, normals, centers, out)
+    dev = src.device
+    if any(t is not None and t.device != dev for t in (normals, centers, out)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    if out is None:
+        out = torch.empty(shape, dtype=elem, device=dev)
+    st = None
+    if stats:
+        st = AugmentStats(torch.empty(G, steps, 6, dtype=torch.float32, device=dev), torch.empty(G, steps, 6, dtype=torch.float32, device=dev),
+                          torch.empty(G, steps, 2, dtype=torch.int32, device=dev))
+    a = L.AugmentArgs()
+    a.src, a.n_stride, a.t_stride, a.normals = src.data_ptr(), n_stride, t_stride, (normals.data_ptr() if K else None)
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.G, a.n, a.K, a.h = G, n, K, steps
+    a.sigma, a.sd_floor, a.clip_lo, a.clip_hi = sigma, sd_floor, lo, hi
+    a.out = out.data_ptr()
+    if st is not None:
+        a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    return (out, st) if stats else out
+
+
+def augment_tokens(tokens, n_samples, n_augmented, normals, centers, tok_vocab, *, steps=1, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0),
+                   out=None, stats=False):
+    """Gaussian proposal augmentation of action tokens (cover_augment_tokens): tokens int64 [G * n_samples, >= 7 steps] (unit column
+    stride, any row stride; candidate i belongs to prompt i // n_samples) -> int64 [G * S, 7 steps], S = n_samples + n_augmented. Per
+    prompt, rows 0..n_samples-1 are the input rows verbatim; the n_augmented rows behind them are drawn per (step, dim < 6) from the
+    Gaussian fitted to the samples' de-tokenised values centers[clamp(tok_vocab - token - 1)] -- fp32 chain mean, sd with ddof 1 (0 for
+    one sample) floored at sd_floor, v = mean + (sigma * sd) * normals[g, k, t, d] clipped to clip = (lo, hi) -- and stored as the token
+    of the nearest centre (first minimum). A NaN normal lands on clip lo. The gripper token of every augmented row is that of the
+    lowest-index sample in the majority class (value >= 0.5, the verifier's rule); ON A TIE THE CLASS OF SAMPLE 0 WINS. normals fp32
+    [G, n_augmented, steps, 6] (host.augmentation_normals): the same normals give the same tokens. centers fp32 [n_centers].
+    Downstream code takes the result as it takes sampled tokens, with group_size = S. stats=True -> (out, AugmentStats).
+    One launch, no workspace, recordable."""
+    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1):
+        raise L.CoverError("augment_tokens: tokens must be int64 [rows, >= 7 steps] with unit column stride")
+    steps = int(steps)
+    if steps < 1 or tokens.shape[1] < 7 * steps or (tokens.shape[0] > 1 and tokens.stride(0) < 7 * steps):
+        raise L.CoverError(f"augment_tokens: steps >= 1 and 7 * steps <= columns are required (got steps={steps}, tokens {tuple(tokens.shape)})")
+    if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 1 or centers.numel() < 1 or not centers.is_contiguous():
+        raise L.CoverError("augment_tokens: centers must be contiguous fp32 [n_centers >= 1]")
+    return _augment("augment_tokens", lambda h: h.cover_augment_tokens, tokens, torch.int64, max(tokens.stride(0), 7 * steps), 7,
+                    tokens.shape[0], steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, 7 * steps),
+                    stats, centers=centers, tok_vocab=tok_vocab)
+
+
+def augment_actions(actions, n_samples, n_augmented, normals, *, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0), out=None, stats=False):
+    """The same for a flow-matching policy's chunks (cover_augment_actions): actions fp32 [G * n_samples, steps, >= 7] with unit last
+    stride and any other strides -- a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place -> contiguous fp32 [G * S, steps, 7].
+    The first n_samples rows per prompt are the input's first 7 dims bit for bit; augmented values are stored as they are (clipped to
+    clip; +-inf = no clip), the gripper float is that of the lowest-index sample in the majority class (>= 0.5), a tie going to the class
+    of sample 0. See augment_tokens for the arithmetic."""
+    if not torch.is_tensor(actions) or actions.dtype != torch.float32 or actions.dim() != 3 or actions.shape[2] < 7 or actions.stride(2) != 1:
+        raise L.CoverError("augment_actions: actions must be fp32 [rows, steps, >= 7] with unit last stride")
+    N, steps = actions.shape[0], actions.shape[1]
+    return _augment("augment_actions", lambda h: h.cover_augment_actions, actions, torch.float32, actions.stride(0), actions.stride(1), N, steps,
+                    n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, steps, 7), stats)
 
 
 # ------------------------------------------------------------------------------------------------ beam search

@@ -520,8 +520,15 @@ class PI0Policy:
         return ids.to(dev), mask.to(dev).bool()
 
     @torch.no_grad()
-    def select_action(self, batch: dict, noise: Optional[torch.Tensor] = None, noise_std: float = 1.0) -> collections.deque:
-        """Returns the deque itself (the local modification of modeling_pi0.py:303-307); the caller copies and clears it."""
+    def select_action(self, batch: dict, noise: Optional[torch.Tensor] = None, noise_std: float = 1.0, augment=None) -> collections.deque:
+        """Returns the deque itself (the local modification of modeling_pi0.py:303-307); the caller copies and clears it.
+        augment (host.Augment, default None = the reference's behaviour): the batch holds augment.samples_per_prompt policy samples per
+        prompt in contiguous rows, and every prompt's rows are followed by augment.n_augmented candidates drawn from the diagonal Gaussian
+        fitted to them (ops.augment_actions reads the sliced [B, n_action_steps, 7] view in place, in the policy's normalised space,
+        before unnormalize_action). The queue then holds G * S rows per step, S = samples_per_prompt + n_augmented, the first
+        samples_per_prompt of every S being the policy's own rows bit for bit: pass samples_per_prompt = S and a task_list of G * S to
+        host.verify_and_select. The gripper of the augmented rows is the majority vote of the samples; on a tie they take the class of
+        sample 0, so verify_and_select's in-group vote may then differ from the reference's "winner's sign" rule. action_dim must be 7."""
         if len(self._action_queue) == 0:
             state = normalize_state(batch["observation.state"], self._norm.get("state", IDENTITY))
             images, img_masks = self.prepare_images(batch)
@@ -530,6 +537,11 @@ class PI0Policy:
             actions = self.model.sample_actions(images, img_masks, lang_tokens, lang_masks, state, noise=noise,
                                                 noise_std=noise_std)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
+            if augment is not None:
+                if self.config.action_dim != 7:
+                    raise ops.L.CoverError(f"select_action(augment=): action_dim must be 7 (got {self.config.action_dim})")
+                actions = ops.augment_actions(actions, augment.samples_per_prompt, augment.n_augmented, augment.normals, sigma=augment.sigma,
+                                              sd_floor=augment.sd_floor, clip=augment.clip)
             actions = unnormalize_action(actions, self._norm.get("action", IDENTITY))
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue

@@ -797,6 +797,45 @@ typedef struct cover_prior_select_args {
 } cover_prior_select_args;
 int cover_prior_select(const cover_prior_select_args* args, void* stream);
 
+/* Gaussian proposal augmentation: K cheap verifier candidates per prompt from the prompt's n policy samples. Candidates of a prompt are
+ * contiguous (candidate i belongs to prompt i / n); the output has S = n + K rows per prompt: rows 0..n-1 are the policy's own samples
+ * copied unchanged (token ids verbatim, floats bit for bit), rows n..S-1 are drawn from a diagonal Gaussian fitted to the samples'
+ * translation / rotation dims with the gripper taken by majority vote, so downstream code sees the same tensor with group_size = S.
+ * One block per prompt, one launch, no workspace, no atomics, recordable. All arithmetic is fp32, one rounding per operation, never an
+ * fma; for group g, step t < h and dim d < 6, with x_j the value of sample j:
+ *   mean  = (((0.0f + x_0) + x_1) + ... + x_{n-1}) / (float)n                       one chain of adds in sample order, one divide
+ *   ss    = the same chain over (x_j - mean) * (x_j - mean);  var = ss / (float)(n - 1), 0 when n == 1
+ *   sd    = fmaxf(sqrtf(var), sd_floor)
+ *   row k : s = sigma * sd;  p = s * z[g][k][t][d];  v = mean + p;  v = fminf(fmaxf(v, clip_lo), clip_hi)
+ *           (a NaN z therefore lands on clip_lo; clip_lo = -inf / clip_hi = +inf mean no clip on that side)
+ * z = normals, fp32 [G][K][h][6], supplied by the caller like the samplers' uniforms: the same z gives the same bits.
+ * Gripper (d == 6), per step: the class of sample j is (x_j >= 0.5f), the verifier's rule; the majority class wins, a tie goes to the
+ * class of sample 0; every augmented row takes the gripper token / float of the lowest-index sample in the winning class.
+ * cover_augment_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (n_stride >= 7 h; t_stride unused),
+ *   x_j = centers[clamp(tok_vocab - token - 1, 0, n_centers - 1)] (cover_tokens_to_histories' rule); out = int64 [G * S][7 h]; an
+ *   augmented value v is stored as tok_vocab - 1 - b, b the FIRST index that minimises fabsf(v - centers[b]) over all n_centers.
+ * cover_augment_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit last
+ *   stride: a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place); centers unused; out = contiguous fp32 [G * S][h][7], v stored.
+ * Optional outputs (NULL = not written): mean_out / sd_out fp32 [G][h][6] (sd after the floor), votes_out int32 [G][h][2] =
+ * (class-0 count, class-1 count).
+ * COVER_EINVAL unless G >= 1, 1 <= n <= 4096, 0 <= K <= 4096, 1 <= h <= 64, G * (n + K) <= 2^20, sigma and sd_floor finite and >= 0,
+ * clip_lo <= clip_hi, src / out non-null, normals non-null when K > 0 and, for tokens, n_stride >= 7 h, centers non-null, n_centers >= 1.
+ * K == 0 copies the originals only. */
+typedef struct cover_augment_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* normals;           /* [G][K][h][6] */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    int n_centers, tok_vocab;
+    int G, n, K, h;
+    float sigma, sd_floor, clip_lo, clip_hi;
+    void* out;                      /* int64 [G * (n + K)][7 h] or fp32 [G * (n + K)][h][7] */
+    float* mean_out; float* sd_out; /* [G][h][6], optional */
+    int* votes_out;                 /* [G][h][2], optional */
+} cover_augment_args;
+int cover_augment_tokens(const cover_augment_args* args, void* stream);
+int cover_augment_actions(const cover_augment_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
