@@ -4,16 +4,11 @@
 // operators with contraction off for the whole file, because hipcc would otherwise fuse d * d + ss and mean + s * z into one v_fma_f32.
 #include "common.h"
 #include "kernels.h"
+#include "augment_fit.h"   // aug_value, augment_group_stats: the fit, shared with proposal_prior.hip
 
 #pragma clang fp contract(off)
 
-// what a raw input element is worth, and what an augmented value is stored as: floats pass through, tokens go through the bin centres
-__device__ __forceinline__ float aug_value(const cover_augment_args& a, float raw) { return raw; }
-__device__ __forceinline__ float aug_value(const cover_augment_args& a, int64_t token) {
-    long long b = (long long)a.tok_vocab - token - 1;   // tokens_to_histories_k's rule
-    b = b < 0 ? 0 : (b > a.n_centers - 1 ? a.n_centers - 1 : b);
-    return a.centers[b];
-}
+// what an augmented value is stored as: floats as they are, tokens as the token of the nearest bin centre
 __device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, float* o) { *o = v; }
 __device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, int64_t* o) {
     // first index that minimises |v - centers[b]|: a plain scan (b is uniform over the wave: the table comes through scalar loads)
@@ -29,53 +24,6 @@ __device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, 
     *o = (int64_t)a.tok_vocab - 1 - bi;
 }
 
-// The statistics of one prompt group, left in LDS: for item i = t * 6 + d < 6 h the mean and s = sigma * sd of (step t, dim d), for
-// step t the index of the sample whose gripper the augmented rows take. `in` is the group's first row; element (j, t, d) at
-// in[j * n_stride + t * t_stride + d]. One thread per item, the samples in index order.
-template <typename T>
-__device__ void augment_group_stats(const cover_augment_args& a, const T* in, long long t_stride, int g, float* s_mean, float* s_s,
-                                    int* s_jwin) {
-    const int n = a.n, h = a.h;
-    for (int i = threadIdx.x; i < 7 * h; i += blockDim.x) {
-        if (i < 6 * h) {
-            const int t = i / 6, d = i - t * 6;
-            const T* x = in + (long long)t * t_stride + d;
-            float sum = 0.0f;
-            for (int j = 0; j < n; ++j) sum = sum + aug_value(a, x[(long long)j * a.n_stride]);
-            const float mean = sum / (float)n;
-            float ss = 0.0f;
-            for (int j = 0; j < n; ++j) {
-                const float dev = aug_value(a, x[(long long)j * a.n_stride]) - mean;
-                const float sq = dev * dev;
-                ss = ss + sq;
-            }
-            const float var = n > 1 ? ss / (float)(n - 1) : 0.0f;
-            const float sd = fmaxf(sqrtf(var), a.sd_floor);
-            s_mean[i] = mean;
-            s_s[i] = a.sigma * sd;
-            if (a.mean_out) a.mean_out[(size_t)g * 6 * h + i] = mean;
-            if (a.sd_out) a.sd_out[(size_t)g * 6 * h + i] = sd;
-        } else {
-            const int t = i - 6 * h;
-            const T* x = in + (long long)t * t_stride + 6;
-            int ones = 0, first0 = -1, first1 = -1;
-            for (int j = 0; j < n; ++j) {
-                const bool c1 = aug_value(a, x[(long long)j * a.n_stride]) >= 0.5f;
-                ones += c1 ? 1 : 0;
-                if (c1 && first1 < 0) first1 = j;
-                if (!c1 && first0 < 0) first0 = j;
-            }
-            const int zeros = n - ones;
-            const bool win1 = ones > zeros || (ones == zeros && first1 == 0);   // a tie goes to the class of sample 0
-            s_jwin[t] = win1 ? first1 : first0;
-            if (a.votes_out) {
-                a.votes_out[((size_t)g * h + t) * 2] = zeros;
-                a.votes_out[((size_t)g * h + t) * 2 + 1] = ones;
-            }
-        }
-    }
-}
-
 // one block per prompt group: statistics -> LDS, the n originals copied, then the block walks (k, t, d) of the K augmented rows in
 // output order (coalesced stores)
 template <typename T>
@@ -85,7 +33,8 @@ __global__ __launch_bounds__(256) void augment_k(cover_augment_args a, long long
     const int g = blockIdx.x, n = a.n, K = a.K, h = a.h, w = 7 * h;
     const T* in = (const T*)a.src + (long long)g * n * a.n_stride;
     T* out = (T*)a.out + (size_t)g * (n + K) * w;
-    augment_group_stats<T>(a, in, t_stride, g, s_mean, s_s, s_jwin);
+    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, a.n, a.h, a.sigma, a.sd_floor, a.mean_out, a.sd_out, a.votes_out};
+    augment_group_stats<T>(f, in, t_stride, g, s_mean, s_s, s_jwin);
     for (int i = threadIdx.x; i < n * w; i += blockDim.x) {
         const int j = i / w, r = i - j * w, t = r / 7, d = r - t * 7;
         out[i] = in[(long long)j * a.n_stride + (long long)t * t_stride + d];

@@ -408,6 +408,18 @@ int cover_augment_actions(const cover_augment_args* a, void* stream) {
     HIPCHK(launch_augment_actions(a, ST(stream)), "augment_actions (" AUGMENT_LIMITS ")");
     return COVER_OK;
 }
+#define PROPOSAL_PRIOR_LIMITS "G >= 1, 1 <= n_fit <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, sigma and sd_floor finite " \
+                              "and > 0 with an fp32 product > 0, src / prior_out required"
+int cover_proposal_prior_tokens(const cover_proposal_prior_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_proposal_prior_tokens: null args");
+    HIPCHK(launch_proposal_prior_tokens(a, ST(stream)), "proposal_prior_tokens (" PROPOSAL_PRIOR_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_proposal_prior_actions(const cover_proposal_prior_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_proposal_prior_actions: null args");
+    HIPCHK(launch_proposal_prior_actions(a, ST(stream)), "proposal_prior_actions (" PROPOSAL_PRIOR_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -532,7 +544,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_workspace); SZ(cover_vit_layer); SZ(cover_vit_desc); SZ(cover_dec_layer); SZ(cover_dec_desc);
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
-    SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args);
+    SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
 #undef SZ
     return 0;
 }

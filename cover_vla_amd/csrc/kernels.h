@@ -106,6 +106,9 @@ size_t gemm_workspace_bytes(int M, int N, int K);
 // ---- augment.hip ---------------------------------------------------------------------------------
 hipError_t launch_augment_tokens(const cover_augment_args* a, hipStream_t st);
 hipError_t launch_augment_actions(const cover_augment_args* a, hipStream_t st);
+// ---- proposal_prior.hip --------------------------------------------------------------------------
+hipError_t launch_proposal_prior_tokens(const cover_proposal_prior_args* a, hipStream_t st);
+hipError_t launch_proposal_prior_actions(const cover_proposal_prior_args* a, hipStream_t st);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
 hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);

@@ -137,6 +137,56 @@ class Augment(_AugmentFields):
         return super().__new__(cls, int(samples_per_prompt), int(n_augmented), normals, float(sigma), float(sd_floor), (float(clip[0]), float(clip[1])))
 
 
+def vote_log_shares(n_fit: int, alpha: float) -> np.ndarray:
+    """The gripper term of the proposal log-density prior (ops.proposal_prior_tokens / ops.proposal_prior_actions, log_share=): fp32
+    numpy [n_fit + 1], entry c = float32(log((c + alpha) / (n_fit + 2 alpha))) computed in float64 -- the add-alpha estimate of the
+    share of a gripper class that c of the n_fit fitted samples voted for. It is made on the host so that the device takes no
+    logarithm and the prior stays a fixed bit pattern; move it to the device once (torch.from_numpy(...).to(dev)). alpha = 0 gives -inf
+    at c = 0: a row whose class no sample voted for can then never win (cover_prior_select's rule for -inf). No alpha is recommended."""
+    if isinstance(n_fit, bool) or not isinstance(n_fit, (int, np.integer)) or not 1 <= n_fit <= 4096:
+        raise ValueError(f"vote_log_shares: an integer 1 <= n_fit <= 4096 is required (got {n_fit!r})")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.floating, np.integer)) or not (math.isfinite(alpha) and alpha >= 0):
+        raise ValueError(f"vote_log_shares: alpha must be a finite number >= 0 (got {alpha!r})")
+    c = np.arange(int(n_fit) + 1, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.log((c + float(alpha)) / (float(n_fit) + 2.0 * float(alpha))).astype(np.float32)
+
+
+class _ProposalPriorFields(NamedTuple):
+    samples_per_prompt: int
+    sigma: float
+    sd_floor: float
+    log_share: Any = None
+
+
+class ProposalPrior(_ProposalPriorFields):
+    """What PI0Policy.proposal_prior is set to (policy.proposal_prior = ProposalPrior(...); None = off): every row of the action batch gets the unnormalised log-density of the
+    diagonal Gaussian fitted to its prompt's samples_per_prompt policy samples (ops.proposal_prior_actions, in the policy's normalised
+    action space; with augment= the augmented rows behind the samples are scored under the same fit), kept as
+    policy.last_proposal_prior for verify_and_select(candidate_prior=, prior_beta=). sigma scales the fitted standard deviation and
+    sd_floor is its lower bound, both > 0 and both required; log_share: None or fp32 [samples_per_prompt + 1] on the policy's device
+    (vote_log_shares), the gripper term. Values are checked here (CoverError), shapes against the batch in ops.proposal_prior_actions.
+    No default sigma, floor or alpha is recommended."""
+    __slots__ = ()
+
+    def __new__(cls, samples_per_prompt, sigma, sd_floor, log_share=None):
+        import ctypes
+        import torch
+        from ._lib import CoverError
+        f32 = lambda v: ctypes.c_float(v).value                     # the value the launch receives
+        if isinstance(samples_per_prompt, bool) or not isinstance(samples_per_prompt, (int, np.integer)) or not 1 <= samples_per_prompt <= 4096:
+            raise CoverError(f"ProposalPrior: an integer 1 <= samples_per_prompt <= 4096 is required (got {samples_per_prompt!r})")
+        for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(f32(v)) and f32(v) > 0):
+                raise CoverError(f"ProposalPrior: {name} must be a finite number > 0 in fp32 (got {v!r})")
+        if not f32(f32(sigma) * f32(sd_floor)) > 0:
+            raise CoverError(f"ProposalPrior: the fp32 product sigma * sd_floor must be > 0 (got {sigma!r} * {sd_floor!r})")
+        if log_share is not None and (not torch.is_tensor(log_share) or log_share.dtype != torch.float32
+                                      or tuple(log_share.shape) != (samples_per_prompt + 1,)):
+            raise CoverError(f"ProposalPrior: log_share must be None or an fp32 tensor [samples_per_prompt + 1 = {samples_per_prompt + 1}]")
+        return super().__new__(cls, int(samples_per_prompt), float(sigma), float(sd_floor), log_share)
+
+
 class TokenGrammar(NamedTuple):
     """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
     allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)

@@ -504,3 +504,14 @@ class OpenVLA:
         tokens. One launch; the policy is not run. Off by default: nothing calls this."""
         return ops.augment_tokens(tokens, n_samples, n_augmented, normals, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
                                   sigma=sigma, sd_floor=sd_floor)
+
+    def proposal_prior(self, tokens: torch.Tensor, group_rows: int, n_fit: int, *, sigma, sd_floor, log_share=None):
+        """The proposal log-density prior of action-token chunks (ops.proposal_prior_tokens with this model's tok_vocab, bin centres and
+        steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] -> fp32 [P * group_rows], per row the unnormalised log-density of the
+        diagonal Gaussian fitted to the first n_fit rows of its prompt (the fit augment draws from) plus, with log_share
+        (host.vote_log_shares on the device), the log share of the row's gripper class. After augment(tokens, n, K, ...) pass
+        group_rows = n + K and n_fit = n; on sampled tokens alone group_rows = n_fit = n. The result is the [N] prior ops.prior_select
+        and score_histories(prior=, prior_beta=) take with group_size = group_rows. sigma and sd_floor must be > 0; none is
+        recommended. One launch; the policy is not run. Off by default: nothing calls this."""
+        return ops.proposal_prior_tokens(tokens, group_rows, n_fit, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
+                                         sigma=sigma, sd_floor=sd_floor, log_share=log_share)

@@ -1341,6 +1341,29 @@ class AugmentStats(NamedTuple):
     votes: torch.Tensor    # int32 [G, steps, 2]: (class-0 count, class-1 count) of the gripper vote
 
 
+def _augment_stats(G, steps, dev):
+    return AugmentStats(torch.empty(G, steps, 6, dtype=torch.float32, device=dev), torch.empty(G, steps, 6, dtype=torch.float32, device=dev),
+                        torch.empty(G, steps, 2, dtype=torch.int32, device=dev))
+
+
+def _token_rows(what, tokens, steps, centers):
+    """The input checks of the token forms (augment_tokens, proposal_prior_tokens) -> (steps, row stride in elements)."""
+    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1):
+        raise L.CoverError(f"{what}: tokens must be int64 [rows, >= 7 steps] with unit column stride")
+    steps = int(steps)
+    if steps < 1 or tokens.shape[1] < 7 * steps or (tokens.shape[0] > 1 and tokens.stride(0) < 7 * steps):
+        raise L.CoverError(f"{what}: steps >= 1 and 7 * steps <= columns are required (got steps={steps}, tokens {tuple(tokens.shape)})")
+    if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 1 or centers.numel() < 1 or not centers.is_contiguous():
+        raise L.CoverError(f"{what}: centers must be contiguous fp32 [n_centers >= 1]")
+    return steps, max(tokens.stride(0), 7 * steps)
+
+
+def _action_rows(what, actions):
+    """The input check of the float forms (augment_actions, proposal_prior_actions)."""
+    if not torch.is_tensor(actions) or actions.dtype != torch.float32 or actions.dim() != 3 or actions.shape[2] < 7 or actions.stride(2) != 1:
+        raise L.CoverError(f"{what}: actions must be fp32 [rows, steps, >= 7] with unit last stride")
+
+
 def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, out_shape,
              stats, centers=None, tok_vocab=0):
     """The checks and the launch both augment wrappers share. src: the input tensor; elem: its dtype; out_shape(G, S) -> the output's shape."""
@@ -1374,10 +1397,7 @@ def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_aug
         raise L.CoverError(f"{what}: every tensor must be on one device")
     if out is None:
         out = torch.empty(shape, dtype=elem, device=dev)
-    st = None
-    if stats:
-        st = AugmentStats(torch.empty(G, steps, 6, dtype=torch.float32, device=dev), torch.empty(G, steps, 6, dtype=torch.float32, device=dev),
-                          torch.empty(G, steps, 2, dtype=torch.int32, device=dev))
+    st = _augment_stats(G, steps, dev) if stats else None
     a = L.AugmentArgs()
     a.src, a.n_stride, a.t_stride, a.normals = src.data_ptr(), n_stride, t_stride, (normals.data_ptr() if K else None)
     if centers is not None:
@@ -1403,14 +1423,8 @@ def augment_tokens(tokens, n_samples, n_augmented, normals, centers, tok_vocab, 
     [G, n_augmented, steps, 6] (host.augmentation_normals): the same normals give the same tokens. centers fp32 [n_centers].
     Downstream code takes the result as it takes sampled tokens, with group_size = S. stats=True -> (out, AugmentStats).
     One launch, no workspace, recordable."""
-    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1):
-        raise L.CoverError("augment_tokens: tokens must be int64 [rows, >= 7 steps] with unit column stride")
-    steps = int(steps)
-    if steps < 1 or tokens.shape[1] < 7 * steps or (tokens.shape[0] > 1 and tokens.stride(0) < 7 * steps):
-        raise L.CoverError(f"augment_tokens: steps >= 1 and 7 * steps <= columns are required (got steps={steps}, tokens {tuple(tokens.shape)})")
-    if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 1 or centers.numel() < 1 or not centers.is_contiguous():
-        raise L.CoverError("augment_tokens: centers must be contiguous fp32 [n_centers >= 1]")
-    return _augment("augment_tokens", lambda h: h.cover_augment_tokens, tokens, torch.int64, max(tokens.stride(0), 7 * steps), 7,
+    steps, n_stride = _token_rows("augment_tokens", tokens, steps, centers)
+    return _augment("augment_tokens", lambda h: h.cover_augment_tokens, tokens, torch.int64, n_stride, 7,
                     tokens.shape[0], steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, 7 * steps),
                     stats, centers=centers, tok_vocab=tok_vocab)
 
@@ -1421,11 +1435,89 @@ def augment_actions(actions, n_samples, n_augmented, normals, *, sigma=1.0, sd_f
     The first n_samples rows per prompt are the input's first 7 dims bit for bit; augmented values are stored as they are (clipped to
     clip; +-inf = no clip), the gripper float is that of the lowest-index sample in the majority class (>= 0.5), a tie going to the class
     of sample 0. See augment_tokens for the arithmetic."""
-    if not torch.is_tensor(actions) or actions.dtype != torch.float32 or actions.dim() != 3 or actions.shape[2] < 7 or actions.stride(2) != 1:
-        raise L.CoverError("augment_actions: actions must be fp32 [rows, steps, >= 7] with unit last stride")
+    _action_rows("augment_actions", actions)
     N, steps = actions.shape[0], actions.shape[1]
     return _augment("augment_actions", lambda h: h.cover_augment_actions, actions, torch.float32, actions.stride(0), actions.stride(1), N, steps,
                     n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, steps, 7), stats)
+
+
+# ------------------------------------------------------------------------------------------------ proposal log-density prior
+def _proposal_prior(what, fn, src, n_stride, t_stride, N, steps, group_rows, n_fit, sigma, sd_floor, log_share, out, stats, centers=None,
+                    tok_vocab=0):
+    """The checks and the launch both proposal-prior wrappers share."""
+    ints = (int, np.integer)
+    if isinstance(group_rows, bool) or isinstance(n_fit, bool) or not (isinstance(group_rows, ints) and isinstance(n_fit, ints)):
+        raise L.CoverError(f"{what}: group_rows and n_fit must be integers (got {group_rows!r}, {n_fit!r})")
+    S, n = int(group_rows), int(n_fit)
+    if not 1 <= n <= S <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= n_fit <= group_rows <= 4096 and rows % group_rows == 0 are required "
+                           f"(got rows={N}, group_rows={S}, n_fit={n})")
+    G = N // S
+    if not 1 <= steps <= 64 or N > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
+    vals = []
+    for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+            raise L.CoverError(f"{what}: {name} must be a number (got {v!r})")
+        v = float(v)
+        if not (math.isfinite(v) and math.isfinite(C.c_float(v).value) and C.c_float(v).value > 0.0):
+            raise L.CoverError(f"{what}: {name} must be finite and > 0 in fp32 (got {v})")
+        vals.append(C.c_float(v).value)
+    sigma, sd_floor = vals
+    if not C.c_float(sigma * sd_floor).value > 0.0:
+        raise L.CoverError(f"{what}: the fp32 product sigma * sd_floor must be > 0 (got {sigma} * {sd_floor})")
+    if log_share is not None and (not torch.is_tensor(log_share) or log_share.dtype != torch.float32 or tuple(log_share.shape) != (n + 1,)
+                                  or not log_share.is_contiguous()):
+        raise L.CoverError(f"{what}: log_share must be contiguous fp32 [n_fit + 1] = [{n + 1}] (host.vote_log_shares)")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
+        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
+    _chk_dev(src, centers, log_share, out)
+    dev = src.device
+    if any(t is not None and t.device != dev for t in (centers, log_share, out)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=dev)
+    st = _augment_stats(G, steps, dev) if stats else None
+    a = L.ProposalPriorArgs()
+    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    if log_share is not None:
+        a.log_share = log_share.data_ptr()
+    a.G, a.group_rows, a.n_fit, a.h = G, S, n, steps
+    a.sigma, a.sd_floor = sigma, sd_floor
+    a.prior_out = out.data_ptr()
+    if st is not None:
+        a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    return (out, st) if stats else out
+
+
+def proposal_prior_tokens(tokens, group_rows, n_fit, centers, tok_vocab, *, steps=1, sigma, sd_floor, log_share=None, out=None, stats=False):
+    """Proposal log-density prior of action tokens (cover_proposal_prior_tokens): tokens int64 [G * group_rows, >= 7 steps] (unit column
+    stride, any row stride; row i belongs to prompt i // group_rows) -> fp32 [G * group_rows]. Per prompt the diagonal Gaussian of
+    augment_tokens is fitted to the first n_fit rows' de-tokenised values centers[clamp(tok_vocab - token - 1)] (the same device
+    function: chain mean, sd with ddof 1, 0 for one row, floored at sd_floor) and every row r of the group gets
+    p = -0.5 * sum_{t, d < 6} ((x - mean) / (sigma * sd))^2, one fp32 chain in (step, dim) order, five roundings per term. That is the
+    UNNORMALISED log-density: the -sum log(sigma * sd) term is left out (no logarithm on the device; it is the same for every row of a
+    prompt). log_share fp32 [n_fit + 1] (host.vote_log_shares) adds, per step, log_share[c], c = how many of the n_fit rows share the
+    row's gripper class (value >= 0.5) at that step; None = the gripper contributes nothing; an entry may be -inf. The result is the
+    [N] prior prior_select / compute_max_similarity_scores_batch(candidate_prior=) take, with group_size = group_rows -- after
+    augment_tokens group_rows = n_samples + n_augmented and n_fit = n_samples; group_rows == n_fit scores plain policy samples among
+    their siblings. sigma and sd_floor must be > 0 (no default is chosen). A NaN appears only in the float form. stats=True ->
+    (prior, AugmentStats) of the fit. One launch, no workspace, recordable."""
+    steps, n_stride = _token_rows("proposal_prior_tokens", tokens, steps, centers)
+    return _proposal_prior("proposal_prior_tokens", lambda h: h.cover_proposal_prior_tokens, tokens, n_stride, 7, tokens.shape[0], steps,
+                           group_rows, n_fit, sigma, sd_floor, log_share, out, stats, centers=centers, tok_vocab=tok_vocab)
+
+
+def proposal_prior_actions(actions, group_rows, n_fit, *, sigma, sd_floor, log_share=None, out=None, stats=False):
+    """The same for a flow-matching policy's chunks (cover_proposal_prior_actions): actions fp32 [G * group_rows, steps, >= 7] with unit
+    last stride and any other strides -- a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place -> fp32 [G * group_rows]. A
+    NaN element of a row that is not among the n_fit fitted ones gives a NaN prior for that row only. See proposal_prior_tokens."""
+    _action_rows("proposal_prior_actions", actions)
+    return _proposal_prior("proposal_prior_actions", lambda h: h.cover_proposal_prior_actions, actions, actions.stride(0), actions.stride(1),
+                           actions.shape[0], actions.shape[1], group_rows, n_fit, sigma, sd_floor, log_share, out, stats)
 
 
 # ------------------------------------------------------------------------------------------------ beam search

@@ -451,6 +451,8 @@ class PI0Policy:
         mv = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).to(dev)
         self._norm = {k: (m, mv(a), mv(b)) for k, (m, a, b) in norm.items()}
         self._preprocess_adapter = None
+        self.proposal_prior = None                # host.ProposalPrior or None (off): what select_action scores its rows with, see there
+        self.last_proposal_prior = None           # fp32 [rows] on the device, set by a select_action that ran with self.proposal_prior set
         self.reset()
 
     @classmethod
@@ -528,8 +530,25 @@ class PI0Policy:
         before unnormalize_action). The queue then holds G * S rows per step, S = samples_per_prompt + n_augmented, the first
         samples_per_prompt of every S being the policy's own rows bit for bit: pass samples_per_prompt = S and a task_list of G * S to
         host.verify_and_select. The gripper of the augmented rows is the majority vote of the samples; on a tie they take the class of
-        sample 0, so verify_and_select's in-group vote may then differ from the reference's "winner's sign" rule. action_dim must be 7."""
+        sample 0, so verify_and_select's in-group vote may then differ from the reference's "winner's sign" rule. action_dim must be 7.
+        self.proposal_prior (a host.ProposalPrior set on the policy; None, the default = nothing is launched): every row of the queue
+        gets the unnormalised log-density of the diagonal Gaussian fitted to its prompt's proposal_prior.samples_per_prompt policy samples
+        (ops.proposal_prior_actions on the normalised [rows, n_action_steps, 7] view, after the augmentation when augment= is given:
+        group_rows = samples_per_prompt + n_augmented, else samples_per_prompt; before unnormalize_action). It is kept as
+        self.last_proposal_prior, fp32 [rows] on the device, the candidate_prior of host.verify_and_select(candidate_prior=, prior_beta=).
+        A call that finds the queue filled, or the attribute None, leaves last_proposal_prior as it is. It is an attribute and no
+        keyword, as PI0FASTPolicy's scoring options are: this method's parameter list is the reference's plus augment."""
         if len(self._action_queue) == 0:
+            proposal_prior = self.proposal_prior
+            if proposal_prior is not None:                 # checked before the policy runs
+                from .host import ProposalPrior
+                if not isinstance(proposal_prior, ProposalPrior):
+                    raise ops.L.CoverError(f"PI0Policy.proposal_prior must be None or a host.ProposalPrior (got {type(proposal_prior).__name__})")
+                if self.config.action_dim != 7:
+                    raise ops.L.CoverError(f"PI0Policy.proposal_prior: action_dim must be 7 (got {self.config.action_dim})")
+                if augment is not None and augment.samples_per_prompt != proposal_prior.samples_per_prompt:
+                    raise ops.L.CoverError(f"select_action: augment and proposal_prior disagree on samples_per_prompt "
+                                           f"({augment.samples_per_prompt} != {proposal_prior.samples_per_prompt})")
             state = normalize_state(batch["observation.state"], self._norm.get("state", IDENTITY))
             images, img_masks = self.prepare_images(batch)
             state = pad_vector(state, self.config.max_state_dim)
@@ -542,6 +561,11 @@ class PI0Policy:
                     raise ops.L.CoverError(f"select_action(augment=): action_dim must be 7 (got {self.config.action_dim})")
                 actions = ops.augment_actions(actions, augment.samples_per_prompt, augment.n_augmented, augment.normals, sigma=augment.sigma,
                                               sd_floor=augment.sd_floor, clip=augment.clip)
+            if proposal_prior is not None:
+                n_fit = proposal_prior.samples_per_prompt
+                self.last_proposal_prior = ops.proposal_prior_actions(
+                    actions, n_fit + (augment.n_augmented if augment is not None else 0), n_fit, sigma=proposal_prior.sigma,
+                    sd_floor=proposal_prior.sd_floor, log_share=proposal_prior.log_share)
             actions = unnormalize_action(actions, self._norm.get("action", IDENTITY))
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue

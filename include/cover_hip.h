@@ -836,6 +836,46 @@ typedef struct cover_augment_args {
 int cover_augment_tokens(const cover_augment_args* args, void* stream);
 int cover_augment_actions(const cover_augment_args* args, void* stream);
 
+/* Proposal log-density prior: for every row of a prompt group, the unnormalised log-density under the diagonal Gaussian fitted to the
+ * group's first n_fit rows (the distribution cover_augment_* draws its rows from; with group_rows == n_fit, how typical a policy sample
+ * is among its siblings), plus optionally the log share of the row's gripper class. A group is group_rows (S) contiguous rows, row i
+ * belongs to group i / S; the output is fp32 [G * S], the summed prior cover_prior_select takes with steps = 1. One block per group, one
+ * launch, no workspace, no atomics, recordable. All arithmetic is fp32, one rounding per operation, never an fma, and no logarithm is
+ * taken on the device. For group g, step t < h and dim d < 6:
+ *   mean, sd = cover_augment_*'s fit over rows 0..n_fit-1 (the same device function: chain mean, var with n_fit - 1, 0 for one row,
+ *              sd = fmaxf(sqrtf(var), sd_floor));  s = sigma * sd
+ *   row r   : acc = 0.0f;  for t in step order, d = 0..5:  dev = x - mean;  z = dev / s;  sq = z * z;  acc = acc + sq
+ *             p = -0.5f * acc
+ *             log_share != NULL: for t in step order: c = the count, among rows 0..n_fit-1 at step t, of the class (x_6 >= 0.5f) row r
+ *             has at step t;  p = p + log_share[c]
+ *             prior_out[g * S + r] = p
+ * The -sum log s term of the log-density is NOT included (it is the same for every row of a group). log_share = fp32 [n_fit + 1],
+ * supplied by the caller (host.vote_log_shares); an entry may be -inf. A NaN element gives a NaN prior for its own row when the row is
+ * not among the fitted ones.
+ * cover_proposal_prior_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (t_stride unused),
+ *   x = centers[clamp(tok_vocab - token - 1, 0, n_centers - 1)].
+ * cover_proposal_prior_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit
+ *   last stride); centers unused.
+ * Optional outputs (NULL = not written): mean_out / sd_out fp32 [G][h][6] (sd after the floor), votes_out int32 [G][h][2], as
+ * cover_augment_* writes them.
+ * COVER_EINVAL unless G >= 1, 1 <= n_fit <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, sigma and sd_floor finite and > 0
+ * with an fp32 product > 0 (so s > 0 and dev / s is never 0 / 0), src / prior_out non-null and, for tokens, n_stride >= 7 h, centers
+ * non-null, n_centers >= 1. */
+typedef struct cover_proposal_prior_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    const float* log_share;         /* [n_fit + 1], optional */
+    int n_centers, tok_vocab;
+    int G, group_rows, n_fit, h;
+    float sigma, sd_floor;
+    float* prior_out;               /* [G * group_rows] */
+    float* mean_out; float* sd_out; /* [G][h][6], optional */
+    int* votes_out;                 /* [G][h][2], optional */
+} cover_proposal_prior_args;
+int cover_proposal_prior_tokens(const cover_proposal_prior_args* args, void* stream);
+int cover_proposal_prior_actions(const cover_proposal_prior_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *

@@ -1,7 +1,8 @@
-"""Gaussian proposal augmentation, timed: (1) the median launch time of cover_augment_tokens / cover_augment_actions at two shapes,
+"""Gaussian proposal augmentation, timed: (1) the median launch time of cover_augment_tokens / cover_augment_actions at two shapes and
+of cover_proposal_prior_tokens / cover_proposal_prior_actions over their output (G = 8 groups of S = 64 rows, 4 of them fitted),
 (2) one OpenVLA + CoVer decision with P = 8 prompts, n = 4 policy samples and K = 60 augmented candidates per prompt (512 verifier
 candidates) beside bench.py's N = 32 decision (the same Pipeline object, the same process, decisions of the two kinds interleaved).
-Reuses bench.py's pipeline classes; bench.py itself is untouched. Usage: python tools/augment_timing.py [--small] [--steps 20] [--warmup 3]"""
+Reuses bench.py's pipeline classes; bench.py itself is untouched. Usage: python tools/augment_timing.py [--launch-only] [--small] [--steps 20] [--warmup 3]"""
 import argparse
 import concurrent.futures
 import json
@@ -29,8 +30,15 @@ def launch_times(dev, reps=30, per_rep=20):
         z = host.augmentation_normals(G, K, h, seed=1).to(dev)
         o_tok = torch.empty(G * (n + K), 7 * h, dtype=torch.int64, device=dev)
         o_act = torch.empty(G * (n + K), h, 7, dtype=torch.float32, device=dev)
+        S = n + K
+        ls = torch.from_numpy(host.vote_log_shares(n, 1.0)).to(dev)
+        o_pt, o_pa = torch.empty(G * S, device=dev), torch.empty(G * S, device=dev)
         forms = {"tokens": lambda: ops.augment_tokens(tok, n, K, z, centers, 32000, steps=h, out=o_tok),
-                 "actions": lambda: ops.augment_actions(act, n, K, z, out=o_act)}
+                 "actions": lambda: ops.augment_actions(act, n, K, z, out=o_act),
+                 # the prior of the rows the two launches above left in o_tok / o_act (the warm-up fills them before these are timed)
+                 "prior_tokens": lambda: ops.proposal_prior_tokens(o_tok, S, n, centers, 32000, steps=h, sigma=1.0, sd_floor=1e-3, log_share=ls,
+                                                                   out=o_pt),
+                 "prior_actions": lambda: ops.proposal_prior_actions(o_act, S, n, sigma=1.0, sd_floor=1e-3, log_share=ls, out=o_pa)}
         for name, fn in forms.items():
             for _ in range(10):
                 fn()
@@ -42,6 +50,7 @@ def launch_times(dev, reps=30, per_rep=20):
                     fn()
                 ms.append(t.stop() / per_rep)
             out[f"{name}_{G}x{n}x{K}x{h}_us"] = round(float(np.median(ms)) * 1e3, 2)
+            out[f"{name}_{G}x{n}x{K}x{h}_us_min_max"] = [round(min(ms) * 1e3, 2), round(max(ms) * 1e3, 2)]
     return out
 
 
@@ -79,10 +88,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--augmented", type=int, default=60, help="K per prompt (60: 8 x (4 + 60) = 512 verifier candidates)")
+    ap.add_argument("--launch-only", action="store_true", help="part (1) only: no pipeline is built")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     res = {"launch": launch_times(dev)}
+    if a.launch_only:
+        print(json.dumps(res))
+        return
     pipe = bench.Pipeline(dev, small=a.small)
     P, n, K = len(pipe.prompt_ids), pipe.n_samples, a.augmented
     z = host.augmentation_normals(P, K, 1, seed=0).to(dev)
