@@ -184,6 +184,13 @@ class PriorSelectArgs(C.Structure):
                 ("ranked_out", c_p)]
 
 
+class MemberScoresArgs(C.Structure):
+    _fields_ = [("it", c_p), ("act", c_p), ("scores", c_p), ("n_members", c_i), ("N", c_i), ("dim", c_i), ("group_size", c_i),
+                ("kappa", c_f), ("mode", c_i), ("member_scores_out", c_p), ("mean_out", c_p), ("spread_out", c_p), ("min_out", c_p),
+                ("min_member_out", c_p), ("robust_out", c_p), ("result_out", c_p), ("best_out", c_p), ("member_result_out", c_p),
+                ("member_best_out", c_p)]
+
+
 class AugmentArgs(C.Structure):
     _fields_ = [("src", c_p), ("n_stride", c_ll), ("t_stride", c_ll), ("normals", c_p), ("centers", c_p),
                 ("n_centers", c_i), ("tok_vocab", c_i), ("G", c_i), ("n", c_i), ("K", c_i), ("h", c_i),
@@ -280,7 +287,7 @@ _STRUCTS = {
     "cover_token_topn_rows_args": TokenTopnRowsArgs, "cover_token_allow": TokenAllow, "cover_token_ref": TokenRef, "cover_decode_feedback_args": DecodeFeedbackArgs,
     "cover_token_fsm": TokenFsm,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_augment_args": AugmentArgs,
-    "cover_proposal_prior_args": ProposalPriorArgs,
+    "cover_proposal_prior_args": ProposalPriorArgs, "cover_member_scores_args": MemberScoresArgs,
     "cover_beam_merge_args": BeamMergeArgs,
     "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
     "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
@@ -356,6 +363,7 @@ SYMBOLS = {
     "cover_score_select": (c_i, [_P(ScoreSelectArgs), c_p]),
     "cover_group_argmax": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "cover_prior_select": (c_i, [_P(PriorSelectArgs), c_p]),
+    "cover_member_scores": (c_i, [_P(MemberScoresArgs), c_p]),
     "cover_augment_tokens": (c_i, [_P(AugmentArgs), c_p]),
     "cover_augment_actions": (c_i, [_P(AugmentArgs), c_p]),
     "cover_proposal_prior_tokens": (c_i, [_P(ProposalPriorArgs), c_p]),

@@ -396,6 +396,13 @@ int cover_prior_select(const cover_prior_select_args* a, void* stream) {
            "beta finite and >= 0, scores / logprobs / prior_out / combined_out / result_out / best_out required, ranked_out with top_m > 0)");
     return COVER_OK;
 }
+int cover_member_scores(const cover_member_scores_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_member_scores: null args");
+    HIPCHK(launch_member_scores(a, ST(stream)),
+           "member_scores (1 <= n_members <= 16, N % group_size == 0, N / group_size <= 4096, 1 <= dim <= 4096, kappa finite and >= 0, "
+           "mode 0 (lcb) or 1 (min, with kappa == 0), every pointer required)");
+    return COVER_OK;
+}
 #define AUGMENT_LIMITS "G >= 1, 1 <= n <= 4096, 0 <= K <= 4096, 1 <= h <= 64, G * (n + K) <= 2^20, sigma and sd_floor finite and >= 0, " \
                        "clip_lo <= clip_hi, src / out required, normals with K > 0"
 int cover_augment_tokens(const cover_augment_args* a, void* stream) {
@@ -545,6 +552,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
+    SZ(cover_member_scores_args);
 #undef SZ
     return 0;
 }

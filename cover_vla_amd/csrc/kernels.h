@@ -102,6 +102,7 @@ hipError_t launch_actions_to_histories(const float* actions, long long n_stride,
                                        uint8_t* pad, hipStream_t st);
 hipError_t launch_group_argmax(const float* scores, int N, int gs, int* result, float* best, hipStream_t st);
 hipError_t launch_prior_select(const cover_prior_select_args* a, hipStream_t st);
+hipError_t launch_member_scores(const cover_member_scores_args* a, hipStream_t st);
 size_t gemm_workspace_bytes(int M, int N, int K);
 // ---- augment.hip ---------------------------------------------------------------------------------
 hipError_t launch_augment_tokens(const cover_augment_args* a, hipStream_t st);

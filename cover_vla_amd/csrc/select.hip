@@ -290,6 +290,93 @@ hipError_t launch_score_select(const cover_score_select_args* a, hipStream_t st)
     return hipGetLastError();
 }
 
+// Per-member scores (cover_member_scores): what the fused score above throws away. score_rows_k's geometry -- one wave per candidate,
+// 16 candidates per block -- with one lane-strided chain and one butterfly per member; lane m keeps s_m, and every lane then runs the
+// same member-order chains over the broadcast values (no indexed register array), lane 0 stores. The results are compared with a numpy
+// restatement as bit patterns, so contraction is off in the kernel body: every product is rounded before it is added.
+__global__ __launch_bounds__(1024) void member_rows_k(cover_member_scores_args a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int n = blockIdx.x * 16 + w;
+    if (n >= a.N) return;
+    const int M = a.n_members, dim = a.dim;
+    float mine = 0.0f;   // lane m < M: s_m
+    for (int m = 0; m < M; ++m) {
+        const float* it = a.it + (size_t)m * dim;
+        const float* act = a.act + ((size_t)m * a.N + n) * dim;
+        float p = 0.0f;
+        for (int d = lane; d < dim; d += 64) {
+            const float prod = it[d] * act[d];
+            p = p + prod;
+        }
+        const float s = wave_sum(p);
+        if (lane == m) mine = s;
+        if (lane == 0) a.member_scores_out[(size_t)m * a.N + n] = s;
+    }
+    float t = 0.0f;
+    for (int m = 0; m < M; ++m) t = t + __shfl(mine, m);
+    const float mean = t / (float)M;
+    float ss = 0.0f;
+    for (int m = 0; m < M; ++m) {
+        const float dv = __shfl(mine, m) - mean;
+        const float sq = dv * dv;
+        ss = ss + sq;
+    }
+    const float var = ss / (float)M;
+    const float spread = sqrtf(var);
+    float mn = __shfl(mine, 0);
+    int arg = 0;
+    for (int m = 1; m < M; ++m) {
+        const float s = __shfl(mine, m);
+        if (s < mn) {   // first minimum wins, a NaN never replaces
+            mn = s;
+            arg = m;
+        }
+    }
+    float robust = mn;
+    if (a.mode == COVER_MEMBER_LCB) {
+        robust = a.scores[n];
+        if (a.kappa != 0.0f) {   // kappa == 0: the fused score's own bits, no product
+            const float pen = a.kappa * spread;
+            robust = robust - pen;
+        }
+    }
+    if (lane == 0) {
+        a.mean_out[n] = mean;
+        a.spread_out[n] = spread;
+        a.min_out[n] = mn;
+        a.min_member_out[n] = arg;
+        a.robust_out[n] = robust;
+    }
+}
+// block 0: the robust decision; block 1 + m: member m's own decision -- each IS group_argmax_dev, so each equals cover_group_argmax on its row
+__global__ __launch_bounds__(256) void member_argmax_k(cover_member_scores_args a) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float gmean[4096];
+    if (blockIdx.x == 0) {
+        group_argmax_dev(a.robust_out, a.N, a.group_size, a.result_out, a.best_out, gmean, sv, si);
+    } else {
+        const int m = blockIdx.x - 1;
+        group_argmax_dev(a.member_scores_out + (size_t)m * a.N, a.N, a.group_size, a.member_result_out + 4 * m, a.member_best_out + 2 * m,
+                         gmean, sv, si);
+    }
+}
+hipError_t launch_member_scores(const cover_member_scores_args* a, hipStream_t st) {
+    if (a->n_members < 1 || a->n_members > 16 || a->N < 1 || a->group_size < 1 || a->N % a->group_size != 0 ||
+        a->N / a->group_size > 4096 || a->dim < 1 || a->dim > 4096)
+        return hipErrorInvalidValue;
+    if (!(a->kappa >= 0.0f) || !(a->kappa <= 3.402823466e+38f)) return hipErrorInvalidValue;   // finite, >= 0 (a NaN fails both)
+    if ((a->mode != COVER_MEMBER_LCB && a->mode != COVER_MEMBER_MIN) || (a->mode == COVER_MEMBER_MIN && a->kappa != 0.0f))
+        return hipErrorInvalidValue;
+    if (!a->it || !a->act || !a->scores || !a->member_scores_out || !a->mean_out || !a->spread_out || !a->min_out || !a->min_member_out ||
+        !a->robust_out || !a->result_out || !a->best_out || !a->member_result_out || !a->member_best_out)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(member_rows_k, dim3((a->N + 15) / 16), dim3(1024), 0, st, *a);
+    hipLaunchKernelGGL(member_argmax_k, dim3(1 + a->n_members), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // tokens -> verifier histories on the device (one thread per (candidate, history row))
 // ---------------------------------------------------------------------------------------------------

@@ -335,12 +335,13 @@ def process_inputs(action_queue: Sequence[np.ndarray], verifier_action: bool, ac
 
 def verify_and_select(verifier, raw_image, task_description: str, task_list: Sequence[str], action_queue, action_history,
                       samples_per_prompt: int, n_action_steps: int = 4, threshold: float = 0.1, stats=None,
-                      process_image: bool = True, candidate_prior=None, prior_beta: float = 0.0):
+                      process_image: bool = True, candidate_prior=None, prior_beta: float = 0.0, member_kappa: Optional[float] = None,
+                      member_mode: str = "lcb"):
     """run_simpler_eval_with_openpi.py:329-401: stage 1 scores candidate 0 under the current instruction; if its score
     is < threshold, stage 2 scores all candidates grouped per prompt; then the gripper majority vote inside the winner's
     prompt group and extraction of the winner's remaining steps.
     action_queue: n_action_steps arrays [B,7] (host). Returns dict(execute_action, max_score, max_instruction,
-    global_action_idx, remaining (deque of [1,7]), history_row, prior_beta).
+    global_action_idx, remaining (deque of [1,7]), history_row, prior_beta, member_kappa).
     candidate_prior ([B] sequence log-probabilities of the candidates under the policy, e.g. PI0FASTPolicy.last_sequence_logprobs, or
     [B, steps] per-step values) with prior_beta > 0: stage 2 selects on score + prior_beta * prior (stage 1 scores one candidate: a
     prior cannot change it). The two keywords reach the verifier only then, so a verifier that does not know them keeps working;
@@ -348,9 +349,18 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     When the candidates were drawn with per-candidate sampling parameters (sampling_ladder), candidate_prior should be the reference
     log-probabilities -- the tensor OpenVLA.sample / generate_tokens return with prior_temperature, or
     PI0FASTPolicy.last_sequence_prior_logprobs -- which score every candidate at ONE temperature, unfiltered; the return_logprobs values
-    are taken under each candidate's own rung and do not compare across rungs. No reference temperature or prior_beta is chosen here."""
+    are taken under each candidate's own rung and do not compare across rungs. No reference temperature or prior_beta is chosen here.
+    member_kappa (finite, >= 0; None = off) with member_mode ("lcb" or "min") makes BOTH stages disagreement-aware
+    (EfficientEnsembleMerged.score_histories): the stage-1 gate compares candidate 0's robust score -- its fused score less member_kappa
+    times the spread of the ensemble members' own scores, or the worst member's score -- with the threshold, a pessimistic gate, and
+    stage 2 selects on the robust score (plus the prior, when one is used). The two keywords reach the verifier only when member_kappa
+    is not None. The dict carries member_kappa and, when the verifier keeps last_member_stats, the winner's `spread` and
+    `member_agreement`, the number of members whose own grouped arg-max is the decision. No member_kappa is recommended."""
     if not (prior_beta >= 0.0 and math.isfinite(prior_beta)):
         raise ValueError(f"verify_and_select: prior_beta must be finite and >= 0 (got {prior_beta})")
+    if member_kappa is not None and not (member_kappa >= 0.0 and math.isfinite(member_kappa)):
+        raise ValueError(f"verify_and_select: member_kappa must be finite and >= 0 (got {member_kappa})")
+    member_kw = {} if member_kappa is None else dict(member_kappa=member_kappa, member_mode=member_mode)
     use_prior = candidate_prior is not None and prior_beta > 0
     B = len(task_list)
     num_past = min(len(action_history), 6)
@@ -361,13 +371,13 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     images = [raw_image] * B
     max_score, max_instruction, max_hist, gidx = verifier.compute_max_similarity_scores_batch(
         images=images[0:1], instructions=[task_description], all_action_histories=hist_v[0:1],
-        cfg_repeat_language_instructions=1)
+        cfg_repeat_language_instructions=1, **member_kw)
     stage2 = False
     if max_score < threshold:
         max_score, _, max_hist, gidx = verifier.compute_max_similarity_scores_batch(
             images=images, instructions=[task_description] * B, all_action_histories=hist_v,
             cfg_repeat_language_instructions=samples_per_prompt,
-            **(dict(candidate_prior=candidate_prior, prior_beta=prior_beta) if use_prior else {}))
+            **(dict(candidate_prior=candidate_prior, prior_beta=prior_beta) if use_prior else {}), **member_kw)
         max_instruction = task_list[int(gidx)]
         stage2 = True
     gidx = int(gidx)
@@ -388,7 +398,16 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
                global_action_idx=gidx, remaining=remaining, history_row=max_hist[num_past].copy(), prior_beta=float(prior_beta))
     if use_prior and stage2:
         out["prior"] = _winner_prior(candidate_prior, gidx)
+    out["member_kappa"] = None if member_kappa is None else float(member_kappa)
+    stats = getattr(verifier, "last_member_stats", None) if member_kappa is not None else None
+    if stats is not None:      # the latest scoring call's: stage 2's when it ran, else stage 1's one candidate
+        out["spread"] = float(_host_array(stats["spread"])[gidx])
+        out["member_agreement"] = int((_host_array(stats["member_result"])[:, 0] == gidx).sum())
     return out
+
+
+def _host_array(x) -> np.ndarray:
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
 def _winner_prior(candidate_prior, gidx: int) -> float:

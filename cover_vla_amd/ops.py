@@ -1333,6 +1333,61 @@ def prior_select(scores, logprobs, group_size, beta, *, tokens=None, pad_token_i
     return out
 
 
+MEMBER_MODES = {"lcb": 0, "min": 1}
+
+
+def member_scores(it, act, scores, group_size, kappa=0.0, mode="lcb"):
+    """Per-member scores of the verifier ensemble and a disagreement-aware score (cover_member_scores). it fp32 [M, dim] and act fp32
+    [M, N, dim] are the per-member unit rows score_select takes, scores fp32 [N] the fused scores it returned (read, never written); all
+    contiguous, on one device, 1 <= M <= 16, 1 <= dim <= 4096. Returns a dict of device tensors: member_scores [M, N] (member m's own
+    cosine for every candidate), mean [N], spread [N] (the population standard deviation over the members; exactly 0 for M = 1), min [N]
+    and min_member int32 [N] (the first member that attains it), robust [N], result int32 [4] / best fp32 [2] as group_argmax gives
+    them on robust, member_result int32 [M, 4] / member_best fp32 [M, 2] as group_argmax gives them on each member's row.
+    mode "lcb": robust = scores exactly when kappa == 0, else round(scores - round(kappa * spread)); mode "min": robust = min, and kappa
+    must be 0. kappa is finite and >= 0; no default penalty is recommended. Every sum is one fixed fp32 chain (include/cover_hip.h), so
+    the results are fixed bit patterns. Two launches, no workspace, recordable."""
+    import math
+    if not all(torch.is_tensor(t) and t.dtype == torch.float32 for t in (it, act, scores)):
+        raise L.CoverError("member_scores: it, act and scores must be fp32 tensors")
+    if it.dim() != 2 or act.dim() != 3 or scores.dim() != 1:
+        raise L.CoverError(f"member_scores: it [M, dim], act [M, N, dim] and scores [N] are required (got {tuple(it.shape)}, "
+                           f"{tuple(act.shape)}, {tuple(scores.shape)})")
+    M, N, dim = act.shape
+    if tuple(it.shape) != (M, dim) or scores.numel() != N:
+        raise L.CoverError(f"member_scores: it {tuple(it.shape)} and scores {tuple(scores.shape)} do not match act {tuple(act.shape)}")
+    if not (it.is_contiguous() and act.is_contiguous() and scores.is_contiguous()):
+        raise L.CoverError("member_scores: it, act and scores must be contiguous")
+    if not 1 <= M <= 16 or N < 1 or not 1 <= dim <= 4096:
+        raise L.CoverError(f"member_scores: 1 <= M <= 16, N >= 1 and 1 <= dim <= 4096 are required (got M={M}, N={N}, dim={dim})")
+    group_size = int(group_size)
+    if group_size < 1 or N % group_size != 0 or N // group_size > 4096:
+        raise L.CoverError(f"member_scores: N % group_size == 0 and N / group_size <= 4096 are required (got N={N}, group_size={group_size})")
+    if mode not in MEMBER_MODES:
+        raise L.CoverError(f"member_scores: mode must be 'lcb' or 'min' (got {mode!r})")
+    kappa = float(kappa)
+    if not (math.isfinite(kappa) and kappa >= 0.0 and math.isfinite(C.c_float(kappa).value)):
+        raise L.CoverError(f"member_scores: kappa must be finite and >= 0 (got {kappa})")
+    if mode == "min" and kappa != 0.0:
+        raise L.CoverError(f"member_scores: mode 'min' takes no penalty, kappa must be 0 (got {kappa})")
+    _chk_dev(it, act, scores)
+    if act.device != it.device or scores.device != it.device:
+        raise L.CoverError("member_scores: it, act and scores must be on one device")
+    dev = it.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = {"member_scores": torch.empty(M, N, **f32), "mean": torch.empty(N, **f32), "spread": torch.empty(N, **f32),
+           "min": torch.empty(N, **f32), "min_member": torch.empty(N, **i32), "robust": torch.empty(N, **f32),
+           "result": torch.empty(4, **i32), "best": torch.empty(2, **f32),
+           "member_result": torch.empty(M, 4, **i32), "member_best": torch.empty(M, 2, **f32)}
+    a = L.MemberScoresArgs()
+    a.it, a.act, a.scores = it.data_ptr(), act.data_ptr(), scores.data_ptr()
+    a.n_members, a.N, a.dim, a.group_size, a.kappa, a.mode = M, N, dim, group_size, kappa, MEMBER_MODES[mode]
+    for k, t in out.items():
+        setattr(a, k + "_out", t.data_ptr())
+    L.check(L.lib().cover_member_scores(C.byref(a), _stream()), "member_scores")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ proposal augmentation
 class AugmentStats(NamedTuple):
     """What augment_tokens / augment_actions return beside the output with stats=True."""

@@ -372,6 +372,7 @@ class EfficientEnsembleMerged:
         merged .pt itself, read with torch.load(weights_only=True) (efficient_ensemble_merged.py:37-53 unpickles it; this side never does). encoder/preprocess/tokenizer: the SigLIP2 towers and the open_clip
         CPU transforms are injected (they are un-vendored pip dependencies of the reference, :57,69)."""
         self.device = device
+        self.last_member_stats = None            # the dict of the latest score_histories call that was given member_kappa
         dev = torch.device(device)
         if isinstance(merged_checkpoint, str):   # a converted directory (safetensors + JSON) or a .pt read WITHOUT arbitrary unpickling
             from .loaders import load_verifier_checkpoint
@@ -458,7 +459,8 @@ class EfficientEnsembleMerged:
 
     def score_histories(self, its: torch.Tensor, all_action_histories, group_size=1, pad: Optional[torch.Tensor] = None, *,
                         prior: Optional[torch.Tensor] = None, prior_beta: float = 0.0, length_normalize: bool = False,
-                        prior_tokens: Optional[torch.Tensor] = None, pad_token_id: Optional[int] = None, top_m: int = 0):
+                        prior_tokens: Optional[torch.Tensor] = None, pad_token_id: Optional[int] = None, top_m: int = 0,
+                        member_kappa: Optional[float] = None, member_mode: str = "lcb"):
         """Trajectory encoder per candidate + fusion + scoring + grouped arg-max against precomputed image-text embeddings.
         all_action_histories: list of [h<=10, 7] host arrays (reference format), OR an already padded DEVICE tensor
         fp32 [N,10,7] together with its padding mask `pad` uint8 [N,10] (ops.tokens_to_histories): no host round trip.
@@ -466,7 +468,14 @@ class EfficientEnsembleMerged:
         prior_tokens / pad_token_id and length_normalize) makes the decision the grouped arg-max of scores + prior_beta * prior: one
         ops.prior_select launch behind ops.score_select then supplies `result` / `best` (best[0] is the winner's COMBINED score) and the
         dict gains prior, combined, group_mean and ranked (the best top_m of the winning group). top_m > 0 without a prior ranks by the
-        verifier score alone (beta 0). With prior None and top_m == 0 (the default) nothing else is launched or returned."""
+        verifier score alone (beta 0). With prior None and top_m == 0 (the default) nothing else is launched or returned.
+        member_kappa (finite, >= 0; None, the default, launches and returns nothing more) makes the decision disagreement-aware: one
+        ops.member_scores call behind ops.score_select scores every candidate under every member on its own and the dict gains
+        member_scores, mean, spread, min, min_member, robust, member_result and member_best. `result` / `best` are then the grouped
+        arg-max of `robust` -- member_mode "lcb": scores - member_kappa * spread (the scores' own bits at member_kappa 0), "min": the
+        worst member's score, member_kappa 0 -- while `scores` stays the fused score. With a prior or top_m as well, ops.prior_select
+        is fed `robust` in place of `scores`: combined = robust + prior_beta * prior, and `result` / `best` come from it as above.
+        The dict of the latest such call is kept as self.last_member_stats."""
         if torch.is_tensor(all_action_histories) and all_action_histories.is_cuda:
             hb = all_action_histories.contiguous()
         else:
@@ -485,24 +494,32 @@ class EfficientEnsembleMerged:
                 acts[i] = m.trajectory(hb, pad)
         scores, result, best, fit, fact = ops.score_select(its, acts, group_size)
         out = {"scores": scores, "result": result, "best": best, "its": its, "acts": acts, "fused_it": fit, "fused_act": fact}
+        base = scores                   # what the prior is added to and the ranking is made on
+        if member_kappa is not None:
+            out.update(ops.member_scores(its.contiguous(), acts, scores, group_size, member_kappa, member_mode))   # result / best: the robust decision
+            base = out["robust"]
         if prior is not None or top_m:
             if prior is None:           # rank by the verifier score alone: beta 0 never reads the (summed) prior into the decision
-                sel = ops.prior_select(scores, scores, group_size, 0.0, top_m=top_m)
+                sel = ops.prior_select(base, base, group_size, 0.0, top_m=top_m)
                 del sel["prior"]        # (the scores stood in for the unread log-probabilities)
             else:
-                sel = ops.prior_select(scores, prior, group_size, prior_beta, tokens=prior_tokens, pad_token_id=pad_token_id,
+                sel = ops.prior_select(base, prior, group_size, prior_beta, tokens=prior_tokens, pad_token_id=pad_token_id,
                                        length_normalize=length_normalize, top_m=top_m)
             out.update(sel)
+        if member_kappa is not None:
+            self.last_member_stats = out
         return out
 
-    def score_features(self, patch_features, text_features, all_action_histories, group_size=1, candidate_prior=None, prior_beta=0.0):
+    def score_features(self, patch_features, text_features, all_action_histories, group_size=1, candidate_prior=None, prior_beta=0.0,
+                       member_kappa=None, member_mode="lcb"):
         """Scores every candidate history against ONE (image, text) pair given its features. Returns a dict with the
         device tensors (scores [N], result int32[4], best f32[2]) plus per-member embeddings. candidate_prior ([N] or [N, steps]
-        log-probabilities, host or device) with prior_beta: the decision is made on scores + prior_beta * prior (score_histories)."""
+        log-probabilities, host or device) with prior_beta: the decision is made on scores + prior_beta * prior (score_histories).
+        member_kappa / member_mode: the decision is made on the disagreement-aware robust score (score_histories)."""
         if candidate_prior is not None:
             candidate_prior = torch.as_tensor(candidate_prior, dtype=torch.float32).to(self._dev)
         return self.score_histories(self.image_text_embeddings(patch_features, text_features), all_action_histories, group_size,
-                                    prior=candidate_prior, prior_beta=prior_beta)
+                                    prior=candidate_prior, prior_beta=prior_beta, member_kappa=member_kappa, member_mode=member_mode)
 
     def fuse_embeddings(self, image, instruction, action_histories):
         """efficient_ensemble_merged.py:249-293 -> (fused_image_text [N,512] (the one pair's embedding, a row per history),
@@ -535,14 +552,19 @@ class EfficientEnsembleMerged:
         return self.extract_shared_features(img_tensor, toks)
 
     def compute_max_similarity_scores_batch(self, images, instructions, all_action_histories,
-                                            cfg_repeat_language_instructions=1, candidate_prior=None, prior_beta=0.0):
+                                            cfg_repeat_language_instructions=1, candidate_prior=None, prior_beta=0.0,
+                                            member_kappa=None, member_mode="lcb"):
         """efficient_ensemble_merged.py:309-454. The reference scores candidates against the FIRST (image, text) pair only
         (reference_scores = similarity_matrix[0], :421-425), on both of its encode paths, so one pair is encoded here.
         candidate_prior ([N] or [N, steps] policy log-probabilities) with prior_beta selects on score + prior_beta * prior; the
-        returned max_score is then the winner's COMBINED score, not its cosine score."""
+        returned max_score is then the winner's COMBINED score, not its cosine score. member_kappa (None = off) with member_mode
+        selects on the disagreement-aware robust score (score_histories); the returned max_score is then the winner's ROBUST score --
+        or, with a prior as well, its combined score robust + prior_beta * prior -- and the per-member figures are in
+        self.last_member_stats."""
         group_size = cfg_repeat_language_instructions
         pf, tf = self._encode_pair(images[0], instructions[0])
-        r = self.score_features(pf, tf, all_action_histories, group_size, candidate_prior=candidate_prior, prior_beta=prior_beta)
+        r = self.score_features(pf, tf, all_action_histories, group_size, candidate_prior=candidate_prior, prior_beta=prior_beta,
+                                member_kappa=member_kappa, member_mode=member_mode)
         result = r["result"].cpu()
         best = r["best"].cpu()
         gidx, gbest = int(result[0]), int(result[1])

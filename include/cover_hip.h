@@ -797,6 +797,45 @@ typedef struct cover_prior_select_args {
 } cover_prior_select_args;
 int cover_prior_select(const cover_prior_select_args* args, void* stream);
 
+/* Per-member scores of the verifier ensemble and a disagreement-aware score. cover_score_select keeps one number per candidate, the
+ * cosine of the member-AVERAGED embeddings; this entry scores every candidate under every member on its own (it / act are the per-member
+ * unit rows cover_score_select takes, so a dot product is that member's cosine) and derives from them the ensemble's mean, spread and
+ * worst member, a robust score, the grouped arg-max of the robust score and each member's own grouped arg-max. Two launches behind each
+ * other, no workspace, no atomics, recordable. All arithmetic is fp32, one rounding per operation, never an fma; for candidate n:
+ *   s_m       = member m's score: lane l of a 64-lane wave runs p = 0.0f; for d = l, l + 64, ... < dim: prod = it[m][d] * act[m][n][d];
+ *               p = p + prod (a lane with no d keeps 0.0f); the 64 partials are added by the xor butterfly v = v + v[lane ^ o],
+ *               o = 32, 16, 8, 4, 2, 1. member_scores_out[m * N + n] = s_m.
+ *   mean      = (((0.0f + s_0) + s_1) + ... + s_{M-1}) / (float)M
+ *   spread    = sqrtf(ss / (float)M), ss the same chain over dv * dv, dv = s_m - mean: the POPULATION form (the members are the whole
+ *               ensemble); M == 1 gives exactly 0.
+ *   min       = the smallest s_m, min_member the first m that attains it (s_m < min replaces, so a NaN never does).
+ *   robust    = mode 0 (lcb): scores[n] exactly when kappa == 0.0f (no product is formed), else round(scores[n] - round(kappa * spread));
+ *               mode 1 (min): min.
+ *   result_out / best_out               = cover_group_argmax on robust (the same device code)
+ *   member_result_out[m] / member_best_out[m] = cover_group_argmax on member_scores_out + m * N
+ * scores = the [N] fused scores cover_score_select wrote; read only.
+ * COVER_EINVAL, and nothing launched, unless 1 <= n_members <= 16, N >= 1, group_size >= 1, N % group_size == 0, N / group_size <= 4096,
+ * 1 <= dim <= 4096, kappa finite and >= 0, mode 0 or 1, kappa == 0 in mode 1 and every pointer non-null. */
+typedef struct cover_member_scores_args {
+    const float* it;                /* [n_members][dim] */
+    const float* act;               /* [n_members][N][dim] */
+    const float* scores;            /* [N] fused scores */
+    int n_members, N, dim, group_size;
+    float kappa; int mode;          /* COVER_MEMBER_LCB / COVER_MEMBER_MIN */
+    float* member_scores_out;       /* [n_members][N] */
+    float* mean_out;                /* [N] */
+    float* spread_out;              /* [N] */
+    float* min_out;                 /* [N] */
+    int* min_member_out;            /* int32 [N] */
+    float* robust_out;              /* [N] */
+    int* result_out;                /* int32 [4], as cover_group_argmax on robust */
+    float* best_out;                /* float [2] */
+    int* member_result_out;         /* int32 [n_members][4] */
+    float* member_best_out;         /* float [n_members][2] */
+} cover_member_scores_args;
+enum { COVER_MEMBER_LCB = 0, COVER_MEMBER_MIN = 1 };
+int cover_member_scores(const cover_member_scores_args* args, void* stream);
+
 /* Gaussian proposal augmentation: K cheap verifier candidates per prompt from the prompt's n policy samples. Candidates of a prompt are
  * contiguous (candidate i belongs to prompt i / n); the output has S = n + K rows per prompt: rows 0..n-1 are the policy's own samples
  * copied unchanged (token ids verbatim, floats bit for bit), rows n..S-1 are drawn from a diagonal Gaussian fitted to the samples'
