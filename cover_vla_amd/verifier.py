@@ -14,9 +14,8 @@ the reference; the frozen SigLIP2 towers run in bf16 through the shared ViT kern
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence
-
 import os
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -30,8 +29,30 @@ def _dev_sd(sd, dev):
     return {k: (_f32(v, dev) if torch.is_tensor(v) else v) for k, v in sd.items()}
 
 
+def _member_batch() -> bool:
+    """COVER_MEMBER_BATCH=0 (A/B runs): every member runs as a stack of one instead of all members per launch."""
+    return os.environ.get("COVER_MEMBER_BATCH", "1") != "0"
+
+
+def _pad_mask(hist: torch.Tensor, pad_value: float, dev) -> torch.Tensor:
+    """hist [N, T, A] -> uint8 [N, T] on dev, 1 where the step is padding (efficient_ensemble_merged.py:229: a comparison where `hist`
+    lives, no arithmetic)."""
+    return (hist[:, :, 0] == pad_value).to(torch.uint8).to(dev).contiguous()
+
+
+def _stack(ts: List[torch.Tensor]) -> torch.Tensor:
+    """[G, ...] of G same-shaped contiguous tensors; a lone tensor is viewed, not copied."""
+    return ts[0].unsqueeze(0) if len(ts) == 1 else torch.stack(ts).contiguous()
+
+
+def _stackable(sds: List[Optional[dict]]) -> bool:
+    """The state dicts (None = the member has no such module) have the same keys and tensor shapes."""
+    sig = lambda sd: None if sd is None else {k: (tuple(v.shape) if torch.is_tensor(v) else None) for k, v in sd.items()}
+    return all(sig(sd) == sig(sds[0]) for sd in sds)
+
+
 class _Pooling:
-    """AttentionPooling (model.py:76-112) with num_readouts = 1: one learned query cross-attends the kv tokens."""
+    """Weights of one AttentionPooling (model.py:76-112) with num_readouts = 1; `_PoolingStack` runs them."""
 
     def __init__(self, sd, dev, heads=8):
         self.sd = _dev_sd(sd, dev)
@@ -48,28 +69,10 @@ class _Pooling:
         self.w_kv = torch.cat(ws, 0).contiguous()
         self.b_kv = torch.cat(bs, 0).contiguous()
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        """x fp32 [T, input_dim] -> [1, dim]."""
-        sd, E, H = self.sd, self.dim, self.heads
-        T = x.shape[0]
-        kv = ops.gemm_f32(x, self.w_kv, bias=self.b_kv)  # [T, n_layers*2*E]
-        q = sd["query"].view(1, E)
-        ld = kv.shape[1]
-        for i in range(self.n_layers):
-            p = f"blocks.{i}."
-            q = ops.layernorm_f32(q, sd[p + "q_layer_norm.weight"], sd[p + "q_layer_norm.bias"])
-            qp = ops.gemm_f32(q, sd[p + "attention.q_proj_weight"], bias=sd[p + "attention.in_proj_bias"][:E])
-            k = kv[:, (2 * i) * E:(2 * i + 1) * E]
-            v = kv[:, (2 * i + 1) * E:(2 * i + 2) * E]
-            a = ops.mha_f32(qp, k, v, 1, 1, T, H, E // H, (E, E), (T * ld, ld), (T * ld, ld))
-            q = ops.gemm_f32(a.view(1, E), sd[p + "attention.out_proj.weight"], bias=sd[p + "attention.out_proj.bias"], residual=q)
-            q = ops.layernorm_f32(q, sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"])
-            h = ops.gemm_f32(q, sd[p + "mlp.fc1.weight"], bias=sd[p + "mlp.fc1.bias"], act="gelu_erf")
-            q = ops.gemm_f32(h, sd[p + "mlp.fc2.weight"], bias=sd[p + "mlp.fc2.bias"], residual=q)
-        return ops.layernorm_f32(q, sd["layer_norm.weight"], sd["layer_norm.bias"])
-
 
 class _Member:
+    """One ensemble member's weights, softmax temperature, padding value and trajectory depth; the stacks below run them."""
+
     def __init__(self, comp: dict, dev):
         self.dev = dev
         ta = comp["text_aware_visual_extraction"]
@@ -90,168 +93,161 @@ class _Member:
             self.se, self.traj, self.traj_layers = None, None, 0
         self.pad_value = float(comp["action_padding_value"])
 
-    def image_text(self, pf: torch.Tensor, tf: torch.Tensor) -> torch.Tensor:
-        """pf fp32 [P, D], tf fp32 [T, D] unit rows -> unit [1, 512] (efficient_ensemble_merged.py:216-223)."""
-        sim = ops.gemm_f32(tf, pf)                               # [T, P]
-        ops.softmax_rows_f32(sim, self.inv_temp)
-        pfpe = ops.add_f32(pf, self.pos_emb)
-        taf = ops.gemm_f32(sim, pfpe, b_is_kn=True)              # [T, D]
-        vt = self.vision(taf)
-        tt = self.text(tf)
-        comb = torch.empty(1, vt.shape[1] + tt.shape[1], dtype=torch.float32, device=self.dev)
-        comb[:, :tt.shape[1]].copy_(tt)   # cat([text_token, vision_token]) (device copy, no arithmetic)
-        comb[:, tt.shape[1]:].copy_(vt)
-        y = ops.gemm_f32(comb, self.ip["weight"], bias=self.ip["bias"])
-        return ops.l2norm_rows_f32(y)
-
-    def trajectory(self, hist: torch.Tensor, pad: torch.Tensor) -> torch.Tensor:
-        """hist fp32 [N, 10, 7], pad uint8 [N, 10] -> unit [N, 512] (efficient_ensemble_merged.py:226-245)."""
-        N, T, A = hist.shape
-        if self.mlp is not None:   # flat_actions -> complex_action_encoder -> L2 norm (:241-245); padding rows are plain inputs
-            m = self.mlp
-            h = ops.gemm_f32(hist.reshape(N, T * A), m["0.weight"], bias=m["0.bias"])
-            h = ops.act_f32(ops.layernorm_f32(h, m["1.weight"], m["1.bias"]), "relu")
-            return ops.l2norm_rows_f32(ops.gemm_f32(h, m["4.weight"], bias=m["4.bias"]))
-        sd, E, H = self.traj, self.se["weight"].shape[0], 8
-        x = ops.gemm_f32(hist.view(N * T, A), self.se["weight"], bias=self.se["bias"])
-        for i in range(self.traj_layers):
-            p = f"layers.{i}."
-            qkv = ops.gemm_f32(x, sd[p + "self_attn.in_proj_weight"], bias=sd[p + "self_attn.in_proj_bias"])  # [N*T, 3E]
-            a = ops.mha_f32(qkv, qkv[:, E:], qkv[:, 2 * E:], N, T, T, H, E // H, (T * 3 * E, 3 * E), (T * 3 * E, 3 * E),
-                            (T * 3 * E, 3 * E), key_pad=pad)
-            y = ops.gemm_f32(a.view(N * T, E), sd[p + "self_attn.out_proj.weight"], bias=sd[p + "self_attn.out_proj.bias"], residual=x)
-            x = ops.layernorm_f32(y, sd[p + "norm1.weight"], sd[p + "norm1.bias"])
-            h = ops.gemm_f32(x, sd[p + "linear1.weight"], bias=sd[p + "linear1.bias"], act="relu")
-            y = ops.gemm_f32(h, sd[p + "linear2.weight"], bias=sd[p + "linear2.bias"], residual=x)
-            x = ops.layernorm_f32(y, sd[p + "norm2.weight"], sd[p + "norm2.bias"])
-        m = ops.masked_mean_f32(x, pad, N, T, E)
-        return ops.l2norm_rows_f32(m)
-
 
 class _PoolingStack:
-    """`_Pooling` of all members in batched launches (member = batch index)."""
+    """AttentionPooling of G members (member = batch index): one learned query per member cross-attends that member's kv tokens."""
 
-    def __init__(self, pools: List["_Pooling"]):
+    def __init__(self, pools: List[_Pooling]):
         p0 = pools[0]
         self.G, self.L, self.E, self.H = len(pools), p0.n_layers, p0.dim, p0.heads
-        st = lambda k: torch.stack([pp.sd[k] for pp in pools]).contiguous()
-        self.sd = {k: st(k) for k in p0.sd if torch.is_tensor(p0.sd[k])}
-        self.w_kv = torch.stack([pp.w_kv for pp in pools]).contiguous()
-        self.b_kv = torch.stack([pp.b_kv for pp in pools]).contiguous()
-        self.q_b = [torch.stack([pp.sd[f"blocks.{i}.attention.in_proj_bias"][:p0.dim] for pp in pools]).contiguous()
-                    for i in range(p0.n_layers)]
+        self.sd = {k: _stack([pp.sd[k] for pp in pools]) for k in p0.sd if torch.is_tensor(p0.sd[k])}
+        self.w_kv, self.b_kv = _stack([pp.w_kv for pp in pools]), _stack([pp.b_kv for pp in pools])
+        self.q_b = [_stack([pp.sd[f"blocks.{i}.attention.in_proj_bias"][:p0.dim] for pp in pools]) for i in range(p0.n_layers)]
 
     def __call__(self, x: torch.Tensor, shared: bool) -> torch.Tensor:
         """x fp32 [T, Din] (shared by every member) or [G, T, Din] -> [G, E]."""
         sd, G, E, H = self.sd, self.G, self.E, self.H
         T, Din = x.shape[-2], x.shape[-1]
         ld = self.w_kv.shape[1]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
         kv = ops.gemm_f32(x, self.w_kv, bias=self.b_kv, batch=G, a_bs=0 if shared else T * Din, b_bs=ld * Din, c_bs=T * ld,
-                          bias_bs=ld, M=T, N=ld, K=Din)                                  # [G, T, L*2E]
+                          bias_bs=ld, M=T, N=ld, K=Din, out=new(G, T, ld))               # [G, T, L*2E]
         q = sd["query"].reshape(G, E)
+        # member g's row of a [G, K] operand times its [N, K] weight (row stride K = batch stride: no [G, 1, K] views on the host path)
         bg = lambda a_, w_, b_, N_, K_, **kw: ops.gemm_f32(a_, w_, bias=b_, batch=G, a_bs=K_, b_bs=N_ * K_, c_bs=N_, bias_bs=N_,
-                                                           M=1, N=N_, K=K_, **kw).view(G, N_)
+                                                           M=1, N=N_, K=K_, out=new(G, N_), **kw)
         for i in range(self.L):
             p = f"blocks.{i}."
             q = ops.layernorm_f32_grouped(q, sd[p + "q_layer_norm.weight"], sd[p + "q_layer_norm.bias"], 1)
-            qp = bg(q.view(G, 1, E), sd[p + "attention.q_proj_weight"], self.q_b[i], E, E)
+            qp = bg(q, sd[p + "attention.q_proj_weight"], self.q_b[i], E, E)
             k = kv[:, :, (2 * i) * E:(2 * i + 1) * E]
             v = kv[:, :, (2 * i + 1) * E:(2 * i + 2) * E]
-            a = ops.mha_f32(qp, k, v, G, 1, T, H, E // H, (E, E), (T * ld, ld), (T * ld, ld))
-            q = bg(a.view(G, 1, E), sd[p + "attention.out_proj.weight"], sd[p + "attention.out_proj.bias"], E, E, residual=q.view(G, 1, E))
+            a = ops.mha_f32(qp, k, v, G, 1, T, H, E // H, (E, E), (T * ld, ld), (T * ld, ld))        # [G, 1, E]
+            q = bg(a, sd[p + "attention.out_proj.weight"], sd[p + "attention.out_proj.bias"], E, E, residual=q)
             q = ops.layernorm_f32_grouped(q, sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"], 1)
             F = sd[p + "mlp.fc1.weight"].shape[1]
-            h = bg(q.view(G, 1, E), sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], F, E, act="gelu_erf")
-            q = bg(h.view(G, 1, F), sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], E, F, residual=q.view(G, 1, E))
+            h = bg(q, sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], F, E, act="gelu_erf")
+            q = bg(h, sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], E, F, residual=q)
         return ops.layernorm_f32_grouped(q, sd["layer_norm.weight"], sd["layer_norm.bias"], 1)
 
 
-class _ImageTextStack:
-    """`_Member.image_text` of all members in batched launches: a third of the ~150 tiny fp32 launches of the member loop,
-    same per-element arithmetic (bit-identical)."""
+class _Stack:
+    """A trainable head of G >= 1 ensemble members as ONE chain of fp32 launches with the member index as the batch dimension
+    of every GEMM / attention / norm: 1/G of the ~150 tiny launches of a member loop (a third at the headline's three members; the
+    chains are latency-bound, ~10 us per launch, so this is ~3x off the verifier tail), same per-element arithmetic, bit-identical
+    results. A lone member is a stack of one: the same launches as an unbatched chain (batch strides are not read at batch 1, save
+    by the GEMM's plan, see tests/test_verifier_cpu.py). Members that cannot be stacked (`ok` False: other shapes, depths or
+    encoder kinds) and COVER_MEMBER_BATCH=0 run `singles`, one stack of one per member, each into its member's slice of `out`."""
 
-    def __init__(self, members: List["_Member"]):
-        m0 = members[0]
-        self.G, self.dev = len(members), m0.dev
-        same = lambda a, b: set(a) == set(b) and all((not torch.is_tensor(a[k])) or a[k].shape == b[k].shape for k in a)
-        self.ok = all(same(m0.vision.sd, mm.vision.sd) and same(m0.text.sd, mm.text.sd) and mm.pos_emb.shape == m0.pos_emb.shape and
-                      mm.ip["weight"].shape == m0.ip["weight"].shape and mm.vision.heads == m0.vision.heads and
-                      mm.text.heads == m0.text.heads for mm in members)
-        if not self.ok:
-            return
-        self.inv_temp = [mm.inv_temp for mm in members]
-        self.pos = torch.cat([mm.pos_emb.reshape(-1, mm.pos_emb.shape[-1]) for mm in members], 0).contiguous()   # [G*P, D]
-        self.vision, self.text = _PoolingStack([mm.vision for mm in members]), _PoolingStack([mm.text for mm in members])
-        self.ip_w = torch.stack([mm.ip["weight"] for mm in members]).contiguous()
-        self.ip_b = torch.stack([mm.ip["bias"] for mm in members]).contiguous()
+    def __init__(self, members: List[_Member]):
+        self.G, self.dev = len(members), members[0].dev
+        self.ok = self.G == 1 or self.stackable(members)
+        if self.ok:
+            self.build(members)
+        self.singles = [self] if self.G == 1 else [type(self)([m]) for m in members]
 
-    def __call__(self, pf: torch.Tensor, tf: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    def __call__(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """run(a, b, out) of the subclass; out's leading dimension is the member."""
+        if self.G == 1 or (self.ok and _member_batch()):
+            self.run(a, b, out)
+        else:
+            for i, single in enumerate(self.singles):
+                single.run(a, b, out[i:i + 1])
+        return out
+
+
+class _ImageTextStack(_Stack):
+    """TextAwareVisualExtraction, the vision and text poolings and the input projection (efficient_ensemble_merged.py:216-223)."""
+
+    @staticmethod
+    def stackable(ms: List[_Member]) -> bool:
+        return (_stackable([m.vision.sd for m in ms]) and _stackable([m.text.sd for m in ms]) and _stackable([m.ip for m in ms]) and
+                len({(m.pos_emb.shape, m.vision.heads, m.text.heads) for m in ms}) == 1)
+
+    def build(self, ms: List[_Member]):
+        self.inv_temp = [m.inv_temp for m in ms]
+        self.pos = _stack([m.pos_emb.reshape(-1, m.pos_emb.shape[-1]) for m in ms]).flatten(0, 1)                # [G*P, D]
+        self.vision, self.text = _PoolingStack([m.vision for m in ms]), _PoolingStack([m.text for m in ms])
+        self.ip_w, self.ip_b = _stack([m.ip["weight"] for m in ms]), _stack([m.ip["bias"] for m in ms])
+
+    def run(self, pf: torch.Tensor, tf: torch.Tensor, out: torch.Tensor):
         """pf fp32 [P, D], tf fp32 [T, D] unit rows -> out fp32 [G, 512] unit rows."""
         G = self.G
         P, D = pf.shape
         T = tf.shape[0]
-        sim = ops.gemm_f32(tf, pf, batch=G, a_bs=0, b_bs=0, c_bs=T * P, M=T, N=P, K=D)   # the same product, one copy per member
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)
+        sim = ops.gemm_f32(tf, pf, batch=G, a_bs=0, b_bs=0, c_bs=T * P, M=T, N=P, K=D, out=new(G, T, P))   # the same product, one copy per member
         for gi in range(G):
             ops.softmax_rows_f32(sim[gi], self.inv_temp[gi])
-        pfpe = ops.add_f32(self.pos, pf)                                                 # pos_emb[g] + pf (b rows cycle)
-        taf = ops.gemm_f32(sim, pfpe.view(G, P, D), b_is_kn=True, batch=G, a_bs=T * P, b_bs=P * D, c_bs=T * D, M=T, N=D, K=P)
+        pfpe = ops.add_f32(self.pos, pf)                                                 # [G*P, D]: pos_emb[g] + pf (b rows cycle)
+        taf = ops.gemm_f32(sim, pfpe, b_is_kn=True, batch=G, a_bs=T * P, b_bs=P * D, c_bs=T * D, M=T, N=D, K=P, out=new(G, T, D))
         vt = self.vision(taf, shared=False)
         tt = self.text(tf, shared=True)
         E1, E2 = tt.shape[1], vt.shape[1]
-        comb = torch.empty(G, E1 + E2, dtype=torch.float32, device=self.dev)
+        comb = new(G, E1 + E2)
         comb[:, :E1].copy_(tt)     # cat([text_token, vision_token]) (device copies, no arithmetic)
         comb[:, E1:].copy_(vt)
         No = self.ip_w.shape[1]
-        y = ops.gemm_f32(comb.view(G, 1, E1 + E2), self.ip_w, bias=self.ip_b, batch=G, a_bs=E1 + E2, b_bs=No * (E1 + E2), c_bs=No,
-                         bias_bs=No, M=1, N=No, K=E1 + E2)
-        return ops.l2norm_rows_f32(y.view(G, No), out=out)
+        y = ops.gemm_f32(comb, self.ip_w, bias=self.ip_b, batch=G, a_bs=E1 + E2, b_bs=No * (E1 + E2), c_bs=No, bias_bs=No,
+                         M=1, N=No, K=E1 + E2, out=new(G, No))
+        ops.l2norm_rows_f32(y, out=out)
 
 
-class _TrajectoryStack:
-    """The trajectory encoders of ALL ensemble members as batched launches (members have one architecture): every GEMM /
-    attention / norm of `_Member.trajectory` runs once with the member index as the batch dimension, i.e. a third of the
-    launches of the member loop with the same per-element arithmetic (bit-identical results). The chains are latency-bound
-    (~10 us per launch), so this is ~3x off the verifier tail."""
+class _TrajectoryStack(_Stack):
+    """The action encoder (efficient_ensemble_merged.py:226-245): per-step Linear + TransformerEncoder + masked mean, or the MLP
+    `complex_action_encoder` over the flattened history (use_transformer = False), then the L2 norm."""
 
-    def __init__(self, members: List["_Member"]):
-        m0 = members[0]
-        self.n, self.layers, self.dev = len(members), m0.traj_layers, m0.dev
-        self.ok = all(mm.mlp is None for mm in members) and all(mm.traj_layers == m0.traj_layers and mm.se["weight"].shape == m0.se["weight"].shape and
-                      all(mm.traj[k].shape == m0.traj[k].shape for k in m0.traj) for mm in members)
-        if not self.ok:
-            return
-        st = lambda d, k: torch.stack([mm_[k] for mm_ in d]).contiguous()
-        self.se_w, self.se_b = st([mm.se for mm in members], "weight"), st([mm.se for mm in members], "bias")
-        self.w = {k: st([mm.traj for mm in members], k) for k in m0.traj}
-        self.E = m0.se["weight"].shape[0]
+    @staticmethod
+    def stackable(ms: List[_Member]) -> bool:
+        return _stackable([m.se for m in ms]) and _stackable([m.traj for m in ms]) and _stackable([m.mlp for m in ms])
 
-    def __call__(self, hist: torch.Tensor, pad: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        """hist fp32 [N,10,7], pad uint8 [N,10] -> out fp32 [M, N, E] unit rows (member m = `_Member.trajectory` of member m)."""
-        G, E, H = self.n, self.E, 8
+    def build(self, ms: List[_Member]):
+        st = lambda sds: None if sds[0] is None else {k: _stack([sd[k] for sd in sds]) for k in sds[0]}
+        self.se, self.w, self.mlp = st([m.se for m in ms]), st([m.traj for m in ms]), st([m.mlp for m in ms])
+        self.layers = ms[0].traj_layers
+
+    def run(self, hist: torch.Tensor, pad: torch.Tensor, out: torch.Tensor):
+        """hist fp32 [N, 10, 7], pad uint8 [N, 10] -> out fp32 [G, N, 512] unit rows."""
+        (self._transformer if self.mlp is None else self._mlp)(hist, pad, out)
+
+    def _mlp(self, hist, pad, out):
+        """Linear -> LayerNorm -> ReLU -> (Dropout) -> Linear -> L2 norm (:241-245); padding rows are plain inputs."""
+        G, m = self.G, self.mlp
+        N, K = hist.shape[0], hist.shape[1] * hist.shape[2]
+        Hd, No = m["0.weight"].shape[1], m["4.weight"].shape[1]
+        new = lambda cols: torch.empty(G * N, cols, dtype=torch.float32, device=self.dev)      # member g: rows g*N .. (g+1)*N - 1
+        h = ops.gemm_f32(hist.view(N, K), m["0.weight"], bias=m["0.bias"], batch=G, a_bs=0, b_bs=Hd * K, c_bs=N * Hd, bias_bs=Hd,
+                         M=N, N=Hd, K=K, out=new(Hd))
+        h = ops.act_f32(ops.layernorm_f32_grouped(h, m["1.weight"], m["1.bias"], N), "relu")
+        y = ops.gemm_f32(h, m["4.weight"], bias=m["4.bias"], batch=G, a_bs=N * Hd, b_bs=No * Hd, c_bs=N * No, bias_bs=No,
+                         M=N, N=No, K=Hd, out=new(No))
+        ops.l2norm_rows_f32(y, out=out.view(G * N, No))
+
+    def _transformer(self, hist, pad, out):
+        G, w, H = self.G, self.w, 8
         N, T, A = hist.shape
-        R = N * T
-        w = self.w
-        x = ops.gemm_f32(hist.view(R, A), self.se_w, bias=self.se_b, batch=G, a_bs=0, b_bs=E * A, c_bs=R * E, bias_bs=E,
-                         M=R, N=E, K=A)                                                # [G, R, E]
-        pad_g = pad.repeat(G, 1).contiguous()
+        E, R = self.se["weight"].shape[1], N * T
+        new = lambda cols: torch.empty(G * R, cols, dtype=torch.float32, device=self.dev)      # member g: rows g*R .. (g+1)*R - 1
+        x = ops.gemm_f32(hist.view(R, A), self.se["weight"], bias=self.se["bias"], batch=G, a_bs=0, b_bs=E * A, c_bs=R * E, bias_bs=E,
+                         M=R, N=E, K=A, out=new(E))
+        pad_g = pad if G == 1 else pad.repeat(G, 1).contiguous()
         for i in range(self.layers):
             p = f"layers.{i}."
             qkv = ops.gemm_f32(x, w[p + "self_attn.in_proj_weight"], bias=w[p + "self_attn.in_proj_bias"], batch=G,
-                               a_bs=R * E, b_bs=3 * E * E, c_bs=R * 3 * E, bias_bs=3 * E, M=R, N=3 * E, K=E)
-            q2 = qkv.view(G * R, 3 * E)
-            a = ops.mha_f32(q2, q2[:, E:], q2[:, 2 * E:], G * N, T, T, H, E // H, (T * 3 * E, 3 * E), (T * 3 * E, 3 * E),
-                            (T * 3 * E, 3 * E), key_pad=pad_g)
-            y = ops.gemm_f32(a.view(G, R, E), w[p + "self_attn.out_proj.weight"], bias=w[p + "self_attn.out_proj.bias"],
-                             residual=x, batch=G, a_bs=R * E, b_bs=E * E, c_bs=R * E, bias_bs=E, M=R, N=E, K=E)
-            x = ops.layernorm_f32_grouped(y.view(G * R, E), w[p + "norm1.weight"], w[p + "norm1.bias"], R).view(G, R, E)
+                               a_bs=R * E, b_bs=3 * E * E, c_bs=R * 3 * E, bias_bs=3 * E, M=R, N=3 * E, K=E, out=new(3 * E))
+            a = ops.mha_f32(qkv, qkv[:, E:], qkv[:, 2 * E:], G * N, T, T, H, E // H, (T * 3 * E, 3 * E), (T * 3 * E, 3 * E),
+                            (T * 3 * E, 3 * E), key_pad=pad_g)                                                  # [G*N, T, E]
+            y = ops.gemm_f32(a, w[p + "self_attn.out_proj.weight"], bias=w[p + "self_attn.out_proj.bias"],
+                             residual=x, batch=G, a_bs=R * E, b_bs=E * E, c_bs=R * E, bias_bs=E, M=R, N=E, K=E, out=new(E))
+            x = ops.layernorm_f32_grouped(y, w[p + "norm1.weight"], w[p + "norm1.bias"], R)
             F = w[p + "linear1.weight"].shape[1]
             h = ops.gemm_f32(x, w[p + "linear1.weight"], bias=w[p + "linear1.bias"], act="relu", batch=G, a_bs=R * E,
-                             b_bs=F * E, c_bs=R * F, bias_bs=F, M=R, N=F, K=E)
+                             b_bs=F * E, c_bs=R * F, bias_bs=F, M=R, N=F, K=E, out=new(F))
             y = ops.gemm_f32(h, w[p + "linear2.weight"], bias=w[p + "linear2.bias"], residual=x, batch=G, a_bs=R * F,
-                             b_bs=E * F, c_bs=R * E, bias_bs=E, M=R, N=E, K=F)
-            x = ops.layernorm_f32_grouped(y.view(G * R, E), w[p + "norm2.weight"], w[p + "norm2.bias"], R).view(G, R, E)
-        m = ops.masked_mean_f32(x.view(G * R, E), pad_g, G * N, T, E)
-        return ops.l2norm_rows_f32(m, out=out.view(G * N, E))
+                             b_bs=E * F, c_bs=R * E, bias_bs=E, M=R, N=E, K=F, out=new(E))
+            x = ops.layernorm_f32_grouped(y, w[p + "norm2.weight"], w[p + "norm2.bias"], R)
+        m = ops.masked_mean_f32(x, pad_g, G * N, T, E)
+        ops.l2norm_rows_f32(m, out=out.view(G * N, E))
 
 
 class VLASigLIP2Bridge:
@@ -267,6 +263,7 @@ class VLASigLIP2Bridge:
         L.lib()
         self.device = torch.device(device)
         self.member = _Member(component, self.device)
+        self.image_text, self.trajectory = _ImageTextStack([self.member]), _TrajectoryStack([self.member])
         self.logit_scale = float(logit_scale)
         self.encoder = encoder
         self.history_length, self.action_dim = 10, 7
@@ -282,9 +279,9 @@ class VLASigLIP2Bridge:
             raise ValueError(f"batch sizes differ: images {B}, texts {tf.shape[0]}, histories {hist.shape[0]}")
         it = torch.empty(B, 512, dtype=torch.float32, device=self.device)
         for b in range(B):                                   # per-sample text-aware heads (:368-377)
-            it[b:b + 1].copy_(self.member.image_text(pf[b], tf[b]))
-        pad = (hist[:, :, 0] == self.member.pad_value).to(torch.uint8).contiguous()   # :384 (a comparison, no arithmetic)
-        act = self.member.trajectory(hist.contiguous(), pad)                           # :380-412
+            self.image_text(pf[b], tf[b], it[b:b + 1])
+        pad = _pad_mask(hist, self.member.pad_value, self.device)                      # :384
+        act = self.trajectory(hist.contiguous(), pad, torch.empty(1, B, 512, dtype=torch.float32, device=self.device))[0]   # :380-412
         scale = float(np.exp(np.float32(self.logit_scale)))                            # :414
         image_logits = ops.gemm_f32(it, act, alpha=scale)                              # :416
         action_logits = ops.gemm_f32(act, it, alpha=scale)                             # :417
@@ -387,8 +384,8 @@ class EfficientEnsembleMerged:
             self.backbone, self.use_transformer = ck["backbone"], ck["use_transformer"]
             self.history_length, self.action_dim, self.num_models = ck["history_length"], ck["action_dim"], ck["num_models"]
         self.trainable_models = [_Member(c, dev) for c in ck["ensemble_components"]]
-        self._traj_stack = _TrajectoryStack(self.trainable_models) if self.num_models > 1 else None
-        self._it_stack = _ImageTextStack(self.trainable_models) if self.num_models > 1 else None
+        self._traj_stack, self._it_stack = _TrajectoryStack(self.trainable_models), _ImageTextStack(self.trainable_models)
+        self._shared_graphs = {}                 # shared_embeddings_graph's captured graphs by input shapes
         if preprocess is None:
             # open_clip's transform for the SigLIP2 checkpoints (:69) restated: Resize(BICUBIC, squash) + ToTensor + Normalize(.5)
             from .imaging import siglip_preprocess
@@ -402,7 +399,7 @@ class EfficientEnsembleMerged:
         return self.encoder.extract_features(img_tensor.to(self._dev), text_tokens.to(self._dev))
 
     def _pad_histories(self, all_action_histories):
-        """efficient_ensemble_merged.py:378-390 (front pad with -5 to length 10) + the padding mask of :229."""
+        """efficient_ensemble_merged.py:378-390: front pad with -5 to length 10 -> host fp32 [N, 10, 7] (`_pad_mask` makes the mask of :229)."""
         max_len = 10
         out = []
         for ah in all_action_histories:
@@ -416,9 +413,10 @@ class EfficientEnsembleMerged:
     def get_embeddings_from_model_batch(self, model_idx, patch_features, text_features, action_histories_batch):
         m = self.trainable_models[model_idx]
         hb = action_histories_batch.float().to(self._dev).contiguous()
-        pad = (action_histories_batch[:, :, 0].cpu() == m.pad_value).to(torch.uint8).to(self._dev).contiguous()
-        it = m.image_text(patch_features[0].contiguous(), text_features[0].contiguous())
-        act = m.trajectory(hb, pad)
+        pad = _pad_mask(action_histories_batch.cpu(), m.pad_value, self._dev)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self._dev)
+        it = self._it_stack.singles[model_idx](patch_features[0].contiguous(), text_features[0].contiguous(), new(1, 512))
+        act = self._traj_stack.singles[model_idx](hb, pad, new(1, hb.shape[0], 512))[0]
         return it.expand(hb.shape[0], -1), act
 
     def shared_embeddings_graph(self, img_tensor: torch.Tensor, text_tokens: torch.Tensor) -> torch.Tensor:
@@ -427,10 +425,8 @@ class EfficientEnsembleMerged:
         call, and the two towers -- 576 and 64 rows, a fraction of the chip each -- overlap. Same kernels, same results as the eager pair of
         calls. Returns the per-member embeddings [M, 512] (a static tensor, overwritten by the next call)."""
         key = (tuple(img_tensor.shape), tuple(text_tokens.shape))
-        st = self._shared_graphs.get(key) if hasattr(self, "_shared_graphs") else None
+        st = self._shared_graphs.get(key)
         if st is None:
-            if not hasattr(self, "_shared_graphs"):
-                self._shared_graphs = {}
             img = torch.empty_like(img_tensor, device=self._dev)
             txt = torch.empty_like(text_tokens, device=self._dev)
             side = torch.cuda.Stream(device=self._dev)
@@ -451,11 +447,7 @@ class EfficientEnsembleMerged:
         pf = patch_features[0].to(self._dev).contiguous()
         tf = text_features[0].to(self._dev).contiguous()
         its = torch.empty(self.num_models, 512, dtype=torch.float32, device=self._dev)
-        if self._it_stack is not None and self._it_stack.ok and os.environ.get("COVER_MEMBER_BATCH", "1") != "0":
-            return self._it_stack(pf, tf, its)          # all members per launch
-        for i, m in enumerate(self.trainable_models):
-            its[i] = m.image_text(pf, tf)[0]
-        return its
+        return self._it_stack(pf, tf, its)
 
     def score_histories(self, its: torch.Tensor, all_action_histories, group_size=1, pad: Optional[torch.Tensor] = None, *,
                         prior: Optional[torch.Tensor] = None, prior_beta: float = 0.0, length_normalize: bool = False,
@@ -480,18 +472,12 @@ class EfficientEnsembleMerged:
             hb = all_action_histories.contiguous()
         else:
             hb = self._pad_histories(all_action_histories)
-            pad = (hb[:, :, 0] == self.trainable_models[0].pad_value).to(torch.uint8).to(self._dev).contiguous()
+            pad = _pad_mask(hb, self.trainable_models[0].pad_value, self._dev)
             hb = hb.to(self._dev).contiguous()
         N = hb.shape[0]
-        acts = torch.empty(self.num_models, N, 512, dtype=torch.float32, device=self._dev)
-
         # (members on separate HIP streams were tried: the tail shrinks 1.95 -> 1.47 ms but every decode pass of the policy
-        # slows by ~0.17 ms with the extra queues alive -- a net loss, so the members stay sequential)
-        if self._traj_stack is not None and self._traj_stack.ok and os.environ.get("COVER_MEMBER_BATCH", "1") != "0":
-            self._traj_stack(hb, pad, acts)           # all members per launch
-        else:
-            for i, m in enumerate(self.trainable_models):
-                acts[i] = m.trajectory(hb, pad)
+        # slows by ~0.17 ms with the extra queues alive -- a net loss, so the members share one chain of launches)
+        acts = self._traj_stack(hb, pad, torch.empty(self.num_models, N, 512, dtype=torch.float32, device=self._dev))
         scores, result, best, fit, fact = ops.score_select(its, acts, group_size)
         out = {"scores": scores, "result": result, "best": best, "its": its, "acts": acts, "fused_it": fit, "fused_act": fact}
         base = scores                   # what the prior is added to and the ranking is made on

@@ -160,25 +160,48 @@ def test_verifier_contrastive_forward_matches_reference_golden(dev, name):
         net(None, None, hist)                      # no encoder attached: refuses instead of guessing features
 
 
-def test_verifier_members_batched_equals_member_loop(dev):
-    """All members' trajectory encoders as batched launches (member = batch index) == the per-member loop, bit for bit."""
+def _two_depths():
+    """A 4-layer and a 2-layer member: two 2-member checkpoints and the splice of one component of each (members that cannot be stacked)."""
+    a, b = synth.verifier_checkpoint(2, seed=5, traj_layers=4), synth.verifier_checkpoint(2, seed=6, traj_layers=2)
+    return {"ensemble_components": [a["ensemble_components"][0], b["ensemble_components"][1]]}, (a, 0), (b, 1)
+
+
+@pytest.mark.parametrize("case", ["members3_n32_g4", "one_candidate_short_history", "mlp_encoder", "nonuniform_members", "patches16"])
+def test_verifier_members_batched_equals_member_loop(dev, case):
+    """The heads of all members as batched launches (member = batch index) == one stack of one per member (COVER_MEMBER_BATCH=0), bit for
+    bit: at one candidate with a one-step history (attention rows with all keys but one padded, 10 rows), for the MLP action encoder, with
+    fewer than 32 patch columns, and for members of different depths, which take the per-member route either way and must equal each
+    component scored on its own through get_embeddings_from_model_batch."""
     from cover_vla_amd.verifier import EfficientEnsembleMerged
-    ckpt = synth.verifier_checkpoint(3, seed=5)
-    pf, tf, hists = synth.verifier_inputs(32, seed=5)
+    alone = ()
+    if case == "members3_n32_g4":
+        ckpt, (pf, tf, hists), group = synth.verifier_checkpoint(3, seed=5), synth.verifier_inputs(32, seed=5), 4
+    elif case == "one_candidate_short_history":
+        ckpt, (pf, tf, hists), group = synth.verifier_checkpoint(3, seed=5), synth.verifier_inputs(1, seed=5, min_hist=1), 1
+        assert len(hists[0]) == 1
+    elif case == "mlp_encoder":
+        ckpt, (pf, tf, hists), group = synth.verifier_checkpoint(2, seed=5, use_transformer=False), synth.verifier_inputs(8, seed=5), 2
+    elif case == "nonuniform_members":
+        (ckpt, *alone), (pf, tf, hists), group = _two_depths(), synth.verifier_inputs(6, seed=5), 2
+    else:
+        ckpt, (pf, tf, hists), group = synth.verifier_checkpoint(3, seed=5, num_patches=16), synth.verifier_inputs(5, seed=5, num_patches=16), 1
     ens = EfficientEnsembleMerged(ckpt, device="cuda:0")
-    assert ens._traj_stack is not None and ens._traj_stack.ok
-    assert ens._it_stack is not None and ens._it_stack.ok
+    assert ens._it_stack.ok and ens._traj_stack.ok == (not alone)
     its = ens.image_text_embeddings(pf, tf)
-    rb = ens.score_histories(its, hists, 4)
+    rb = ens.score_histories(its, hists, group)
     os.environ["COVER_MEMBER_BATCH"] = "0"
     try:
         its_loop = ens.image_text_embeddings(pf, tf)
-        rl = ens.score_histories(its, hists, 4)
+        rl = ens.score_histories(its, hists, group)
     finally:
         os.environ.pop("COVER_MEMBER_BATCH", None)
     assert torch.equal(its, its_loop)
     assert torch.equal(rb["acts"], rl["acts"]) and torch.equal(rb["scores"], rl["scores"])
     assert int(rb["result"][0]) == int(rl["result"][0])
+    for m, (ck_alone, idx) in enumerate(alone):
+        it, act = EfficientEnsembleMerged(ck_alone, device="cuda:0").get_embeddings_from_model_batch(
+            idx, pf.to(dev), tf.to(dev), ens._pad_histories(hists))
+        assert torch.equal(it[0], its[m]) and torch.equal(act, rb["acts"][m])
 
 
 # ------------------------------------------------------------------------------------------------ pi0 sampler
