@@ -4,25 +4,10 @@
 // operators with contraction off for the whole file, because hipcc would otherwise fuse d * d + ss and mean + s * z into one v_fma_f32.
 #include "common.h"
 #include "kernels.h"
-#include "augment_fit.h"   // aug_value, augment_group_stats: the fit, shared with proposal_prior.hip
+#include "augment_fit.h"   // aug_value, augment_group_stats: the fit, shared with proposal_prior.hip and refine.hip
+#include "augment_draw.h"  // aug_store, augment_draw_rows: the draw, shared with refine.hip
 
 #pragma clang fp contract(off)
-
-// what an augmented value is stored as: floats as they are, tokens as the token of the nearest bin centre
-__device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, float* o) { *o = v; }
-__device__ __forceinline__ void aug_store(const cover_augment_args& a, float v, int64_t* o) {
-    // first index that minimises |v - centers[b]|: a plain scan (b is uniform over the wave: the table comes through scalar loads)
-    float best = fabsf(v - a.centers[0]);
-    int bi = 0;
-    for (int b = 1; b < a.n_centers; ++b) {
-        const float dist = fabsf(v - a.centers[b]);
-        if (dist < best) {
-            best = dist;
-            bi = b;
-        }
-    }
-    *o = (int64_t)a.tok_vocab - 1 - bi;
-}
 
 // one block per prompt group: statistics -> LDS, the n originals copied, then the block walks (k, t, d) of the K augmented rows in
 // output order (coalesced stores)
@@ -40,19 +25,7 @@ __global__ __launch_bounds__(256) void augment_k(cover_augment_args a, long long
         out[i] = in[(long long)j * a.n_stride + (long long)t * t_stride + d];
     }
     __syncthreads();
-    out += (size_t)n * w;
-    const float* z = a.normals + (size_t)g * K * 6 * h;
-    for (int i = threadIdx.x; i < K * w; i += blockDim.x) {
-        const int k = i / w, r = i - k * w, t = r / 7, d = r - t * 7;
-        if (d == 6) {
-            out[i] = in[(long long)s_jwin[t] * a.n_stride + (long long)t * t_stride + 6];
-            continue;
-        }
-        const float p = s_s[t * 6 + d] * z[((size_t)k * h + t) * 6 + d];
-        float v = s_mean[t * 6 + d] + p;
-        v = fminf(fmaxf(v, a.clip_lo), a.clip_hi);
-        aug_store(a, v, out + i);
-    }
+    augment_draw_rows<T>(f, in, t_stride, out + (size_t)n * w, a.normals + (size_t)g * K * 6 * h, K, a.clip_lo, a.clip_hi, s_mean, s_s, s_jwin);
 }
 
 static bool augment_args_ok(const cover_augment_args* a) {

@@ -427,6 +427,19 @@ int cover_proposal_prior_actions(const cover_proposal_prior_args* a, void* strea
     HIPCHK(launch_proposal_prior_actions(a, ST(stream)), "proposal_prior_actions (" PROPOSAL_PRIOR_LIMITS ")");
     return COVER_OK;
 }
+#define REFINE_LIMITS "G >= 1, 1 <= n_elite <= group_rows <= 4096, 0 <= K <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, " \
+                      "G * (n_elite + K) <= 2^20, sigma and sd_floor finite and >= 0, clip_lo <= clip_hi, src / scores / out required, " \
+                      "normals with K > 0"
+int cover_refine_tokens(const cover_refine_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_refine_tokens: null args");
+    HIPCHK(launch_refine_tokens(a, ST(stream)), "refine_tokens (" REFINE_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_refine_actions(const cover_refine_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_refine_actions: null args");
+    HIPCHK(launch_refine_actions(a, ST(stream)), "refine_actions (" REFINE_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -552,7 +565,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
-    SZ(cover_member_scores_args);
+    SZ(cover_member_scores_args); SZ(cover_refine_args);
 #undef SZ
     return 0;
 }

@@ -505,6 +505,21 @@ class OpenVLA:
         return ops.augment_tokens(tokens, n_samples, n_augmented, normals, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
                                   sigma=sigma, sd_floor=sd_floor)
 
+    def refine(self, tokens: torch.Tensor, scores: torch.Tensor, group_rows: int, n_elite: int, normals: torch.Tensor, *, sigma=1.0,
+               sd_floor=0.0, elites=False):
+        """Verifier-guided refinement of scored chunks, one round of the cross-entropy method (ops.refine_tokens with this model's
+        tok_vocab, bin centres and steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] (sampled, augmented or already refined) and
+        their scores fp32 [P * group_rows] (score_histories' scores, robust or combined) -> int64 [P * (n_elite + n_new), n_gen],
+        n_new = normals.shape[1]; per prompt the n_elite best-scored rows verbatim, best first (equal scores by ascending row, a NaN
+        last), then n_new rows drawn as augment draws them from the Gaussian refitted on those elites; on a gripper tie they take the
+        class of the best elite. normals fp32 [P, n_new, n_gen // 7, 6] on the device (host.augmentation_normals, a fresh seed per
+        round). The result goes where augment's goes, with group_size = n_elite + n_new and n_fit = n_elite. elites=True ->
+        (tokens, ops.RefineElites). One launch; the policy is not run. Off by default: nothing calls this."""
+        if not torch.is_tensor(normals) or normals.dim() != 4:
+            raise L.CoverError("OpenVLA.refine: normals must be an fp32 tensor [prompts, n_new, n_gen // 7, 6]")
+        return ops.refine_tokens(tokens, scores, group_rows, n_elite, normals.shape[1], normals, self.bin_centers(), self.c["tok_vocab"],
+                                 steps=self.n_gen // 7, sigma=sigma, sd_floor=sd_floor, elites=elites)
+
     def proposal_prior(self, tokens: torch.Tensor, group_rows: int, n_fit: int, *, sigma, sd_floor, log_share=None):
         """The proposal log-density prior of action-token chunks (ops.proposal_prior_tokens with this model's tok_vocab, bin centres and
         steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] -> fp32 [P * group_rows], per row the unnormalised log-density of the

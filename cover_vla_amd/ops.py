@@ -1419,17 +1419,8 @@ def _action_rows(what, actions):
         raise L.CoverError(f"{what}: actions must be fp32 [rows, steps, >= 7] with unit last stride")
 
 
-def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, out_shape,
-             stats, centers=None, tok_vocab=0):
-    """The checks and the launch both augment wrappers share. src: the input tensor; elem: its dtype; out_shape(G, S) -> the output's shape."""
-    n, K = int(n_samples), int(n_augmented)
-    if not 1 <= n <= 4096 or not 0 <= K <= 4096 or N < 1 or N % n != 0:
-        raise L.CoverError(f"{what}: 1 <= n_samples <= 4096, 0 <= n_augmented <= 4096 and rows % n_samples == 0 are required "
-                           f"(got rows={N}, n_samples={n}, n_augmented={K})")
-    G, S = N // n, n + K
-    if not 1 <= steps <= 64 or G * S > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64 and prompts * (n_samples + n_augmented) <= 2^20 are required (got steps={steps}, "
-                           f"prompts={G})")
+def _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip):
+    """The checks of what a draw takes (augment_*, refine_*): the normals' layout and the values -> (sigma, sd_floor, clip lo, clip hi)."""
     if not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != (G, K, steps, 6) or not normals.is_contiguous():
         raise L.CoverError(f"{what}: normals must be contiguous fp32 [prompts, n_augmented, steps, 6] = [{G}, {K}, {steps}, 6] "
                            f"(got {tuple(normals.shape) if torch.is_tensor(normals) else type(normals).__name__})")
@@ -1443,6 +1434,21 @@ def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_aug
         raise L.CoverError(f"{what}: clip must be a (lo, hi) pair") from None
     if not lo <= hi:
         raise L.CoverError(f"{what}: clip lo <= hi is required, +-inf = no clip (got {clip})")
+    return sigma, sd_floor, lo, hi
+
+
+def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, out_shape,
+             stats, centers=None, tok_vocab=0):
+    """The checks and the launch both augment wrappers share. src: the input tensor; elem: its dtype; out_shape(G, S) -> the output's shape."""
+    n, K = int(n_samples), int(n_augmented)
+    if not 1 <= n <= 4096 or not 0 <= K <= 4096 or N < 1 or N % n != 0:
+        raise L.CoverError(f"{what}: 1 <= n_samples <= 4096, 0 <= n_augmented <= 4096 and rows % n_samples == 0 are required "
+                           f"(got rows={N}, n_samples={n}, n_augmented={K})")
+    G, S = N // n, n + K
+    if not 1 <= steps <= 64 or G * S > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and prompts * (n_samples + n_augmented) <= 2^20 are required (got steps={steps}, "
+                           f"prompts={G})")
+    sigma, sd_floor, lo, hi = _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip)
     shape = out_shape(G, S)
     if out is not None and (not torch.is_tensor(out) or out.dtype != elem or tuple(out.shape) != shape or not out.is_contiguous()):
         raise L.CoverError(f"{what}: out must be a contiguous {elem} tensor of shape {shape}")
@@ -1573,6 +1579,90 @@ def proposal_prior_actions(actions, group_rows, n_fit, *, sigma, sd_floor, log_s
     _action_rows("proposal_prior_actions", actions)
     return _proposal_prior("proposal_prior_actions", lambda h: h.cover_proposal_prior_actions, actions, actions.stride(0), actions.stride(1),
                            actions.shape[0], actions.shape[1], group_rows, n_fit, sigma, sd_floor, log_share, out, stats)
+
+
+# ------------------------------------------------------------------------------------------------ verifier-guided refinement
+class RefineElites(NamedTuple):
+    """What refine_tokens / refine_actions return beside the output with elites=True."""
+    rows: torch.Tensor     # int32 [G, n_elite]: the index in the input of the row gathered to output row r of group g
+    scores: torch.Tensor   # fp32 [G, n_elite]: its score, bit for bit
+
+
+def _refine(what, fn, src, elem, n_stride, t_stride, N, steps, scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out,
+            out_shape, stats, elites, centers=None, tok_vocab=0):
+    """The checks and the launch both refine wrappers share. out_shape(G, rows per group) -> the output's shape."""
+    ints = (int, np.integer)
+    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, n_elite, n_new)):
+        raise L.CoverError(f"{what}: group_rows, n_elite and n_new must be integers (got {group_rows!r}, {n_elite!r}, {n_new!r})")
+    S, m, K = int(group_rows), int(n_elite), int(n_new)
+    if not 1 <= m <= S <= 4096 or not 0 <= K <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= n_elite <= group_rows <= 4096, 0 <= n_new <= 4096 and rows % group_rows == 0 are required "
+                           f"(got rows={N}, group_rows={S}, n_elite={m}, n_new={K})")
+    G = N // S
+    if not 1 <= steps <= 64 or N > 1 << 20 or G * (m + K) > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64, rows <= 2^20 and prompts * (n_elite + n_new) <= 2^20 are required (got steps={steps}, "
+                           f"rows={N}, prompts={G})")
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or not scores.is_contiguous():
+        raise L.CoverError(f"{what}: scores must be contiguous fp32 [rows] = [{N}] "
+                           f"(got {tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__})")
+    sigma, sd_floor, lo, hi = _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip)
+    shape = out_shape(G, m + K)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != elem or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise L.CoverError(f"{what}: out must be a contiguous {elem} tensor of shape {shape}")
+    _chk_dev(src, scores, normals, centers, out)
+    dev = src.device
+    if any(t is not None and t.device != dev for t in (scores, normals, centers, out)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    if out is None:
+        out = torch.empty(shape, dtype=elem, device=dev)
+    st = _augment_stats(G, steps, dev) if stats else None
+    el = RefineElites(torch.empty(G, m, dtype=torch.int32, device=dev), torch.empty(G, m, dtype=torch.float32, device=dev)) if elites else None
+    a = L.RefineArgs()
+    a.src, a.n_stride, a.t_stride, a.scores = src.data_ptr(), n_stride, t_stride, scores.data_ptr()
+    a.normals = normals.data_ptr() if K else None
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.G, a.group_rows, a.n_elite, a.K, a.h = G, S, m, K, steps
+    a.sigma, a.sd_floor, a.clip_lo, a.clip_hi = sigma, sd_floor, lo, hi
+    a.out = out.data_ptr()
+    if el is not None:
+        a.elite_rows_out, a.elite_scores_out = el.rows.data_ptr(), el.scores.data_ptr()
+    if st is not None:
+        a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    res = (out,) + ((st,) if stats else ()) + ((el,) if elites else ())
+    return res if len(res) > 1 else out
+
+
+def refine_tokens(tokens, scores, group_rows, n_elite, n_new, normals, centers, tok_vocab, *, steps=1, sigma=1.0, sd_floor=0.0,
+                  clip=(-1.0, 1.0), out=None, stats=False, elites=False):
+    """Verifier-guided refinement of action tokens, one round of the cross-entropy method per prompt (cover_refine_tokens): tokens int64
+    [G * group_rows, >= 7 steps] (unit column stride, any row stride; row i belongs to prompt i // group_rows) with scores fp32 [rows],
+    contiguous, one per row -- whatever the decision was made on (score_histories' scores, robust or combined) -> int64
+    [G * (n_elite + n_new), 7 steps]. Per prompt, output rows 0..n_elite-1 are the n_elite best-scored input rows verbatim, best first;
+    the n_new rows behind them are EXACTLY the rows augment_tokens draws from those n_elite rows with the same normals (fp32
+    [G, n_new, steps, 6], host.augmentation_normals), sigma, sd_floor and clip: the Gaussian is refitted on the elites, its chains run in
+    rank order. RANKING: higher score first, equal scores (-0.0 == +0.0) by ascending row index; a NaN score ranks behind every number,
+    -inf included, NaNs among themselves by ascending index. On a gripper TIE the new rows take the class of the best elite. n_new == 0 is
+    a pure top-n_elite gather. Downstream code takes the result as it takes augment_tokens' output, with group_size = n_elite + n_new and
+    n_fit = n_elite. stats=True adds the AugmentStats of the fit, elites=True adds RefineElites (the gathered rows' input indices and
+    scores): -> out, (out, stats), (out, elites) or (out, stats, elites). One launch, no workspace, recordable."""
+    steps, n_stride = _token_rows("refine_tokens", tokens, steps, centers)
+    return _refine("refine_tokens", lambda h: h.cover_refine_tokens, tokens, torch.int64, n_stride, 7, tokens.shape[0], steps, scores,
+                   group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out, lambda G, R: (G * R, 7 * steps), stats, elites,
+                   centers=centers, tok_vocab=tok_vocab)
+
+
+def refine_actions(actions, scores, group_rows, n_elite, n_new, normals, *, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0), out=None,
+                   stats=False, elites=False):
+    """The same for a flow-matching policy's chunks (cover_refine_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last
+    stride and any other strides -- a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place -> contiguous fp32
+    [G * (n_elite + n_new), steps, 7]. The elites are the input's first 7 dims bit for bit; the new rows are augment_actions' on them
+    (a gripper tie goes to the class of the best elite). See refine_tokens for the ranking and the returns."""
+    _action_rows("refine_actions", actions)
+    return _refine("refine_actions", lambda h: h.cover_refine_actions, actions, torch.float32, actions.stride(0), actions.stride(1),
+                   actions.shape[0], actions.shape[1], scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out,
+                   lambda G, R: (G * R, actions.shape[1], 7), stats, elites)
 
 
 # ------------------------------------------------------------------------------------------------ beam search

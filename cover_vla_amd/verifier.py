@@ -496,6 +496,46 @@ class EfficientEnsembleMerged:
             self.last_member_stats = out
         return out
 
+    def score_refined(self, its: torch.Tensor, candidates, group_rows: int, *, to_histories, refine, normals, n_elite: int, prior_fn=None,
+                      **score_kw):
+        """Verifier-guided refinement, the loop: score, then per entry of `normals` one round of the cross-entropy method -- keep every
+        prompt's n_elite best rows, refit the proposal on them, draw new rows, score again. Nothing but the composition of existing calls;
+        the policy is not run. candidates: the rows in the policy's own form (OpenVLA: int64 tokens [P * group_rows, n_gen]), group_rows
+        per prompt. to_histories(cands) -> (hb, pad), what score_histories takes (ops.tokens_to_histories with the model's table and the
+        past actions). refine(cands, values, group_rows, n_elite, z) -> the n_elite + z.shape[1] rows per prompt, elites first
+        (OpenVLA.refine), or (rows, elites) with elites.rows their indices in cands (OpenVLA.refine(elites=True)). normals: a sequence of R
+        device tensors fp32 [P, K_r, steps, 6], one per round (host.augmentation_normals with a fresh seed each). prior_fn(cands,
+        group_rows, n_fit) -> the [N] prior of that round's rows (OpenVLA.proposal_prior; n_fit is None in round 0, where the caller
+        knows how its candidates were made, and n_elite later); None = no prior (a `prior` among score_kw is for the given candidates, so
+        it is accepted only with an empty `normals`). score_kw goes to every score_histories call (member_kappa, member_mode, prior_beta,
+        top_m, ...).
+        Round 0 scores the given candidates. Each later round refines on the per-candidate value the previous decision was made on --
+        `combined` if that dict has it, else `robust`, else `scores` -- and scores the new rows with group_size = n_elite + K_r. Returns the
+        LAST score_histories dict plus `candidates` (the final rows, which `result` indexes) and `rounds` (per round, round 0 included, a
+        dict of that round's `best`, `result` and `elite_rows`: None in round 0 and when refine returns no elites). The elites are
+        carried verbatim, so a row-wise scorer's best value per prompt never decreases; no n_elite, K, round count or sigma is
+        recommended. With an empty `normals` this is one score_histories call and nothing else is launched."""
+        normals = list(normals)
+        if "prior" in score_kw and (prior_fn is not None or normals):
+            raise L.CoverError("score_refined: prior= belongs to the given candidates only; pass prior_fn to score refined rows under a prior")
+        cands, S, n_fit, elite_rows, rounds = candidates, int(group_rows), None, None, []
+        for r in range(len(normals) + 1):
+            if r > 0:
+                values = out["combined"] if "combined" in out else out["robust"] if "robust" in out else out["scores"]
+                z = normals[r - 1]
+                got = refine(cands, values, S, n_elite, z)
+                cands, elite_rows = (got[0], getattr(got[1], "rows", got[1])) if isinstance(got, tuple) else (got, None)
+                S, n_fit = int(n_elite) + int(z.shape[1]), int(n_elite)
+            hb, pad = to_histories(cands)
+            kw = dict(score_kw)
+            if prior_fn is not None:
+                kw["prior"] = prior_fn(cands, S, n_fit)
+            out = self.score_histories(its, hb, S, pad=pad, **kw)
+            rounds.append({"best": out["best"], "result": out["result"], "elite_rows": elite_rows})
+        out = dict(out)
+        out["candidates"], out["rounds"] = cands, rounds
+        return out
+
     def score_features(self, patch_features, text_features, all_action_histories, group_size=1, candidate_prior=None, prior_beta=0.0,
                        member_kappa=None, member_mode="lcb"):
         """Scores every candidate history against ONE (image, text) pair given its features. Returns a dict with the

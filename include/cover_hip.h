@@ -915,6 +915,56 @@ typedef struct cover_proposal_prior_args {
 int cover_proposal_prior_tokens(const cover_proposal_prior_args* args, void* stream);
 int cover_proposal_prior_actions(const cover_proposal_prior_args* args, void* stream);
 
+/* Verifier-guided refinement: one round of the cross-entropy method per prompt group, on the device. A group is group_rows (S) contiguous
+ * candidate rows (row i belongs to group i / S) with one fp32 score per row -- whatever the decision was made on: the verifier's scores,
+ * cover_member_scores' robust or cover_prior_select's combined. Per group the n_elite (m) best-scored rows are kept, the diagonal Gaussian
+ * of cover_augment_* is refitted on them and K new rows are drawn from it; the output has m + K rows per group, so downstream code sees
+ * what cover_augment_* would have given it, with group_size = m + K and n_fit = m. One 256-thread block per group, one launch, no
+ * workspace, no atomics, recordable.
+ * Ranking: row j of the group ranks before row j' when its score is higher, or the scores are equal (-0.0 and +0.0 are one score) and
+ *   j < j'. A NaN score (either sign) ranks behind every number, -inf included; NaNs among themselves rank by ascending index. (A bitonic
+ *   sort in LDS of the unique 64-bit keys (descending-order image of the score, all ones for a NaN) << 32 | j, padded to a power of two
+ *   with all-ones keys: the order is this rule whatever the schedule.)
+ * Gather: output row r < m of group g is the input row of rank r, verbatim -- tokens: the ids of its first 7 h columns; actions: the
+ *   first 7 dims of every step, bit for bit. elite_rows_out[g][r] = g * S + j, that row's index in the input; elite_scores_out[g][r] =
+ *   scores[g * S + j], bit for bit (a NaN keeps its payload).
+ * Fit and draw: rows m..m+K-1 of group g are EXACTLY rows n..n+K-1 that cover_augment_tokens / cover_augment_actions give with
+ *   src = the group's m gathered rows (n = m, n_stride = 7 h, t_stride = 7), the same normals, sigma, sd_floor, clip and centre table --
+ *   the same device functions, so rounding by rounding, with x_r the value of the elite of rank r:
+ *   mean  = (((0.0f + x_0) + x_1) + ... + x_{m-1}) / (float)m                       one chain of adds in RANK order, best elite first
+ *   ss    = the same chain over (x_r - mean) * (x_r - mean);  var = ss / (float)(m - 1), 0 when m == 1
+ *   sd    = fmaxf(sqrtf(var), sd_floor)
+ *   row k : s = sigma * sd;  p = s * z[g][k][t][d];  v = mean + p;  v = fminf(fmaxf(v, clip_lo), clip_hi)
+ *   all fp32, one rounding per operation, never an fma. Gripper (d == 6), per step: the majority class (x >= 0.5f) of the elites wins, a
+ *   tie goes to the class of the BEST elite; every drawn row takes the gripper token / float of the best-ranked elite in the winning class.
+ * cover_refine_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (n_stride >= 7 h; t_stride unused);
+ *   out = int64 [G * (m + K)][7 h]; values through centers / tok_vocab as in cover_augment_tokens.
+ * cover_refine_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit last
+ *   stride: a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place); centers unused; out = contiguous fp32 [G * (m + K)][h][7].
+ * Only the cells named above are read: nothing of src outside the [rows][h][7] view. out must not overlap src.
+ * Optional outputs (NULL = not written): elite_rows_out int32 [G][m], elite_scores_out fp32 [G][m], mean_out / sd_out fp32 [G][h][6]
+ * (sd after the floor), votes_out int32 [G][h][2] = (class-0 count, class-1 count) among the elites.
+ * COVER_EINVAL, and nothing launched, unless G >= 1, 1 <= n_elite <= group_rows <= 4096, 0 <= K <= 4096, 1 <= h <= 64,
+ * G * group_rows <= 2^20, G * (n_elite + K) <= 2^20, sigma and sd_floor finite and >= 0, clip_lo <= clip_hi, src / scores / out non-null,
+ * normals non-null when K > 0 and, for tokens, n_stride >= 7 h, centers non-null, n_centers >= 1. K == 0 is a pure top-m gather. */
+typedef struct cover_refine_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* scores;            /* [G * group_rows] */
+    const float* normals;           /* [G][K][h][6] */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    int n_centers, tok_vocab;
+    int G, group_rows, n_elite, K, h, _pad;
+    float sigma, sd_floor, clip_lo, clip_hi;
+    void* out;                      /* int64 [G * (n_elite + K)][7 h] or fp32 [G * (n_elite + K)][h][7] */
+    int* elite_rows_out;            /* int32 [G][n_elite], optional */
+    float* elite_scores_out;        /* [G][n_elite], optional */
+    float* mean_out; float* sd_out; /* [G][h][6], optional */
+    int* votes_out;                 /* [G][h][2], optional */
+} cover_refine_args;
+int cover_refine_tokens(const cover_refine_args* args, void* stream);
+int cover_refine_actions(const cover_refine_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
