@@ -4,7 +4,10 @@
 #include "common.h"
 #include "kernels.h"
 
-// (value, index) arg-max with smallest-index tie break
+// (value, index) arg-max with smallest-index tie break. A NaN never wins (both comparisons are false for it), so a range that holds
+// nothing but NaNs leaves the index at ARGMAX_NONE: the caller turns that into the first index of the range -- the one NaN rule of
+// every arg-max in this file (and of the greedy row of sample.hip).
+#define ARGMAX_NONE 0x7fffffff
 __device__ __forceinline__ void argmax_combine(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) {
         v = ov;
@@ -38,13 +41,14 @@ __global__ __launch_bounds__(256) void token_select_k(cover_token_select_args a)
     const int row = blockIdx.x;
     const float* lg = a.logits + (size_t)row * a.ld;
     float v = -INFINITY;
-    int idx = 0x7fffffff;
+    int idx = ARGMAX_NONE;
     for (int c = a.lo + threadIdx.x; c < a.hi; c += 256) argmax_combine(v, idx, lg[c], c);
     block_argmax(v, idx, sv, si);
     if (a.uniform == nullptr) {
         if (threadIdx.x == 0) {
-            a.token_out[row] = idx;
-            if (a.logit_out) a.logit_out[row] = v;
+            const bool none = idx == ARGMAX_NONE;   // a row of NaNs has no maximum: the first column, and its NaN
+            a.token_out[row] = none ? a.lo : idx;
+            if (a.logit_out) a.logit_out[row] = none ? lg[a.lo] : v;
         }
         return;
     }
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(1024) void token_argmax_wide_k(cover_token_select_a
     const int row = blockIdx.x;
     const float* lg = a.logits + (size_t)row * a.ld;
     float v = -INFINITY;
-    int idx = 0x7fffffff;
+    int idx = ARGMAX_NONE;
     const int n4 = (a.hi - a.lo) >> 2;
     const float4* p = (const float4*)(lg + a.lo);
     auto take = [&](const float4& x, int c) {
@@ -111,8 +115,9 @@ __global__ __launch_bounds__(1024) void token_argmax_wide_k(cover_token_select_a
     for (int t = a.lo + 4 * n4 + threadIdx.x; t < a.hi; t += 1024) argmax_combine(v, idx, lg[t], t);
     block_argmax(v, idx, sv, si);
     if (threadIdx.x == 0) {
-        a.token_out[row] = idx;
-        if (a.logit_out) a.logit_out[row] = v;
+        const bool none = idx == ARGMAX_NONE;   // as token_select_k
+        a.token_out[row] = none ? a.lo : idx;
+        if (a.logit_out) a.logit_out[row] = none ? lg[a.lo] : v;
     }
 }
 hipError_t launch_token_select(const cover_token_select_args* a, hipStream_t st) {
@@ -140,15 +145,20 @@ __device__ void group_argmax_dev(const float* scores, int N, int gs, int* result
     }
     __syncthreads();
     float v = -INFINITY;
-    int idx = 0x7fffffff;
+    int idx = ARGMAX_NONE;
     for (int gi = threadIdx.x; gi < G; gi += blockDim.x) argmax_combine(v, idx, gmean_s[gi], gi);
     block_argmax(v, idx, sv, si);
-    const int bg = idx;
-    const float bgm = v;
+    const bool no_group = idx == ARGMAX_NONE;   // every group mean a NaN: group 0, and its mean
+    const int bg = no_group ? 0 : idx;
+    const float bgm = no_group ? gmean_s[0] : v;
     float v2 = -INFINITY;
-    int i2 = 0x7fffffff;
+    int i2 = ARGMAX_NONE;
     for (int j = threadIdx.x; j < gs; j += blockDim.x) argmax_combine(v2, i2, scores[bg * gs + j], j);
     block_argmax(v2, i2, sv, si);
+    if (i2 == ARGMAX_NONE) {                    // the winning group all NaN: its first candidate, and its score
+        i2 = 0;
+        v2 = scores[bg * gs];
+    }
     if (threadIdx.x == 0) {
         result[0] = bg * gs + i2;
         result[1] = bg;

@@ -637,7 +637,11 @@ def sincos_time_embed(time, dim, min_period, max_period, out=None):
 
 # ------------------------------------------------------------------------------------------------ selection
 def token_select(logits, lo, hi, uniform=None, temperature=1.0, out_tok=None, out_logit=None):
-    """out_tok int64 [rows] / out_logit fp32 [rows] (contiguous, e.g. a row of a [steps, rows] buffer): written in place of fresh tensors."""
+    """cover_token_select over columns [lo, hi) of fp32 logits [rows, >= hi]: uniform None = greedy (the first maximum), else the inverse-CDF
+    pick at `temperature` with uniform fp32 [rows] (hi - lo <= 4096, temperature > 0). Returns (token int64 [rows], its logit fp32 [rows]).
+    out_tok int64 [rows] / out_logit fp32 [rows] (contiguous, e.g. a row of a [steps, rows] buffer): written in place of fresh tensors.
+    A NaN never wins the greedy comparison; a row of NaNs gives token lo and the NaN at lo, so the id is always inside [lo, hi). A sampled
+    row that contains a NaN gives some id inside [lo, hi) and leaves the other rows as they would be without it."""
     _chk_dev(logits, uniform, out_tok, out_logit)
     rows = logits.shape[0]
     tok = torch.empty(rows, dtype=torch.int64, device=logits.device) if out_tok is None else out_tok
@@ -1224,7 +1228,8 @@ def decode_feedback(pick, done, tok_out, step, eos, pad, force=None, lp=None, lp
 
 
 def score_select(it, act, group_size):
-    """it [members, dim], act [members, N, dim] fp32 -> (scores [N], result int32[4], best f32[2], fused_it, fused_act)."""
+    """it [members, dim], act [members, N, dim] fp32 -> (scores [N], result int32[4], best f32[2], fused_it, fused_act). result / best are
+    group_argmax's on scores, NaN rule included (members that cancel average to a zero vector, whose score is 0 / 0)."""
     _chk_dev(it, act)
     m, N, dim = act.shape
     dev = it.device
@@ -1272,6 +1277,9 @@ def actions_to_histories(actions, n_use, past, lo_hi=None, pad_value=-5.0):
 
 
 def group_argmax(scores, group_size):
+    """scores fp32 [N] -> (result int32 [4] = {global index, group, index in group, 0}, best fp32 [2] = {that score, its group's mean}):
+    cover_group_argmax, first maximum wins at both levels. A NaN never wins; where nothing wins (every group mean a NaN, or the taken
+    group all NaN) the pick is index 0, so result is always in range and best carries the picked values' own bits."""
     _chk_dev(scores)
     result = torch.empty(4, dtype=torch.int32, device=scores.device)
     best = torch.empty(2, dtype=torch.float32, device=scores.device)

@@ -437,7 +437,15 @@ int cover_sincos_time_embed(const float* time, int B, int dim, double min_period
 /* Action-token decode head (OpenVLA profile; the 256-bin arithmetic the reference carries at
  * INT-ACT/src/experiments/policies/policy_wrapper.py:259-266). logits fp32 [rows][ld]; greedy: first arg-max over
  * [lo, hi); sampling: softmax((logits - max)/temperature) over [lo, hi), inverse CDF in index order with the
- * host-supplied uniform u[row]. */
+ * host-supplied uniform u[row].
+ * NaN rule of every arg-max in this library (here, cover_group_argmax and the greedy row of cover_token_sample_rows): a NaN
+ * never wins a comparison, and if nothing wins the pick is the first index of the range. Greedy: NaNs among numbers are passed
+ * over; a row whose [lo, hi) holds only NaNs gives token_out = lo and logit_out = logits[row][lo] (that NaN's own bits) -- always
+ * an id inside [lo, hi). logit_out carries the bits of the picked logit in every case (so -0.0 stays -0.0).
+ * Sampling: a row that contains a NaN is unspecified beyond "token_out is in [lo, hi), logit_out is the logit at that token and
+ * the other rows of the launch are unaffected".
+ * COVER_EINVAL, and nothing launched: hi <= lo; with a uniform, hi - lo > 4096 or a temperature that is not > 0 (a NaN included).
+ * rows <= 0 succeeds and writes nothing. */
 typedef struct cover_token_select_args {
     const float* logits; long long ld; int rows; int lo, hi;
     const float* uniform;   /* [rows] in [0,1) or NULL for greedy */
@@ -562,7 +570,7 @@ int cover_token_topn(const cover_token_topn_args* args, void* stream);
  *                         wherever that call runs its own kernel (a filtered row, or hi - lo > 4096), bit for bit; logprob_out is
  *                         cover_token_logprob of the pick with the row's parameters, bit for bit, always.
  *   temperature[r] == 0   a greedy row: token_out = the first arg-max of the input floats over [lo, hi) (cover_token_select's greedy rule:
- *                         the lowest index among equal maxima), logit_out its logit, kept_out = hi - lo, logprob_out = lp(token) at
+ *                         the lowest index among equal maxima, lo and its NaN for a row of NaNs), logit_out its logit, kept_out = hi - lo, logprob_out = lp(token) at
  *                         temperature 1 with both filters off (cover_token_logprob's value, bit for bit). top_k[r], top_p[r] and
  *                         uniform[r] are not read. cover_token_logprob_rows / cover_token_topn_rows score and rank a greedy row at
  *                         temperature 1, unfiltered.
@@ -761,7 +769,11 @@ int cover_tokens_to_histories_steps(const int64_t* tokens, int ld_tokens, int N,
 int cover_actions_to_histories(const float* actions, long long n_stride, long long t_stride, int N, int n_use, const float* lo_hi,
                                const float* past, int n_past, float pad_value, float* hist_out, uint8_t* pad_out, void* stream);
 
-/* grouped arg-max over already-computed (e.g. all-gathered) scores: same selection rule as above */
+/* grouped arg-max over already-computed (e.g. all-gathered) scores: same selection rule as above. Group mean = index-order fp32 sum /
+ * (float)group_size; the first maximal mean wins, then the first maximal score inside that group. NaN rule (cover_token_select's): a
+ * NaN never wins and if nothing wins the pick is index 0 -- a group holding a NaN has a NaN mean and is passed over; if every group
+ * mean is a NaN, group 0 is taken; if every score of the taken group is a NaN, its candidate 0. result_out is therefore always in
+ * range. best_out = {scores[result_out[0]], mean of group result_out[1]}, their own bits, NaNs included. */
 int cover_group_argmax(const float* scores, int N, int group_size, int* result_out, float* best_out, void* stream);
 
 /* Prior-weighted selection: the grouped arg-max of combined[n] = scores[n] + beta * prior[n], where prior[n] is the candidate's sequence
@@ -773,7 +785,8 @@ int cover_group_argmax(const float* scores, int N, int group_size, int* result_o
  *   combined[n] = scores[n] exactly when beta == 0.0f (no product: a -inf prior cannot make a NaN), else
  *                 round(scores[n] + round(beta * prior[n])): two fp32 roundings, never an fma. A -inf prior gives -inf.
  *   groups      = cover_group_argmax on combined (the same device code): group mean = index-order fp32 sum / group_size, first
- *                 maximum wins; a group holding a -inf has mean -inf; if every group does, group 0 wins.
+ *                 maximum wins; a group holding a -inf has mean -inf; if every group does, group 0 wins. NaNs in combined follow
+ *                 cover_group_argmax's rule: never a winner, and group 0 / candidate 0 if nothing wins.
  *   ranked[r]   = global index of the member of the winning group with rank r < top_m in (descending combined, ascending index)
  *                 order, so ranked[0] == result_out[0].
  * The two stride pairs (in elements) read candidate-major [N][steps] and step-major [steps][N] buffers alike, without a copy.
@@ -813,6 +826,7 @@ int cover_prior_select(const cover_prior_select_args* args, void* stream);
  *               mode 1 (min): min.
  *   result_out / best_out               = cover_group_argmax on robust (the same device code)
  *   member_result_out[m] / member_best_out[m] = cover_group_argmax on member_scores_out + m * N
+ *   (NaN scores included: cover_group_argmax's rule, every index in range)
  * scores = the [N] fused scores cover_score_select wrote; read only.
  * COVER_EINVAL, and nothing launched, unless 1 <= n_members <= 16, N >= 1, group_size >= 1, N % group_size == 0, N / group_size <= 4096,
  * 1 <= dim <= 4096, kappa finite and >= 0, mode 0 or 1, kappa == 0 in mode 1 and every pointer non-null. */
