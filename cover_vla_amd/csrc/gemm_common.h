@@ -586,9 +586,9 @@ __device__ __forceinline__ void glds4_s(uint32_t voff, const void* sbase, uint32
         : "memory");
 }
 
-// ---- host side: the GEMM plan (gemm_bf16.hip: plan_gemm) and the launches that carry it out
+// ---- host side: the GEMM plan (gemm_plan.hip: plan_gemm) and the launches that carry it out (gemm_bf16.hip, gemm_v3.hip, gemm_fp8.hip)
 
-// tile picks = rows of the tile table in gemm_bf16.hip = the public plan-counter slots (include/cover_hip.h): never renumbered
+// tile picks = rows of the tile table in gemm_plan.hip (k_tiles) = the public plan-counter slots (include/cover_hip.h): never renumbered
 enum TilePick {
     TP_128x128 = 0, TP_64x128 = 1, TP_64x64 = 2, TP_128x128_S4 = 3, TP_256x128 = 4, TP_128x256 = 5, TP_128x128_W8 = 6, TP_64x128_S3 = 7,
     TP_128x128_S3 = 8,                                                    // gemm_tiled (0..8; 3..8: COVER_TILE_PICK only)
@@ -599,7 +599,7 @@ enum TilePick {
     TP_V3K_224x96 = 30,                                                                 // k-split wave pairs (gemm_tiled_v3k); 28, 29, 31: gaps
 };
 
-// weight-streaming plans (gemm_bf16.hip: plan_skinny / plan_skinny2 / plan_skinny3)
+// weight-streaming plans (gemm_plan.hip: plan_skinny / plan_skinny2 / plan_skinny3)
 struct SkinnyPlan {
     int MF, KC, S, nbpb, gx;
     size_t lds, ws_bytes;
@@ -632,6 +632,62 @@ struct GemmPlan {
     bool norm_launch;    // the epilogue's norm runs as its own launch after the GEMM (or its reduction)
     int rcls;            // profiling class of the reduction: 5 behind weight streaming, 6 / 8 / 9 behind ViT-sized / LLM-sized / fp8 tiles
 };
+
+// gemm_plan.hip: the planner (no HIP call) and the plan counters. Hidden: what the library exports is what it exported before the planner had a file
+#define PLAN_API __attribute__((visibility("hidden")))
+// The whole plan of one GEMM: validation, kernel family, grid, and how the K slices are completed.
+// want_slabs: the caller can fold the slabs of a split-K tiled launch itself (launch_gemm_bf16's splits_out).
+PLAN_API hipError_t plan_gemm(GemmPlan& p, int lda, const void* C, int ldc, int M, int N, int K, const EpiDev& epi, const float* ws, size_t ws_bytes,
+                     int variant, bool want_slabs);
+// The weight-streaming plan of variants 3 / 6 and of launch_gemm_skinny_partial (all_slabs: even an unsplit third-generation launch writes its
+// sums as one slab). forced3 (variant 6, tests): the third generation on any legal problem, unsplit.
+PLAN_API hipError_t plan_streaming(GemmPlan& p, int M, int N, int Kp, const float* ws, size_t ws_bytes, bool forced3, bool all_slabs);
+PLAN_API void plan_hit(int slot);   // one launch on plan-counter slot `slot` (cover_gemm_plan_counts)
+
+// profiling class of a weight-streaming launch: 0 = the large (>= 16 MB of weights) GEMMs of an LLM decode pass, i.e. the
+// kernel bench.py's roofline object is about; 3 = small ones (verifier / pi0-expert sized) that are latency-, not HBM-bound
+static inline int sk_class(int N, int K) { return 2.0 * (double)N * (double)K >= 16.0e6 ? 0 : 3; }
+
+// the device-side epilogue description of a cover_gemm_epi (nullptr: the plain epilogue); operand twins that come without their scales are dropped
+static inline EpiDev make_epi(const cover_gemm_epi* e) {
+    EpiDev d;
+    d.bias = e ? e->bias : nullptr;
+    d.residual = e ? e->residual : nullptr;
+    d.res_f32 = e ? e->residual_f32 : 0;
+    d.lscale = e ? e->layer_scale : nullptr;
+    d.ldr = e ? e->ld_residual : 0;
+    d.act = e ? e->act : 0;
+    d.glu = e ? e->glu : 0;
+    d.out_f32 = e ? e->out_f32 : 0;
+    d.out_scale = e ? e->out_scale : 1.0f;
+    if (d.out_scale == 0.0f) d.out_scale = 1.0f;
+    d.norm_w = e ? e->norm_w : nullptr;
+    d.norm_b = e ? e->norm_b : nullptr;
+    d.norm_out = e ? (bf16_t*)e->norm_out : nullptr;
+    d.ld_norm_out = e ? e->ld_norm_out : 0;
+    d.norm_style = e ? e->norm_style : 0;
+    d.norm_w_offset = e ? e->norm_w_offset : 0.f;
+    d.norm_eps = e ? e->norm_eps : 0.f;
+    d.w8 = e ? (const uint8_t*)e->w8 : nullptr;
+    d.w8s = e ? e->w8_scale : nullptr;
+    if (!d.w8 || !d.w8s) { d.w8 = nullptr; d.w8s = nullptr; }
+    d.a8 = e ? (const uint8_t*)e->a8 : nullptr;
+    d.a8s = e ? e->a8_scale : nullptr;
+    d.lda8 = e ? e->ld_a8 : 0;
+    if (!d.a8 || !d.a8s || !d.w8) { d.a8 = nullptr; d.a8s = nullptr; }
+    d.nq8 = e ? (uint8_t*)e->norm_out8 : nullptr;
+    d.nq8s = e ? e->norm_out8_scale : nullptr;
+    d.ldnq8 = e ? e->ld_norm_out8 : 0;
+    if (!d.nq8 || !d.nq8s || !d.norm_out || d.norm_style == 2) { d.nq8 = nullptr; d.nq8s = nullptr; }
+    d.w8_kl = (e && d.w8) ? e->w8_klinear : 0;
+    d.a8mx = (e && d.w8 && e->a8) ? (const uint8_t*)e->a8_mx : nullptr;
+    if (d.a8mx) { d.a8 = (const uint8_t*)e->a8; d.a8s = nullptr; }   // (a8_scale is not needed with block scales)
+    d.o8 = e ? (uint8_t*)e->out8 : nullptr;
+    d.o8mx = e ? (uint8_t*)e->out8_mx : nullptr;
+    d.ldo8 = e ? e->ld_out8 : 0;
+    if (!d.o8 || !d.o8mx) { d.o8 = nullptr; d.o8mx = nullptr; }
+    return d;
+}
 
 // Every GEMM kernel launch: the 160 KiB dynamic-LDS attribute once per kernel and device when the launch needs more than 64 KiB and, with
 // profiling on, the kernel's own start / stop timestamps in a reserved event pair of class cls. Returns the attribute's error, if any

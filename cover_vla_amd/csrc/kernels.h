@@ -7,7 +7,7 @@
 
 typedef uint16_t bf16_t;
 
-// ---- gemm_bf16.hip -------------------------------------------------------------------------------
+// ---- gemm_bf16.hip (kernels, launchers), gemm_plan.hip (the planner: gemm_plan_query, gemm_plan_counts, gemm_workspace_bytes) ----
 // C[M,N] = epi(A[M,K] x W[N,K]^T); W pre-packed by cover_pack_weight_bf16 (fragment-major).
 hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K,
                             const cover_gemm_epi* epi, float* splitk_ws, size_t splitk_ws_bytes, int variant,
@@ -19,7 +19,7 @@ hipError_t launch_gemm_skinny_partial(const bf16_t* A, int lda, const bf16_t* Wp
 #define COVER_GEMM_PLANS 32
 hipError_t gemm_plan_query(const bf16_t* A, int lda, const bf16_t* Wp, const void* C, int ldc, int M, int N, int K, const cover_gemm_epi* epi,
                            const float* ws, size_t ws_bytes, int variant, int* plan);   // cover_gemm_plan: launch_gemm_bf16's plan, nothing launched
-void gemm_plan_counts(long long* out, int n, int reset);   // per-plan launch counters (tests): see gemm_bf16.hip
+void gemm_plan_counts(long long* out, int n, int reset);   // per-plan launch counters (tests): see gemm_plan.hip
 int gemm_v3_probe(unsigned long long* out);                  // 16 words: in-kernel probe of the last gemm_v3.hip launch (g_v3_probe)
 hipError_t launch_quantize_rows_fp8(const bf16_t* W, int ldw, int N, int K, float* scales, bf16_t* Wdq, hipStream_t st);
 hipError_t launch_pack_weight_fp8(const bf16_t* Wdq, int ldw, const float* scales, int N, int K, uint8_t* Wq, float* scales_packed,

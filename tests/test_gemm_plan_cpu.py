@@ -5,7 +5,14 @@ inputs, pinned against literal tables. The tables were recorded from the planner
 
 Pointers are fake, aligned addresses: the planner only checks them for null and alignment."""
 import ctypes as C
+import hashlib
+import os
 import random
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
 
 from cover_vla_amd import _lib
 
@@ -66,12 +73,14 @@ def epi_for(kind, M, N, K):
     return e, nout
 
 
-def plan(M, N, K, kind, variant, ws_bytes, C_ptr=_C, ldc=None):
+def plan(M, N, K, kind, variant, ws_bytes, C_ptr=_C, ldc=None, lda=None, ld_a8=None):
     h = _lib.lib()
     e, nout = epi_for(kind, M, N, K)
+    if ld_a8 is not None and e.a8:
+        e.ld_a8 = ld_a8
     out = (C.c_int * 6)()
-    rc = h.cover_gemm_plan(_A, kp(K), _W, C_ptr, nout if ldc is None else ldc, M, N, K, C.byref(e), _WS if ws_bytes else None, ws_bytes,
-                           variant, out)
+    rc = h.cover_gemm_plan(_A, kp(K) if lda is None else lda, _W, C_ptr, nout if ldc is None else ldc, M, N, K, C.byref(e),
+                           _WS if ws_bytes else None, ws_bytes, variant, out)
     assert rc in (0, EINVAL), rc
     return tuple(out) if rc == 0 else None
 
@@ -238,6 +247,137 @@ def test_gemm_plan_of_the_gpu_tests_shapes(monkeypatch):
 
 def test_gemm_plan_sweep(monkeypatch):
     _check(sweep_cases(), SWEEP_PLANS, monkeypatch)
+
+
+# ---- the wide sweep and the once-per-process knobs. Expectations: tests/golden/gemm_plan_pinned.txt, recorded from a build of the commit BEFORE
+# the planner moved to gemm_plan.hip (its library loaded through COVER_LIB_PATH), never from the tree under test. The file holds the distinct plans
+# ("plan <code> <6-tuple, or - for COVER_EINVAL>"), then two characters per case: "wide" lines in wide_cases() order, one "knob" line per setting in
+# KNOB_SHAPES order; "cases" is the hash of the generated inputs, so the codes cannot drift away from the cases they were recorded for.
+TESTS = os.path.dirname(os.path.abspath(__file__))
+WIDE_KINDS = ["plain", "bias", "gelu", "res", "res_norm", "res_ln", "f32", "glu", "glu_gelu", "w8", "res_norm+w8", "glu+w8", "a8", "res_norm+a8", "glu+a8",
+              "mx", "bias+mx", "res_norm+mx", "glu+a8+out8", "glu_gelu+a8+out8", "a8kl", "res_norm+a8kl"]
+# the boundaries plan_tiles's steps branch on: the 64-row streaming limit, M >= 400 / >= 512 / < 1024, 224-row padding of just over / just under
+# 10 % (407 | 408, 493 | 494, 610 | 611; none: 448, all but a row: 449), the headline row counts
+WIDE_M = [64, 65, 399, 400, 448, 511, 512, 704, 1023, 1024, 2624, 407, 408, 449, 493, 494, 610, 611, 672, 2232, 1, 16, 17, 32, 33]
+WIDE_K = [1920, 2048, 4096, 8192, 128, 1024, 2304, 11008]                                  # (all their own Kp)
+WIDE_N = [4088, 4096, 4104, 16376, 16384, 16392, 12288, 22016, 11008, 8192, 3072, 2560, 1536, 1024, 64, 32]
+WS_MODES = ["none", "small", "sized", "ample"]   # absent | a byte short of two slices | cover_gemm_workspace_bytes | room for eight slices
+PANEL = (1 << 31) - 4096                          # the self-loading kernels' 32-bit lane offset: M * lda * 2 (bf16) or M * ld_a8 (e4m3) below this
+
+
+def ws_bytes_of(mode, M, N, K):
+    sized = _lib.lib().cover_gemm_workspace_bytes(M, N, K)
+    return {"none": 0, "small": 2 * M * N * 4 - 4, "sized": sized, "ample": max(sized, 8 * M * N * 4)}[mode]
+
+
+def panel_ld(side, M, K, esz, gran):
+    """a leading dimension (multiple of gran, >= Kp) that puts the M-row activation panel just below / just above the lane-offset limit"""
+    below = (PANEL - 1) // (M * esz) // gran * gran
+    return max(kp(K), below if side == "below" else below + gran)
+
+
+def wide_cases(seed=20261020):
+    """(M, N, K, kind, variant, ws mode, lda, ld_a8): a cross of the boundary values at variant 0, then a seeded sweep of everything"""
+    out = []
+    for M in WIDE_M[:18]:
+        for K in WIDE_K[:4]:
+            for N in (4096, 4104, 16384, 12288):
+                for kind in ("plain", "res_norm", "glu", "a8", "res_norm+mx", "glu+a8+out8"):
+                    for ws in ("none", "small", "ample"):
+                        out.append((M, N, K, kind, 0, ws, kp(K), kp(K)))
+    rnd = random.Random(seed)
+    for _ in range(3000):
+        kind = rnd.choice(WIDE_KINDS)
+        M = rnd.choice(WIDE_M) if rnd.random() < 0.7 else rnd.randint(1, 2700)
+        K = rnd.choice(WIDE_K) if rnd.random() < 0.7 else 128 * rnd.randint(1, 90) - rnd.choice([0, 0, 64])
+        N = rnd.choice(WIDE_N) if rnd.random() < 0.6 else 8 * rnd.randint(1, 2800)
+        if "glu" in kind:
+            N = max(32, N // 32 * 32)
+        variant = rnd.choice([0, 0, 0, 1, 1, 2, 3, 5, 6])
+        lda = ld_a8 = kp(K)
+        if M > 64 and rnd.random() < 0.15:      # the activation panel on both sides of the 2^31-byte limit
+            lda = panel_ld(rnd.choice(["below", "above"]), M, K, 2, 8)
+        if M > 64 and rnd.random() < 0.15:
+            ld_a8 = panel_ld(rnd.choice(["below", "above"]), M, K, 1, 16)
+        out.append((M, N, K, kind, variant, rnd.choice(WS_MODES), lda, ld_a8))
+    return out
+
+
+def plan_text(case):
+    M, N, K, kind, variant, ws, lda, ld_a8 = case
+    got = plan(M, N, K, kind, variant, ws_bytes_of(ws, M, N, K), lda=lda, ld_a8=ld_a8)
+    return "-" if got is None else " ".join(str(x) for x in got)
+
+
+def pinned():
+    """(plan of each wide case, {setting: plan of each knob shape}) as recorded"""
+    plans, wide, knobs = {}, "", {}
+    with open(os.path.join(TESTS, "golden", "gemm_plan_pinned.txt")) as f:
+        for line in f.read().splitlines():
+            tag, rest = line.split(" ", 1)
+            if tag == "cases":
+                assert rest == hashlib.sha256(repr((wide_cases(), KNOB_SHAPES)).encode()).hexdigest(), "the cases are not the recorded ones"
+            elif tag == "plan":
+                plans[rest[:2]] = rest[3:]
+            elif tag == "wide":
+                wide += rest
+            else:
+                knobs[tuple(rest.split(" ")[0].split("="))] = rest.split(" ")[1]
+    unpack = lambda codes: [plans[codes[i:i + 2]] for i in range(0, len(codes), 2)]   # noqa: E731
+    return unpack(wide), {k: unpack(v) for k, v in knobs.items()}
+
+
+def differing(cases, got, want):
+    assert len(cases) == len(got) == len(want)
+    return [f"{c}: {g}   (recorded: {w})" for c, g, w in zip(cases, got, want) if g != w]
+
+
+def test_gemm_plan_wide_sweep(monkeypatch):
+    monkeypatch.delenv("COVER_FP8_MFMA", raising=False)
+    cases = wide_cases()
+    assert len(cases) >= 5000
+    bad = differing(cases, [plan_text(c) for c in cases], pinned()[0])
+    assert not bad, f"{len(bad)} plans differ:\n" + "\n".join(bad[:40])
+
+
+# (M, N, K, kind, variant, ws mode): 224-row, 256-row and small tiles, fp8 / MX forms, the A/B variant, weight streaming of all generations
+KNOB_SHAPES = [
+    (448, 12288, 4096, "plain", 0, "sized"), (448, 4096, 4096, "res_norm", 0, "sized"), (448, 4096, 11008, "res_norm", 0, "none"),
+    (448, 22016, 4096, "glu", 0, "sized"), (448, 3072, 2048, "plain", 0, "ample"), (2232, 2560, 2048, "plain", 0, "sized"),
+    (704, 12288, 4096, "bias", 0, "sized"), (704, 4096, 11008, "res_norm", 0, "sized"), (2624, 32768, 2048, "glu_gelu", 0, "none"),
+    (200, 4096, 4096, "res_norm", 0, "sized"), (261, 1024, 4096, "res_ln", 0, "sized"), (576, 4096, 1024, "gelu", 0, "sized"),
+    (2048, 4608, 1152, "bias", 0, "none"), (1024, 8192, 2304, "plain", 1, "ample"), (448, 4096, 4096, "res_norm", 2, "sized"),
+    (300, 1024, 1024, "plain", 2, "ample"), (512, 12288, 4096, "a8", 0, "sized"), (512, 22016, 4096, "glu+a8", 0, "sized"),
+    (512, 22016, 4096, "glu+a8+out8", 0, "sized"), (512, 4096, 11008, "res_norm+mx", 0, "sized"), (448, 4096, 11008, "res_norm+a8", 0, "sized"),
+    (448, 22016, 4096, "glu+a8", 0, "sized"), (200, 4096, 4096, "bias+mx", 0, "sized"), (1024, 8192, 2304, "bias+a8", 0, "sized"),
+    (530, 1040, 2304, "bias+a8", 0, "ample"), (16, 12288, 4096, "plain", 0, "sized"), (32, 4096, 11008, "res_norm+w8", 0, "sized"),
+    (64, 32064, 4096, "f32", 0, "sized"), (48, 1024, 2048, "plain", 0, "sized"), (16, 22016, 4096, "glu", 3, "sized"),
+    (32, 4096, 4096, "plain", 5, "sized"), (16, 4096, 4096, "plain", 6, "sized"),
+]
+KNOB_SETTINGS = ([("COVER_TILE_PICK", c) for c in "345678abcdefghinopqru"] + [("COVER_TILE_SPLIT", s) for s in "124"] +
+                 [("COVER_V3_F8", "0"), ("COVER_SKINNY3", "0"), ("COVER_SK_SLOTS", "256")])
+KNOBS = ("COVER_TILE_PICK", "COVER_TILE_SPLIT", "COVER_V3_F8", "COVER_SKINNY3", "COVER_SK_SLOTS", "COVER_FP8_MFMA")
+
+
+@pytest.fixture(scope="module")
+def knob_children():
+    """one fresh child per setting (the knobs are read once per process), eight at a time; the children only plan: no GPU call"""
+    base = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    cmd = [sys.executable, "-c", "from tests.test_gemm_plan_cpu import *\nfor s in KNOB_SHAPES: print(plan_text(s + (kp(s[2]), kp(s[2]))))"]
+    root = os.path.dirname(TESTS)
+    def child(kv):
+        p = subprocess.run(cmd, cwd=root, env=dict(base, **{kv[0]: kv[1]}), capture_output=True, text=True)
+        return p.stdout, p.stderr, p.returncode
+    with ThreadPoolExecutor(8) as pool:
+        return dict(zip(KNOB_SETTINGS, pool.map(child, KNOB_SETTINGS)))
+
+
+@pytest.mark.parametrize("setting", KNOB_SETTINGS, ids=lambda kv: "=".join(kv))
+def test_gemm_plan_under_a_once_per_process_knob(knob_children, setting):
+    stdout, stderr, rc = knob_children[setting]
+    assert rc == 0, stderr
+    bad = differing(KNOB_SHAPES, stdout.splitlines(), pinned()[1][setting])
+    assert not bad, "\n".join(bad)
 
 
 def test_gemm_workspace_bytes_unchanged():
