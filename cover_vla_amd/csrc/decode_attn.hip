@@ -23,6 +23,7 @@
 // Restrictions: T = 1, Hq == Hkv (MHA), D in {64, 128}, every segment COVER_MASK_LEN.
 #include "common.h"
 #include "kernels.h"
+#include "rope.h"
 
 struct DecAttnDev {
     const bf16_t* qkv; int ld_qkv;
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
             }
         }
         if (a.rope_mode != 0) {
-            ppos = ppos < 0 ? 0 : (ppos >= a.n_pos ? a.n_pos - 1 : ppos);
+            ppos = rope_clamp_pos(ppos, a.n_pos);
             const unsigned po = (unsigned)(ppos * HALF + pi);
             cs = a.cos_t[po];
             sn = a.sin_t[po];
@@ -144,14 +145,9 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
         if (a.n_splits > 0) {
             const unsigned ro = (unsigned)pcand * (unsigned)ncols;
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                float v = 0.f;
-#pragma unroll
-                for (int sidx = 0; sidx < 4; ++sidx) v += sidx < a.n_splits ? pv[j][sidx] : 0.f;   // v is never -0: adding +0 is exact
-                for (int sidx = 4; sidx < a.n_splits; ++sidx) v += a.partial[(size_t)sidx * pstride + ro + col[j]];
-                if (a.bias) v += bs[j];
-                x[j] = bfround(v);
-            }
+            for (int j = 0; j < 6; ++j)
+                x[j] = qkv_fold<4>(a.n_splits, [&](int s) { return s < 4 ? pv[j][s] : a.partial[(size_t)s * pstride + ro + col[j]]; },
+                                   a.bias != nullptr, [&] { return bs[j]; });
         }
     }
 
@@ -182,23 +178,25 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
     int it = -1, bcol = -1, bslot = 0, blen = 0;      // iterator state: tile index inside the current run; pool B run
     // (only in the value-split variant: the unsplit one is at its 128-register budget, and its blocks are not the few-units case)
     bool tail_pending = (VS >= 2 && role == 2 && wl == 0 && a.tail_tile >= 0), is_tail = false;
+    auto seg0_tile = [&](int t0) {   // the segment-0 tile of keys [t0, t0 + 32): the 16 candidates are its query rows
+        int key0 = t0 + 8 * (r >> 2) + (r & 3), key1 = key0 + 4;
+        key0 = key0 < a.len0 ? key0 : a.len0 - 1;
+        key1 = key1 < a.len0 ? key1 : a.len0 - 1;
+        kbase = a.k0 + h * a.k0_h;
+        ko0 = key0 * a.k0_t + g * 8;
+        ko1 = key1 * a.k0_t + g * 8;
+        vbase = a.vt0 + h * a.vt0_h + t0;
+        vo = r * a.vt0_d + g * 8;
+        vstep = 16 * a.vt0_d;
+        vmask = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vmask |= (q_ok && t0 + 8 * g + e < a.len0) ? (1u << e) : 0u;
+    };
     auto next_tile = [&]() -> bool {
         if (role == 0) {            // segment 0: tiles wl, wl + WA, ...
             it = it < 0 ? wl : it + a.WA;
-            const int t0 = 32 * it;
-            if (t0 >= a.len0 || it == a.tail_tile) return false;   // (the tail tile belongs to the first pool-C wave)
-            int key0 = t0 + 8 * (r >> 2) + (r & 3), key1 = key0 + 4;
-            key0 = key0 < a.len0 ? key0 : a.len0 - 1;
-            key1 = key1 < a.len0 ? key1 : a.len0 - 1;
-            kbase = a.k0 + h * a.k0_h;
-            ko0 = key0 * a.k0_t + g * 8;
-            ko1 = key1 * a.k0_t + g * 8;
-            vbase = a.vt0 + h * a.vt0_h + t0;
-            vo = r * a.vt0_d + g * 8;
-            vstep = 16 * a.vt0_d;
-            vmask = 0;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vmask |= (q_ok && t0 + 8 * g + e < a.len0) ? (1u << e) : 0u;
+            if (32 * it >= a.len0 || it == a.tail_tile) return false;   // (the tail tile belongs to the first pool-C wave)
+            seg0_tile(32 * it);
             return true;
         }
         if (role == 1) {            // segment 1: the runs (distinct prompt slots) p = wl, wl + WB, ... of the block, all their tiles
@@ -237,22 +235,10 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
         const int tb = 8 * it;
         if (tb >= a.len2) {
             if (VS < 2 || !tail_pending) return false;
-            // the segment-0 tail tile (pool A has exactly one wave per FULL tile): described like a pool-A tile
+            // the segment-0 tail tile (pool A has exactly one wave per FULL tile)
             tail_pending = false;
             is_tail = true;
-            const int t0 = 32 * a.tail_tile;
-            int key0 = t0 + 8 * (r >> 2) + (r & 3), key1 = key0 + 4;
-            key0 = key0 < a.len0 ? key0 : a.len0 - 1;
-            key1 = key1 < a.len0 ? key1 : a.len0 - 1;
-            kbase = a.k0 + h * a.k0_h;
-            ko0 = key0 * a.k0_t + g * 8;
-            ko1 = key1 * a.k0_t + g * 8;
-            vbase = a.vt0 + h * a.vt0_h + t0;
-            vo = r * a.vt0_d + g * 8;
-            vstep = 16 * a.vt0_d;
-            vmask = 0;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vmask |= (q_ok && t0 + 8 * g + e < a.len0) ? (1u << e) : 0u;
+            seg0_tile(32 * a.tail_tile);
             return true;
         }
         int cg = tile * 16 + cl + (r >> 2), cv = tile * 16 + cl + g;
@@ -285,18 +271,9 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
     };
     // ---------------- phase 1b: RoPE, q / k_new / v_new -> LDS, k_new / v_new -> own cache segment ----------------
     if (p1) {
-        if (p1_ok) {
-            if (a.rope_mode == 2) {
-                cs = bfround(cs); sn = bfround(sn);
-                const float a1 = bfround(bfround(x[0] * cs) + bfround(-x[1] * sn)), a2 = bfround(bfround(x[1] * cs) + bfround(x[0] * sn));
-                const float b1 = bfround(bfround(x[2] * cs) + bfround(-x[3] * sn)), b2 = bfround(bfround(x[3] * cs) + bfround(x[2] * sn));
-                x[0] = a1; x[1] = a2; x[2] = b1; x[3] = b2;
-            } else if (a.rope_mode != 0) {
-#pragma clang fp contract(off)   // same uncontracted arithmetic as rope_kv_write (torch rounds each product)
-                const float a1 = x[0] * cs - x[1] * sn, a2 = x[1] * cs + x[0] * sn;
-                const float b1 = x[2] * cs - x[3] * sn, b2 = x[3] * cs + x[2] * sn;
-                x[0] = a1; x[1] = a2; x[2] = b1; x[3] = b2;
-            }
+        if (p1_ok && a.rope_mode != 0) {
+            rope_rotate(a.rope_mode, x[0], x[1], cs, sn, x[0], x[1]);
+            rope_rotate(a.rope_mode, x[2], x[3], cs, sn, x[2], x[3]);
         }
         qs[pc * D + pi] = f2bf(x[0]);
         qs[pc * D + pi + HALF] = f2bf(x[1]);
@@ -340,17 +317,18 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
     int dbg_tiles = 0;
 #endif
     int sw = w;                                        // state slot this wave is writing
+    auto empty_state = [&](int s) {                    // slot s holds the state of no keys (merging it is exact)
+#pragma unroll
+        for (int i = 0; i < DB * 4; ++i) so[s * OW + i * 64 + lane] = 0.f;
+        if (g == 0) {
+            sm[s * 16 + r] = -INFINITY;
+            sl[s * 16 + r] = 0.f;
+        }
+    };
 #pragma clang loop unroll(disable)
     while (have) {
         if (VS >= 2 && is_tail && sw == w) {   // switching to the extra slot: close this wave's own slot first
-            if (first) {
-#pragma unroll
-                for (int i = 0; i < DB * 4; ++i) so[w * OW + i * 64 + lane] = 0.f;
-                if (g == 0) {
-                    sm[w * 16 + r] = -INFINITY;
-                    sl[w * 16 + r] = 0.f;
-                }
-            }
+            if (first) empty_state(w);
             sw = DA_NW;
             first = true;
         }
@@ -440,22 +418,8 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
     DAW(3, wall_clock64());
     DAW(5, (unsigned long long)dbg_tiles);
 #endif
-    if (first && sw == w) {   // a wave without a tile contributes the empty state
-#pragma unroll
-        for (int i = 0; i < DB * 4; ++i) so[w * OW + i * 64 + lane] = 0.f;
-        if (g == 0) {
-            sm[w * 16 + r] = -INFINITY;
-            sl[w * 16 + r] = 0.f;
-        }
-    }
-    if (role == 2 && wl == 0 && sw == w) {   // no tail tile: the extra slot is empty
-#pragma unroll
-        for (int i = 0; i < DB * 4; ++i) so[DA_NW * OW + i * 64 + lane] = 0.f;
-        if (g == 0) {
-            sm[DA_NW * 16 + r] = -INFINITY;
-            sl[DA_NW * 16 + r] = 0.f;
-        }
-    }
+    if (first && sw == w) empty_state(w);                        // a wave without a tile contributes the empty state
+    if (role == 2 && wl == 0 && sw == w) empty_state(DA_NW);     // no tail tile: the extra slot is empty
 
     // ---------------- phase 3: merge the waves' states in wave order ----------------
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only again: the cache stores drain behind the merge
@@ -489,6 +453,33 @@ __global__ __launch_bounds__(1024) void decode_attn_fused_k(DecAttnDev a) {
         *op = f2bf(o[0]);
     }
     DAT(3);
+}
+
+// What depends on the problem's size alone: the wave pools, the segment-0 tail tile and the value split VS (= gridDim.z).
+struct DecAttnPlan { int WA, WC, tail_tile, VS; };
+static DecAttnPlan decode_attn_plan(int N, int H, int D, int len0) {
+    DecAttnPlan p;
+    // wave pools (see the header comment): 4 waves for segment 2 (4 candidates each), one wave per segment-0 tile up to 9,
+    // the rest (>= 3) for the distinct prompts of a block
+    const int nA = (len0 + 31) / 32;
+    p.WC = 4;
+    p.WA = nA < 9 ? nA : 9;
+    p.tail_tile = -1;
+    // few (candidate tile, head) units: split the value columns over two blocks each (see the kernel's VS comment)
+    static const char* vs_env = getenv("COVER_DA_VSPLIT");
+    const int units = ((N + 15) / 16) * H;
+    // units <= 64 (N = 32 at 32 heads): four blocks per unit put one block on every CU; the score part is computed four times
+    // over, but a block then pulls 10 instead of 12 KiB per wave-tile and merges a quarter of the columns (decode pass 3.655 ->
+    // 3.58 ms). D = 64 heads have too few columns to split in four.
+    p.VS = vs_env ? (atoi(vs_env) == 4 ? 4 : atoi(vs_env) == 2 ? 2 : 1) : (units <= 64 ? 4 : units <= 128 ? 2 : 1);
+    if (D != 128 && p.VS == 4) p.VS = 2;
+    // Nine segment-0 tiles (257 keys = BOS + 256 patches: eight full tiles and ONE key) would cost pool A a ninth wave and leave
+    // pool B three waves for the four prompts of a block -- one of them then runs two tiles back to back, each a full
+    // global round trip, and the whole block waits for it. The ninth tile goes to the first pool-C wave instead (its own
+    // tile is 8 short keys), into a state slot of its own so that the merge order stays independent of where a candidate sits.
+    static const char* tail_env = getenv("COVER_DA_TAIL");   // experiment knob: 0 keeps nine pool-A waves
+    if (nA == 9 && p.VS >= 2 && !(tail_env && tail_env[0] == '0')) { p.WA = 8; p.tail_tile = 8; }
+    return p;
 }
 
 hipError_t launch_decode_attention_fused(const cover_decode_attn_args* x, hipStream_t st) {
@@ -525,26 +516,9 @@ hipError_t launch_decode_attention_fused(const cover_decode_attn_args* x, hipStr
     a.vt2_slot = s2.vt_slot_stride; a.vt2_h = (int)s2.vt_h_stride; a.vt2_d = (int)s2.vt_d_stride;
     a.slot2 = s2.slot_of_batch; a.len2 = s2.len; a.write_t = x->write_t;
     a.out = (bf16_t*)x->out; a.o_row = x->out_row_stride;
-    // wave pools (see the header comment): 4 waves for segment 2 (4 candidates each), one wave per segment-0 tile up to 9,
-    // the rest (>= 3) for the distinct prompts of a block
-    const int nA = (s0.len + 31) / 32;
-    a.WC = 4;
-    a.WA = nA < 9 ? nA : 9;
-    a.tail_tile = -1;
-    // Nine segment-0 tiles (257 keys = BOS + 256 patches: eight full tiles and ONE key) would cost pool A a ninth wave and leave
-    // pool B three waves for the four prompts of a block -- one of them then runs two tiles back to back, each a full
-    // global round trip, and the whole block waits for it. The ninth tile goes to the first pool-C wave instead (its own
-    // tile is 8 short keys), into a state slot of its own so that the merge order stays independent of where a candidate sits.
-    // few (candidate tile, head) units: split the value columns over two blocks each (see the kernel's VS comment)
-    static const char* vs_env = getenv("COVER_DA_VSPLIT");
-    const int units = ((x->N + 15) / 16) * x->H;
-    // units <= 64 (N = 32 at 32 heads): four blocks per unit put one block on every CU; the score part is computed four times
-    // over, but a block then pulls 10 instead of 12 KiB per wave-tile and merges a quarter of the columns (decode pass 3.655 ->
-    // 3.58 ms). D = 64 heads have too few columns to split in four.
-    int VS = vs_env ? (atoi(vs_env) == 4 ? 4 : atoi(vs_env) == 2 ? 2 : 1) : (units <= 64 ? 4 : units <= 128 ? 2 : 1);
-    if (x->D != 128 && VS == 4) VS = 2;
-    static const char* tail_env = getenv("COVER_DA_TAIL");   // experiment knob: 0 keeps nine pool-A waves
-    if (nA == 9 && VS >= 2 && !(tail_env && tail_env[0] == '0')) { a.WA = 8; a.tail_tile = 8; }
+    const DecAttnPlan p = decode_attn_plan(x->N, x->H, x->D, s0.len);
+    a.WA = p.WA; a.WC = p.WC; a.tail_tile = p.tail_tile;
+    const int VS = p.VS;
     dim3 grid((x->N + 15) / 16, x->H, VS), block(64 * DA_NW);
     const int pid = prof_enabled() ? prof_open(st, 2, 0.0) : -1;
     if (x->D == 128) {

@@ -15,12 +15,13 @@
 // reference has no fp8 path): s_row = smallest 2^e with amax / 2^e <= 448, q = RNE_e4m3(x / s_row); scales of
 // K / V live in the second half of the (bf16-sized) regions: scale index (slot * H + h) * t_cap + t at byte offset region_elems.
 //
-// Arithmetic: RoPE exactly as rope_kv_write (HF rotate_half in bf16 arithmetic, or the pi0 fp32 form); scores q.k in fp32 over
+// Arithmetic: RoPE is rope_kv_write's (rope.h: HF rotate_half in bf16 arithmetic, or the pi0 fp32 form); scores q.k in fp32 over
 // the bf16 / de-quantised values, scaled after the product (eager_attention_forward order), softmax in fp32 with the probabilities
 // rounded to bf16 before PV and the row sum taken over the unrounded ones (as attention.hip); the state handed on is
 // (O / l in fp32, m in scaled-log2 units, l) -- attention.hip's chaining convention (cover_attn_args.state_in_*).
 #include "common.h"
 #include "kernels.h"
+#include "rope.h"
 
 struct OwnAttnDev {
     bf16_t* qkv; int ld_qkv;                 // bf16 [N][3*H*D]; q is rotated IN PLACE (the chained MFMA pass reads it)
@@ -55,10 +56,7 @@ __global__ __launch_bounds__(256) void decode_own_attn_k(OwnAttnDev a) {
     if (h >= a.H) return;                           // (no block barrier below: waves are independent)
     const int slot = a.slot_of_batch ? a.slot_of_batch[n] : n;
     int pos = 0;
-    if (a.rope_mode != 0) {
-        pos = a.positions[n];
-        pos = pos < 0 ? 0 : (pos >= a.n_pos ? a.n_pos - 1 : pos);
-    }
+    if (a.rope_mode != 0) pos = rope_clamp_pos(a.positions[n], a.n_pos);
     // ---- the cached K rows (and, while they fit the registers, V rows) are requested FIRST: they depend on nothing but the slot, and
     //      the q / k / v + RoPE work below then runs under their latency (the chain was: indices -> qkv -> LDS -> K -> scores -> V) ----
     constexpr bool VEARLY = NIT <= 8;
@@ -97,18 +95,12 @@ __global__ __launch_bounds__(256) void decode_own_attn_k(OwnAttnDev a) {
         k1 = bf2f(kp[i]); k2 = bf2f(kp[i + HALF]);
         v1 = bf2f(vp[i]); v2 = bf2f(vp[i + HALF]);
         if (a.rope_mode != 0) {
-            float c = a.cos_t[(size_t)pos * HALF + i], s = a.sin_t[(size_t)pos * HALF + i];
-            if (a.rope_mode == 2) {   // HF rotate_half in bf16 arithmetic (rope_kv_write's expressions)
-                c = bfround(c); s = bfround(s);
-                const float o1 = bfround(bfround(q1 * c) + bfround(-q2 * s)), o2 = bfround(bfround(q2 * c) + bfround(q1 * s));
-                const float p1 = bfround(bfround(k1 * c) + bfround(-k2 * s)), p2 = bfround(bfround(k2 * c) + bfround(k1 * s));
-                q1 = o1; q2 = o2; k1 = p1; k2 = p2;
-            } else {                  // apply_rope (paligemma_with_expert.py:34-57): fp32, one rounding
-#pragma clang fp contract(off)
-                const float o1 = bfround(q1 * c - q2 * s), o2 = bfround(q2 * c + q1 * s);
-                const float p1 = bfround(k1 * c - k2 * s), p2 = bfround(k2 * c + k1 * s);
-                q1 = o1; q2 = o2; k1 = p1; k2 = p2;
-            }
+            const float c = a.cos_t[(size_t)pos * HALF + i], s = a.sin_t[(size_t)pos * HALF + i];
+            float o1, o2, p1, p2;
+            rope_rotate(a.rope_mode, q1, q2, c, s, o1, o2);
+            rope_rotate(a.rope_mode, k1, k2, c, s, p1, p2);
+            // this pass goes on computing with the rotated values: the one rounding that rope_kv_write leaves to its store (mode 2: no change)
+            q1 = bfround(o1); q2 = bfround(o2); k1 = bfround(p1); k2 = bfround(p2);
             bf16_t* qw = row + (size_t)h * D;       // rotated q back in place for the chained pass over the shared segments
             qw[i] = f2bf(q1); qw[i + HALF] = f2bf(q2);
         }

@@ -2,6 +2,7 @@
 // All bf16 traffic is 16 bytes per lane; reductions are wave shuffles + one LDS hop per block.
 #include "common.h"
 #include "kernels.h"
+#include "rope.h"
 
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm / RMSNorm: one 256-thread block per row, row cached in registers (dim <= 8192, dim % 8 == 0)
@@ -187,8 +188,8 @@ hipError_t launch_rmsnorm(const void* x, int x_f32, int ldx, const float* w, flo
 // V placement for multi-token groups (prefill): lanes = 64 CONSECUTIVE TOKENS of one (batch element, kv head), a wave = one
 // 8-wide d chunk of them. Each lane reads its token's 16 bytes; each of the eight stores then writes 64 consecutive tokens of
 // one V^T row = one 128-byte line, where the (row, head)-per-wave form writes one 2-byte element into each of 64 lines.
-__device__ __forceinline__ bool rope_v_tokens(const cover_rope_args& a) { return a.T >= 16 && a.n_splits <= 0 && (a.D & 7) == 0 && (a.ld_qkv & 7) == 0 && (((uintptr_t)a.qkv) & 15) == 0; }
-__device__ __forceinline__ int rope_v_waves(const cover_rope_args& a) { return a.B * a.Hkv * (a.D >> 3) * ((a.T + 63) >> 6); }
+__host__ __device__ __forceinline__ bool rope_v_tokens(const cover_rope_args& a) { return a.T >= 16 && a.n_splits <= 0 && (a.D & 7) == 0 && (a.ld_qkv & 7) == 0 && (((uintptr_t)a.qkv) & 15) == 0; }
+__host__ __device__ __forceinline__ int rope_v_waves(const cover_rope_args& a) { return a.B * a.Hkv * (a.D >> 3) * ((a.T + 63) >> 6); }
 __device__ __forceinline__ void rope_v_body(const cover_rope_args& a, int wid) {
     const int lane = threadIdx.x & 63;
     const int tg = (a.T + 63) >> 6, dch = a.D >> 3;
@@ -212,7 +213,7 @@ __device__ __forceinline__ void rope_v_body(const cover_rope_args& a, int wid) {
 // q / k heads of multi-token groups, vectorised: a lane owns 8 consecutive elements of BOTH halves of one (row, head) -- two 16-byte
 // loads, the 2 x 32 bytes of its cos / sin entries, two 16-byte stores -- so a wave rotates 64 / (D / 16) heads instead of one
 // (prefill of a 7B decoder, 448 rows x 64 q / k heads: 28 672 one-head waves of 2-byte accesses were 5 rounds of resident waves, each a
-// chain of three dependent loads). Same per-element arithmetic as the scalar body below.
+// chain of three dependent loads).
 __host__ __device__ __forceinline__ bool rope_qk_vec(const cover_rope_args& a) {
     return a.T >= 16 && a.n_splits <= 0 && (a.ld_qkv & 7) == 0 && (((uintptr_t)a.qkv) & 15) == 0 && (a.D == 64 || a.D == 128 || a.D == 256) &&
            a.rope_mode != 0 && (((uintptr_t)a.cos_table | (uintptr_t)a.sin_table) & 15) == 0 &&
@@ -234,8 +235,7 @@ __device__ __forceinline__ void rope_qk_vec_body(const cover_rope_args& a, int w
         const int tt = a.t_offset + (a.t_offset_of_batch ? a.t_offset_of_batch[b] : 0) + t;
         dst = (bf16_t*)a.k_cache + (size_t)slot * a.k_slot_stride + (size_t)tt * a.k_t_stride + (size_t)(hh - a.Hq) * a.k_h_stride;
     }
-    int pos = a.positions ? a.positions[row] : t;
-    pos = pos < 0 ? 0 : (pos >= a.n_pos ? a.n_pos - 1 : pos);
+    const int pos = rope_clamp_pos(a.positions ? a.positions[row] : t, a.n_pos);
     const float* ct = a.cos_table + (size_t)pos * half + c * 8;
     const float* sn = a.sin_table + (size_t)pos * half + c * 8;
     const uint4 u1 = *(const uint4*)(src + c * 8), u2 = *(const uint4*)(src + half + c * 8);
@@ -247,16 +247,7 @@ __device__ __forceinline__ void rope_qk_vec_body(const cover_rope_args& a, int w
     for (int e = 0; e < 8; ++e) {
         const float x1 = __uint_as_float((e & 1) ? (w1[e >> 1] & 0xffff0000u) : (w1[e >> 1] << 16));
         const float x2 = __uint_as_float((e & 1) ? (w2[e >> 1] & 0xffff0000u) : (w2[e >> 1] << 16));
-        float cc = cv[e], ss = sv[e];
-        if (a.rope_mode == 2) {  // HF rotate_half in bf16 arithmetic
-            cc = bfround(cc); ss = bfround(ss);
-            o1[e] = bfround(bfround(x1 * cc) + bfround(-x2 * ss));
-            o2[e] = bfround(bfround(x2 * cc) + bfround(x1 * ss));
-        } else {  // apply_rope (paligemma_with_expert.py:34-57): fp32, one rounding
-#pragma clang fp contract(off)   // torch rounds each product: no FMA here
-            o1[e] = x1 * cc - x2 * ss;
-            o2[e] = x2 * cc + x1 * ss;
-        }
+        rope_rotate(a.rope_mode, x1, x2, cv[e], sv[e], o1[e], o2[e]);
     }
     uint4 r1, r2;
     r1.x = pack_bf2(o1[0], o1[1]); r1.y = pack_bf2(o1[2], o1[3]); r1.z = pack_bf2(o1[4], o1[5]); r1.w = pack_bf2(o1[6], o1[7]);
@@ -297,10 +288,7 @@ __device__ __forceinline__ void rope_kv_body(const cover_rope_args& a, int wid) 
     const size_t pstride = (size_t)rows * ncols;
     auto ld = [&](int d) -> float {
         if (a.n_splits <= 0) return bf2f(src[d]);
-        float v = 0.f;
-        for (int s = 0; s < a.n_splits; ++s) v += a.partial[s * pstride + pbase + d];
-        if (a.bias) v += a.bias[hh * a.D + d];
-        return bfround(v);
+        return qkv_fold(a.n_splits, [&](int s) { return a.partial[s * pstride + pbase + d]; }, a.bias != nullptr, [&] { return a.bias[hh * a.D + d]; });
     };
 
     if (hh >= a.Hq + a.Hkv) {  // V head -> transposed cache
@@ -319,22 +307,13 @@ __device__ __forceinline__ void rope_kv_body(const cover_rope_args& a, int wid) 
             for (int d = lane; d < a.D; d += 64) dst[d] = f2bf(ld(d));
         return;
     }
-    int pos = a.positions ? a.positions[row] : t;
-    pos = pos < 0 ? 0 : (pos >= a.n_pos ? a.n_pos - 1 : pos);
+    const int pos = rope_clamp_pos(a.positions ? a.positions[row] : t, a.n_pos);
     const float* ct = a.cos_table + (size_t)pos * half;
     const float* stb = a.sin_table + (size_t)pos * half;
     for (int i = lane; i < half; i += 64) {
         const float x1 = ld(i), x2 = ld(i + half);
-        float c = ct[i], s = stb[i], o1, o2;
-        if (a.rope_mode == 2) {  // HF rotate_half in bf16 arithmetic
-            c = bfround(c); s = bfround(s);
-            o1 = bfround(bfround(x1 * c) + bfround(-x2 * s));
-            o2 = bfround(bfround(x2 * c) + bfround(x1 * s));
-        } else {  // apply_rope (paligemma_with_expert.py:34-57): fp32, one rounding
-#pragma clang fp contract(off)   // torch rounds each product: no FMA here
-            o1 = x1 * c - x2 * s;
-            o2 = x2 * c + x1 * s;
-        }
+        float o1, o2;
+        rope_rotate(a.rope_mode, x1, x2, ct[i], stb[i], o1, o2);
         dst[i] = f2bf(o1);
         dst[i + half] = f2bf(o2);
     }
@@ -352,11 +331,10 @@ static bool rope_args_ok(const cover_rope_args* a) {
     return a->vt_cache && !(a->D & 1) && (a->rope_mode == 0 || (a->cos_table && a->sin_table));
 }
 static long long rope_waves_host(const cover_rope_args* a) {
-    const bool vt = a->T >= 16 && a->n_splits <= 0 && (a->D & 7) == 0 && (a->ld_qkv & 7) == 0 && (((uintptr_t)a->qkv) & 15) == 0;
-    if (!vt) return (long long)a->B * a->T * (a->Hq + 2 * a->Hkv);
+    if (!rope_v_tokens(*a)) return (long long)a->B * a->T * (a->Hq + 2 * a->Hkv);
     const long long ipw = rope_qk_vec(*a) ? 64 / (a->D >> 4) : 1;
     const long long qk_waves = (a->rope_mode == 0 && !a->k_cache) ? 0 : ((long long)a->B * a->T * (a->Hq + a->Hkv) + ipw - 1) / ipw;
-    return qk_waves + (long long)a->B * a->Hkv * (a->D >> 3) * ((a->T + 63) >> 6);
+    return qk_waves + rope_v_waves(*a);
 }
 hipError_t launch_rope_kv_write_pair(const cover_rope_args* a0, const cover_rope_args* a1, hipStream_t st) {
     const long long w0 = rope_waves_host(a0), w1 = rope_waves_host(a1);
@@ -370,8 +348,7 @@ hipError_t launch_rope_kv_write_pair(const cover_rope_args* a0, const cover_rope
 hipError_t launch_rope_kv_write(const cover_rope_args* a, hipStream_t st) {
     const long long waves = rope_waves_host(a);
     if (waves <= 0) return hipSuccess;
-    if (!a->vt_cache || (a->D & 1)) return hipErrorInvalidValue;
-    if (a->rope_mode != 0 && (!a->cos_table || !a->sin_table)) return hipErrorInvalidValue;
+    if (!rope_args_ok(a)) return hipErrorInvalidValue;
     const int blocks = (int)((waves + 3) / 4);
     hipLaunchKernelGGL(rope_kv_write_k, dim3(blocks), dim3(256), 0, st, *a);
     return hipGetLastError();

@@ -296,6 +296,13 @@ def attention_pair_plan(a0: "L.AttnArgs", a1: "L.AttnArgs") -> bool:
     return bool(dual.value)
 
 
+def _fill_rope(a, positions, cos, sin, rope_mode) -> None:
+    """the position / table fields that the rope, fused-decode and own-token argument structs share"""
+    a.positions, a.cos_table, a.sin_table = _ptr(positions), _ptr(cos), _ptr(sin)
+    a.n_pos = cos.shape[0] if cos is not None else 0
+    a.rope_mode = rope_mode
+
+
 def decode_attention_fused(qkv, N, H, D, scale, segments, write_t, out, *, positions=None, cos=None, sin=None, rope_mode=0,
                            partial=None, bias=None):
     """RoPE + KV append + [shared | per-prompt | own] attention for one new token per candidate, one launch."""
@@ -305,9 +312,7 @@ def decode_attention_fused(qkv, N, H, D, scale, segments, write_t, out, *, posit
     if partial is not None:
         a.n_splits, a.partial, a.bias = partial.shape[0], partial.data_ptr(), _ptr(bias)
     a.N, a.H, a.D, a.scale = N, H, D, scale
-    a.positions, a.cos_table, a.sin_table = _ptr(positions), _ptr(cos), _ptr(sin)
-    a.n_pos = cos.shape[0] if cos is not None else 0
-    a.rope_mode = rope_mode
+    _fill_rope(a, positions, cos, sin, rope_mode)
     for i, sg in enumerate(segments):
         fill_segment(a.seg[i], sg)
     a.write_t = write_t
@@ -325,9 +330,7 @@ def decode_own_attention(qkv, N, H, D, scale, k_own, v_own, t_cap, write_t, stat
     a = L.OwnAttnArgs()
     a.qkv, a.ld_qkv = qkv.data_ptr(), qkv.stride(0)
     a.N, a.H, a.D, a.scale = N, H, D, scale
-    a.positions, a.cos_table, a.sin_table = _ptr(positions), _ptr(cos), _ptr(sin)
-    a.n_pos = cos.shape[0] if cos is not None else 0
-    a.rope_mode = rope_mode
+    _fill_rope(a, positions, cos, sin, rope_mode)
     a.k, a.v = k_own.data_ptr(), v_own.data_ptr()
     a.fp8 = 1 if k_own.dtype == torch.uint8 else 0
     a.k_scale, a.v_scale = _ptr(k_scale), _ptr(v_scale)
@@ -386,10 +389,7 @@ def rope_args(qkv, B, T, Hq, Hkv, D, *, positions=None, cos=None, sin=None, rope
         assert bias is None, "bias is part of the split-K fold: it needs partial"
     a.qkv, a.ld_qkv = qkv.data_ptr(), qkv.stride(0)
     a.B, a.T, a.Hq, a.Hkv, a.D = B, T, Hq, Hkv, D
-    a.positions = _ptr(positions)
-    a.cos_table, a.sin_table = _ptr(cos), _ptr(sin)
-    a.n_pos = cos.shape[0] if cos is not None else 0
-    a.rope_mode = rope_mode
+    _fill_rope(a, positions, cos, sin, rope_mode)
     a.k_cache = None if k_cache is None else k_cache.data_ptr() + 2 * k_offset
     a.k_slot_stride, a.k_t_stride, a.k_h_stride = k_strides
     a.vt_cache = vt_cache.data_ptr() + 2 * vt_offset

@@ -585,7 +585,9 @@ def rope_fallbacks():
 
 
 def rope_folds():
-    return [rope_case(T, 64, mode, heads=(4, 2), B=B, pos="clamp", S=S, bias=bias, cache_pad=True, tag=f"fold_S{S}" + ("_bias" if bias else ""))
+    """S = 6: more slabs than the four that the fused decode launch holds in registers (its fold is compared with rope_kv_write's)"""
+    many = [rope_case(1, 64, mode, heads=(4, 2), B=5, pos="clamp", S=6, bias=True, cache_pad=True, tag="fold_S6_bias") for mode in (0, 2)]
+    return many + [rope_case(T, 64, mode, heads=(4, 2), B=B, pos="clamp", S=S, bias=bias, cache_pad=True, tag=f"fold_S{S}" + ("_bias" if bias else ""))
             for (T, B) in ((1, 5), (24, 2)) for mode in (0, 2) for S in (1, 3) for bias in (False, True)]
 
 

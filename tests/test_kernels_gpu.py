@@ -838,6 +838,15 @@ def test_decode_attention_fused_matches_three_launch_path(dev, D, H, N, write_t,
     _decode_attention_case(dev, D, H, N, write_t, mode, from_partials, permute_slots=False)
 
 
+@pytest.mark.parametrize("D,H", [(128, 8), (64, 4)])
+@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("n_splits", [1, 4, 6])
+def test_decode_attention_fused_folds_any_number_of_slabs(dev, D, H, mode, n_splits):
+    """The QKV GEMM hands over up to 8 split-K slabs: one, exactly the four the kernel holds in registers, and more than four (read in a
+    loop). N = 21: a partly filled second candidate tile. Appended K / V^T bit-equal to rope_kv_write folding the same slabs."""
+    _decode_attention_case(dev, D, H, 21, 3, mode, True, permute_slots=False, n_splits=n_splits)
+
+
 def test_decode_attention_fused_at_many_units_with_long_own_segments(dev):
     """The regime where cover_decoder_forward switches from the fused launch to the three-launch path (>= 768 (tile, head) units and
     > 16 own keys, BASELINE config 5): both paths must agree there too. N = 400 candidates x 32 heads, 20 own keys."""
@@ -970,14 +979,14 @@ def test_decode_own_attention_chain_matches_fp32_torch(dev, D, H, N, S, steps, m
             assert rel_l2(o, e) < 8e-3 and (o - e).abs().max() < 4e-2, (t, rel_l2(o, e), (o - e).abs().max())
 
 
-def _decode_attention_case(dev, D, H, N, write_t, mode, from_partials, permute_slots, slot_pattern="grouped", check_fp32=False):
+def _decode_attention_case(dev, D, H, N, write_t, mode, from_partials, permute_slots, slot_pattern="grouped", check_fp32=False, n_splits=3):
     # one launch (RoPE + KV append + [shared | per-prompt | own] attention) == rope_kv_write + attention over 3 segments
     # (N = 144: more than 128 (candidate tile, head) units for H = 8, i.e. the unsplit VS = 1 variant; fewer: VS = 2)
     T0, T1, cap2, npos = 257, 24, 32, 320
     g = torch.Generator().manual_seed(1000 * N + 10 * write_t + mode)
     ncol = 3 * H * D
     if from_partials:
-        part = torch.randn(3, N, ncol, generator=g) * 0.6
+        part = torch.randn(n_splits, N, ncol, generator=g) * 0.6
         bias = torch.randn(ncol, generator=g) * 0.1
         qkv = bf(part.sum(0) + bias)
     else:

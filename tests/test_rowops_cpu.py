@@ -267,7 +267,8 @@ def test_case_tables_reach_every_path_and_cell():
     for aligned, others in R.rope_fallbacks():
         assert R.rope_path(aligned) == "vtok_vecqk"
         assert [R.rope_path(c) for c in others] == ["scalar", "scalar", "vtok_scalarqk", "vtok_scalarqk"]
-    assert all(R.rope_path(c) == "scalar" for c in R.rope_folds()) and len(R.rope_folds()) == 16
+    assert all(R.rope_path(c) == "scalar" for c in R.rope_folds()) and len(R.rope_folds()) == 18
+    assert sorted({c["S"] for c in R.rope_folds()}) == [1, 3, 6]                  # one slab, the product's three, more than four
     for name, c0, c1 in R.rope_pairs():
         w = [R.rope_waves(c0), R.rope_waves(c1)]
         assert sorted(w) in ([14, 25], [0, 14], [0, 25]) and all(x % 4 for x in w if x)
