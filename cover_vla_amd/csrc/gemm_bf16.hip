@@ -1,1407 +1,17 @@
-// bf16 GEMM kernels for gfx950: C[M,N] = epi(A[M,K] . W[N,K]^T), fp32 accumulate on v_mfma_f32_16x16x32_bf16.
-//
-// Weight layout (cover_pack_weight_bf16): Wp[nb = n/16][kb = k/32][lane = (n%16) + 16*((k%32)/8)][8 bf16]
-//   -> one 16x32 block = 1 KiB contiguous = exactly the MFMA operand of one wave, lane-linear.
-// Operands are SWAPPED (first MFMA operand = weight fragment, second = activation fragment), so the
-// accumulator of lane (r = lane&15, g = lane>>4) holds C[m = r][n = 4g .. 4g+3]: four consecutive output
-// columns per lane -> 8/16-byte epilogue stores, bias/residual loads are vector loads too.
-//
-// Two kernels:
-//   gemm_tiled   128x128x64 tile, 4 waves (2x2), LDS double buffer. A tile staged with an XOR chunk swizzle
-//                (conflict-free ds_read_b128), W tile staged lane-linear straight from the packed layout.
-//                Staging either async global->LDS (global_load_lds, 16 B/lane) or through registers.
-//   gemm_skinny  M <= 64 (decode / denoise steps): HBM-bound weight streaming. The activation K-chunk lives in
-//                LDS in fragment-major form, every wave streams whole 1 KiB weight blocks straight into VGPRs
-//                (no LDS round trip for the streamed operand), split-K over grid.y with fp32 partials that a
-//                small reduce kernel folds together with the epilogue.
+// bf16 GEMM for gfx950, the entry point: C[M,N] = epi(A[M,K] . W[N,K]^T). launch_gemm_bf16 asks the planner for a GemmPlan, hands it to the
+// kernel family the plan names, and completes a split-K launch. No kernel lives here:
+//   gemm_plan.hip    plan_gemm: which family, tile, grid and K split, and what completes it (host only)
+//   gemm_pack.hip    the packed weight layout every family reads, its packers, the e4m3 row quantiser
+//   gemm_stream.hip  weight streaming, M <= 64: gemm_skinny / gemm_skinny2 / gemm_skinny3 (GK_SKINNY*), launch_gemm_skinny_partial
+//   gemm_tiled.hip   LDS-tiled: gemm_tiled / gemm_tiled_pc (GK_TILED / GK_TILED_PC)
+//   gemm_v3.hip      self-loading 8-wave tiles (GK_V3)
+//   gemm_fp8.hip     tiles on the MX-scaled fp8 matrix instruction (GK_F8_PC / GK_F8_V3)
+//   gemm_reduce.hip  split-K completions: splitk_reduce / splitk_reduce_norm, the norm as its own launch
+//   gemm_common.h    the epilogue shared by all of them, GemmPlan, launch_kernel, and the declarations of the launchers used here
 #include <hip/hip_ext.h>
 #include "common.h"
 #include "kernels.h"
-
-#ifdef COVER_PC_DEBUG
-__device__ unsigned long long g_pc_tl[1024 * 8];   // per block (thread 0): start, loop start, loop end, end, epilogue stamps (100 MHz wall clock)
-#define PCTL(slot) do { if (threadIdx.x == 0) g_pc_tl[((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define PCTL(slot) do { } while (0)
-#endif
-
 #include "gemm_common.h"
-
-
-// ---------------------------------------------------------------------------------------------------
-// Tiled kernel: tile = (2*WM*16) x (2*WN*16) x 64, 4 waves in 2x2, each wave WM x WN MFMA fragments.
-//   <4,4> 128x128 (large GEMMs), <2,4> 64x128, <2,2> 64x64 (ViT-sized GEMMs whose 128x128 grid cannot fill 256 CUs).
-// Optional split-K over gridDim.y: slice s accumulates k-tiles [s*kt_per, ...) and stores raw fp32 partials
-// [S][M][N] that splitk_reduce folds with the epilogue.
-// ---------------------------------------------------------------------------------------------------
-
-template <int WM, int WN, bool GLDS, int NST_ = 2, int WGM = 2, int WGN = 2>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_tiled(const bf16_t* __restrict__ A, int lda,
-                                                  const bf16_t* __restrict__ Wp, void* C, int ldc, int M, int N,
-                                                  int Kp, EpiDev epi, int tiles_m, int tiles_n, int kt_per,
-                                                  float* __restrict__ partial) {
-    constexpr int NW = WGM * WGN;                // waves: a WGM x WGN grid of (WM*16) x (WN*16) wave tiles
-    constexpr int BM_ = WGM * WM * 16, BN_ = WGN * WN * 16;
-    constexpr int A_BYTES = BM_ * BK * 2, B_BYTES = BN_ * BK * 2;
-    constexpr int AI = BM_ / (8 * NW), BI = BN_ / (8 * NW);  // 1-KiB staging instructions per wave per tile
-    constexpr int NST = GLDS ? NST_ : 2;         // LDS stages (NST - 1 k-tiles stay in flight across the barrier)
-    PCTL(0);
-    static_assert(BM_ % (8 * NW) == 0 && BN_ % (8 * NW) == 0, "tile rows must split evenly over the waves");
-    static_assert((NST - 2) * (AI + BI) <= 63, "counted vmcnt must fit its 6-bit field");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* As = smem;                   // [NST][A_BYTES]
-    char* Bs = smem + NST * A_BYTES;   // [NST][B_BYTES]
-
-    // XCD-aware bijective remap of the linear block id: blocks dispatched round-robin over the 8 XCDs get a
-    // contiguous range of tiles each, so the m-tiles that share one weight tile hit the same L2.
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        bid = base + (bid >> 3);
-    }
-    const int tn = bid / tiles_m, tm = bid % tiles_m;
-    const int m0 = tm * BM_, n0 = tn * BN_;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = w / WGN, wn = w % WGN;
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-    const int nk_total = Kp / BK;
-    const int kt0 = blockIdx.y * kt_per;
-    const int nk = min(kt_per, nk_total - kt0);
-
-    // ---- staging addresses ----
-    // A: LDS chunk position p = j*64 + lane: row = p>>3, c = p&7 holds global chunk c ^ (row&7)
-    const bf16_t* a_src[AI];
-    const bf16_t* b_src[BI];
-#pragma unroll
-    for (int i = 0; i < AI; ++i) {
-        const int j = w * AI + i;
-        const int row = j * 8 + (lane >> 3), c = lane & 7;
-        int gr = m0 + row;
-        gr = gr < M ? gr : M - 1;
-        a_src[i] = A + (size_t)gr * lda + (size_t)kt0 * BK + ((c ^ (row & 7)) << 3);
-    }
-#pragma unroll
-    for (int i = 0; i < BI; ++i) {
-        const int j = w * BI + i;
-        const int nbi = j >> 1, kbi = j & 1;
-        int nb = (n0 >> 4) + nbi;
-        nb = nb < N16 ? nb : N16 - 1;
-        b_src[i] = Wp + ((size_t)nb * K32 + (size_t)kt0 * 2 + kbi) * 512 + lane * 8;
-    }
-
-    f32x4 acc[WN][WM];  // [n-block b][m-frag f]
-#pragma unroll
-    for (int b = 0; b < WN; ++b)
-#pragma unroll
-        for (int f = 0; f < WM; ++f) acc[b][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    uint4 ra[AI], rb[BI];
-    const uint32_t as_u32 = __builtin_amdgcn_readfirstlane(lds_addr_u32(As) + w * AI * 1024);
-    const uint32_t bs_u32 = __builtin_amdgcn_readfirstlane(lds_addr_u32(Bs) + w * BI * 1024);
-    auto stage_glds = [&](int buf, int kt) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) glds16_asm(a_src[i] + kt * BK, as_u32 + buf * A_BYTES + i * 1024);
-#pragma unroll
-        for (int i = 0; i < BI; ++i) glds16_asm(b_src[i] + (size_t)kt * 2 * 512, bs_u32 + buf * B_BYTES + i * 1024);
-    };
-    auto stage_load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) ra[i] = *(const uint4*)(a_src[i] + kt * BK);
-#pragma unroll
-        for (int i = 0; i < BI; ++i) rb[i] = *(const uint4*)(b_src[i] + (size_t)kt * 2 * 512);
-    };
-    auto stage_write = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) *(uint4*)(As + buf * A_BYTES + (w * AI + i) * 1024 + lane * 16) = ra[i];
-#pragma unroll
-        for (int i = 0; i < BI; ++i) *(uint4*)(Bs + buf * B_BYTES + (w * BI + i) * 1024 + lane * 16) = rb[i];
-    };
-    const int r = lane & 15, g = lane >> 4;
-    auto compute = [&](int buf) {
-        const char* Ab = As + buf * A_BYTES;
-        const char* Bb = Bs + buf * B_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xf[WM], wf[WN];
-#pragma unroll
-            for (int f = 0; f < WM; ++f) {
-                const int row = wm * (WM * 16) + f * 16 + r;
-                const int c = (ks * 4 + g) ^ (row & 7);
-                xf[f] = as_bf16x8(*(const uint4*)(Ab + (row * 8 + c) * 16));
-            }
-#pragma unroll
-            for (int b = 0; b < WN; ++b)
-                wf[b] = as_bf16x8(*(const uint4*)(Bb + (((wn * WN + b) * 2 + ks) * 64 + lane) * 16));
-#pragma unroll
-            for (int b = 0; b < WN; ++b)
-#pragma unroll
-                for (int f = 0; f < WM; ++f)
-                    acc[b][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[b], xf[f], acc[b][f], 0, 0, 0);
-        }
-    };
-
-    PCTL(1);
-    if (GLDS) {
-        // 3-stage ring, two k-tiles in flight: tile kt is waited for with a COUNTED vmcnt (the AI+BI loads of tile kt+1
-        // stay outstanding across the barrier), a raw s_barrier publishes it, then tile kt+2 is issued into the stage
-        // that compute(kt-1) has just released. __syncthreads() would drain vmcnt to 0 here.
-        if (NST >= 3) {
-            // NST-stage ring, NST-1 k-tiles in flight: tile kt is waited for with a COUNTED vmcnt (the loads of the younger
-            // tiles stay outstanding across the barrier), a raw s_barrier publishes it, then tile kt+NST-1 is issued
-            // into the stage that compute(kt-1) has just released. __syncthreads() would drain vmcnt to 0 here.
-#pragma unroll
-            for (int s = 0; s < NST - 1; ++s)
-                if (s < nk) stage_glds(s, s);
-            int cur = 0;
-            for (int kt = 0; kt < nk; ++kt) {
-                const int younger = nk - 1 - kt;   // tiles issued after kt that may stay in flight
-                if (NST >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (AI + BI)) : "memory");
-                else if (younger >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AI + BI) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (kt + NST - 1 < nk) stage_glds(cur == 0 ? NST - 1 : cur - 1, kt + NST - 1);  // stage (kt-1) % NST
-                compute(cur);
-                cur = cur == NST - 1 ? 0 : cur + 1;
-            }
-        } else {  // 2 stages: smaller LDS footprint -> one more resident block per CU (better when L2->LDS bandwidth-bound)
-            stage_glds(0, 0);
-            for (int kt = 0; kt < nk; ++kt) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (kt + 1 < nk) stage_glds((kt + 1) & 1, kt + 1);
-                compute(kt & 1);
-            }
-        }
-    } else {
-        stage_load(0);
-        stage_write(0);
-        for (int kt = 0; kt < nk; ++kt) {
-            __syncthreads();
-            if (kt + 1 < nk) stage_load(kt + 1);
-            compute(kt & 1);
-            if (kt + 1 < nk) stage_write((kt + 1) & 1);
-        }
-    }
-
-    // ---- epilogue ----
-    PCTL(2);
-    tiled_epilogue_staged<WM, WN, BM_, BN_>(acc, epi, C, ldc, M, N, m0, n0, m0 + wm * (WM * 16), n0 + wn * (WN * 16), r, g, partial, smem,
-                                            NST * (A_BYTES + B_BYTES), tid, 64 * NW);
-    PCTL(3);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Producer / consumer variant of the tiled kernel: 4 MFMA waves (2 x 2) + NL loader waves per block.
-// Cycle counters in gemm_tiled's k-loop (64x128, M = 448) show an MFMA wave spending ~30 % of every k-tile ISSUING its
-// LDS-DMA instructions (the CU's address path is shared, and all waves issue right after their barriers) and ~40 %
-// waiting for the tile issued one iteration earlier. Here the loader waves own every LDS-DMA of the block (piece j of a
-// tile belongs to loader j mod NL) and run NST-1 k-tiles ahead with a counted vmcnt; the MFMA waves only pass one barrier
-// per k-tile and compute:
-//   loader:   wait (own pieces of tile kt landed) -> barrier kt -> issue tile kt+NST-1 into the stage of tile kt-1
-//   consumer: barrier kt sits in the MIDDLE of tile kt-1 (see the software pipeline below); a consumer reaching it holds
-//             every fragment of tile kt-1 in registers, so that stage is free
-// LDS-DMA data is ordered for the consumers by the loaders' vmcnt waits followed by the barrier they pass.
-// ---------------------------------------------------------------------------------------------------
-#ifdef COVER_PC_DEBUG
-__device__ unsigned long long g_pc_dbg[8];   // loader: wait, barrier, issue; consumer: barrier, rest; counts
-extern "C" int cover_pc_debug(unsigned long long* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_dbg), sizeof(g_pc_dbg)) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pc_dbg), z, sizeof(z)); }
-    return 0;
-}
-#define PCT() __builtin_readcyclecounter()
-extern "C" int cover_pc_timeline(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pc_tl), sizeof(g_pc_tl)); }
-#endif
-#ifdef COVER_PC_ABL
-// Ablation builds (tools/dbg/abl_prefill.sh, -DCOVER_PC_ABL=<bits>, compile-time): bit 0 = the MFMA waves skip their MFMAs, bit 1 = they
-// skip the LDS fragment reads, bit 2 = the loaders skip the weight pieces, bit 3 = the loaders skip the activation pieces.
-// Results are garbage by design. (A run-time flag trips a backend bug: "V_CMP_NE_U32 0, $src_shared_base: incorrect register class".)
-#define PC_ABL(bit) ((COVER_PC_ABL) & (bit))
-#else
-#define PC_ABL(bit) 0
-#endif
-template <int WM, int WN, int NST, int NL = 1, int CGM = 2, int CGN = 2>
-__global__ __launch_bounds__(64 * (CGM * CGN + NL)) void gemm_tiled_pc(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ Wp,
-                                                     void* C, int ldc, int M, int N, int Kp, EpiDev epi, int tiles_m,
-                                                     int tiles_n, int kt_per, float* __restrict__ partial) {
-    PCTL(0);
-    constexpr int NCW = CGM * CGN;                            // MFMA waves: a CGM x CGN grid of (WM*16) x (WN*16) wave tiles
-    constexpr int BM_ = CGM * WM * 16, BN_ = CGN * WN * 16;
-    constexpr int A_BYTES = BM_ * BK * 2, B_BYTES = BN_ * BK * 2;
-    constexpr int AT = A_BYTES / 1024, BT = B_BYTES / 1024;   // 1-KiB LDS-DMA instructions per k-tile (all by the loaders)
-    static_assert((NST - 2) * ((AT + BT) / NL) <= 63, "counted vmcnt must fit its 6-bit field");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* As = smem;                   // [NST][A_BYTES]
-    char* Bs = smem + NST * A_BYTES;   // [NST][B_BYTES]
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        bid = base + (bid >> 3);
-    }
-    const int tn = bid / tiles_m, tm = bid % tiles_m;
-    const int m0 = tm * BM_, n0 = tn * BN_;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-    const int nk_total = Kp / BK;
-    const int kt0 = blockIdx.y * kt_per;
-    const int nk = min(kt_per, nk_total - kt0);
-
-    if (w >= NCW) {   // ---------------- loader waves: NL of them, loader l owns the pieces j = l, l + NL, ... of every tile ----------------
-        // (one wave issues an LDS-DMA piece every ~60 cycles; the CU's vector memory path takes 1 KiB per 16 cycles, so a
-        // single loader caps the fill at a quarter of what the CU can pull)
-        constexpr int PT = (AT + BT) / NL;
-        static_assert((AT + BT) % NL == 0 && AT % NL == 0, "pieces must split evenly over the loader waves");
-        static_assert((NST - 2) * PT <= 63, "counted vmcnt must fit its 6-bit field");
-        const int l = w - NCW;
-        const bf16_t* src[PT];
-        uint32_t dst[PT];
-        size_t step[PT];
-        const uint32_t as_u32 = __builtin_amdgcn_readfirstlane(lds_addr_u32(As));
-        const uint32_t bs_u32 = __builtin_amdgcn_readfirstlane(lds_addr_u32(Bs));
-#pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            const int j = l + i * NL;
-            if (j < AT) {   // A: LDS chunk position p = j*64 + lane: row = p>>3, c = p&7 holds global chunk c ^ (row&7)
-                const int row = j * 8 + (lane >> 3), c = lane & 7;
-                int gr = m0 + row;
-                gr = gr < M ? gr : M - 1;
-                src[i] = A + (size_t)gr * lda + (size_t)kt0 * BK + ((c ^ (row & 7)) << 3);
-                dst[i] = as_u32 + j * 1024;
-                step[i] = BK;
-            } else {
-                const int jb = j - AT;
-                const int nbi = jb >> 1, kbi = jb & 1;
-                int nb = (n0 >> 4) + nbi;
-                nb = nb < N16 ? nb : N16 - 1;
-                src[i] = Wp + ((size_t)nb * K32 + (size_t)kt0 * 2 + kbi) * 512 + lane * 8;
-                dst[i] = bs_u32 + jb * 1024;
-                step[i] = 2 * 512;
-            }
-        }
-        // (Register-staged loaders -- plain global loads into two register sets, ds_write_b128 into a 2-stage ring -- were
-        // built and measured: 64x128 o_proj 45 -> 62 us, down 87 -> 151 us, 128x256 at M = 2624 831 -> 641 TF. The LDS-DMA
-        // piece stays, at 64-100 cycles of issue per wave: cycle counters (-DCOVER_PC_DEBUG, tools/exp_pc_debug.py) give per
-        // k-tile of the 128x256 kernel: loader issue 770-1200, data wait 70-100, barrier 270-500; MFMA wave: 900 compute +
-        // 540-690 at the barrier. s_setprio 3 on the loaders changes nothing.)
-        auto issue = [&](int buf, int kt) {
-#pragma unroll
-            for (int i = 0; i < PT; ++i) {
-                const bool is_a = (l + i * NL) < AT;
-                if (!((PC_ABL(4) && !is_a) || (PC_ABL(8) && is_a)))
-                    glds16_asm(src[i] + kt * step[i], dst[i] + buf * (is_a ? A_BYTES : B_BYTES));
-            }
-        };
-#pragma unroll
-        for (int s = 0; s < NST - 1; ++s)
-            if (s < nk) issue(s, s);
-        int cur = 0;
-#ifdef COVER_PC_DEBUG
-        unsigned long long tw = 0, tb = 0, ti = 0;
-#endif
-        for (int kt = 0; kt < nk; ++kt) {
-#ifdef COVER_PC_DEBUG
-            const unsigned long long c0 = PCT();
-#endif
-            const int younger = min(nk - 1 - kt, NST - 2);   // tiles issued after kt that may stay in flight
-            if (NST >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
-            else if (younger >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef COVER_PC_DEBUG
-            const unsigned long long c1 = PCT();
-#endif
-            __builtin_amdgcn_s_barrier();
-#ifdef COVER_PC_DEBUG
-            const unsigned long long c2 = PCT();
-#endif
-            if (kt + NST - 1 < nk) issue(cur == 0 ? NST - 1 : cur - 1, kt + NST - 1);   // stage (kt-1) % NST
-            cur = cur == NST - 1 ? 0 : cur + 1;
-#ifdef COVER_PC_DEBUG
-            const unsigned long long c3 = PCT();
-            tw += c1 - c0; tb += c2 - c1; ti += c3 - c2;
-#endif
-        }
-#ifdef COVER_PC_DEBUG
-        if (lane == 0 && l == 0) { atomicAdd(&g_pc_dbg[0], tw); atomicAdd(&g_pc_dbg[1], tb); atomicAdd(&g_pc_dbg[2], ti); atomicAdd(&g_pc_dbg[5], (unsigned long long)nk); }
-#endif
-        return;
-    }
-    // ---------------- MFMA waves ----------------
-    const int wm = w / CGN, wn = w % CGN;
-    const int r = lane & 15, g = lane >> 4;
-    f32x4 acc[WN][WM];  // [n-block b][m-frag f]
-#pragma unroll
-    for (int b = 0; b < WN; ++b)
-#pragma unroll
-        for (int f = 0; f < WM; ++f) acc[b][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // Software-pipelined over the two 32-wide k-steps of a tile: the fragments of the NEXT step (the next tile's first step
-    // after the mid-tile barrier) are read from LDS before the MFMAs of the current one, so a wave alone on its SIMD
-    // never exposes LDS latency or the barrier between its MFMA groups.
-    //   prologue: barrier 0, read(tile 0, step 0) -> set A
-    //   tile kt:  read(kt, 1) -> B | MFMA(A) | reads returned, barrier kt+1, read(kt+1, 0) -> A | MFMA(B)
-    // A consumer reaching barrier kt+1 holds every fragment of tile kt - 1 and of tile kt in registers (lgkmcnt drained), so
-    // the loader may refill stage (kt-1) % NST... and stage kt % NST is only refilled after barrier kt+2.
-    // The LDS reads are inline asm with hand-counted lgkmcnt waits (the compiler's own bookkeeping drains lgkmcnt to 0
-    // before the first MFMA of a group, i.e. it also waits for the fragments just requested for the NEXT group).
-    const uint32_t a_addr0 = lds_addr_u32(As) + ((wm * (WM * 16) + r) * 8 + ((0 * 4 + g) ^ (r & 7))) * 16;
-    const uint32_t a_addr1 = lds_addr_u32(As) + ((wm * (WM * 16) + r) * 8 + ((1 * 4 + g) ^ (r & 7))) * 16;
-    const uint32_t b_addr = lds_addr_u32(Bs) + (wn * WN * 2 * 64 + lane) * 16;
-    auto read_frags = [&](int stage, int ks, u32x4(&xf)[WM], u32x4(&wf)[WN]) {
-        const uint32_t aa = (ks ? a_addr1 : a_addr0) + stage * A_BYTES;
-        const uint32_t ba = b_addr + stage * B_BYTES + ks * 1024;
-        if (!PC_ABL(2)) {
-#pragma unroll
-            for (int f = 0; f < WM; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xf[f]) : "v"(aa), "n"(f * 2048));
-#pragma unroll
-            for (int b = 0; b < WN; ++b) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[b]) : "v"(ba), "n"(b * 2048));
-        }
-    };
-    auto landed = [&](u32x4(&xf)[WM], u32x4(&wf)[WN]) {   // ties the fragments to the wait that precedes this call
-#pragma unroll
-        for (int f = 0; f < WM; ++f) asm volatile("" : "+v"(xf[f]));
-#pragma unroll
-        for (int b = 0; b < WN; ++b) asm volatile("" : "+v"(wf[b]));
-    };
-    auto mfmas = [&](const u32x4(&xf)[WM], const u32x4(&wf)[WN]) {
-        if (!PC_ABL(1)) {
-#pragma unroll
-            for (int b = 0; b < WN; ++b)
-#pragma unroll
-                for (int f = 0; f < WM; ++f)
-                    acc[b][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[b]), __builtin_bit_cast(bf16x8, xf[f]), acc[b][f], 0, 0, 0);
-        }
-    };
-#ifdef COVER_PC_ABL
-    u32x4 xa[WM] = {}, wa[WN] = {}, xb[WM] = {}, wb[WN] = {};   // (the read-skipping arm multiplies whatever is here)
-#else
-    u32x4 xa[WM], wa[WN], xb[WM], wb[WN];
-#endif
-    int cur = 0;
-#if defined(COVER_PC_PRIO) && COVER_PC_PRIO
-    __builtin_amdgcn_s_setprio(COVER_PC_PRIO);   // experiment: static issue priority for the MFMA waves over the loader waves (guide T5, static form)
-#endif
-    __builtin_amdgcn_s_barrier();
-    PCTL(1);
-#ifdef COVER_PC_DEBUG
-    unsigned long long dbg_bar = 0;
-    const unsigned long long dbg_t0 = PCT();
-    const unsigned long long dbg_w0 = wall_clock64();
-#endif
-    read_frags(0, 0, xa, wa);
-    for (int kt = 0; kt < nk; ++kt) {
-        read_frags(cur, 1, xb, wb);
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(WM + WN));   // set A (older) has landed, set B stays in flight
-        landed(xa, wa);
-        mfmas(xa, wa);
-        __builtin_amdgcn_sched_barrier(0);
-        cur = cur == NST - 1 ? 0 : cur + 1;
-        if (kt + 1 < nk) {
-#ifdef COVER_PC_DEBUG
-            const unsigned long long c0 = PCT();
-#endif
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef COVER_PC_DEBUG
-            dbg_bar += PCT() - c0;
-#endif
-            read_frags(cur, 0, xa, wa);
-            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(WM + WN));
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)");
-        }
-        landed(xb, wb);
-        mfmas(xb, wb);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#ifdef COVER_PC_DEBUG
-    if (lane == 0 && w == 0) { atomicAdd(&g_pc_dbg[3], dbg_bar); atomicAdd(&g_pc_dbg[4], PCT() - dbg_t0); atomicAdd(&g_pc_dbg[6], wall_clock64() - dbg_w0); }
-#endif
-    PCTL(2);
-    tiled_epilogue_staged<WM, WN, BM_, BN_>(acc, epi, C, ldc, M, N, m0, n0, m0 + wm * (WM * 16), n0 + wn * (WN * 16), r, g, partial, smem,
-                                            NST * (A_BYTES + B_BYTES), tid, 64 * NCW);
-    PCTL(3);
-}
-
-// k offset (inside a 64-aligned chunk) of the 8-wide run that lane group gg multiplies in 32-deep step kst. The bf16 image and the default e4m3
-// image hold k = 32 kst + 8 gg there; the k-linear e4m3 image (cover_pack_weight_fp8_klinear: the 16 bytes of a lane in a 64-deep block are 16
-// CONSECUTIVE k -- the matrix instruction's own k order, in which an MX block scale covers 32 neighbouring columns) holds k = 64 (kst / 2) + 16 gg + 8 (kst % 2).
-template <bool W8>
-__device__ __forceinline__ int x_run_k(int kst, int gg, int kl) {
-    if constexpr (W8) return kl ? ((kst >> 1) << 6) + gg * 16 + (kst & 1) * 8 : kst * 32 + gg * 8;
-    else return kst * 32 + gg * 8;
-}
-
-// MFMA weight fragment of 32-deep step u of a 256-deep item: bf16 items hold it as loaded; e4m3 items (16 bytes per lane = the
-// 8-wide k runs of steps 2j and 2j + 1) are converted with v_cvt_scalef32_pk_bf16_fp8 (scale 1: exact, every e4m3 value is a
-// bf16 value)
-template <bool W8, int NLD>
-__device__ __forceinline__ bf16x8 wfrag(const u32x4 (&v)[NLD], int u) {
-    if constexpr (!W8) {
-        return __builtin_bit_cast(bf16x8, v[u]);
-    } else {
-        const u32x4 q = v[u >> 1];
-        const uint32_t lo = (u & 1) ? q.z : q.x, hi = (u & 1) ? q.w : q.y;
-        uint32_t o[4];
-        o[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
-        o[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
-        o[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
-        o[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
-        return __builtin_bit_cast(bf16x8, (u32x4){o[0], o[1], o[2], o[3]});
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Weight-streaming kernel (M <= 64)
-// ---------------------------------------------------------------------------------------------------
-// grid = (ceil(N16 / nb_per_block), S); block = 512 threads (8 waves). LDS = MF*16 rows x KC x 2 B, fragment-major:
-//   xs[ks][f][lane][16 B].  partial[s][m][n] fp32.
-template <int MF>
-__global__ __launch_bounds__(512) void gemm_skinny(const bf16_t* __restrict__ A, int lda,
-                                                   const bf16_t* __restrict__ Wp, float* __restrict__ partial, int M,
-                                                   int N, int Kp, int KC, int nb_per_block) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int s = blockIdx.y;
-    const int k0 = s * KC;
-    const int kc = min(KC, Kp - k0);  // multiple of 128
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-
-    // ---- stage the activation chunk: coalesced 16-B reads along k, scattered into fragment-major LDS ----
-    {
-        const int cpr = kc >> 3;  // 16-B chunks per row
-        const int total = MF * 16 * cpr;
-        for (int c = tid; c < total; c += 512) {
-            const int row = c / cpr, kc8 = c - row * cpr;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (row < M) v = *(const uint4*)(A + (size_t)row * lda + k0 + kc8 * 8);
-            const int ks = kc8 >> 2, gg = kc8 & 3, f = row >> 4, rr = row & 15;
-            *(uint4*)(smem + (((ks * MF + f) * 64) + rr + 16 * gg) * 16) = v;
-        }
-    }
-    __syncthreads();
-
-    const int nb_begin = blockIdx.x * nb_per_block;
-    const int nb_end = min(N16, nb_begin + nb_per_block);
-    const int nbatch = kc >> 7;  // batches of 4 k-steps (128 k)
-    const int r = lane & 15, g = lane >> 4;
-
-    // One continuous stream over (n-block, k-batch): loads run two batches (8 KiB per wave) ahead and keep flowing
-    // across n-block boundaries, so the HBM pipe never drains while a wave finishes one block of output columns.
-    const int n_nb = (nb_end - nb_begin - w + 7) / 8;  // n-blocks of this wave: nb_begin + w + 8*i
-    const int total = n_nb > 0 ? n_nb * nbatch : 0;
-    const u32x4* wbase = (const u32x4*)(Wp + ((size_t)(nb_begin + w) * K32 + (k0 >> 5)) * 512) + lane;
-    const size_t nb_stride = (size_t)8 * K32 * 64;  // u32x4 units between consecutive n-blocks of this wave
-    f32x4 acc[MF];
-#pragma unroll
-    for (int f = 0; f < MF; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 b0[4], b1[4], b2[4];
-    auto load4 = [&](u32x4(&dst)[4], int fidx) {
-        const int i = fidx / nbatch, b = fidx - i * nbatch;
-        const u32x4* src = wbase + (size_t)i * nb_stride + (size_t)b * 4 * 64;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) dst[u] = __builtin_nontemporal_load(src + u * 64);
-    };
-    auto comp4 = [&](u32x4(&src)[4], int fidx) {
-        const int i = fidx / nbatch, b = fidx - i * nbatch;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int ks = b * 4 + u;
-            const bf16x8 wf = __builtin_bit_cast(bf16x8, src[u]);
-#pragma unroll
-            for (int f = 0; f < MF; ++f) {
-                const bf16x8 xf = as_bf16x8(*(const uint4*)(smem + ((ks * MF + f) * 64 + lane) * 16));
-                acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[f], 0, 0, 0);
-            }
-        }
-        if (b == nbatch - 1) {  // finished this n-block's K-slice: partial[s][m][n], lane holds m = f*16 + r, n = nb*16 + 4g..
-            const int nb = nb_begin + w + 8 * i;
-#pragma unroll
-            for (int f = 0; f < MF; ++f) {
-                const int m = f * 16 + r;
-                const int n = nb * 16 + 4 * g;
-                if (m < M && n < N) {
-                    float* o = partial + ((size_t)s * M + m) * N + n;
-                    if (n + 3 < N && ((((uintptr_t)o) & 15) == 0)) {
-                        *(float4*)o = make_float4(acc[f][0], acc[f][1], acc[f][2], acc[f][3]);
-                    } else {
-                        for (int e = 0; e < 4; ++e)
-                            if (n + e < N) o[e] = acc[f][e];
-                    }
-                }
-                acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    };
-    if (total > 0) load4(b0, 0);
-    if (total > 1) load4(b1, 1);
-    for (int fi = 0; fi < total; fi += 3) {
-        if (fi + 2 < total) load4(b2, fi + 2);
-        comp4(b0, fi);
-        if (fi + 1 < total) {
-            if (fi + 3 < total) load4(b0, fi + 3);
-            comp4(b1, fi + 1);
-        }
-        if (fi + 2 < total) {
-            if (fi + 4 < total) load4(b1, fi + 4);
-            comp4(b2, fi + 2);
-        }
-    }
-}
-
-// out = epi(sum_s partial[s]) AND norm_out = rmsnorm(out) / layernorm(out): one 512-thread block per output row
-// (N % 8 == 0, N <= 8192, no GLU, bf16 output). The statistics are taken over the bf16-ROUNDED outputs, i.e. exactly what
-// the separate norm kernel would read back, with that kernel's arithmetic.
-// block sum of a 512-thread block through LDS with an LDS-ONLY barrier: __syncthreads() would also wait for the stores
-// of C still in flight (their acknowledgement is ~1 us on the critical path of a kernel that lasts ~6). `red` is written
-// once per call: a second call in the same kernel takes a different slice.
-__device__ __forceinline__ float block_sum_lds(float v, float* red) {
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t += red[i];
-    return t;
-}
-
-#ifdef COVER_RN_DEBUG
-__device__ unsigned long long g_rn_dbg[512 * 8];   // per block (thread 0): start, slabs landed, epilogue done, before / after the block sum, end
-extern "C" int cover_rn_debug(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rn_dbg), sizeof(g_rn_dbg)); }
-#define RNT(slot) do { if (threadIdx.x == 0) g_rn_dbg[(blockIdx.x & 511) * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define RNT(slot) do { } while (0)
-#endif
-#ifndef COVER_RN_RES_EARLY
-#define COVER_RN_RES_EARLY 1   // 0 = the operand loads BEHIND the slab sums (rounds 1-5), for A/B builds
-#endif
-// (one row by one 512-thread block; red = 16 floats of LDS)
-__device__ __forceinline__ void reduce_norm_row(const float* __restrict__ partial, int S, bf16_t* C, int ldc, int M, int N, const EpiDev& epi,
-                                                const int m, float* red) {
-    RNT(0);
-    float vals[2][8];
-    float q = 0.f;
-    // the norm weights do not depend on anything: requested first, so their latency hides under the slab loads instead
-    // of following the block reduction (the stores to C in between keep the compiler from hoisting them itself)
-    float4 nw[2][2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int n0 = (threadIdx.x + c * 512) * 8;
-        if (n0 < N) {
-            nw[c][0] = *(const float4*)(epi.norm_w + n0);
-            nw[c][1] = *(const float4*)(epi.norm_w + n0 + 4);
-        }
-    }
-    // Round 6: with a residual-only epilogue (decoder o_proj / down: x += slab sums, bf16 residual -- two of these launches per layer-step of
-    // every decode pass) the residual chunk is requested in the SAME batch as the first slab loads instead of by epi_value4 behind the slab
-    // sums: the kernel was two dependent memory round trips (slabs 1.1 us, residual 1.1 us of 3.6 us in the per-block timeline,
-    // tools/dbg/rn_timeline.py), now one: 3.6 -> 2.6 us in-kernel, headline 34.31 -> 33.49 ms over three same-box alternations
-    // (profiles/r06_reduce_residual_early_ab.txt). Same arithmetic and rounding points as epi_value4. A general form (bias / layer scale / fp32
-    // residual requested early through uniform branches) measured NO gain on the same decision: the branches cost what the round trip saves.
-    // (A round-2 note here said a 16-byte residual load AHEAD of the slabs had measured slower; behind the first slab batch it does not.)
-    const bool res_only = COVER_RN_RES_EARLY != 0 && epi.residual && !epi.res_f32 && !epi.bias && !epi.lscale && epi.act == ACT_NONE && epi.out_scale == 1.0f &&
-                          (N & 7) == 0 && (((uintptr_t)epi.residual) & 15) == 0 && ((epi.ldr * 2) & 15) == 0;
-#ifndef COVER_RN_BIAS_EARLY
-#define COVER_RN_BIAS_EARLY 1
-#endif
-    // the same for the ViT towers' proj / fc2 reductions (SigLIP, SigLIP2: bias + bf16 residual, no layer scale)
-    const bool res_bias = COVER_RN_BIAS_EARLY != 0 && !res_only && epi.residual && !epi.res_f32 && epi.bias && !epi.lscale && epi.act == ACT_NONE &&
-                          epi.out_scale == 1.0f && (N & 7) == 0 && (((uintptr_t)epi.residual) & 15) == 0 && ((epi.ldr * 2) & 15) == 0 &&
-                          (((uintptr_t)epi.bias) & 15) == 0;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int n0 = (threadIdx.x + c * 512) * 8;
-        if (n0 < N) {
-            float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const float* p0 = partial + (size_t)m * N + n0;
-            const size_t sstride = (size_t)M * N;
-            uint4 rr = make_uint4(0, 0, 0, 0);
-            float4 bq0 = make_float4(0.f, 0.f, 0.f, 0.f), bq1 = bq0;
-            const bf16_t* rsrc = (const bf16_t*)epi.residual + (size_t)m * epi.ldr + n0;
-            int s = 0;
-            for (; s + 4 <= S; s += 4) {  // four slices in flight
-                float4 a[4], b[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a[j] = *(const float4*)(p0 + (s + j) * sstride);
-                    b[j] = *(const float4*)(p0 + (s + j) * sstride + 4);
-                }
-                if (res_only && s == 0) rr = *(const uint4*)rsrc;
-                if (res_bias && s == 0) { rr = *(const uint4*)rsrc; bq0 = *(const float4*)(epi.bias + n0); bq1 = *(const float4*)(epi.bias + n0 + 4); }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[0] += a[j].x; v[1] += a[j].y; v[2] += a[j].z; v[3] += a[j].w;
-                    v[4] += b[j].x; v[5] += b[j].y; v[6] += b[j].z; v[7] += b[j].w;
-                }
-            }
-            for (; s < S; ++s) {
-                const float4 a = *(const float4*)(p0 + s * sstride), b = *(const float4*)(p0 + s * sstride + 4);
-                if (res_only && s == 0) rr = *(const uint4*)rsrc;      // (fewer than four slabs)
-                if (res_bias && s == 0) { rr = *(const uint4*)rsrc; bq0 = *(const float4*)(epi.bias + n0); bq1 = *(const float4*)(epi.bias + n0 + 4); }
-                v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
-            }
-            if (c == 0) RNT(1);
-            if (res_only) {   // epi_value4's arithmetic for a residual-only epilogue: bf16(sum) + residual
-                const uint32_t rw[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    v[2 * i] = bfround(v[2 * i]) + bf2f((bf16_t)(rw[i] & 0xffffu));
-                    v[2 * i + 1] = bfround(v[2 * i + 1]) + bf2f((bf16_t)(rw[i] >> 16));
-                }
-            } else if (res_bias) {   // bf16(sum + bias) + residual
-                const uint32_t rw[4] = {rr.x, rr.y, rr.z, rr.w};
-                const float bv[8] = {bq0.x, bq0.y, bq0.z, bq0.w, bq1.x, bq1.y, bq1.z, bq1.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    v[2 * i] = bfround(v[2 * i] + bv[2 * i]) + bf2f((bf16_t)(rw[i] & 0xffffu));
-                    v[2 * i + 1] = bfround(v[2 * i + 1] + bv[2 * i + 1]) + bf2f((bf16_t)(rw[i] >> 16));
-                }
-            } else {
-                epi_value4(epi, m, n0, N, v);
-                epi_value4(epi, m, n0 + 4, N, v + 4);
-            }
-            if (c == 0) RNT(2);
-            uint4 u;
-            u.x = pack_bf2(v[0], v[1]); u.y = pack_bf2(v[2], v[3]); u.z = pack_bf2(v[4], v[5]); u.w = pack_bf2(v[6], v[7]);
-            *(uint4*)(C + (size_t)m * ldc + n0) = u;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                vals[c][i] = bfround(v[i]);
-                q += vals[c][i] * vals[c][i];
-            }
-        }
-    }
-    float mean = 0.f, rstd;
-    if (epi.norm_style == 2) {   // LayerNorm (layernorm_bf16_k arithmetic: mean, then the centred second moment)
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-            if ((int)(threadIdx.x + c * 512) * 8 < N)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) sum += vals[c][i];
-        mean = block_sum_lds(sum, red) / N;
-        float q2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-            if ((int)(threadIdx.x + c * 512) * 8 < N)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float d = vals[c][i] - mean;
-                    q2 += d * d;
-                }
-        rstd = rsqrtf(block_sum_lds(q2, red + 8) / N + epi.norm_eps);
-    } else {
-        RNT(3);
-        rstd = rsqrtf(block_sum_lds(q, red) / N + epi.norm_eps);
-        RNT(4);
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int n0 = (threadIdx.x + c * 512) * 8;
-        if (n0 < N) {
-            float o[8];
-            const float wv[8] = {nw[c][0].x, nw[c][0].y, nw[c][0].z, nw[c][0].w, nw[c][1].x, nw[c][1].y, nw[c][1].z, nw[c][1].w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float ww = wv[i];
-                if (epi.norm_style == 2) o[i] = (vals[c][i] - mean) * rstd * ww + (epi.norm_b ? epi.norm_b[n0 + i] : 0.f);
-                else o[i] = epi.norm_style == 1 ? ww * bfround(vals[c][i] * rstd) : vals[c][i] * rstd * (epi.norm_w_offset + ww);
-            }
-            uint4 u;
-            u.x = pack_bf2(o[0], o[1]); u.y = pack_bf2(o[2], o[3]); u.z = pack_bf2(o[4], o[5]); u.w = pack_bf2(o[6], o[7]);
-            *(uint4*)(epi.norm_out + (size_t)m * epi.ld_norm_out + n0) = u;
-            if (epi.nq8) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) vals[c][i] = bfround(o[i]);   // the stored bf16 row is what gets quantised
-            }
-        }
-    }
-    if (epi.nq8) {   // e4m3 twin of the norm_out row (cover_quantize_act_fp8's arithmetic on the stored bf16 values)
-        float mx = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-            if ((int)(threadIdx.x + c * 512) * 8 < N)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(vals[c][i]));
-        mx = wave_max(mx);
-        if ((threadIdx.x & 63) == 0) red[8 + (threadIdx.x >> 6)] = mx;     // (red[0..7] belong to the block sum above)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) t = fmaxf(t, red[8 + i]);
-        const float sc = e4m3_pow2_scale(t), inv = 1.0f / sc;
-        if (threadIdx.x == 0) epi.nq8s[m] = sc;
-        uint8_t* qrow = epi.nq8 + (size_t)m * epi.ldnq8;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n0 = (threadIdx.x + c * 512) * 8;
-            if (n0 < N) store_q8_chunk(qrow, n0, vals[c], inv);
-        }
-        // zero padding up to the row pitch's 128-multiple is the caller's (N % 128 == 0 for the decoder widths this serves)
-    }
-    RNT(5);
-}
-__global__ __launch_bounds__(512) void splitk_reduce_norm(const float* __restrict__ partial, int S, bf16_t* C, int ldc, int M,
-                                                          int N, EpiDev epi) {
-    __shared__ float red[16];
-    reduce_norm_row(partial, S, C, ldc, M, N, epi, blockIdx.x, red);
-}
-
-// slab store of 4 consecutive columns of a split-K partial
-__device__ __forceinline__ void slab_store4(float* o, const float (&v)[4], int n, int N) {
-    if (n + 3 < N && ((((uintptr_t)o) & 15) == 0)) {
-        *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int e = 0; e < 4; ++e)
-            if (n + e < N) o[e] = v[e];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Weight-streaming kernel, second generation: the 8 waves of a block are NG n-groups x KS k-slices. A wave streams
-// NBW n-blocks over ITS 256-wide k-slice of the block's K chunk (KC = 256*KS, staged once in LDS), keeps one
-// accumulator set per n-block, and the KS slices are summed through LDS at the end. Same parallelism as the first
-// generation with KS-times fewer grid-level K splits => KS-times less fp32 partial traffic for the reduce kernel.
-// ---------------------------------------------------------------------------------------------------
-template <int MF, int KS, int NBW, bool W8 = false>
-__global__ __launch_bounds__(512) void gemm_skinny2(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ Wp,
-                                                    float* __restrict__ partial, int M, int N, int Kp, const float* __restrict__ wscale, int kl) {
-    constexpr int NG = 8 / KS, KC = 256 * KS, NBPB = NG * NBW;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ks = w % KS, ng = w / KS;
-    const int s = blockIdx.y;
-    const int k0 = s * KC;
-    const int kc = min(KC, Kp - k0);  // multiple of 128
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-    const int nb_begin = blockIdx.x * NBPB;
-    const int kw0 = ks * 256;               // this wave's k-slice inside the chunk
-    const int nsteps = max(0, min(8, (kc - kw0) >> 5));
-    f32x4 acc[NBW][MF];
-#pragma unroll
-    for (int i = 0; i < NBW; ++i)
-#pragma unroll
-        for (int f = 0; f < MF; ++f) acc[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    constexpr int NLD = W8 ? 4 : 8;               // 16-byte loads per lane per 256-deep item (see gemm_skinny3)
-    auto wsrc = [&](int nb, int k) -> const u32x4* {
-        if constexpr (W8) return (const u32x4*)((const uint8_t*)Wp + ((size_t)nb * (Kp >> 6) + (k >> 6)) * 1024) + lane;
-        else return (const u32x4*)(Wp + ((size_t)nb * K32 + (k >> 5)) * 512) + lane;
-    };
-    u32x4 buf[2][NLD];
-    auto load8 = [&](u32x4(&dst)[NLD], int i) {
-        int nb = nb_begin + ng + NG * i;
-        nb = nb < N16 ? nb : N16 - 1;
-        const u32x4* src = wsrc(nb, k0 + kw0);
-        if (nsteps == 8) {   // whole k-slice: straight-line issue (per-load branches cost ~20 % of the stream rate)
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) dst[u] = __builtin_nontemporal_load(src + u * 64);
-        } else {
-#pragma unroll
-            for (int u = 0; u < NLD; ++u)
-                if (u * (8 / NLD) < nsteps) dst[u] = __builtin_nontemporal_load(src + u * 64);
-        }
-    };
-    constexpr int NFR = (KC / 32) * MF;
-    bool items_done = false;
-    if (kc == KC && nsteps == 8 && NBW > 1) {
-        // whole chunk, whole k-slice: the activation fragments are requested BEFORE the weight blocks (loads return in order:
-        // behind the weights they would hold the first MFMA back until both blocks have landed), without per-element
-        // conditions (rows beyond M re-read row M-1; their outputs are never stored)
-        constexpr int XL = NFR / 8;
-        uint4 xr[XL];
-        const int rr = lane & 15, gg = lane >> 4;
-#pragma unroll
-        for (int j = 0; j < XL; ++j) {
-            const int fi = j * 8 + w, kst = fi / MF, f = fi - kst * MF;
-            int row = f * 16 + rr;
-            row = row < M ? row : M - 1;
-            xr[j] = *(const uint4*)(A + (size_t)row * lda + k0 + x_run_k<W8>(kst, gg, kl));
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int nb = nb_begin + ng + NG * i;
-            nb = nb < N16 ? nb : N16 - 1;
-            const u32x4* src = wsrc(nb, k0 + kw0);
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) buf[i][u] = __builtin_nontemporal_load(src + u * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < XL; ++j) *(uint4*)(smem + (j * 8 + w) * 1024 + lane * 16) = xr[j];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only: the weight blocks stay in flight
-        // the items straight-line as well (fixed step count, unconditional refills): s_waitcnt then counts the younger block
-        // still in flight instead of draining both before the first MFMA
-#pragma unroll
-        for (int i = 0; i < NBW; ++i) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const bf16x8 wf = wfrag<W8>(buf[i & 1], u);
-                const int kst = (kw0 >> 5) + u;
-#pragma unroll
-                for (int f = 0; f < MF; ++f) {
-                    const bf16x8 xf = as_bf16x8(*(const uint4*)(smem + ((kst * MF + f) * 64 + lane) * 16));
-                    acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[i][f], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (i + 2 < NBW) {
-                int nb = nb_begin + ng + NG * (i + 2);
-                nb = nb < N16 ? nb : N16 - 1;
-                const u32x4* src = wsrc(nb, k0 + kw0);
-#pragma unroll
-                for (int u = 0; u < NLD; ++u) buf[i & 1][u] = __builtin_nontemporal_load(src + u * 64);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        items_done = true;
-    } else {
-        load8(buf[0], 0);  // the first two weight blocks are in flight while the activation chunk is staged
-        if (NBW > 1) load8(buf[1], 1);
-        {   // stage the activation chunk (fragment-major), zero beyond kc: wave w moves fragments fi = w, w + 8, ... (fi =
-            // kst*MF + f); lane (rr, gg) owns row f*16 + rr, k = kst*32 + gg*8 -> lane-linear, conflict-free LDS stores
-            const int rr = lane & 15, gg = lane >> 4;
-#pragma unroll 4
-            for (int fi = w; fi < NFR; fi += 8) {
-                const int kst = fi / MF, f = fi - kst * MF;
-                const int row = f * 16 + rr, kk = x_run_k<W8>(kst, gg, kl);
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (row < M && kk < kc) v = *(const uint4*)(A + (size_t)row * lda + k0 + kk);
-                *(uint4*)(smem + fi * 1024 + lane * 16) = v;
-            }
-        }
-        __syncthreads();
-    }
-    auto comp8 = [&](u32x4(&src)[NLD], f32x4(&a)[MF]) {
-        auto step = [&](int u) {
-            const bf16x8 wf = wfrag<W8>(src, u);
-            const int kst = (kw0 >> 5) + u;
-#pragma unroll
-            for (int f = 0; f < MF; ++f) {
-                const bf16x8 xf = as_bf16x8(*(const uint4*)(smem + ((kst * MF + f) * 64 + lane) * 16));
-                a[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, a[f], 0, 0, 0);
-            }
-        };
-        if (nsteps == 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) step(u);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (u < nsteps) step(u);
-        }
-    };
-    if (!items_done) {
-#pragma unroll
-        for (int i = 0; i < NBW; ++i) {
-            comp8(buf[i & 1], acc[i]);
-            if (i + 2 < NBW) load8(buf[i & 1], i + 2);  // refill the buffer just consumed: two blocks stay in flight
-        }
-    }
-    // ---- sum the KS k-slices through LDS (the X chunk is dead now), RB n-blocks per round (<= 64 KiB of LDS) ----
-    constexpr int RB = (8 / MF) < NBW ? (8 / MF) : NBW;
-    const int r = lane & 15, g = lane >> 4;
-    float* red = (float*)smem;  // [w][ii][f][4][64]
-#pragma unroll
-    for (int i0 = 0; i0 < NBW; i0 += RB) {
-        __syncthreads();
-#pragma unroll
-        for (int ii = 0; ii < RB; ++ii)
-            if (i0 + ii < NBW) {
-#pragma unroll
-                for (int f = 0; f < MF; ++f)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) red[(((w * RB + ii) * MF + f) * 4 + e) * 64 + lane] = acc[(i0 + ii) < NBW ? (i0 + ii) : 0][f][e];
-            }
-        __syncthreads();
-        constexpr int NFRAG = NG * RB * MF;
-        for (int j = w; j < NFRAG; j += 8) {
-            const int f = j % MF, ii = (j / MF) % RB, gsel = j / (MF * RB);
-            if (i0 + ii >= NBW) continue;
-            const int nb = nb_begin + gsel + NG * (i0 + ii);
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const int ww = gsel * KS + kk;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += red[(((ww * RB + ii) * MF + f) * 4 + e) * 64 + lane];
-            }
-            const int m = f * 16 + r, n = nb * 16 + 4 * g;
-            if constexpr (W8) {   // per-channel power-of-two scale (packed channel order): exact in fp32, commutes with the slab sum
-                const float4 sc = *(const float4*)(wscale + (size_t)(nb < N16 ? nb : N16 - 1) * 16 + 4 * g);
-                v[0] *= sc.x; v[1] *= sc.y; v[2] *= sc.z; v[3] *= sc.w;
-            }
-            if (nb < N16 && m < M && n < N) slab_store4(partial + ((size_t)s * M + m) * N + n, v, n, N);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Weight-streaming kernel, third generation (M <= 32): NO grid-level split-K. A block owns NG*NBW n-blocks for the WHOLE
-// K range, so the output leaves through the fused epilogue (bias / activation / GLU / residual, bf16 or fp32) and the
-// fp32 partial slabs plus the splitk_reduce launch disappear. The activation panel does not fit LDS at once
-// (32 x 4096 bf16 = 256 KiB): it is streamed in KC-wide chunks through a DOUBLE buffer -- the global loads of chunk c+1
-// are issued before chunk c's MFMAs and written to the other buffer after them, one barrier per chunk -- while the
-// weight stream (NBUF x 8 KiB per wave in flight, non-temporal) runs across chunk boundaries without draining.
-// Waves: NG n-groups x KS k-slices of 256 inside every chunk, accumulators live across chunks, KS-way LDS reduction at
-// the end as in the second generation. grid = ceil(N16 / (NG*NBW)).
-// ---------------------------------------------------------------------------------------------------
-#ifdef COVER_SK_DEBUG
-__device__ unsigned long long g_sk_dbg[1024 * 4];   // per block: start, chunk 0 staged, last MFMA done, end (100 MHz wall clock)
-extern "C" int cover_sk_debug(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sk_dbg), sizeof(g_sk_dbg));
-}
-#define SKT(slot) do { if (threadIdx.x == 0) g_sk_dbg[((blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 4 + (slot)] = wall_clock64(); } while (0)
-#else
-#define SKT(slot) do { } while (0)
-#endif
-template <int MF, int KS, int NBW, int NBUF, bool W8 = false>
-__global__ __launch_bounds__(512) void gemm_skinny3(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ Wp,
-                                                    void* C, int ldc, int M, int N, int Kp, EpiDev epi,
-                                                    float* __restrict__ partial, int kper, const float* __restrict__ wscale, int kl) {
-    SKT(0);
-    constexpr int NG = 8 / KS, KC = 256 * KS, NBPB = NG * NBW;
-    constexpr int XB = MF * 16 * KC * 2;          // bytes of one activation chunk (fragment-major)
-    constexpr int XL = XB / (512 * 16);           // 16-B loads per thread per chunk
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][XB]; the reduction buffer aliases it at the end
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ks = w % KS, ng = w / KS;
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-    const int nb_begin = blockIdx.x * NBPB;
-    // optional grid-level split-K (narrow outputs: n-blocks alone cannot fill the chip): slice s = blockIdx.y owns
-    // k in [kb, ke) and leaves raw fp32 partial sums [s][M][N] for the reduction / the fused decode attention
-    const int kb = blockIdx.y * kper;
-    const int ke = min(Kp, kb + kper);
-    const int nchunks = (ke - kb + KC - 1) / KC;
-    const int kw0 = ks * 256;                     // this wave's k-slice inside every chunk
-    f32x4 acc[NBW][MF];
-#pragma unroll
-    for (int i = 0; i < NBW; ++i)
-#pragma unroll
-        for (int f = 0; f < MF; ++f) acc[i][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // weight stream: item t = (chunk c = t / NBW, n-block i = t % NBW) -> 8 x 1 KiB (this wave's 256 k of that chunk)
-    const int items = nchunks * NBW;
-    auto steps_of = [&](int c) { return max(0, min(8, (min(KC, ke - kb - c * KC) - kw0) >> 5)); };
-    // W8: e4m3 weights (cover_pack_weight_fp8: 1 KiB per 16 n x 64 k block, a lane's 16 bytes = its 8-wide k runs of two
-    // consecutive 32-deep steps): half the bytes per item, de-quantised to bf16 fragments in registers (exact), the
-    // power-of-two per-channel scale applied to the fp32 sums after the k-slice reduction (exact)
-    constexpr int NLD = W8 ? 4 : 8;               // 16-byte loads per lane per 256-deep item
-    auto wsrc = [&](int nb, int k) -> const u32x4* {
-        if constexpr (W8) return (const u32x4*)((const uint8_t*)Wp + ((size_t)nb * (Kp >> 6) + (k >> 6)) * 1024) + lane;
-        else return (const u32x4*)(Wp + ((size_t)nb * K32 + (k >> 5)) * 512) + lane;
-    };
-    u32x4 buf[NBUF][NLD];
-    auto load8 = [&](u32x4(&dst)[NLD], int t) {
-        const int c = t / NBW, i = t - c * NBW;
-        int nb = nb_begin + ng + NG * i;
-        nb = nb < N16 ? nb : N16 - 1;
-        const int nst = steps_of(c);
-        const u32x4* src = wsrc(nb, kb + c * KC + kw0);
-        if (nst == 8) {   // whole k-slice (every chunk but a ragged last one): straight-line issue
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) dst[u] = __builtin_nontemporal_load(src + u * 64);
-        } else {
-#pragma unroll
-            for (int u = 0; u < NLD; ++u)
-                if (u * (8 / NLD) < nst) dst[u] = __builtin_nontemporal_load(src + u * 64);
-        }
-    };
-    // activation chunk staging through registers: wave w moves fragments fi = j*8 + w (fi = kst*MF + f); lane
-    // (rr, gg) = (lane & 15, lane >> 4) owns the 16 bytes of row f*16 + rr, k = kst*32 + gg*8, so the LDS image of a
-    // fragment is lane-linear and a wave's 16-byte stores are one contiguous KiB (a row-major thread map lands 16 lanes
-    // of every store on one bank)
-    static_assert(XL * 8 == (KC / 32) * MF, "fragments must split evenly over the waves");
-    uint4 xr[XL];
-    const int srr = lane & 15, sgg = lane >> 4;
-    auto x_load = [&](int c) {
-        const int k0 = kb + c * KC, kc = min(KC, ke - k0);
-#pragma unroll
-        for (int j = 0; j < XL; ++j) {
-            const int fi = j * 8 + w, kst = fi / MF, f = fi - kst * MF;
-            const int row = f * 16 + srr, kk = x_run_k<W8>(kst, sgg, kl);
-            xr[j] = make_uint4(0, 0, 0, 0);
-            if (row < M && kk < kc) xr[j] = *(const uint4*)(A + (size_t)row * lda + k0 + kk);
-        }
-    };
-    auto x_write = [&](int b) {
-#pragma unroll
-        for (int j = 0; j < XL; ++j) *(uint4*)(smem + b * XB + (j * 8 + w) * 1024 + lane * 16) = xr[j];
-    };
-    auto comp8 = [&](u32x4(&src)[NLD], f32x4(&a)[MF], int c) {
-        const int nst = steps_of(c);
-        const char* xb = smem + (c & 1) * XB;
-        auto step = [&](int u) {
-            const bf16x8 wf = wfrag<W8>(src, u);
-            const int kst = (kw0 >> 5) + u;
-#pragma unroll
-            for (int f = 0; f < MF; ++f) {
-                const bf16x8 xf = as_bf16x8(*(const uint4*)(xb + ((kst * MF + f) * 64 + lane) * 16));
-                a[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, a[f], 0, 0, 0);
-            }
-        };
-        if (nst == 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) step(u);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (u < nst) step(u);
-        }
-    };
-
-    // prologue. The activation chunk is requested BEFORE the first NBUF weight items: loads return in order, so with the
-    // weights first the chunk (and with it the first MFMA, and with that the first REFILL of a weight buffer) would wait for
-    // all NBUF x 8 KiB per wave to land -- the stream would drain its whole initial window before issuing anything new.
-    if (items >= NBUF && min(KC, ke - kb) == KC) {   // straight-line: the compiler counts the weight loads behind the chunk's
-        {   // whole first chunk: no per-element conditions (rows beyond M re-read row M-1; their outputs are never stored)
-#pragma unroll
-            for (int j = 0; j < XL; ++j) {
-                const int fi = j * 8 + w, kst = fi / MF, f = fi - kst * MF;
-                int row = f * 16 + srr;
-                row = row < M ? row : M - 1;
-                xr[j] = *(const uint4*)(A + (size_t)row * lda + kb + x_run_k<W8>(kst, sgg, kl));
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NBUF; ++b) {
-            int nb = nb_begin + ng + NG * b;
-            nb = nb < N16 ? nb : N16 - 1;
-            const u32x4* src = wsrc(nb, kb + kw0);
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) buf[b][u] = __builtin_nontemporal_load(src + u * 64);
-        }
-        x_write(0);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only: the weight items stay in flight
-        SKT(1);
-    } else {
-#pragma unroll
-        for (int b = 0; b < NBUF; ++b)
-            if (b < items) load8(buf[b], b);
-        x_load(0);
-        x_write(0);
-        __syncthreads();
-    }
-    // Steady state: chunk c is full and so is chunk c+1. Everything in the body is straight-line (unconditional loads, fixed
-    // step counts), so the compiler's s_waitcnt before the first MFMA of an item counts exactly the loads issued after that
-    // item's (two younger items + the next activation chunk stay in flight). With the refill behind an `if`, it emitted
-    // vmcnt(0) at every item: the wave drained its whole window 3-4 times per chunk.
-    int c0 = 0;
-    if (items >= NBUF && min(KC, ke - kb) == KC) {
-        const bool last_full = ((ke - kb) % KC) == 0;
-        const int nfast = last_full ? nchunks - 1 : nchunks - 2;   // chunks whose successor is a full chunk
-        for (; c0 < nfast; ++c0) {
-            const int k1 = kb + (c0 + 1) * KC;
-#pragma unroll
-            for (int j = 0; j < XL; ++j) {
-                const int fi = j * 8 + w, kst = fi / MF, f = fi - kst * MF;
-                int row = f * 16 + srr;
-                row = row < M ? row : M - 1;
-                xr[j] = *(const uint4*)(A + (size_t)row * lda + k1 + x_run_k<W8>(kst, sgg, kl));
-            }
-            __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise hoists the first MFMAs of all items and sinks the refills)
-            const char* xb = smem + (c0 & 1) * XB;
-#pragma unroll
-            for (int i = 0; i < NBW; ++i) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const bf16x8 wf = wfrag<W8>(buf[i % NBUF], u);
-                    const int kst = (kw0 >> 5) + u;
-#pragma unroll
-                    for (int f = 0; f < MF; ++f) {
-                        const bf16x8 xf = as_bf16x8(*(const uint4*)(xb + ((kst * MF + f) * 64 + lane) * 16));
-                        acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[i][f], 0, 0, 0);
-                    }
-                }
-                int nb = nb_begin + ng + NG * i;
-                nb = nb < N16 ? nb : N16 - 1;
-                const u32x4* src = wsrc(nb, k1 + kw0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < NLD; ++u) buf[i % NBUF][u] = __builtin_nontemporal_load(src + u * 64);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            x_write((c0 + 1) & 1);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        if (last_full && c0 == nchunks - 1) {   // the last chunk, full: the same straight-line items without refills
-            const char* xb = smem + (c0 & 1) * XB;
-#pragma unroll
-            for (int i = 0; i < NBW; ++i) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const bf16x8 wf = wfrag<W8>(buf[i % NBUF], u);
-                    const int kst = (kw0 >> 5) + u;
-#pragma unroll
-                    for (int f = 0; f < MF; ++f) {
-                        const bf16x8 xf = as_bf16x8(*(const uint4*)(xb + ((kst * MF + f) * 64 + lane) * 16));
-                        acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[i][f], 0, 0, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            ++c0;
-        }
-    }
-    // remaining chunks (ragged last chunk and its predecessor, or everything for short K): generic bookkeeping
-    int t = c0 * NBW;
-    for (int c = c0; c < nchunks; ++c) {
-        if (c + 1 < nchunks) x_load(c + 1);            // lands underneath this chunk's weight stream
-#pragma unroll
-        for (int i = 0; i < NBW; ++i, ++t) {
-            // buffer of item t is t % NBUF; NBW % NBUF == 0 keeps it static per i
-            comp8(buf[i % NBUF], acc[i], c);
-            if (t + NBUF < items) load8(buf[i % NBUF], t + NBUF);
-        }
-        if (c + 1 < nchunks) {
-            x_write((c + 1) & 1);                      // the other buffer: nobody reads it during chunk c
-            // chunk c+1 visible, chunk c's buffer free for c+2. LDS-only barrier: __syncthreads() would also drain
-            // vmcnt, i.e. the NBUF weight items in flight, at every chunk boundary.
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-    }
-
-    SKT(2);
-    // ---- sum the KS k-slices through LDS, RB n-blocks per round, and leave through the fused epilogue ----
-    constexpr int RB = (8 / MF) < NBW ? (8 / MF) : NBW;
-    const int r = lane & 15, g = lane >> 4;
-    float* red = (float*)smem;  // [w][ii][f][4][64]
-#pragma unroll
-    for (int i0 = 0; i0 < NBW; i0 += RB) {
-        __syncthreads();
-#pragma unroll
-        for (int ii = 0; ii < RB; ++ii)
-            if (i0 + ii < NBW) {
-#pragma unroll
-                for (int f = 0; f < MF; ++f)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) red[(((w * RB + ii) * MF + f) * 4 + e) * 64 + lane] = acc[(i0 + ii) < NBW ? (i0 + ii) : 0][f][e];
-            }
-        __syncthreads();
-        auto slice_sum = [&](int gsel, int ii, int f, float (&v)[4]) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const int ww = gsel * KS + kk;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += red[(((ww * RB + ii) * MF + f) * 4 + e) * 64 + lane];
-            }
-            if constexpr (W8) {   // per-channel power-of-two scale (packed channel order): exact in fp32
-                const int nbs = nb_begin + gsel + NG * (i0 + ii);
-                const float4 sc = *(const float4*)(wscale + (size_t)(nbs < N16 ? nbs : N16 - 1) * 16 + 4 * g);
-                v[0] *= sc.x; v[1] *= sc.y; v[2] *= sc.z; v[3] *= sc.w;
-            }
-        };
-        if (partial) {   // split-K slice: raw sums, the epilogue belongs to whoever folds the slabs
-            constexpr int NFRAG = NG * RB * MF;
-            for (int j = w; j < NFRAG; j += 8) {
-                const int f = j % MF, ii = (j / MF) % RB, gsel = j / (MF * RB);
-                if (i0 + ii >= NBW) continue;
-                const int nb = nb_begin + gsel + NG * (i0 + ii);
-                const int m = f * 16 + r, n = nb * 16 + 4 * g;
-                if (nb < N16 && m < M && n < N) {
-                    float v[4];
-                    slice_sum(gsel, ii, f, v);
-                    slab_store4(partial + ((size_t)blockIdx.y * M + m) * N + n, v, n, N);
-                }
-            }
-        } else if (epi.glu) {   // n-groups 0 / 1 hold the gate / up block of one output block (NG == 2, even nb_begin)
-            constexpr int NFRAG = RB * MF;
-            for (int j = w; j < NFRAG; j += 8) {
-                const int f = j % MF, ii = j / MF;
-                if (i0 + ii >= NBW) continue;
-                const int nb = nb_begin + NG * (i0 + ii);   // gate block (even), up = nb + 1
-                const int m = f * 16 + r;
-                if (nb + 1 < N16 + (N16 & 1) && nb < N16 && m < M) {
-                    float gv[4], uv[4];
-                    slice_sum(0, ii, f, gv);
-                    slice_sum(1, ii, f, uv);
-                    epi_store4_glu(epi, C, ldc, m, (nb >> 1) * 16 + 4 * g, N >> 1, gv, uv);
-                }
-            }
-        } else {
-            constexpr int NFRAG = NG * RB * MF;
-            for (int j = w; j < NFRAG; j += 8) {
-                const int f = j % MF, ii = (j / MF) % RB, gsel = j / (MF * RB);
-                if (i0 + ii >= NBW) continue;
-                const int nb = nb_begin + gsel + NG * (i0 + ii);
-                const int m = f * 16 + r;
-                if (nb < N16 && m < M) {
-                    float v[4];
-                    slice_sum(gsel, ii, f, v);
-                    epi_store4(epi, C, ldc, m, nb * 16 + 4 * g, N, v);
-                }
-            }
-        }
-    }
-    SKT(3);
-}
-
-// out = epi(sum_s partial[s]) ; one thread per 4 output columns
-__global__ __launch_bounds__(256) void splitk_reduce(const float* __restrict__ partial, int S, void* C, int ldc, int M,
-                                                     int N, EpiDev epi) {
-    const int Nout = epi.glu ? (N >> 1) : N;
-    const int groups = (Nout + 3) >> 2;
-    const long long total = (long long)M * groups;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int m = (int)(idx / groups);
-        const int j0 = (int)(idx - (long long)m * groups) * 4;
-        if (epi.glu) {
-            const int ng = (j0 >> 4) * 32 + (j0 & 15);  // gate columns; up = +16
-            float gv[4] = {0, 0, 0, 0}, uv[4] = {0, 0, 0, 0};
-            for (int s = 0; s < S; ++s) {
-                const float* p = partial + ((size_t)s * M + m) * N + ng;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (j0 + i < Nout) {
-                        gv[i] += p[i];
-                        uv[i] += p[16 + i];
-                    }
-            }
-            epi_store4_glu(epi, C, ldc, m, j0, Nout, gv, uv);
-        } else {
-            float v[4] = {0, 0, 0, 0};
-            const float* p0 = partial + (size_t)m * N + j0;
-            const size_t sstride = (size_t)M * N;
-            if (j0 + 3 < N && ((((uintptr_t)p0) | (sstride * sizeof(float))) & 15) == 0) {
-                // whole group of four columns: 16-byte loads, four slabs in flight (a rolled loop with guarded scalar loads is a
-                // chain of S dependent round trips), summed in slab order
-                int s = 0;
-                for (; s + 4 <= S; s += 4) {
-                    float4 a[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) a[j] = *(const float4*)(p0 + (s + j) * sstride);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { v[0] += a[j].x; v[1] += a[j].y; v[2] += a[j].z; v[3] += a[j].w; }
-                }
-                for (; s < S; ++s) {
-                    const float4 a = *(const float4*)(p0 + s * sstride);
-                    v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-                }
-            } else {
-                for (int s = 0; s < S; ++s) {
-                    const float* p = partial + ((size_t)s * M + m) * N + j0;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (j0 + i < N) v[i] += p[i];
-                }
-            }
-            epi_store4(epi, C, ldc, m, j0, N, v);
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// Weight packing: W[N, ldw] row-major -> fragment-major. One thread per 16-B chunk of the packed image.
-// ---------------------------------------------------------------------------------------------------
-__global__ void pack_weight(const bf16_t* __restrict__ W, int ldw, int N, int K, bf16_t* __restrict__ Wp, int Kp,
-                            int glu) {
-    const int K32 = Kp >> 5;
-    const int N16 = (N + 15) >> 4;
-    const long long total = (long long)N16 * K32 * 64;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int lane = (int)(idx & 63);
-        const long long blk = idx >> 6;
-        const int kb = (int)(blk % K32);
-        const int nb = (int)(blk / K32);
-        int n = nb * 16 + (lane & 15);
-        if (glu) {  // packed block 2i = gate rows [16i,16i+16), block 2i+1 = up rows N/2 + [16i,16i+16)
-            const int half = N >> 1;
-            const int i = nb >> 1;
-            n = ((nb & 1) ? half : 0) + i * 16 + (lane & 15);
-            if (i * 16 + (lane & 15) >= half) n = N;  // out of range -> zeros
-        }
-        const int k = kb * 32 + (lane >> 4) * 8;
-        bf16_t v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (n < N && k + e < K) ? W[(size_t)n * ldw + k + e] : (bf16_t)0;
-        *(uint4*)(Wp + idx * 8) = *(const uint4*)v;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Host launchers
-// ---------------------------------------------------------------------------------------------------
-// the norm requested through the epilogue, as its own launch (paths that cannot fold it into a split-K reduction)
-static hipError_t run_norm(const EpiDev& epi, void* C, int ldc, int M, int Nout, hipStream_t st) {
-    if (epi.norm_style == 2)
-        return launch_layernorm_bf16((const bf16_t*)C, ldc, epi.norm_w, epi.norm_b, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st);
-    return launch_rmsnorm(C, 0, ldc, epi.norm_w, epi.norm_w_offset, epi.norm_style, epi.norm_out, epi.ld_norm_out, M, Nout, epi.norm_eps, st,
-                          epi.nq8, epi.ldnq8, epi.nq8s);
-}
-
-// the completion of a planned launch: the split-K reduction (with the norm folded in, or followed by its own norm launch)
-static hipError_t complete_splitk(const GemmPlan& p, const EpiDev& epi, const float* ws, void* C, int ldc, int M, int N, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    if (p.done == GD_REDUCE_NORM) {
-        e = launch_kernel<splitk_reduce_norm>(p.rcls, 0.0, dim3(M), dim3(512), 0, st, ws, p.S, (bf16_t*)C, ldc, M, N, epi);
-    } else if (p.done == GD_REDUCE) {
-        const int Nout = epi.glu ? N / 2 : N;
-        const long long total = (long long)M * ((Nout + 3) / 4);
-        int rb = (int)((total + 255) / 256);
-        if (rb > 2048) rb = 2048;
-        e = launch_kernel<splitk_reduce>(p.rcls, 0.0, dim3(rb), dim3(256), 0, st, ws, p.S, C, ldc, M, N, epi);
-    }
-    if (e == hipSuccess && p.done != GD_NONE) e = hipGetLastError();
-    if (e == hipSuccess && p.norm_launch) e = run_norm(epi, C, ldc, M, epi.glu ? N / 2 : N, st);
-    return e;
-}
-
-// second-generation weight streaming; e4m3 weights for M <= 32 when a twin is given
-static hipError_t launch_skinny2(const Skinny2Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, float* ws, int M, int N, int K, int Kp,
-                                 const uint8_t* w8, const float* w8s, int kl, hipStream_t st) {
-    const dim3 grid(p.gx, p.S), block(512);
-    plan_hit(PLAN_SKINNY2);
-#define SK2(MF_, KS_, NBW_, W8_) launch_kernel<gemm_skinny2<MF_, KS_, NBW_, W8_>>(sk_class(N, K), (W8_ ? 1.0 : 2.0) * (double)N * (double)K, grid, block, p.lds, st, \
-                                                                                   A, lda, W8_ ? (const bf16_t*)w8 : Wp, ws, M, N, Kp, w8s, kl)
-    hipError_t e;
-    if (w8 && w8s && p.MF <= 2) {
-        if (p.MF == 1) e = p.NBW == 6 ? SK2(1, 4, 6, true) : p.NBW == 4 ? SK2(1, 4, 4, true) : p.NBW == 3 ? SK2(1, 4, 3, true) : SK2(1, 4, 2, true);
-        else e = p.NBW == 6 ? SK2(2, 4, 6, true) : p.NBW == 4 ? SK2(2, 4, 4, true) : p.NBW == 3 ? SK2(2, 4, 3, true) : SK2(2, 4, 2, true);
-    } else {
-        if (p.MF == 1) e = p.NBW == 6 ? SK2(1, 4, 6, false) : p.NBW == 4 ? SK2(1, 4, 4, false) : p.NBW == 3 ? SK2(1, 4, 3, false) : SK2(1, 4, 2, false);
-        else if (p.MF == 2) e = p.NBW == 6 ? SK2(2, 4, 6, false) : p.NBW == 4 ? SK2(2, 4, 4, false) : p.NBW == 3 ? SK2(2, 4, 3, false) : SK2(2, 4, 2, false);
-        else if (p.MF == 3) e = SK2(3, 2, 2, false);
-        else e = SK2(4, 2, 2, false);
-    }
-#undef SK2
-    if (e == hipSuccess) e = hipGetLastError();
-    return e;
-}
-
-static hipError_t launch_skinny3(const Skinny3Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N,
-                                 int Kp, const EpiDev& epi, float* partial, hipStream_t st) {
-    const dim3 grid(p.gx, p.S), block(512);
-    plan_hit(PLAN_SKINNY3);
-#define SK3(MF_, NBW_, W8_) launch_kernel<gemm_skinny3<MF_, 4, NBW_, NBW_, W8_>>(sk_class(N, Kp), (W8_ ? 1.0 : 2.0) * (double)N * (double)Kp, grid, block, p.lds, st, \
-                                                                                  A, lda, W8_ ? (const bf16_t*)epi.w8 : Wp, C, ldc, M, N, Kp, epi, partial, p.kper, epi.w8s, epi.w8_kl)
-    hipError_t e;
-    if (epi.w8) {   // e4m3 weight stream
-        if (p.MF == 1) e = p.NBW == 4 ? SK3(1, 4, true) : p.NBW == 3 ? SK3(1, 3, true) : SK3(1, 2, true);
-        else e = p.NBW == 4 ? SK3(2, 4, true) : p.NBW == 3 ? SK3(2, 3, true) : SK3(2, 2, true);
-    } else {
-        if (p.MF == 1) e = p.NBW == 4 ? SK3(1, 4, false) : p.NBW == 3 ? SK3(1, 3, false) : SK3(1, 2, false);
-        else e = p.NBW == 4 ? SK3(2, 4, false) : p.NBW == 3 ? SK3(2, 3, false) : SK3(2, 2, false);
-    }
-#undef SK3
-    if (e == hipSuccess) e = hipGetLastError();
-    return e;
-}
 
 // the LDS-tiled kernels of a GK_TILED / GK_TILED_PC / GK_V3 / GK_F8_* plan
 static hipError_t launch_tiles(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K, int Kp,
@@ -1419,29 +29,7 @@ static hipError_t launch_tiles(const GemmPlan& p, const bf16_t* A, int lda, cons
             partial = (float*)C;
         return launch_gemm_v3(p, A, lda, Wp, C, ldc, M, N, Kp, epi, partial, tcls, twork, st);
     }
-    const dim3 grid(p.tiles_m * p.tiles_n, p.S), block(p.block);
-#define T(KFN) launch_kernel<KFN>(tcls, twork, grid, block, p.lds, st, A, lda, Wp, C, ldc, M, N, Kp, epi, p.tiles_m, p.tiles_n, p.kt_per, partial)
-    hipError_t e;
-    if (p.kind == GK_TILED_PC) {
-        e = T((gemm_tiled_pc<2, 4, 4, 4>));   // 64 x 128 tile, four loader waves + four MFMA waves, four stages (narrow outputs on a long K at a few hundred rows)
-    } else if (variant == 2) {
-        e = p.pick == TP_128x128 ? T((gemm_tiled<4, 4, false, 2, 2, 2>)) : p.pick == TP_64x128 ? T((gemm_tiled<2, 4, false, 2, 2, 2>)) : T((gemm_tiled<2, 2, false, 2, 2, 2>));
-    } else {
-        switch (p.pick) {
-            case TP_128x128: e = T((gemm_tiled<4, 4, true, 2, 2, 2>)); break;
-            case TP_64x128: e = T((gemm_tiled<2, 4, true, 2, 2, 2>)); break;
-            case TP_64x64: e = T((gemm_tiled<2, 2, true, 3, 2, 2>)); break;
-            case TP_128x128_S4: e = T((gemm_tiled<4, 4, true, 4, 2, 2>)); break;
-            case TP_256x128: e = T((gemm_tiled<4, 4, true, 3, 4, 2>)); break;
-            case TP_128x256: e = T((gemm_tiled<4, 4, true, 3, 2, 4>)); break;
-            case TP_64x128_S3: e = T((gemm_tiled<2, 4, true, 3, 2, 2>)); break;
-            case TP_128x128_S3: e = T((gemm_tiled<4, 4, true, 3, 2, 2>)); break;
-            default: e = T((gemm_tiled<2, 4, true, 4, 4, 2>)); break;   // TP_128x128_W8
-        }
-    }
-#undef T
-    if (e == hipSuccess) e = hipGetLastError();
-    return e;
+    return launch_gemm_tiled(p, A, lda, Wp, C, ldc, M, N, Kp, epi, partial, variant, tcls, twork, st);
 }
 
 hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K,
@@ -1456,19 +44,7 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
     switch (p.kind) {
         case GK_SKINNY3: e = launch_skinny3(p.p3, A, lda, Wp, C, ldc, M, N, Kp, epi, partial, st); break;
         case GK_SKINNY2: e = launch_skinny2(p.p2, A, lda, Wp, ws, M, N, K, Kp, epi.w8, epi.w8s, epi.w8_kl, st); break;
-        case GK_SKINNY:
-            plan_hit(PLAN_SKINNY);
-            switch (p.p1.MF) {
-#define SK1(MF_) launch_kernel<gemm_skinny<MF_>>(sk_class(N, K), 2.0 * (double)N * (double)K, dim3(p.p1.gx, p.S), dim3(512), p.lds, st, A, lda, Wp, ws, M, N, Kp, \
-                                                 p.p1.KC, p.p1.nbpb)
-                case 1: e = SK1(1); break;
-                case 2: e = SK1(2); break;
-                case 3: e = SK1(3); break;
-                default: e = SK1(4); break;
-#undef SK1
-            }
-            if (e == hipSuccess) e = hipGetLastError();
-            break;
+        case GK_SKINNY: e = launch_skinny1(p, A, lda, Wp, ws, M, N, K, Kp, st); break;
         default: e = launch_tiles(p, A, lda, Wp, C, ldc, M, N, K, Kp, epi, partial, variant, st); break;
     }
     if (e != hipSuccess) return e;
@@ -1477,119 +53,4 @@ hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C,
         return e;
     }
     return complete_splitk(p, epi, ws, C, ldc, M, N, st);
-}
-
-// Weight-streaming GEMM WITHOUT its reduction: leaves fp32 partials [S][M][N] in ws for a consumer that folds them
-// (the decoder fuses the QKV reduction into rope_kv_write). Returns the number of K slices through *S_out.
-hipError_t launch_gemm_skinny_partial(const bf16_t* A, int lda, const bf16_t* Wp, float* ws, size_t ws_bytes, int M, int N,
-                                      int K, int* S_out, hipStream_t st, const void* w8, const float* w8s) {
-    if (M <= 0 || M > 64 || N <= 0) return hipErrorInvalidValue;
-    const int Kp = (K + 127) / 128 * 128;
-    GemmPlan p = GemmPlan{};
-    hipError_t e = plan_streaming(p, M, N, Kp, ws, ws_bytes, false, true);
-    if (e != hipSuccess) return e;
-    if (p.kind == GK_SKINNY3) {
-        EpiDev none = make_epi(nullptr);
-        if (w8 && w8s) { none.w8 = (const uint8_t*)w8; none.w8s = w8s; }
-        e = launch_skinny3(p.p3, A, lda, Wp, nullptr, 0, M, N, Kp, none, ws, st);
-    } else {
-        e = launch_skinny2(p.p2, A, lda, Wp, ws, M, N, K, Kp, (const uint8_t*)w8, w8s, 0, st);
-    }
-    *S_out = p.S;
-    return e;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// e4m3 weights (BASELINE config 5). Per OUTPUT CHANNEL scale s_n = the smallest power of two with max_k |W[n,k]| / s_n <= 448
-// (the e4m3 maximum); q = RNE_e4m3(W / s_n). A power-of-two scale makes (a) the division exact, (b) s_n * q exactly
-// representable in bf16 (3 mantissa bits of e4m3 inside bf16's 7) -- so the SAME quantised weight exists as an e4m3 image for
-// the HBM-bound weight-streaming kernels (half the bytes) and as a bf16 image for the MFMA-bound tiled kernels, and both
-// give bit-identical GEMM results (products and sums just scale by 2^e).
-//   quantize_rows_fp8_k : W bf16 [N, ldw] -> scales[N] fp32, Wdq bf16 [N, ldw] (= s_n * q, the de-quantised twin)
-//   pack_weight_fp8_k   : Wdq + scales -> packed e4m3 image [n/16][k/64][lane = n%16 + 16*((k%32)/8)][16 B = the lane's 8-wide k run
-//                         of the two 32-deep steps of the 64-block] and the scales in PACKED channel order
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void quantize_rows_fp8_k(const bf16_t* __restrict__ W, int ldw, int K, float* __restrict__ scales,
-                                                           bf16_t* __restrict__ Wdq) {
-    __shared__ float red[16];
-    const int n = blockIdx.x;
-    const bf16_t* w = W + (size_t)n * ldw;
-    float mx = 0.f;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) mx = fmaxf(mx, fabsf(bf2f(w[k])));
-    mx = block_max(mx, red);
-    // smallest power of two s with mx / s <= 448: s = 2^ceil(log2(mx / 448)); frexp gives mx / 448 = f * 2^e with f in [0.5, 1)
-    float s = 1.0f;
-    if (mx > 0.f) {
-        int e;
-        const float f = frexpf(mx / 448.0f, &e);
-        s = ldexpf(1.0f, f == 0.5f ? e - 1 : e);
-    }
-    if (threadIdx.x == 0) scales[n] = s;
-    const float inv = 1.0f / s;   // exact (power of two)
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        const float x = bf2f(w[k]) * inv;
-        const int pk = __builtin_amdgcn_cvt_pk_fp8_f32(x, 0.0f, 0, false);      // RNE to OCP e4m3 (gfx950)
-        const f32x2_t back = __builtin_amdgcn_cvt_pk_f32_fp8((uint32_t)pk, false);
-        Wdq[(size_t)n * ldw + k] = f2bf(back[0] * s);                           // exact: e4m3 value times a power of two
-    }
-}
-
-__global__ void pack_weight_fp8_k(const bf16_t* __restrict__ Wdq, int ldw, const float* __restrict__ scales, int N, int K,
-                                  uint8_t* __restrict__ Wq, float* __restrict__ scales_packed, int Kp, int glu, int kl) {
-    const int K64 = Kp >> 6;
-    const int N16 = (N + 15) >> 4;
-    const long long total = (long long)N16 * K64 * 64;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int lane = (int)(idx & 63);
-        const long long blk = idx >> 6;
-        const int kb = (int)(blk % K64);
-        const int nb = (int)(blk / K64);
-        int n = nb * 16 + (lane & 15);
-        if (glu) {  // packed block 2i = gate rows [16i,16i+16), block 2i+1 = up rows N/2 + [16i,16i+16)  (as pack_weight)
-            const int half = N >> 1, i = nb >> 1;
-            n = ((nb & 1) ? half : 0) + i * 16 + (lane & 15);
-            if (i * 16 + (lane & 15) >= half) n = N;
-        }
-        const float s = n < N ? scales[n] : 1.0f, inv = 1.0f / s;
-        if (kb == 0 && (lane >> 4) == 0) scales_packed[nb * 16 + (lane & 15)] = s;
-        uint32_t o[4];
-#pragma unroll
-        for (int half_ = 0; half_ < 2; ++half_) {      // k32 step 0 / 1 of the 64-block
-            // default image: the lane's 8-wide runs of the two 32-deep steps of the 64-block; k-linear image: the lane's 16 consecutive k of the block
-            const int k = kl ? kb * 64 + (lane >> 4) * 16 + half_ * 8 : kb * 64 + half_ * 32 + (lane >> 4) * 8;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (n < N && k + e < K) ? bf2f(Wdq[(size_t)n * ldw + k + e]) * inv : 0.f;
-            int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-            lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-            int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
-            hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-            o[2 * half_] = (uint32_t)lo;
-            o[2 * half_ + 1] = (uint32_t)hi;
-        }
-        *(uint4*)(Wq + idx * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-hipError_t launch_quantize_rows_fp8(const bf16_t* W, int ldw, int N, int K, float* scales, bf16_t* Wdq, hipStream_t st) {
-    if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(quantize_rows_fp8_k, dim3(N), dim3(256), 0, st, W, ldw, K, scales, Wdq);
-    return hipGetLastError();
-}
-hipError_t launch_pack_weight_fp8(const bf16_t* Wdq, int ldw, const float* scales, int N, int K, uint8_t* Wq, float* scales_packed,
-                                  int Kpad, int glu, hipStream_t st, int kl) {
-    const long long total = (long long)((N + 15) / 16) * (Kpad / 64) * 64;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fp8_k, dim3(blocks), dim3(256), 0, st, Wdq, ldw, scales, N, K, Wq, scales_packed, Kpad, glu, kl);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_weight_bf16(const bf16_t* W, int ldw, int N, int K, bf16_t* Wp, int Kpad, int glu,
-                                   hipStream_t st) {
-    const long long total = (long long)((N + 15) / 16) * (Kpad / 32) * 64;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight, dim3(blocks), dim3(256), 0, st, W, ldw, N, K, Wp, Kpad, glu);
-    return hipGetLastError();
 }

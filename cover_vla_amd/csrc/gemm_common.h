@@ -1,4 +1,4 @@
-// Shared device code of the GEMM kernels (gemm_bf16.hip, gemm_fp8.hip): the epilogue description, the per-group epilogue
+// Shared device code of the GEMM kernels (gemm_tiled.hip, gemm_stream.hip, gemm_reduce.hip, gemm_v3.hip, gemm_fp8.hip): the epilogue description, the per-group epilogue
 // arithmetic with its bf16 rounding points, and the direct / LDS-staged tile epilogues.
 #pragma once
 #include <type_traits>
@@ -586,7 +586,7 @@ __device__ __forceinline__ void glds4_s(uint32_t voff, const void* sbase, uint32
         : "memory");
 }
 
-// ---- host side: the GEMM plan (gemm_plan.hip: plan_gemm) and the launches that carry it out (gemm_bf16.hip, gemm_v3.hip, gemm_fp8.hip)
+// ---- host side: the GEMM plan (gemm_plan.hip: plan_gemm) and the launches that carry it out (gemm_bf16.hip routes to gemm_stream.hip, gemm_tiled.hip, gemm_v3.hip, gemm_fp8.hip)
 
 // tile picks = rows of the tile table in gemm_plan.hip (k_tiles) = the public plan-counter slots (include/cover_hip.h): never renumbered
 enum TilePick {
@@ -706,6 +706,20 @@ static inline hipError_t launch_kernel(int cls, double work, dim3 grid, dim3 blo
         hipLaunchKernelGGL(kfn, grid, block, lds, st, args...);
     return hipSuccess;
 }
+
+// gemm_tiled.hip: the launch of a GK_TILED / GK_TILED_PC plan
+PLAN_API hipError_t launch_gemm_tiled(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp,
+                                      const EpiDev& epi, float* partial, int variant, int prof_cls, double prof_work, hipStream_t st);
+
+// gemm_stream.hip: the three weight-streaming generations (GK_SKINNY / GK_SKINNY2 / GK_SKINNY3 plans)
+PLAN_API hipError_t launch_skinny1(const GemmPlan& p, const bf16_t* A, int lda, const bf16_t* Wp, float* ws, int M, int N, int K, int Kp, hipStream_t st);
+PLAN_API hipError_t launch_skinny2(const Skinny2Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, float* ws, int M, int N, int K, int Kp,
+                                   const uint8_t* w8, const float* w8s, int kl, hipStream_t st);
+PLAN_API hipError_t launch_skinny3(const Skinny3Plan& p, const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int Kp,
+                                   const EpiDev& epi, float* partial, hipStream_t st);
+
+// gemm_reduce.hip: the completion of a planned launch (GemmPlan.done, GemmPlan.norm_launch)
+PLAN_API hipError_t complete_splitk(const GemmPlan& p, const EpiDev& epi, const float* ws, void* C, int ldc, int M, int N, hipStream_t st);
 
 // gemm_fp8.hip: the LDS-tiled GEMM on the MX-scaled fp8 matrix instruction (GK_F8_PC / GK_F8_V3 plans)
 bool gemm_fp8_tiled_supported(int pick);

@@ -1,6 +1,6 @@
 // The GEMM planner: which kernel family, tile, grid and K split launch_gemm_bf16 (gemm_bf16.hip) takes for a problem, and what completes
-// it. Host code only and no HIP call: cover_gemm_plan answers from here without a GPU, and the launchers in gemm_bf16.hip / gemm_v3.hip /
-// gemm_fp8.hip carry out the GemmPlan (gemm_common.h) they are handed. The measurement comments are the record of why each rule exists.
+// it. Host code only and no HIP call: cover_gemm_plan answers from here without a GPU, and the launchers in gemm_stream.hip / gemm_tiled.hip /
+// gemm_v3.hip / gemm_fp8.hip / gemm_reduce.hip carry out the GemmPlan (gemm_common.h) they are handed. The measurement comments are the record of why each rule exists.
 #include <stdlib.h>
 #include <atomic>
 #include "gemm_common.h"

@@ -1,6 +1,6 @@
 // Self-loading 8-wave tiled bf16 GEMM for gfx950 ("v3"): C[M,N] = epi(A[M,K] . W[N,K]^T), fp32 accumulate on v_mfma_f32_16x16x32_bf16.
 //
-// Same operand layouts, LDS images and epilogue as gemm_tiled_pc (gemm_bf16.hip): packed fragment-major weights, activation rows
+// Same operand layouts, LDS images and epilogue as gemm_tiled_pc (gemm_tiled.hip): packed fragment-major weights, activation rows
 // staged with the XOR chunk swizzle on the SOURCE address of the LDS-DMA, accumulators acc[n-block][m-fragment]. What differs is who
 // does what, and when:
 //   * no loader waves. gemm_tiled_pc's 4 loader waves make the block 12 waves = 3 per SIMD = 168 registers per lane, which is what the

@@ -7,7 +7,8 @@
 
 typedef uint16_t bf16_t;
 
-// ---- gemm_bf16.hip (kernels, launchers), gemm_plan.hip (the planner: gemm_plan_query, gemm_plan_counts, gemm_workspace_bytes) ----
+// ---- gemm_bf16.hip (the entry point; it maps the kernel families to their files: gemm_stream.hip, gemm_tiled.hip, gemm_reduce.hip, gemm_pack.hip),
+// ---- gemm_plan.hip (the planner: gemm_plan_query, gemm_plan_counts, gemm_workspace_bytes) ----
 // C[M,N] = epi(A[M,K] x W[N,K]^T); W pre-packed by cover_pack_weight_bf16 (fragment-major).
 hipError_t launch_gemm_bf16(const bf16_t* A, int lda, const bf16_t* Wp, void* C, int ldc, int M, int N, int K,
                             const cover_gemm_epi* epi, float* splitk_ws, size_t splitk_ws_bytes, int variant,

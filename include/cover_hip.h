@@ -147,7 +147,7 @@ size_t cover_gemm_workspace_bytes(int M, int N, int K);
 int cover_gemm_bf16(const void* A, int lda, const void* Wp, void* C, int ldc, int M, int N, int K,
                     const cover_gemm_epi* epi, void* splitk_ws, size_t splitk_ws_bytes, int variant, void* stream);
 /* Which kernel plan every GEMM launch of this process took since the last reset (test / audit hook: a parity test can assert
- * that a shape really ran on the tile it means to cover). counts[i], i = index into the tile table of launch_gemm_bf16 (gemm_bf16.hip):
+ * that a shape really ran on the tile it means to cover). counts[i], i = index into the tile table of launch_gemm_bf16 (gemm_plan.hip):
  *   [0..8]  gemm_tiled: 0 128x128, 1 64x128, 2 64x64 (3 stages), 3 128x128 (4 stages), 4 256x128, 5 128x256, 6 128x128 (8 waves), 7 64x128 (3 stages),
  *           8 128x128 (3 stages)        [10] gemm_tiled_pc 64x128, four loader waves, 4 stages (bf16; 9, 11..18 exist as fp8 kernels only and count in [21])
  *   [19] second-generation weight streaming (gemm_skinny2)   [20] third generation (gemm_skinny3)   [21] fp8 MFMA tiles (any)   [22] first generation

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prefill GEMMs of a 7B decoder at M = 448 (256 patch rows + 8 x 24 text rows), weights rotating over enough copies to stay out of
 the Infinity Cache: us per launch and TFLOP/s per shape, plus the sum over a layer (what roofline_mfma.prefill measures).
-Usage: python tools/dbg/bench_prefill.py [M] [reps]   (environment knobs of gemm_bf16.hip apply: COVER_TILE_PICK, COVER_LIB_PATH ...)
+Usage: python tools/dbg/bench_prefill.py [M] [reps]   (the planner's environment knobs, gemm_plan.hip, apply: COVER_TILE_PICK, COVER_LIB_PATH ...)
 FP8=1: e4m3 weights + pre-quantised e4m3 activation rows (the config-5 decode GEMMs at M = 512; the quantiser launch is timed on its own)."""
 import os
 import sys
