@@ -211,6 +211,13 @@ class RefineArgs(C.Structure):
                 ("out", c_p), ("elite_rows_out", c_p), ("elite_scores_out", c_p), ("mean_out", c_p), ("sd_out", c_p), ("votes_out", c_p)]
 
 
+class SmoothArgs(C.Structure):
+    _fields_ = [("src", c_p), ("n_stride", c_ll), ("t_stride", c_ll), ("scores", c_p), ("dim_scale", c_p), ("centers", c_p),
+                ("n_centers", c_i), ("tok_vocab", c_i), ("G", c_i), ("group_rows", c_i), ("h", c_i), ("split_gripper", c_i),
+                ("radius2", c_f), ("shrink", c_f),
+                ("smoothed_out", c_p), ("density_out", c_p), ("neighbours_out", c_p), ("group_mean_out", c_p)]
+
+
 class BeamMergeArgs(C.Structure):
     _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("feed_pad", c_ll),
                 ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p), ("cum_out", c_p),
@@ -295,7 +302,7 @@ _STRUCTS = {
     "cover_token_fsm": TokenFsm,
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_augment_args": AugmentArgs,
     "cover_proposal_prior_args": ProposalPriorArgs, "cover_member_scores_args": MemberScoresArgs,
-    "cover_refine_args": RefineArgs,
+    "cover_refine_args": RefineArgs, "cover_smooth_args": SmoothArgs,
     "cover_beam_merge_args": BeamMergeArgs,
     "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
     "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
@@ -378,6 +385,8 @@ SYMBOLS = {
     "cover_proposal_prior_actions": (c_i, [_P(ProposalPriorArgs), c_p]),
     "cover_refine_tokens": (c_i, [_P(RefineArgs), c_p]),
     "cover_refine_actions": (c_i, [_P(RefineArgs), c_p]),
+    "cover_smooth_scores_tokens": (c_i, [_P(SmoothArgs), c_p]),
+    "cover_smooth_scores_actions": (c_i, [_P(SmoothArgs), c_p]),
     "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
     "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
     "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),

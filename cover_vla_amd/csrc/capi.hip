@@ -440,6 +440,18 @@ int cover_refine_actions(const cover_refine_args* a, void* stream) {
     HIPCHK(launch_refine_actions(a, ST(stream)), "refine_actions (" REFINE_LIMITS ")");
     return COVER_OK;
 }
+#define SMOOTH_LIMITS "G >= 1, 1 <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, radius2 finite and > 0, shrink finite and " \
+                      ">= 0, src / scores / dim_scale / smoothed_out required"
+int cover_smooth_scores_tokens(const cover_smooth_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_smooth_scores_tokens: null args");
+    HIPCHK(launch_smooth_scores_tokens(a, ST(stream)), "smooth_scores_tokens (" SMOOTH_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_smooth_scores_actions(const cover_smooth_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_smooth_scores_actions: null args");
+    HIPCHK(launch_smooth_scores_actions(a, ST(stream)), "smooth_scores_actions (" SMOOTH_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -565,7 +577,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
-    SZ(cover_member_scores_args); SZ(cover_refine_args);
+    SZ(cover_member_scores_args); SZ(cover_refine_args); SZ(cover_smooth_args);
 #undef SZ
     return 0;
 }

@@ -187,6 +187,54 @@ class ProposalPrior(_ProposalPriorFields):
         return super().__new__(cls, int(samples_per_prompt), float(sigma), float(sd_floor), log_share)
 
 
+class _SmoothFields(NamedTuple):
+    radius: float
+    dim_scale: Any
+    shrink: float = 0.0
+    split_gripper: bool = True
+
+
+_SMOOTH_SCALES = {}      # (dim_scale, device) -> the fp32 [6] device tensor: one upload per device
+
+
+class Smooth(_SmoothFields):
+    """What score_histories(smooth=), verify_and_select(smooth=) and OpenVLA.smooth_scores take: every candidate's score is replaced by
+    the kernel-weighted mean of its prompt group's scores, weight max(0, 1 - d2 / radius^2) with d2 the squared distance of the rows'
+    translation / rotation values scaled per dim by dim_scale (a 6-sequence of finite numbers >= 0; 0 leaves a dim out), shrunk towards
+    the group's mean score: (sum w s + shrink * mean) / (sum w + shrink) (ops.smooth_scores_tokens: the arithmetic). split_gripper: rows
+    of different gripper class (value >= 0.5) do not back each other. radius > 0 and shrink >= 0, both finite. Values are checked here
+    (CoverError), shapes against the rows in ops. No default radius or scale exists and no radius, scale or shrink is recommended: there
+    is no task-success data to choose them on."""
+    __slots__ = ()
+
+    def __new__(cls, radius, dim_scale, shrink=0.0, split_gripper=True):
+        import ctypes
+        from ._lib import CoverError
+        from .ops import smooth_dim_scale
+        f32 = lambda v: ctypes.c_float(v).value                     # the value the launch receives
+        for name, v in (("radius", radius), ("shrink", shrink)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(f32(v))):
+                raise CoverError(f"Smooth: {name} must be a finite number (got {v!r})")
+        if not (f32(radius) > 0 and math.isfinite(f32(f32(radius) * f32(radius))) and f32(f32(radius) * f32(radius)) > 0):
+            raise CoverError(f"Smooth: radius must be > 0 with a finite fp32 square > 0 (got {radius!r})")
+        if not shrink >= 0:
+            raise CoverError(f"Smooth: shrink must be >= 0 (got {shrink!r})")
+        scale = tuple(float(v) for v in smooth_dim_scale(dim_scale, "Smooth"))
+        return super().__new__(cls, float(radius), scale, float(shrink), bool(split_gripper))
+
+    def scale_on(self, device):
+        """dim_scale as the fp32 [6] tensor the launch reads, uploaded once per device."""
+        import torch
+        key = (self.dim_scale, str(torch.device(device)))
+        if key not in _SMOOTH_SCALES:
+            _SMOOTH_SCALES[key] = torch.tensor(self.dim_scale, dtype=torch.float32).to(device)
+        return _SMOOTH_SCALES[key]
+
+    def kwargs(self, device) -> dict:
+        """The keywords of ops.smooth_scores_tokens / ops.smooth_scores_actions."""
+        return dict(radius=self.radius, dim_scale=self.scale_on(device), shrink=self.shrink, split_gripper=self.split_gripper)
+
+
 class TokenGrammar(NamedTuple):
     """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
     allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)
@@ -336,7 +384,7 @@ def process_inputs(action_queue: Sequence[np.ndarray], verifier_action: bool, ac
 def verify_and_select(verifier, raw_image, task_description: str, task_list: Sequence[str], action_queue, action_history,
                       samples_per_prompt: int, n_action_steps: int = 4, threshold: float = 0.1, stats=None,
                       process_image: bool = True, candidate_prior=None, prior_beta: float = 0.0, member_kappa: Optional[float] = None,
-                      member_mode: str = "lcb"):
+                      member_mode: str = "lcb", smooth: Optional["Smooth"] = None):
     """run_simpler_eval_with_openpi.py:329-401: stage 1 scores candidate 0 under the current instruction; if its score
     is < threshold, stage 2 scores all candidates grouped per prompt; then the gripper majority vote inside the winner's
     prompt group and extraction of the winner's remaining steps.
@@ -355,7 +403,13 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     times the spread of the ensemble members' own scores, or the worst member's score -- with the threshold, a pessimistic gate, and
     stage 2 selects on the robust score (plus the prior, when one is used). The two keywords reach the verifier only when member_kappa
     is not None. The dict carries member_kappa and, when the verifier keeps last_member_stats, the winner's `spread` and
-    `member_agreement`, the number of members whose own grouped arg-max is the decision. No member_kappa is recommended."""
+    `member_agreement`, the number of members whose own grouped arg-max is the decision. No member_kappa is recommended.
+    smooth (a Smooth; None = off): stage 2 selects on the neighbourhood-smoothed score (EfficientEnsembleMerged.score_histories), the
+    smoothed robust score with member_kappa, plus the prior when one is used. Forwarded as candidate_prior is: to stage 2 only (stage 1
+    scores one candidate, which has no neighbours), and only when not None. When the verifier keeps last_smooth_stats and stage 2 ran,
+    the dict carries the winner's `neighbours`. No radius, scale or shrink is recommended."""
+    if smooth is not None and not isinstance(smooth, Smooth):
+        raise ValueError("verify_and_select: smooth must be a host.Smooth or None")
     if not (prior_beta >= 0.0 and math.isfinite(prior_beta)):
         raise ValueError(f"verify_and_select: prior_beta must be finite and >= 0 (got {prior_beta})")
     if member_kappa is not None and not (member_kappa >= 0.0 and math.isfinite(member_kappa)):
@@ -377,7 +431,8 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
         max_score, _, max_hist, gidx = verifier.compute_max_similarity_scores_batch(
             images=images, instructions=[task_description] * B, all_action_histories=hist_v,
             cfg_repeat_language_instructions=samples_per_prompt,
-            **(dict(candidate_prior=candidate_prior, prior_beta=prior_beta) if use_prior else {}), **member_kw)
+            **(dict(candidate_prior=candidate_prior, prior_beta=prior_beta) if use_prior else {}), **member_kw,
+            **({} if smooth is None else dict(smooth=smooth)))
         max_instruction = task_list[int(gidx)]
         stage2 = True
     gidx = int(gidx)
@@ -403,6 +458,9 @@ def verify_and_select(verifier, raw_image, task_description: str, task_list: Seq
     if stats is not None:      # the latest scoring call's: stage 2's when it ran, else stage 1's one candidate
         out["spread"] = float(_host_array(stats["spread"])[gidx])
         out["member_agreement"] = int((_host_array(stats["member_result"])[:, 0] == gidx).sum())
+    stats = getattr(verifier, "last_smooth_stats", None) if smooth is not None and stage2 else None
+    if stats is not None:
+        out["neighbours"] = int(_host_array(stats["neighbours"])[gidx])
     return out
 
 

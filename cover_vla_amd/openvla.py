@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import ops
+from . import host, ops
 from .graphs import ReplayGraph
 from .ops import RowParam
 from .models import BF, Decoder, KvGeometry, VitTower, _f32
@@ -519,6 +519,19 @@ class OpenVLA:
             raise L.CoverError("OpenVLA.refine: normals must be an fp32 tensor [prompts, n_new, n_gen // 7, 6]")
         return ops.refine_tokens(tokens, scores, group_rows, n_elite, normals.shape[1], normals, self.bin_centers(), self.c["tok_vocab"],
                                  steps=self.n_gen // 7, sigma=sigma, sd_floor=sd_floor, elites=elites)
+
+    def smooth_scores(self, tokens: torch.Tensor, scores: torch.Tensor, group_rows: int, smooth, *, stats=False):
+        """Neighbourhood-smoothed scores of scored chunks (ops.smooth_scores_tokens with this model's tok_vocab, bin centres and
+        steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] (sampled, augmented or refined) and their scores fp32 [P * group_rows]
+        (score_histories' scores or robust) -> fp32 [P * group_rows], every score replaced by the kernel-weighted mean of its prompt's
+        scores over the rows' de-tokenised translation / rotation values, shrunk towards the prompt's mean score. smooth: a host.Smooth
+        (radius, dim_scale, shrink, split_gripper; none has a default or a recommended value). The result goes where scores go:
+        ops.group_argmax, ops.prior_select, refine. stats=True -> (smoothed, ops.SmoothStats). One launch; the policy is not run. Off by
+        default: nothing calls this."""
+        if not isinstance(smooth, host.Smooth):
+            raise L.CoverError("OpenVLA.smooth_scores: smooth must be a host.Smooth")
+        return ops.smooth_scores_tokens(tokens, scores, group_rows, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
+                                        stats=stats, **smooth.kwargs(tokens.device))
 
     def proposal_prior(self, tokens: torch.Tensor, group_rows: int, n_fit: int, *, sigma, sd_floor, log_share=None):
         """The proposal log-density prior of action-token chunks (ops.proposal_prior_tokens with this model's tok_vocab, bin centres and

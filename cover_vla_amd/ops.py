@@ -1673,6 +1673,111 @@ def refine_actions(actions, scores, group_rows, n_elite, n_new, normals, *, sigm
                    lambda G, R: (G * R, actions.shape[1], 7), stats, elites)
 
 
+# ------------------------------------------------------------------------------------------------ neighbourhood-smoothed scores
+class SmoothStats(NamedTuple):
+    """What smooth_scores_tokens / smooth_scores_actions return beside the smoothed scores with stats=True."""
+    density: torch.Tensor      # fp32 [rows]: the row's summed pair weights (self included) / group_rows
+    neighbours: torch.Tensor   # int32 [rows]: the rows of its group with a weight > 0, self included
+    group_mean: torch.Tensor   # fp32 [G]: the mean of the group's finite scores (0.0 when it has none)
+
+
+def smooth_dim_scale(dim_scale, what="smooth_dim_scale") -> np.ndarray:
+    """The host check of a smoothing scale: a 6-sequence of finite numbers >= 0 (in fp32 as well) -> fp32 numpy [6]."""
+    try:
+        v = np.asarray(dim_scale, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise L.CoverError(f"{what}: dim_scale must be 6 numbers (got {dim_scale!r})") from None
+    if v.shape != (6,):
+        raise L.CoverError(f"{what}: dim_scale must have 6 entries, one per translation / rotation dim (got shape {v.shape})")
+    with np.errstate(over="ignore"):
+        f = v.astype(np.float32)
+    if not (np.isfinite(v).all() and np.isfinite(f).all() and (v >= 0).all()):
+        raise L.CoverError(f"{what}: every dim_scale entry must be finite and >= 0 (got {dim_scale!r})")
+    return f
+
+
+def _smooth(what, fn, src, n_stride, t_stride, N, steps, scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats,
+            centers=None, tok_vocab=0):
+    """The checks and the launch both smoothing wrappers share."""
+    if isinstance(group_rows, bool) or not isinstance(group_rows, (int, np.integer)):
+        raise L.CoverError(f"{what}: group_rows must be an integer (got {group_rows!r})")
+    S = int(group_rows)
+    if not 1 <= S <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= group_rows <= 4096 and rows % group_rows == 0 are required (got rows={N}, group_rows={S})")
+    G = N // S
+    if not 1 <= steps <= 64 or N > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or not scores.is_contiguous():
+        raise L.CoverError(f"{what}: scores must be contiguous fp32 [rows] = [{N}] "
+                           f"(got {tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__})")
+    for name, v in (("radius", radius), ("shrink", shrink)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not math.isfinite(v):
+            raise L.CoverError(f"{what}: {name} must be a finite number (got {v!r})")
+    r = C.c_float(float(radius)).value
+    radius2 = C.c_float(r * r).value            # squared once, in fp32 (the product of two fp32 values is exact in float64)
+    shrink = C.c_float(float(shrink)).value
+    if not (r > 0.0 and math.isfinite(radius2) and radius2 > 0.0):
+        raise L.CoverError(f"{what}: radius must be > 0 with a finite fp32 square > 0 (got {radius!r})")
+    if not (math.isfinite(shrink) and shrink >= 0.0):
+        raise L.CoverError(f"{what}: shrink must be finite and >= 0 (got {shrink!r})")
+    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Smooth's upload: validated there, once
+        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
+            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
+    else:
+        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
+    _chk_dev(src, scores, centers, out)
+    dev = src.device
+    dim_scale = dim_scale.to(dev)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
+        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
+    if any(t is not None and t.device != dev for t in (scores, dim_scale, centers, out)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=dev)
+    st = SmoothStats(torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                     torch.empty(G, dtype=torch.float32, device=dev)) if stats else None
+    a = L.SmoothArgs()
+    a.src, a.n_stride, a.t_stride, a.scores, a.dim_scale = src.data_ptr(), n_stride, t_stride, scores.data_ptr(), dim_scale.data_ptr()
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.G, a.group_rows, a.h, a.split_gripper = G, S, steps, 1 if split_gripper else 0
+    a.radius2, a.shrink = radius2, shrink
+    a.smoothed_out = out.data_ptr()
+    if st is not None:
+        a.density_out, a.neighbours_out, a.group_mean_out = st.density.data_ptr(), st.neighbours.data_ptr(), st.group_mean.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    return (out, st) if stats else out
+
+
+def smooth_scores_tokens(tokens, scores, group_rows, centers, tok_vocab, *, steps=1, radius, dim_scale, shrink=0.0, split_gripper=True,
+                         out=None, stats=False):
+    """Neighbourhood-smoothed scores of action tokens (cover_smooth_scores_tokens): tokens int64 [G * group_rows, >= 7 steps] (unit column
+    stride, any row stride; row i belongs to prompt i // group_rows) with scores fp32 [rows], contiguous -- score_histories' scores or
+    robust -> fp32 [rows], which goes where those go (group_argmax, prior_select, refine_tokens). Every row's score is replaced by the
+    kernel-weighted mean of its group's scores, w = max(0, 1 - d2 / radius^2) with d2 = sum over (step, dim < 6) of
+    ((x_n - x_j) * dim_scale[dim])^2 on the de-tokenised values centers[clamp(tok_vocab - token - 1)], shrunk towards the mean m0 of the
+    group's finite scores: (sum w s + shrink * m0) / (sum w + shrink); shrink == 0 is the plain local mean. The row itself has weight 1.
+    split_gripper: rows whose gripper class (value >= 0.5) differs at any step have weight 0. A dim of scale 0 is left out, a NaN there
+    included. A row whose own score is not finite keeps it bit for bit and is no evidence for the others. radius is squared once in fp32;
+    dim_scale is a 6-sequence of finite numbers >= 0, validated here and uploaded, or an fp32 [6] tensor already on the device
+    (host.Smooth's, validated there; on the device a negative or non-finite entry makes every pair weight 0). No radius, scale or shrink
+    is chosen or recommended: there is no task-success data to choose them on. stats=True -> (smoothed, SmoothStats). Every rounding is
+    specified in include/cover_hip.h. One launch, no workspace, recordable."""
+    steps, n_stride = _token_rows("smooth_scores_tokens", tokens, steps, centers)
+    return _smooth("smooth_scores_tokens", lambda h: h.cover_smooth_scores_tokens, tokens, n_stride, 7, tokens.shape[0], steps, scores,
+                   group_rows, radius, dim_scale, shrink, split_gripper, out, stats, centers=centers, tok_vocab=tok_vocab)
+
+
+def smooth_scores_actions(actions, scores, group_rows, *, radius, dim_scale, shrink=0.0, split_gripper=True, out=None, stats=False):
+    """The same for float rows (cover_smooth_scores_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last stride and any
+    other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer, or the padded history tensor [N, 10, 7]
+    score_histories holds (rows and pads that are equal within a group contribute exact zeros to the distance). A NaN element in a dim
+    of non-zero scale isolates its row: every pair weight with it is 0. See smooth_scores_tokens."""
+    _action_rows("smooth_scores_actions", actions)
+    return _smooth("smooth_scores_actions", lambda h: h.cover_smooth_scores_actions, actions, actions.stride(0), actions.stride(1),
+                   actions.shape[0], actions.shape[1], scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats)
+
+
 # ------------------------------------------------------------------------------------------------ beam search
 def beam_merge(cum, cand_tok, cand_lp, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None, out_step_lp=None):
     """One beam-search step over G = rows / n_beams prompt groups (cover_beam_merge; row g * n_beams + b is beam b of group g).

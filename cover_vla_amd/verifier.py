@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import ops
+from . import host, ops
 from .models import BF, VitTower, _f32
 
 
@@ -370,6 +370,7 @@ class EfficientEnsembleMerged:
         CPU transforms are injected (they are un-vendored pip dependencies of the reference, :57,69)."""
         self.device = device
         self.last_member_stats = None            # the dict of the latest score_histories call that was given member_kappa
+        self.last_smooth_stats = None            # the dict of the latest compute_max_similarity_scores_batch call that was given smooth
         dev = torch.device(device)
         if isinstance(merged_checkpoint, str):   # a converted directory (safetensors + JSON) or a .pt read WITHOUT arbitrary unpickling
             from .loaders import load_verifier_checkpoint
@@ -452,7 +453,7 @@ class EfficientEnsembleMerged:
     def score_histories(self, its: torch.Tensor, all_action_histories, group_size=1, pad: Optional[torch.Tensor] = None, *,
                         prior: Optional[torch.Tensor] = None, prior_beta: float = 0.0, length_normalize: bool = False,
                         prior_tokens: Optional[torch.Tensor] = None, pad_token_id: Optional[int] = None, top_m: int = 0,
-                        member_kappa: Optional[float] = None, member_mode: str = "lcb"):
+                        member_kappa: Optional[float] = None, member_mode: str = "lcb", smooth: Optional[host.Smooth] = None):
         """Trajectory encoder per candidate + fusion + scoring + grouped arg-max against precomputed image-text embeddings.
         all_action_histories: list of [h<=10, 7] host arrays (reference format), OR an already padded DEVICE tensor
         fp32 [N,10,7] together with its padding mask `pad` uint8 [N,10] (ops.tokens_to_histories): no host round trip.
@@ -467,7 +468,16 @@ class EfficientEnsembleMerged:
         arg-max of `robust` -- member_mode "lcb": scores - member_kappa * spread (the scores' own bits at member_kappa 0), "min": the
         worst member's score, member_kappa 0 -- while `scores` stays the fused score. With a prior or top_m as well, ops.prior_select
         is fed `robust` in place of `scores`: combined = robust + prior_beta * prior, and `result` / `best` come from it as above.
-        The dict of the latest such call is kept as self.last_member_stats."""
+        The dict of the latest such call is kept as self.last_member_stats.
+        smooth (a host.Smooth; None, the default, launches and returns nothing more) makes the decision neighbourhood-aware: one
+        ops.smooth_scores_actions launch replaces every candidate's value -- `robust` with member_kappa, else `scores` -- by the
+        kernel-weighted mean of its group's values over the history tensor itself (steps = its 10 rows; past rows and pads are equal
+        within a group and contribute exact zeros, so the distance is that of the candidates' own steps in the verifier's input space),
+        shrunk towards the group's mean. The dict gains smoothed, density, neighbours and smooth_group_mean; `result` / `best` are the
+        grouped arg-max of `smoothed` while `scores` (and `robust`) stay what they were. With a prior or top_m as well, ops.prior_select
+        is fed `smoothed`: combined = smoothed + prior_beta * prior. No radius, scale or shrink is recommended."""
+        if smooth is not None and not isinstance(smooth, host.Smooth):
+            raise L.CoverError("score_histories: smooth must be a host.Smooth or None")
         if torch.is_tensor(all_action_histories) and all_action_histories.is_cuda:
             hb = all_action_histories.contiguous()
         else:
@@ -484,6 +494,11 @@ class EfficientEnsembleMerged:
         if member_kappa is not None:
             out.update(ops.member_scores(its.contiguous(), acts, scores, group_size, member_kappa, member_mode))   # result / best: the robust decision
             base = out["robust"]
+        if smooth is not None:
+            base, st = ops.smooth_scores_actions(hb, base, group_size, stats=True, **smooth.kwargs(self._dev))
+            out.update(smoothed=base, density=st.density, neighbours=st.neighbours, smooth_group_mean=st.group_mean)
+            if prior is None and not top_m:
+                out["result"], out["best"] = ops.group_argmax(base, group_size)
         if prior is not None or top_m:
             if prior is None:           # rank by the verifier score alone: beta 0 never reads the (summed) prior into the decision
                 sel = ops.prior_select(base, base, group_size, 0.0, top_m=top_m)
@@ -510,7 +525,7 @@ class EfficientEnsembleMerged:
         it is accepted only with an empty `normals`). score_kw goes to every score_histories call (member_kappa, member_mode, prior_beta,
         top_m, ...).
         Round 0 scores the given candidates. Each later round refines on the per-candidate value the previous decision was made on --
-        `combined` if that dict has it, else `robust`, else `scores` -- and scores the new rows with group_size = n_elite + K_r. Returns the
+        `combined` if that dict has it, else `smoothed`, else `robust`, else `scores` -- and scores the new rows with group_size = n_elite + K_r. Returns the
         LAST score_histories dict plus `candidates` (the final rows, which `result` indexes) and `rounds` (per round, round 0 included, a
         dict of that round's `best`, `result` and `elite_rows`: None in round 0 and when refine returns no elites). The elites are
         carried verbatim, so a row-wise scorer's best value per prompt never decreases; no n_elite, K, round count or sigma is
@@ -521,7 +536,7 @@ class EfficientEnsembleMerged:
         cands, S, n_fit, elite_rows, rounds = candidates, int(group_rows), None, None, []
         for r in range(len(normals) + 1):
             if r > 0:
-                values = out["combined"] if "combined" in out else out["robust"] if "robust" in out else out["scores"]
+                values = next(out[k] for k in ("combined", "smoothed", "robust", "scores") if k in out)
                 z = normals[r - 1]
                 got = refine(cands, values, S, n_elite, z)
                 cands, elite_rows = (got[0], getattr(got[1], "rows", got[1])) if isinstance(got, tuple) else (got, None)
@@ -537,15 +552,17 @@ class EfficientEnsembleMerged:
         return out
 
     def score_features(self, patch_features, text_features, all_action_histories, group_size=1, candidate_prior=None, prior_beta=0.0,
-                       member_kappa=None, member_mode="lcb"):
+                       member_kappa=None, member_mode="lcb", smooth=None):
         """Scores every candidate history against ONE (image, text) pair given its features. Returns a dict with the
         device tensors (scores [N], result int32[4], best f32[2]) plus per-member embeddings. candidate_prior ([N] or [N, steps]
         log-probabilities, host or device) with prior_beta: the decision is made on scores + prior_beta * prior (score_histories).
-        member_kappa / member_mode: the decision is made on the disagreement-aware robust score (score_histories)."""
+        member_kappa / member_mode: the decision is made on the disagreement-aware robust score (score_histories). smooth (a
+        host.Smooth): the decision is made on the neighbourhood-smoothed score (score_histories)."""
         if candidate_prior is not None:
             candidate_prior = torch.as_tensor(candidate_prior, dtype=torch.float32).to(self._dev)
         return self.score_histories(self.image_text_embeddings(patch_features, text_features), all_action_histories, group_size,
-                                    prior=candidate_prior, prior_beta=prior_beta, member_kappa=member_kappa, member_mode=member_mode)
+                                    prior=candidate_prior, prior_beta=prior_beta, member_kappa=member_kappa, member_mode=member_mode,
+                                    smooth=smooth)
 
     def fuse_embeddings(self, image, instruction, action_histories):
         """efficient_ensemble_merged.py:249-293 -> (fused_image_text [N,512] (the one pair's embedding, a row per history),
@@ -579,18 +596,22 @@ class EfficientEnsembleMerged:
 
     def compute_max_similarity_scores_batch(self, images, instructions, all_action_histories,
                                             cfg_repeat_language_instructions=1, candidate_prior=None, prior_beta=0.0,
-                                            member_kappa=None, member_mode="lcb"):
+                                            member_kappa=None, member_mode="lcb", smooth=None):
         """efficient_ensemble_merged.py:309-454. The reference scores candidates against the FIRST (image, text) pair only
         (reference_scores = similarity_matrix[0], :421-425), on both of its encode paths, so one pair is encoded here.
         candidate_prior ([N] or [N, steps] policy log-probabilities) with prior_beta selects on score + prior_beta * prior; the
         returned max_score is then the winner's COMBINED score, not its cosine score. member_kappa (None = off) with member_mode
         selects on the disagreement-aware robust score (score_histories); the returned max_score is then the winner's ROBUST score --
         or, with a prior as well, its combined score robust + prior_beta * prior -- and the per-member figures are in
-        self.last_member_stats."""
+        self.last_member_stats. smooth (a host.Smooth; None = off) selects on the neighbourhood-smoothed score (score_histories); the
+        returned max_score is then the winner's SMOOTHED score, or its combined score with a prior; the dict of that call is kept as
+        self.last_smooth_stats."""
         group_size = cfg_repeat_language_instructions
         pf, tf = self._encode_pair(images[0], instructions[0])
         r = self.score_features(pf, tf, all_action_histories, group_size, candidate_prior=candidate_prior, prior_beta=prior_beta,
-                                member_kappa=member_kappa, member_mode=member_mode)
+                                member_kappa=member_kappa, member_mode=member_mode, smooth=smooth)
+        if smooth is not None:
+            self.last_smooth_stats = r
         result = r["result"].cpu()
         best = r["best"].cpu()
         gidx, gbest = int(result[0]), int(result[1])

@@ -979,6 +979,56 @@ typedef struct cover_refine_args {
 int cover_refine_tokens(const cover_refine_args* args, void* stream);
 int cover_refine_actions(const cover_refine_args* args, void* stream);
 
+/* Neighbourhood-smoothed scores: per prompt group a kernel-weighted local mean (Nadaraya-Watson) of one fp32 score per row over the rows'
+ * positions in the 6-D action space, shrunk towards the group mean where a row has few neighbours. A group is group_rows (S) contiguous
+ * rows (row i belongs to group i / S) with one fp32 score per row -- the verifier's scores or cover_member_scores' robust; the output is
+ * fp32 [G * S] and goes where those go (cover_group_argmax, cover_prior_select, cover_refine_*). One wave per row, 16 rows per block,
+ * several blocks per group; the group's values pass through LDS in tiles of rows. One launch, no workspace, no atomics, recordable; no
+ * result depends on the tiling. All arithmetic is fp32, one rounding per operation, never an fma.
+ * Pair weight of row n and row j != n of one group, x the rows' values:
+ *   d2 = 0.0f;  for t in step order, d = 0..5 with dim_scale[d] != 0:  diff = x_n - x_j;  sc = diff * dim_scale[d];  sq = sc * sc;
+ *   d2 = d2 + sq   (a dim whose scale is 0 is not read into the sum: a NaN there is invisible)
+ *   w = (d2 < radius2) ? 1.0f - d2 / radius2 : 0.0f   a divide, then a subtract; a NaN d2 fails the comparison, so w = 0
+ *   split_gripper != 0: if the classes (x_6 >= 0.5f) of n and j differ at any step, w = 0. Dim 6 never enters d2.
+ *   The self pair j == n has w = 1.0f by definition. A dim_scale entry that is negative or not finite makes every pair weight 0 (the
+ *   self pair keeps 1); there is no trap.
+ * Row sums, lane l of the row's wave: num = den = dsum = 0.0f, cnt = 0; for j = l, l + 64, ... < S in ascending order, where w > 0:
+ *   dsum = dsum + w;  cnt += 1;  and if scores[j] is finite:  den = den + w;  prod = w * scores[j];  num = num + prod
+ *   (where w == 0 no product is formed). The 64 partials of num, den and dsum each meet in the xor butterfly v = v + v[lane ^ o],
+ *   o = 32, 16, ..., 1; cnt is an integer sum.
+ * Group mean m0: the same lane-strided chain (sum = sum + scores[j] over the finite scores) and butterfly, divided once by (float)count
+ *   of the finite scores; with no finite score in the group no divide is made, m0 is unused and group_mean_out holds 0.0f.
+ * Result: a row whose own score is not finite (NaN, +-inf) stores its score bit for bit (a NaN keeps its payload; a -inf from a prior
+ *   stays -inf). Every other row has den >= 1 through its self term:
+ *   shrink == 0:  smoothed = num / den   (no product is formed)
+ *   otherwise  :  tm = shrink * m0;  nn = num + tm;  dd = den + shrink;  smoothed = nn / dd
+ * cover_smooth_scores_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (n_stride >= 7 h; t_stride
+ *   unused), x = centers[clamp(tok_vocab - token - 1, 0, n_centers - 1)] (cover_tokens_to_histories' rule).
+ * cover_smooth_scores_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit last
+ *   stride: a [B, steps, 7] view of a [B, chunk, 32] buffer, or a padded history tensor [N, 10, 7], is read in place); centers unused.
+ * Only the cells named above are read: nothing of src outside the [rows][h][7] view.
+ * Optional outputs (NULL = not written): density_out fp32 [G * S] = dsum / (float)S, neighbours_out int32 [G * S] = cnt (self included),
+ * group_mean_out fp32 [G].
+ * COVER_EINVAL, and nothing launched, unless G >= 1, 1 <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, radius2 finite and
+ * > 0, shrink finite and >= 0, src / scores / dim_scale / smoothed_out non-null and, for tokens, n_stride >= 7 h, centers non-null,
+ * n_centers >= 1. dim_scale is device memory: the caller validates its values (finite, >= 0). */
+typedef struct cover_smooth_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* scores;            /* [G * group_rows] */
+    const float* dim_scale;         /* [6], device */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    int n_centers, tok_vocab;
+    int G, group_rows, h, split_gripper;
+    float radius2, shrink;
+    float* smoothed_out;            /* [G * group_rows] */
+    float* density_out;             /* [G * group_rows], optional */
+    int* neighbours_out;            /* int32 [G * group_rows], optional */
+    float* group_mean_out;          /* [G], optional */
+} cover_smooth_args;
+int cover_smooth_scores_tokens(const cover_smooth_args* args, void* stream);
+int cover_smooth_scores_actions(const cover_smooth_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
