@@ -452,6 +452,19 @@ int cover_smooth_scores_actions(const cover_smooth_args* a, void* stream) {
     HIPCHK(launch_smooth_scores_actions(a, ST(stream)), "smooth_scores_actions (" SMOOTH_LIMITS ")");
     return COVER_OK;
 }
+#define COHERENCE_LIMITS "G >= 1, 1 <= group_rows <= 4096, 1 <= R <= 4096, 1 <= h <= 64, 1 <= hr <= 64, 0 <= shift < hr, G * group_rows <= 2^20, " \
+                         "ref_g_stride 0 or >= (R - 1) * ref_r_stride + 7 hr, ref_r_stride >= 7 hr, w_g_stride 0 or R, gripper_penalty finite " \
+                         "and >= 0, src / ref / ref_weight / step_weight / dim_scale / prior_out required"
+int cover_coherence_prior_tokens(const cover_coherence_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_coherence_prior_tokens: null args");
+    HIPCHK(launch_coherence_prior_tokens(a, ST(stream)), "coherence_prior_tokens (" COHERENCE_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_coherence_prior_actions(const cover_coherence_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_coherence_prior_actions: null args");
+    HIPCHK(launch_coherence_prior_actions(a, ST(stream)), "coherence_prior_actions (" COHERENCE_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -577,7 +590,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_dec_group); SZ(cover_dec_pass); SZ(cover_decode_attn_args); SZ(cover_own_attn_args);
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
-    SZ(cover_member_scores_args); SZ(cover_refine_args); SZ(cover_smooth_args);
+    SZ(cover_member_scores_args); SZ(cover_refine_args); SZ(cover_smooth_args); SZ(cover_coherence_args);
 #undef SZ
     return 0;
 }

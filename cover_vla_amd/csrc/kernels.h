@@ -117,6 +117,9 @@ hipError_t launch_refine_actions(const cover_refine_args* a, hipStream_t st);
 // ---- smooth.hip ----------------------------------------------------------------------------------
 hipError_t launch_smooth_scores_tokens(const cover_smooth_args* a, hipStream_t st);
 hipError_t launch_smooth_scores_actions(const cover_smooth_args* a, hipStream_t st);
+// ---- coherence.hip -------------------------------------------------------------------------------
+hipError_t launch_coherence_prior_tokens(const cover_coherence_args* a, hipStream_t st);
+hipError_t launch_coherence_prior_actions(const cover_coherence_args* a, hipStream_t st);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
 hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);

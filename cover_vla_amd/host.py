@@ -235,6 +235,73 @@ class Smooth(_SmoothFields):
         return dict(radius=self.radius, dim_scale=self.scale_on(device), shrink=self.shrink, split_gripper=self.split_gripper)
 
 
+def coherence_step_weights(h: int, decay: float) -> np.ndarray:
+    """The step weights of the chunk-coherence prior (ops.coherence_prior_tokens / ops.coherence_prior_actions, step_weight=): fp32 numpy
+    [h], entry t = float32(decay ** t) computed in float64 -- step t of a candidate counts decay^t, the early steps (which are executed
+    first) the most. It is made on the host so that the device takes no pow and the prior stays a fixed bit pattern; move it to the
+    device once (torch.from_numpy(...).to(dev); host.Coherence does). decay must be finite and in (0, 1]; 1 weighs every step alike.
+    No decay is recommended."""
+    if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 1 <= h <= 64:
+        raise ValueError(f"coherence_step_weights: an integer 1 <= h <= 64 is required (got {h!r})")
+    if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)) or not (math.isfinite(decay) and 0 < decay <= 1):
+        raise ValueError(f"coherence_step_weights: decay must be a finite number in (0, 1] (got {decay!r})")
+    return (np.float64(decay) ** np.arange(int(h), dtype=np.float64)).astype(np.float32)
+
+
+class _CoherenceFields(NamedTuple):
+    dim_scale: Any
+    decay: float
+    gripper_penalty: float = 0.0
+
+
+_COHERENCE_UPLOADS = {}  # ("scale", dim_scale, device) / ("steps", decay, h, device) -> the fp32 device tensor: one upload per device
+
+
+class Coherence(_CoherenceFields):
+    """What OpenVLA.coherence_prior takes and PI0Policy.coherence holds: every candidate gets the prior -sum_r w_r D(candidate, r) over
+    a set of reference chunks, D the sum over the overlapping steps t of decay^t * (the squared distance of the translation / rotation
+    values scaled per dim by dim_scale, plus gripper_penalty where the gripper classes (value >= 0.5) differ) (ops.coherence_prior_tokens:
+    the arithmetic). dim_scale: a 6-sequence of finite numbers >= 0 (0 leaves a dim out); decay finite and in (0, 1]; gripper_penalty
+    finite and >= 0. Values are checked here (CoverError), shapes against the rows in ops. The references, their weights and the weight
+    the prior gets beside other priors are the caller's. No default decay or scale exists and no decay, scale, penalty or mixing weight
+    is recommended: there is no task-success data to choose them on."""
+    __slots__ = ()
+
+    def __new__(cls, dim_scale, decay, gripper_penalty=0.0):
+        import ctypes
+        from ._lib import CoverError
+        from .ops import smooth_dim_scale
+        for name, v in (("decay", decay), ("gripper_penalty", gripper_penalty)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(ctypes.c_float(v).value)):
+                raise CoverError(f"Coherence: {name} must be a finite number (got {v!r})")
+        if not 0 < decay <= 1:
+            raise CoverError(f"Coherence: decay must be in (0, 1] (got {decay!r})")
+        if not gripper_penalty >= 0:
+            raise CoverError(f"Coherence: gripper_penalty must be >= 0 (got {gripper_penalty!r})")
+        scale = tuple(float(v) for v in smooth_dim_scale(dim_scale, "Coherence"))
+        return super().__new__(cls, scale, float(decay), float(gripper_penalty))
+
+    def scale_on(self, device):
+        """dim_scale as the fp32 [6] tensor the launch reads, uploaded once per device."""
+        import torch
+        key = ("scale", self.dim_scale, str(torch.device(device)))
+        if key not in _COHERENCE_UPLOADS:
+            _COHERENCE_UPLOADS[key] = torch.tensor(self.dim_scale, dtype=torch.float32).to(device)
+        return _COHERENCE_UPLOADS[key]
+
+    def steps_on(self, device, h):
+        """coherence_step_weights(h, decay) as the fp32 [h] tensor the launch reads, uploaded once per device and h."""
+        import torch
+        key = ("steps", self.decay, int(h), str(torch.device(device)))
+        if key not in _COHERENCE_UPLOADS:
+            _COHERENCE_UPLOADS[key] = torch.from_numpy(coherence_step_weights(int(h), self.decay)).to(device)
+        return _COHERENCE_UPLOADS[key]
+
+    def kwargs(self, device, h) -> dict:
+        """The keywords of ops.coherence_prior_tokens / ops.coherence_prior_actions for candidates of h steps."""
+        return dict(step_weight=self.steps_on(device, h), dim_scale=self.scale_on(device), gripper_penalty=self.gripper_penalty)
+
+
 class TokenGrammar(NamedTuple):
     """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
     allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)

@@ -533,6 +533,37 @@ class OpenVLA:
         return ops.smooth_scores_tokens(tokens, scores, group_rows, self.bin_centers(), self.c["tok_vocab"], steps=self.n_gen // 7,
                                         stats=stats, **smooth.kwargs(tokens.device))
 
+    def coherence_prior(self, tokens: torch.Tensor, group_rows: int, coherence, *, ref_tokens=None, ref_actions=None, ref_weight=None,
+                        shift=0, stats=False):
+        """The chunk-coherence prior of action-token chunks (ops.coherence_prior_tokens with this model's tok_vocab, bin centres and
+        steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] (sampled, augmented or refined) -> fp32 [P * group_rows], per row minus
+        the weighted, step-decayed squared distance to the reference chunks. Exactly one of ref_tokens (int64 [R, 7 hr] or
+        [P, R, 7 hr], de-tokenised here through bin_centers() with tokens_to_histories' clamp rule, in torch) and ref_actions (fp32
+        [R, hr, 7] or [P, R, hr, 7], in the de-tokenised space) is given. ref_weight: fp32 [R] or [P, R], signed; None = all ones.
+        shift: candidate step t meets reference step t + shift (the steps of the reference chunk already executed). coherence: a
+        host.Coherence (dim_scale, decay, gripper_penalty; none has a default or a recommended value). One reference holding the last
+        committed chunk, shift = the steps executed since, is the backward coherence; the group's own rows at +1/S with a weak policy's
+        at -1/S' is the forward contrast. The result is a prior: ops.prior_select's, score_histories(prior=),
+        verify_and_select(candidate_prior=). stats=True -> (prior, ops.CoherenceStats). One launch; the policy is not run. Off by
+        default: nothing calls this."""
+        if not isinstance(coherence, host.Coherence):
+            raise L.CoverError("OpenVLA.coherence_prior: coherence must be a host.Coherence")
+        if (ref_tokens is None) == (ref_actions is None):
+            raise L.CoverError("OpenVLA.coherence_prior: exactly one of ref_tokens and ref_actions is required")
+        steps = self.n_gen // 7
+        if ref_tokens is not None:
+            if not torch.is_tensor(ref_tokens) or ref_tokens.dtype != torch.int64 or ref_tokens.dim() not in (2, 3) or ref_tokens.shape[-1] % 7 != 0:
+                raise L.CoverError("OpenVLA.coherence_prior: ref_tokens must be int64 [R, 7 hr] or [prompts, R, 7 hr]")
+            cen = self.bin_centers()
+            b = (self.c["tok_vocab"] - ref_tokens.to(cen.device) - 1).clamp(0, cen.numel() - 1)
+            ref_actions = cen[b].reshape(*ref_tokens.shape[:-1], ref_tokens.shape[-1] // 7, 7).contiguous()
+        if not torch.is_tensor(ref_actions) or ref_actions.dim() not in (3, 4):
+            raise L.CoverError("OpenVLA.coherence_prior: ref_actions must be fp32 [R, hr, 7] or [prompts, R, hr, 7]")
+        if ref_weight is None:
+            ref_weight = torch.ones(ref_actions.shape[-3], dtype=torch.float32, device=ref_actions.device)
+        return ops.coherence_prior_tokens(tokens, group_rows, ref_actions, ref_weight, self.bin_centers(), self.c["tok_vocab"], steps=steps,
+                                          shift=shift, stats=stats, **coherence.kwargs(tokens.device, steps))
+
     def proposal_prior(self, tokens: torch.Tensor, group_rows: int, n_fit: int, *, sigma, sd_floor, log_share=None):
         """The proposal log-density prior of action-token chunks (ops.proposal_prior_tokens with this model's tok_vocab, bin centres and
         steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] -> fp32 [P * group_rows], per row the unnormalised log-density of the

@@ -1778,6 +1778,109 @@ def smooth_scores_actions(actions, scores, group_rows, *, radius, dim_scale, shr
                    actions.shape[0], actions.shape[1], scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats)
 
 
+# ------------------------------------------------------------------------------------------------ chunk-coherence prior
+class CoherenceStats(NamedTuple):
+    """What coherence_prior_tokens / coherence_prior_actions return beside the prior with stats=True."""
+    min_dist: torch.Tensor     # fp32 [rows]: the smallest distance D to a reference of non-zero weight (+inf when there is none)
+    nearest: torch.Tensor      # int32 [rows]: that reference's index, the lowest on a tie (-1 when there is none)
+
+
+def _coherence(what, fn, src, n_stride, t_stride, N, steps, group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty,
+               out, stats, centers=None, tok_vocab=0):
+    """The checks and the launch both coherence wrappers share."""
+    ints = (int, np.integer)
+    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, shift)):
+        raise L.CoverError(f"{what}: group_rows and shift must be integers (got {group_rows!r}, {shift!r})")
+    S, shift = int(group_rows), int(shift)
+    if not 1 <= S <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= group_rows <= 4096 and rows % group_rows == 0 are required (got rows={N}, group_rows={S})")
+    G = N // S
+    if not 1 <= steps <= 64 or N > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
+    if not torch.is_tensor(ref) or ref.dtype != torch.float32 or ref.dim() not in (3, 4) or ref.shape[-1] != 7 or not ref.is_contiguous():
+        raise L.CoverError(f"{what}: ref must be contiguous fp32 [R, hr, 7] (shared) or [prompts, R, hr, 7] "
+                           f"(got {tuple(ref.shape) if torch.is_tensor(ref) else type(ref).__name__})")
+    R, hr = int(ref.shape[-3]), int(ref.shape[-2])
+    if ref.dim() == 4 and ref.shape[0] != G:
+        raise L.CoverError(f"{what}: a per-prompt ref must have one set per prompt: [{G}, R, hr, 7] (got {tuple(ref.shape)})")
+    if not 1 <= R <= 4096 or not 1 <= hr <= 64 or not 0 <= shift < hr:
+        raise L.CoverError(f"{what}: 1 <= R <= 4096, 1 <= hr <= 64 and 0 <= shift < hr are required (got R={R}, hr={hr}, shift={shift})")
+    if (not torch.is_tensor(ref_weight) or ref_weight.dtype != torch.float32 or tuple(ref_weight.shape) not in ((R,), (G, R))
+            or not ref_weight.is_contiguous()):
+        raise L.CoverError(f"{what}: ref_weight must be contiguous fp32 [R] = [{R}] (shared) or [prompts, R] = [{G}, {R}] "
+                           f"(got {tuple(ref_weight.shape) if torch.is_tensor(ref_weight) else type(ref_weight).__name__})")
+    if not torch.is_tensor(step_weight) or step_weight.dtype != torch.float32 or tuple(step_weight.shape) != (steps,) or not step_weight.is_contiguous():
+        raise L.CoverError(f"{what}: step_weight must be contiguous fp32 [steps] = [{steps}] (host.coherence_step_weights makes it) "
+                           f"(got {tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__})")
+    if (isinstance(gripper_penalty, bool) or not isinstance(gripper_penalty, (int, float, np.floating, np.integer))
+            or not math.isfinite(gripper_penalty)):
+        raise L.CoverError(f"{what}: gripper_penalty must be a finite number (got {gripper_penalty!r})")
+    penalty = C.c_float(float(gripper_penalty)).value
+    if not (math.isfinite(penalty) and penalty >= 0.0):
+        raise L.CoverError(f"{what}: gripper_penalty must be finite and >= 0 (got {gripper_penalty!r})")
+    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Coherence's upload: validated there, once
+        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
+            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
+    else:
+        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
+    _chk_dev(src, ref, ref_weight, step_weight, centers, out)
+    dev = src.device
+    dim_scale = dim_scale.to(dev)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
+        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
+    if any(t is not None and t.device != dev for t in (ref, ref_weight, step_weight, dim_scale, centers, out)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=dev)
+    st = CoherenceStats(torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)) if stats else None
+    a = L.CoherenceArgs()
+    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.ref, a.ref_g_stride, a.ref_r_stride = ref.data_ptr(), (R * hr * 7 if ref.dim() == 4 else 0), hr * 7
+    a.ref_weight, a.w_g_stride = ref_weight.data_ptr(), (R if ref_weight.dim() == 2 else 0)
+    a.step_weight, a.dim_scale = step_weight.data_ptr(), dim_scale.data_ptr()
+    a.G, a.group_rows, a.h, a.R, a.hr, a.shift, a.gripper_penalty = G, S, steps, R, hr, shift, penalty
+    a.prior_out = out.data_ptr()
+    if st is not None:
+        a.min_dist_out, a.nearest_out = st.min_dist.data_ptr(), st.nearest.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    return (out, st) if stats else out
+
+
+def coherence_prior_tokens(tokens, group_rows, ref, ref_weight, centers, tok_vocab, *, steps=1, shift=0, step_weight, dim_scale,
+                           gripper_penalty=0.0, out=None, stats=False):
+    """The chunk-coherence prior of action tokens (cover_coherence_prior_tokens): tokens int64 [G * group_rows, >= 7 steps] (unit column
+    stride, any row stride; row i belongs to prompt i // group_rows) -> fp32 [rows], per row minus the weighted sum over the reference
+    chunks r of ref_weight[r] * D(row, r), D = sum over the overlapping steps t of step_weight[t] * (sum over dim < 6 of
+    ((x - y) * dim_scale[dim])^2 + gripper_penalty where the gripper classes (value >= 0.5) differ), x the de-tokenised value
+    centers[clamp(tok_vocab - token - 1)] at candidate step t and y the reference value at step t + shift; the overlap is
+    min(steps, hr - shift) steps. ref: fp32 [R, hr, 7] shared by all prompts, or [G, R, hr, 7]; ref_weight: fp32 [R] or [G, R], signed
+    (a positive weight pulls towards a reference, a negative one pushes away; a reference of weight 0 is not read into a sum, a NaN there
+    included). One reference of weight 1 holding the unexecuted tail of the last committed chunk is the backward coherence of
+    Bidirectional Decoding; the group's own rows at +1/S with a weak policy's rows at -1/S' is its forward contrast. The result is a
+    prior (higher = more coherent): prior_select's prior, score_histories(prior=), verify_and_select(candidate_prior=), added to other
+    priors with plain torch. step_weight: fp32 [steps] on the device (host.coherence_step_weights); dim_scale: a 6-sequence of finite
+    numbers >= 0 (0 leaves a dim out), validated here and uploaded, or an fp32 [6] tensor already on the device (host.Coherence's,
+    validated there; on the device a negative or non-finite entry makes every prior NaN). A NaN candidate element gives its own row a NaN
+    prior. No decay, scale, penalty or mixing weight is chosen or recommended: there is no task-success data to choose them on.
+    stats=True -> (prior, CoherenceStats). Every rounding is specified in include/cover_hip.h. One launch, no workspace, recordable."""
+    steps, n_stride = _token_rows("coherence_prior_tokens", tokens, steps, centers)
+    return _coherence("coherence_prior_tokens", lambda h: h.cover_coherence_prior_tokens, tokens, n_stride, 7, tokens.shape[0], steps,
+                      group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out, stats, centers=centers,
+                      tok_vocab=tok_vocab)
+
+
+def coherence_prior_actions(actions, group_rows, ref, ref_weight, *, shift=0, step_weight, dim_scale, gripper_penalty=0.0, out=None,
+                            stats=False):
+    """The same for float rows (cover_coherence_prior_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last stride and any
+    other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer. See coherence_prior_tokens."""
+    _action_rows("coherence_prior_actions", actions)
+    return _coherence("coherence_prior_actions", lambda h: h.cover_coherence_prior_actions, actions, actions.stride(0), actions.stride(1),
+                      actions.shape[0], actions.shape[1], group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out,
+                      stats)
+
+
 # ------------------------------------------------------------------------------------------------ beam search
 def beam_merge(cum, cand_tok, cand_lp, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None, out_step_lp=None):
     """One beam-search step over G = rows / n_beams prompt groups (cover_beam_merge; row g * n_beams + b is beam b of group g).

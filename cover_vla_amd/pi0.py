@@ -453,6 +453,8 @@ class PI0Policy:
         self._preprocess_adapter = None
         self.proposal_prior = None                # host.ProposalPrior or None (off): what select_action scores its rows with, see there
         self.last_proposal_prior = None           # fp32 [rows] on the device, set by a select_action that ran with self.proposal_prior set
+        self.coherence = None                     # host.Coherence or None (off): the chunk-coherence prior of select_action's rows, see there
+        self._last_sampled = None                 # (the last sampled batch [B, chunk, max_action_dim], rows per prompt of the queue, policy samples per prompt)
         self.reset()
 
     @classmethod
@@ -484,6 +486,33 @@ class PI0Policy:
     def reset(self):
         """modeling_pi0.py:256-258."""
         self._action_queue = collections.deque([], maxlen=self.config.n_action_steps)
+        self.committed_tail = None                # fp32 [1, chunk_size - n_action_steps, 7] on the device: commit()
+        self.last_coherence_prior = None          # fp32 [rows] on the device: select_action with self.coherence and a committed tail
+        self._last_sampled = None
+
+    def commit(self, row: int):
+        """Tells the policy which candidate the control loop executes: row is the global_action_idx host.verify_and_select returned
+        for the rows of the last select_action that sampled. The normalised steps [n_action_steps : chunk_size] of that row of the last
+        sampled batch -- what the policy predicted beyond the steps that are executed now -- are kept (a copy) as self.committed_tail,
+        fp32 [1, chunk_size - n_action_steps, 7] on the device, the reference of the next decision's coherence prior (select_action);
+        None when chunk_size == n_action_steps, where nothing is predicted beyond the executed steps. A row that augment= drew has no
+        such steps (only n_action_steps are drawn): CoverError. Returns committed_tail."""
+        if self._last_sampled is None:
+            raise ops.L.CoverError("PI0Policy.commit: no sampled batch (call select_action first; reset() forgets the batch)")
+        if self.config.action_dim != 7:
+            raise ops.L.CoverError(f"PI0Policy.commit: action_dim must be 7 (got {self.config.action_dim})")
+        chunks, S, n = self._last_sampled
+        rows = chunks.shape[0] // n * S
+        if isinstance(row, bool) or not isinstance(row, (int, np.integer)) or not 0 <= row < rows:
+            raise ops.L.CoverError(f"PI0Policy.commit: row must be an integer in [0, {rows}) (got {row!r})")
+        g, j = divmod(int(row), S)
+        if j >= n:
+            raise ops.L.CoverError(f"PI0Policy.commit: row {row} is an augmented candidate: it has no steps beyond n_action_steps")
+        if self.config.chunk_size == self.config.n_action_steps:
+            self.committed_tail = None
+        else:
+            self.committed_tail = chunks[g * n + j, self.config.n_action_steps: self.config.chunk_size, :7].to(torch.float32).clone().unsqueeze(0)
+        return self.committed_tail
 
     def prepare_images(self, batch):
         """modeling_pi0.py:344-387: every configured camera present in the batch is resized with padding to
@@ -537,8 +566,23 @@ class PI0Policy:
         group_rows = samples_per_prompt + n_augmented, else samples_per_prompt; before unnormalize_action). It is kept as
         self.last_proposal_prior, fp32 [rows] on the device, the candidate_prior of host.verify_and_select(candidate_prior=, prior_beta=).
         A call that finds the queue filled, or the attribute None, leaves last_proposal_prior as it is. It is an attribute and no
-        keyword, as PI0FASTPolicy's scoring options are: this method's parameter list is the reference's plus augment."""
+        keyword, as PI0FASTPolicy's scoring options are: this method's parameter list is the reference's plus augment.
+        self.coherence (a host.Coherence set on the policy; None, the default = nothing is launched) with a self.committed_tail (set by
+        commit(row) after the last decision): every row of the queue gets the chunk-coherence prior against that tail
+        (ops.coherence_prior_actions on the same normalised [rows, n_action_steps, 7] view, after the augmentation when augment= is
+        given; one reference shared by all rows, weight 1, shift 0: step t of a new candidate is compared with step n_action_steps + t
+        of the chunk committed last time, over min(n_action_steps, chunk_size - n_action_steps) steps). It is kept as
+        self.last_coherence_prior, fp32 [rows] on the device; the caller combines priors with plain torch, for example
+        candidate_prior = last_proposal_prior + c * last_coherence_prior (no c is recommended). A call that finds the queue filled, the
+        attribute None or no committed tail launches nothing and leaves last_coherence_prior as it is; reset() clears both."""
         if len(self._action_queue) == 0:
+            coherence = self.coherence if self.committed_tail is not None else None
+            if self.coherence is not None:                 # checked before the policy runs
+                from .host import Coherence
+                if not isinstance(self.coherence, Coherence):
+                    raise ops.L.CoverError(f"PI0Policy.coherence must be None or a host.Coherence (got {type(self.coherence).__name__})")
+                if self.config.action_dim != 7:
+                    raise ops.L.CoverError(f"PI0Policy.coherence: action_dim must be 7 (got {self.config.action_dim})")
             proposal_prior = self.proposal_prior
             if proposal_prior is not None:                 # checked before the policy runs
                 from .host import ProposalPrior
@@ -555,6 +599,8 @@ class PI0Policy:
             lang_tokens, lang_masks = self.prepare_language(batch)
             actions = self.model.sample_actions(images, img_masks, lang_tokens, lang_masks, state, noise=noise,
                                                 noise_std=noise_std)
+            n_own = augment.samples_per_prompt if augment is not None else 1
+            self._last_sampled = (actions, n_own + (augment.n_augmented if augment is not None else 0), n_own)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
             if augment is not None:
                 if self.config.action_dim != 7:
@@ -566,6 +612,12 @@ class PI0Policy:
                 self.last_proposal_prior = ops.proposal_prior_actions(
                     actions, n_fit + (augment.n_augmented if augment is not None else 0), n_fit, sigma=proposal_prior.sigma,
                     sd_floor=proposal_prior.sd_floor, log_share=proposal_prior.log_share)
+            if coherence is not None:
+                rows = actions.shape[0]
+                S = max(d for d in range(1, min(rows, 4096) + 1) if rows % d == 0)   # one shared reference: the grouping is free
+                ones = torch.ones(1, dtype=torch.float32, device=actions.device)
+                self.last_coherence_prior = ops.coherence_prior_actions(
+                    actions, S, self.committed_tail, ones, shift=0, **coherence.kwargs(actions.device, self.config.n_action_steps))
             actions = unnormalize_action(actions, self._norm.get("action", IDENTITY))
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue

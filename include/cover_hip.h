@@ -1029,6 +1029,68 @@ typedef struct cover_smooth_args {
 int cover_smooth_scores_tokens(const cover_smooth_args* args, void* stream);
 int cover_smooth_scores_actions(const cover_smooth_args* args, void* stream);
 
+/* Chunk-coherence prior: per candidate row the negated, signed-weighted sum of its step-weighted squared distances to a set of reference
+ * chunks. With one reference of weight 1 -- the unexecuted tail of the chunk committed at the last decision -- it is the backward
+ * coherence of Bidirectional Decoding (Liu et al., 2024); with a group's strong rows at positive and a weak policy's rows at negative
+ * weights it is the forward contrast. A group is group_rows (S) contiguous candidate rows (row i belongs to group i / S); the output is
+ * fp32 [G * S], a prior (higher = more coherent) that goes where priors go: cover_prior_select's prior. One wave per row, 16 rows per
+ * block, several blocks per group; the reference rows pass through LDS in tiles. One launch, no workspace, no atomics, recordable; no
+ * result depends on the tiling. All arithmetic is fp32, one rounding per operation, never an fma.
+ * Candidate step t is compared with reference step t + shift; the overlap is T = min(h, hr - shift) steps.
+ * Pair (row n, reference r), x the candidate value and y the reference value:
+ *   D = 0.0f
+ *   for t = 0..T-1 in order:
+ *     e = 0.0f
+ *     for d = 0..5 with dim_scale[d] != 0:  diff = x - y;  s = diff * dim_scale[d];  sq = s * s;  e = e + sq
+ *       (a dim whose scale is 0 is not read into the sum: a NaN there is invisible)
+ *     if gripper_penalty != 0 and the classes (x_6 >= 0.5f) and (y_6 >= 0.5f) differ:  e = e + gripper_penalty
+ *     p = step_weight[t] * e;  D = D + p
+ * Row n, lane l of the row's wave:
+ *   acc = 0.0f;  for r = l, l + 64, ... < R ascending, where w_r != 0:  prod = w_r * D;  acc = acc + prod
+ *   (a reference of weight 0 is never read into a sum, so a NaN there is invisible). The 64 partials meet in the xor butterfly
+ *   v = v + v[lane ^ o], o = 32, 16, ..., 1.
+ *   prior_out[g * S + n] = -acc as a sign-bit flip: a candidate that equals its only reference stores 0x80000000. A NaN acc stores the
+ *   one NaN 0x7FC00000 (the payload and sign of an arithmetic NaN are not specified). A NaN candidate element inside the overlap, in a
+ *   dim of non-zero scale, gives its row a NaN prior (given a reference of non-zero weight) and no other row.
+ *   A dim_scale entry that is negative or not finite makes every prior of the launch 0x7FC00000, every min_dist +inf and every nearest
+ *   -1; there is no trap.
+ * Optional outputs (NULL = not written): min_dist_out fp32 [G * S], the smallest D over the references with w_r != 0 whose D is not NaN
+ *   (+inf when there is none); nearest_out int32 [G * S], the index r of that reference, the lowest r on a tie (-1 when there is none).
+ *   It is the lexicographic (D, r) minimum, so it does not depend on the schedule.
+ * cover_coherence_prior_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (n_stride >= 7 h; t_stride
+ *   unused), x = centers[clamp(tok_vocab - token - 1, 0, n_centers - 1)] (cover_tokens_to_histories' rule).
+ * cover_coherence_prior_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit last
+ *   stride: a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place); centers unused.
+ * ref is fp32 in both forms: element (g, r, t, d) at ref[g * ref_g_stride + r * ref_r_stride + t * 7 + d], R rows of hr steps;
+ *   ref_g_stride == 0 is one reference set shared by all groups. ref_weight is fp32, signed: element (g, r) at
+ *   ref_weight[g * w_g_stride + r], w_g_stride 0 or R. step_weight fp32 [h] (the caller's, made on the host: the device takes no pow),
+ *   dim_scale fp32 [6]; all of them device memory.
+ * Only the cells named above are read: nothing of src outside the first T steps of its [rows][h][7] view, nothing of ref outside steps
+ * shift .. shift + T - 1 of its [R][hr][7] rows.
+ * COVER_EINVAL, and nothing launched, unless G >= 1, 1 <= group_rows <= 4096, 1 <= R <= 4096, 1 <= h <= 64, 1 <= hr <= 64,
+ * 0 <= shift < hr, G * group_rows <= 2^20, ref_g_stride == 0 or >= (R - 1) * ref_r_stride + 7 hr, ref_r_stride >= 7 hr, w_g_stride 0 or
+ * R, gripper_penalty finite and >= 0, src / ref / ref_weight / step_weight / dim_scale / prior_out non-null and, for tokens,
+ * n_stride >= 7 h, centers non-null, n_centers >= 1. */
+typedef struct cover_coherence_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    int n_centers, tok_vocab;
+    const float* ref;               /* fp32 reference chunks */
+    long long ref_g_stride, ref_r_stride;   /* in elements */
+    const float* ref_weight;        /* signed, [R] or [G][R] */
+    long long w_g_stride;           /* 0 or R */
+    const float* step_weight;       /* [h] */
+    const float* dim_scale;         /* [6] */
+    int G, group_rows, h, R, hr, shift;
+    float gripper_penalty;
+    float* prior_out;               /* [G * group_rows] */
+    float* min_dist_out;            /* [G * group_rows], optional */
+    int* nearest_out;               /* int32 [G * group_rows], optional */
+} cover_coherence_args;
+int cover_coherence_prior_tokens(const cover_coherence_args* args, void* stream);
+int cover_coherence_prior_actions(const cover_coherence_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
