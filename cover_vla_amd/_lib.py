@@ -226,6 +226,15 @@ class CoherenceArgs(C.Structure):
                 ("prior_out", c_p), ("min_dist_out", c_p), ("nearest_out", c_p)]
 
 
+class DiverseArgs(C.Structure):
+    _fields_ = [("src", c_p), ("n_stride", c_ll), ("t_stride", c_ll), ("centers", c_p), ("n_centers", c_i), ("tok_vocab", c_i),
+                ("quality", c_p), ("step_weight", c_p), ("dim_scale", c_p),
+                ("G", c_i), ("group_rows", c_i), ("m", c_i), ("h", c_i),
+                ("weight", c_f), ("cover_dist", c_f), ("gripper_penalty", c_f), ("_pad", c_f),
+                ("picked_rows_out", c_p), ("count_out", c_p), ("pick_value_out", c_p), ("pick_dist_out", c_p), ("assign_out", c_p),
+                ("row_dist_out", c_p), ("out", c_p)]
+
+
 class BeamMergeArgs(C.Structure):
     _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("feed_pad", c_ll),
                 ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p), ("cum_out", c_p),
@@ -311,6 +320,7 @@ _STRUCTS = {
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_augment_args": AugmentArgs,
     "cover_proposal_prior_args": ProposalPriorArgs, "cover_member_scores_args": MemberScoresArgs,
     "cover_refine_args": RefineArgs, "cover_smooth_args": SmoothArgs, "cover_coherence_args": CoherenceArgs,
+    "cover_diverse_args": DiverseArgs,
     "cover_beam_merge_args": BeamMergeArgs,
     "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
     "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
@@ -397,6 +407,8 @@ SYMBOLS = {
     "cover_smooth_scores_actions": (c_i, [_P(SmoothArgs), c_p]),
     "cover_coherence_prior_tokens": (c_i, [_P(CoherenceArgs), c_p]),
     "cover_coherence_prior_actions": (c_i, [_P(CoherenceArgs), c_p]),
+    "cover_diverse_subset_tokens": (c_i, [_P(DiverseArgs), c_p]),
+    "cover_diverse_subset_actions": (c_i, [_P(DiverseArgs), c_p]),
     "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
     "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
     "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),

@@ -465,6 +465,18 @@ int cover_coherence_prior_actions(const cover_coherence_args* a, void* stream) {
     HIPCHK(launch_coherence_prior_actions(a, ST(stream)), "coherence_prior_actions (" COHERENCE_LIMITS ")");
     return COVER_OK;
 }
+#define DIVERSE_LIMITS "G >= 1, 1 <= m <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, weight finite and >= 0, cover_dist not " \
+                       "NaN and < +inf, gripper_penalty finite and >= 0, src / step_weight / dim_scale / picked_rows_out required"
+int cover_diverse_subset_tokens(const cover_diverse_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_diverse_subset_tokens: null args");
+    HIPCHK(launch_diverse_subset_tokens(a, ST(stream)), "diverse_subset_tokens (" DIVERSE_LIMITS ", n_stride >= 7 h, centers required, n_centers >= 1)");
+    return COVER_OK;
+}
+int cover_diverse_subset_actions(const cover_diverse_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_diverse_subset_actions: null args");
+    HIPCHK(launch_diverse_subset_actions(a, ST(stream)), "diverse_subset_actions (" DIVERSE_LIMITS ")");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -591,6 +603,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
     SZ(cover_member_scores_args); SZ(cover_refine_args); SZ(cover_smooth_args); SZ(cover_coherence_args);
+    SZ(cover_diverse_args);
 #undef SZ
     return 0;
 }

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "augment_fit.h"
+#include "chunk_dist.h"   // chunk_pair_dist: the pair distance, shared with diverse.hip
 
 #pragma clang fp contract(off)
 
@@ -16,30 +17,6 @@
 #define COHERENCE_ROWS_PER_BLOCK 16   // one wave each
 #define COHERENCE_TILE_FLOATS 12288   // the LDS budget of one r-tile (48 KiB) while more than 64 references fit
 #define COHERENCE_MAX_TILE 1024       // references per r-tile at the narrowest row
-
-__device__ __forceinline__ bool coherence_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-// D of one (candidate, reference) pair: x / y point at the rows' [T][7] values of the overlap (step stride 7)
-__device__ __forceinline__ float coherence_pair_dist(const float* x, const float* y, int T, const float* sc, const float* step_weight,
-                                                     float penalty) {
-    float D = 0.0f;
-    for (int t = 0; t < T; ++t) {
-        float e = 0.0f;
-#pragma unroll
-        for (int d = 0; d < 6; ++d) {
-            if (sc[d] != 0.0f) {   // a dim of scale 0 is not read into the sum: a NaN there is invisible
-                const float diff = x[7 * t + d] - y[7 * t + d];
-                const float s = diff * sc[d];
-                const float sq = s * s;
-                e = e + sq;
-            }
-        }
-        if (penalty != 0.0f && ((x[7 * t + 6] >= 0.5f) != (y[7 * t + 6] >= 0.5f))) e = e + penalty;
-        const float p = step_weight[t] * e;
-        D = D + p;
-    }
-    return D;
-}
 
 // the lexicographic (D, r) minimum; r < 0 is "none yet"
 __device__ __forceinline__ void coherence_take_min(float& bd, int& br, float d, int r) {
@@ -69,12 +46,7 @@ __global__ __launch_bounds__(1024) void coherence_k(cover_coherence_args a, long
     const float* wt = a.ref_weight + (long long)g * a.w_g_stride;
     const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, 0, a.h, 0.0f, 0.0f, nullptr, nullptr, nullptr};
     float sc[6];
-    bool usable = true;            // a negative or non-finite scale: every prior of the launch is NaN
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        sc[d] = a.dim_scale[d];
-        if (!(sc[d] >= 0.0f) || !coherence_finite(sc[d])) usable = false;
-    }
+    const bool usable = chunk_load_scale(a.dim_scale, sc);   // a negative or non-finite scale: every prior of the launch is NaN
     for (int i = threadIdx.x; i < COHERENCE_ROWS_PER_BLOCK * w7; i += blockDim.x) {
         const int r = i / w7, c = i - r * w7, t = c / 7, d = c - t * 7;
         if (n0 + r < S) s_own[r * stride + c] = aug_value(f, in[(long long)(n0 + r) * a.n_stride + (long long)t * t_stride + d]);
@@ -97,7 +69,7 @@ __global__ __launch_bounds__(1024) void coherence_k(cover_coherence_args a, long
                 const int r = r0 + rr;
                 const float w = wt[r];
                 if (w != 0.0f) {   // a reference of weight 0 is never read into a sum
-                    const float D = coherence_pair_dist(x, s_y + rr * stride, To, sc, s_sw, a.gripper_penalty);
+                    const float D = chunk_pair_dist(x, s_y + rr * stride, To, sc, s_sw, a.gripper_penalty);
                     const float prod = w * D;
                     acc = acc + prod;
                     if (D == D) coherence_take_min(bd, br, D, r);   // a NaN D is never the minimum; r ascends within a lane

@@ -120,6 +120,9 @@ hipError_t launch_smooth_scores_actions(const cover_smooth_args* a, hipStream_t 
 // ---- coherence.hip -------------------------------------------------------------------------------
 hipError_t launch_coherence_prior_tokens(const cover_coherence_args* a, hipStream_t st);
 hipError_t launch_coherence_prior_actions(const cover_coherence_args* a, hipStream_t st);
+// ---- diverse.hip ---------------------------------------------------------------------------------
+hipError_t launch_diverse_subset_tokens(const cover_diverse_args* a, hipStream_t st);
+hipError_t launch_diverse_subset_actions(const cover_diverse_args* a, hipStream_t st);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
 hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);

@@ -302,6 +302,78 @@ class Coherence(_CoherenceFields):
         return dict(step_weight=self.steps_on(device, h), dim_scale=self.scale_on(device), gripper_penalty=self.gripper_penalty)
 
 
+class _DiversityFields(NamedTuple):
+    keep: int
+    weight: float
+    dim_scale: Any
+    decay: float
+    gripper_penalty: float
+    cover_dist: float = -1.0
+
+
+class Diversity(_DiversityFields):
+    """What OpenVLA.diverse_subset takes and PI0Policy.diverse holds: of every prompt's candidate rows at most `keep` are kept, picked
+    greedily by quality + weight * (distance to the nearest row already picked), the distance being Coherence's between two rows of the
+    group: the sum over the steps t of decay^t * (the squared distance of the translation / rotation values scaled per dim by dim_scale,
+    plus gripper_penalty where the gripper classes (value >= 0.5) differ) (ops.diverse_subset_tokens: the arithmetic). Rows whose
+    distance to a pick is <= cover_dist are left out: 0 removes exact duplicates, r > 0 ends the selection once the group is covered,
+    a negative value (the default) switches the rule off. keep: an integer 1..4096; weight finite and >= 0 (0 = a pure top-keep by
+    quality); dim_scale: a 6-sequence of finite numbers >= 0 (0 leaves a dim out); decay finite and in (0, 1]; gripper_penalty finite and
+    >= 0; cover_dist any number below +inf. Values are checked here (CoverError), shapes against the rows in ops. No default keep,
+    weight, decay or scale exists and no value of any field is recommended: there is no task-success data to choose them on."""
+    __slots__ = ()
+
+    def __new__(cls, keep, weight, dim_scale, decay, gripper_penalty, cover_dist=-1.0):
+        import ctypes
+        from ._lib import CoverError
+        from .ops import smooth_dim_scale
+        f32 = lambda v: ctypes.c_float(v).value                     # the value the launch receives
+        if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or not 1 <= keep <= 4096:
+            raise CoverError(f"Diversity: keep must be an integer in [1, 4096] (got {keep!r})")
+        for name, v in (("weight", weight), ("decay", decay), ("gripper_penalty", gripper_penalty)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(f32(v))):
+                raise CoverError(f"Diversity: {name} must be a finite number (got {v!r})")
+        if not weight >= 0:
+            raise CoverError(f"Diversity: weight must be >= 0 (got {weight!r})")
+        if not 0 < decay <= 1:
+            raise CoverError(f"Diversity: decay must be in (0, 1] (got {decay!r})")
+        if not gripper_penalty >= 0:
+            raise CoverError(f"Diversity: gripper_penalty must be >= 0 (got {gripper_penalty!r})")
+        if isinstance(cover_dist, bool) or not isinstance(cover_dist, (int, float)) or math.isnan(cover_dist) or not f32(cover_dist) < math.inf:
+            raise CoverError(f"Diversity: cover_dist must be a number below +inf in fp32; negative = off (got {cover_dist!r})")
+        scale = tuple(float(v) for v in smooth_dim_scale(dim_scale, "Diversity"))
+        return super().__new__(cls, int(keep), float(weight), scale, float(decay), float(gripper_penalty), float(cover_dist))
+
+    def kwargs(self, device, h) -> dict:
+        """The keywords of ops.diverse_subset_tokens / ops.diverse_subset_actions for rows of h steps (keep is positional there). The
+        step weights and the scale are Coherence's uploads: one per device."""
+        coh = Coherence(self.dim_scale, self.decay, self.gripper_penalty)
+        return dict(weight=self.weight, cover_dist=self.cover_dist, step_weight=coh.steps_on(device, h), dim_scale=coh.scale_on(device),
+                    gripper_penalty=self.gripper_penalty)
+
+
+def spread_scores(scores_kept, subset, group_rows):
+    """The scores of a pruned verifier call on the rows they stand for: scores_kept fp32 [G * keep] (score_histories' scores of
+    subset.rows, group_size = keep), subset the ops.DiverseSubset of G groups of group_rows rows -> fp32 [G * group_rows], every input
+    row carrying the score of the slot subset.assign names (its nearest pick; a picked row its own slot, or an earlier pick's it equals)
+    and -inf where assign is -1 (a row with a non-finite element, or a group with no pick): such a row never wins ops.group_argmax /
+    ops.prior_select. The result goes where scores of the original rows go -- ops.group_argmax, smooth_scores, refine -- with
+    group_size = group_rows. Plain torch indexing on the scores' device, no host synchronisation."""
+    import torch
+    if isinstance(group_rows, bool) or not isinstance(group_rows, (int, np.integer)) or group_rows < 1:
+        raise ValueError(f"spread_scores: group_rows must be an integer >= 1 (got {group_rows!r})")
+    G, keep = subset.picked.shape
+    if not torch.is_tensor(scores_kept) or scores_kept.dtype != torch.float32 or tuple(scores_kept.shape) != (G * keep,):
+        raise ValueError(f"spread_scores: scores_kept must be fp32 [G * keep] = [{G * keep}] "
+                         f"(got {tuple(scores_kept.shape) if torch.is_tensor(scores_kept) else type(scores_kept).__name__})")
+    if tuple(subset.assign.shape) != (G * int(group_rows),):
+        raise ValueError(f"spread_scores: subset.assign has {tuple(subset.assign.shape)} entries, not G * group_rows = {G * int(group_rows)}")
+    assign = subset.assign.to(torch.int64)
+    group = torch.arange(G * int(group_rows), device=assign.device) // int(group_rows)
+    taken = scores_kept[group * keep + assign.clamp(min=0)]
+    return torch.where(assign >= 0, taken, torch.full_like(taken, -math.inf))
+
+
 class TokenGrammar(NamedTuple):
     """What PI0FASTTokens.generate_tokens(grammar=) takes: the allowed-token sets and the per-row automaton that picks among them."""
     allow: Any         # ops.TokenAllow (bits over the vocabulary; set_of_row is made per call)

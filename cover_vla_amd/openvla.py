@@ -564,6 +564,21 @@ class OpenVLA:
         return ops.coherence_prior_tokens(tokens, group_rows, ref_actions, ref_weight, self.bin_centers(), self.c["tok_vocab"], steps=steps,
                                           shift=shift, stats=stats, **coherence.kwargs(tokens.device, steps))
 
+    def diverse_subset(self, tokens: torch.Tensor, group_rows: int, diversity, *, quality=None, steps=1):
+        """A diverse subset of action-token chunks (ops.diverse_subset_tokens with this model's tok_vocab and bin centres): tokens int64
+        [P * group_rows, >= 7 steps] (sampled, augmented or refined) -> ops.DiverseSubset with diversity.keep rows per prompt, picked
+        greedily by quality + diversity.weight * (distance to the nearest row already picked); rows within diversity.cover_dist of a pick
+        are left out (0: exact duplicates; negative: off). quality: fp32 [P * group_rows] or None -- before the verifier a policy
+        log-probability or a prior, after it the scores (then .rows is the diverse shortlist). steps: the action steps a row holds, as
+        tokens_to_histories' n_use; the distance runs over them. .rows goes to ops.tokens_to_histories / score_histories with
+        group_size = keep; host.spread_scores takes the kept rows' scores back to the input rows. diversity: a host.Diversity (keep,
+        weight, dim_scale, decay, gripper_penalty, cover_dist; none has a recommended value). One launch; the policy is not run. Off by
+        default: nothing calls this."""
+        if not isinstance(diversity, host.Diversity):
+            raise L.CoverError("OpenVLA.diverse_subset: diversity must be a host.Diversity")
+        return ops.diverse_subset_tokens(tokens, group_rows, diversity.keep, self.bin_centers(), self.c["tok_vocab"], steps=steps,
+                                         quality=quality, **diversity.kwargs(tokens.device, steps))
+
     def proposal_prior(self, tokens: torch.Tensor, group_rows: int, n_fit: int, *, sigma, sd_floor, log_share=None):
         """The proposal log-density prior of action-token chunks (ops.proposal_prior_tokens with this model's tok_vocab, bin centres and
         steps = n_gen // 7): tokens int64 [P * group_rows, n_gen] -> fp32 [P * group_rows], per row the unnormalised log-density of the

@@ -1881,6 +1881,118 @@ def coherence_prior_actions(actions, group_rows, ref, ref_weight, *, shift=0, st
                       stats)
 
 
+# ------------------------------------------------------------------------------------------------ diverse candidate subsets
+class DiverseSubset(NamedTuple):
+    """What diverse_subset_tokens / diverse_subset_actions return (G prompt groups of group_rows rows, keep slots per group)."""
+    rows: torch.Tensor         # int64 [G * keep, 7 steps] or fp32 [G * keep, steps, 7]: the picked rows verbatim; an unfilled slot repeats
+                               # the group's slot 0 (a group with no pick: its input row 0), so the shape is fixed
+    picked: torch.Tensor       # int32 [G, keep]: the input row g * group_rows + j of each slot, -1 = unfilled
+    count: torch.Tensor        # int32 [G]: the picks made
+    value: torch.Tensor        # fp32 [G, keep]: quality + weight * dist at pick time (slot 0: the quality); NaN (0x7FC00000) = unfilled
+    dist: torch.Tensor         # fp32 [G, keep]: the distance to the nearest earlier pick at pick time; +inf for slot 0 and unfilled slots
+    assign: torch.Tensor       # int32 [G * group_rows]: the slot of the nearest pick of every input row, -1 where there is none
+    row_dist: torch.Tensor     # fp32 [G * group_rows]: the distance to it (+inf where there is none)
+
+    @property
+    def valid(self) -> torch.Tensor:
+        """bool [G, keep]: the slots that hold a pick."""
+        return self.picked >= 0
+
+
+def _diverse(what, fn, src, elem, n_stride, t_stride, N, steps, group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale,
+             gripper_penalty, out_shape, centers=None, tok_vocab=0):
+    """The checks and the launch both diverse-subset wrappers share. out_shape(rows) -> the gathered output's shape."""
+    ints = (int, np.integer)
+    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, keep)):
+        raise L.CoverError(f"{what}: group_rows and keep must be integers (got {group_rows!r}, {keep!r})")
+    S, m = int(group_rows), int(keep)
+    if not 1 <= m <= S <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= keep <= group_rows <= 4096 and rows % group_rows == 0 are required "
+                           f"(got rows={N}, group_rows={S}, keep={m})")
+    G = N // S
+    if not 1 <= steps <= 64 or N > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
+    if quality is not None and (not torch.is_tensor(quality) or quality.dtype != torch.float32 or tuple(quality.shape) != (N,)
+                                or not quality.is_contiguous()):
+        raise L.CoverError(f"{what}: quality must be None or contiguous fp32 [rows] = [{N}] "
+                           f"(got {tuple(quality.shape) if torch.is_tensor(quality) else type(quality).__name__})")
+    if not torch.is_tensor(step_weight) or step_weight.dtype != torch.float32 or tuple(step_weight.shape) != (steps,) or not step_weight.is_contiguous():
+        raise L.CoverError(f"{what}: step_weight must be contiguous fp32 [steps] = [{steps}] (host.coherence_step_weights makes it) "
+                           f"(got {tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__})")
+    for name, v in (("weight", weight), ("cover_dist", cover_dist), ("gripper_penalty", gripper_penalty)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or math.isnan(v):
+            raise L.CoverError(f"{what}: {name} must be a number (got {v!r})")
+    weight, cover, penalty = (C.c_float(float(v)).value for v in (weight, cover_dist, gripper_penalty))
+    if not (math.isfinite(weight) and weight >= 0.0):
+        raise L.CoverError(f"{what}: weight must be finite and >= 0 (got {weight!r})")
+    if not cover < math.inf:
+        raise L.CoverError(f"{what}: cover_dist must be < +inf in fp32; a negative value switches the covering rule off (got {cover_dist!r})")
+    if not (math.isfinite(penalty) and penalty >= 0.0):
+        raise L.CoverError(f"{what}: gripper_penalty must be finite and >= 0 (got {gripper_penalty!r})")
+    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Diversity's upload: validated there, once
+        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
+            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
+    else:
+        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
+    _chk_dev(src, quality, step_weight, centers)
+    dev = src.device
+    dim_scale = dim_scale.to(dev)
+    if any(t is not None and t.device != dev for t in (quality, step_weight, dim_scale, centers)):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    res = DiverseSubset(torch.empty(out_shape(G * m), dtype=elem, device=dev), torch.empty(G, m, **i32), torch.empty(G, **i32),
+                        torch.empty(G, m, **f32), torch.empty(G, m, **f32), torch.empty(N, **i32), torch.empty(N, **f32))
+    a = L.DiverseArgs()
+    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
+    if centers is not None:
+        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.quality = quality.data_ptr() if quality is not None else None
+    a.step_weight, a.dim_scale = step_weight.data_ptr(), dim_scale.data_ptr()
+    a.G, a.group_rows, a.m, a.h = G, S, m, steps
+    a.weight, a.cover_dist, a.gripper_penalty = weight, cover, penalty
+    a.out, a.picked_rows_out, a.count_out = res.rows.data_ptr(), res.picked.data_ptr(), res.count.data_ptr()
+    a.pick_value_out, a.pick_dist_out = res.value.data_ptr(), res.dist.data_ptr()
+    a.assign_out, a.row_dist_out = res.assign.data_ptr(), res.row_dist.data_ptr()
+    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    return res
+
+
+def diverse_subset_tokens(tokens, group_rows, keep, centers, tok_vocab, *, steps=1, quality=None, weight, cover_dist=-1.0, step_weight,
+                          dim_scale, gripper_penalty=0.0):
+    """A diverse subset of action-token chunks (cover_diverse_subset_tokens): tokens int64 [G * group_rows, >= 7 steps] (unit column
+    stride, any row stride; row i belongs to prompt i // group_rows) -> DiverseSubset with at most keep rows per prompt, chosen greedily:
+    pick 0 is the row of the largest quality (lowest index on a tie), every later pick the row that maximises quality + weight * (its
+    distance to the nearest row already picked) among the rows not picked yet whose distance to the nearest pick exceeds cover_dist.
+    The distance is coherence_prior_tokens' D between two rows of the group: the sum over the steps t of step_weight[t] * (sum over
+    dim < 6 of ((x - y) * dim_scale[dim])^2 + gripper_penalty where the gripper classes (value >= 0.5) differ) on the de-tokenised
+    values centers[clamp(tok_vocab - token - 1)]. quality: fp32 [rows] or None (all 0): whatever is known -- a policy log-probability,
+    the proposal or coherence prior before the verifier, the verifier's scores after it. weight == 0 picks in refine_tokens' rank order;
+    quality None with weight > 0 is the farthest-point traversal from row 0. cover_dist < 0: off; 0: a row equal to a pick (in the dims
+    that count) is never picked, so duplicates cost no verifier row; r > 0: the selection ends once every row lies within r of a pick,
+    count adapts. A row with a NaN quality or a non-finite element the distance reads is never picked (a NaN in a dim of scale 0 or in
+    dim 6 is invisible); rows tie-break by ascending index, so the result is a fixed function of the inputs. The unfilled slots of
+    .rows repeat slot 0, so .rows goes to tokens_to_histories / score_histories with group_size = keep as it is; host.spread_scores
+    takes the scores back to the input rows through .assign. step_weight: fp32 [steps] on the device (host.coherence_step_weights);
+    dim_scale: a 6-sequence of finite numbers >= 0, validated here and uploaded, or an fp32 [6] tensor already on the device
+    (host.Diversity's, validated there; on the device a negative or non-finite entry makes count 0). No keep, weight, scale or covering
+    distance is chosen or recommended: there is no task-success data to choose them on. Every rounding is specified in
+    include/cover_hip.h. One launch, no workspace, recordable."""
+    steps, n_stride = _token_rows("diverse_subset_tokens", tokens, steps, centers)
+    return _diverse("diverse_subset_tokens", lambda h: h.cover_diverse_subset_tokens, tokens, torch.int64, n_stride, 7, tokens.shape[0],
+                    steps, group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty,
+                    lambda R: (R, 7 * steps), centers=centers, tok_vocab=tok_vocab)
+
+
+def diverse_subset_actions(actions, group_rows, keep, *, quality=None, weight, cover_dist=-1.0, step_weight, dim_scale, gripper_penalty=0.0):
+    """The same for float rows (cover_diverse_subset_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last stride and any
+    other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer -> DiverseSubset whose .rows is contiguous fp32
+    [G * keep, steps, 7], the picked rows' first 7 dims bit for bit. See diverse_subset_tokens."""
+    _action_rows("diverse_subset_actions", actions)
+    return _diverse("diverse_subset_actions", lambda h: h.cover_diverse_subset_actions, actions, torch.float32, actions.stride(0),
+                    actions.stride(1), actions.shape[0], actions.shape[1], group_rows, keep, quality, weight, cover_dist, step_weight,
+                    dim_scale, gripper_penalty, lambda R: (R, actions.shape[1], 7))
+
+
 # ------------------------------------------------------------------------------------------------ beam search
 def beam_merge(cum, cand_tok, cand_lp, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None, out_step_lp=None):
     """One beam-search step over G = rows / n_beams prompt groups (cover_beam_merge; row g * n_beams + b is beam b of group g).

@@ -454,6 +454,7 @@ class PI0Policy:
         self.proposal_prior = None                # host.ProposalPrior or None (off): what select_action scores its rows with, see there
         self.last_proposal_prior = None           # fp32 [rows] on the device, set by a select_action that ran with self.proposal_prior set
         self.coherence = None                     # host.Coherence or None (off): the chunk-coherence prior of select_action's rows, see there
+        self.diverse = None                       # host.Diversity or None (off): select_action keeps a diverse subset of its rows, see there
         self._last_sampled = None                 # (the last sampled batch [B, chunk, max_action_dim], rows per prompt of the queue, policy samples per prompt)
         self.reset()
 
@@ -488,6 +489,7 @@ class PI0Policy:
         self._action_queue = collections.deque([], maxlen=self.config.n_action_steps)
         self.committed_tail = None                # fp32 [1, chunk_size - n_action_steps, 7] on the device: commit()
         self.last_coherence_prior = None          # fp32 [rows] on the device: select_action with self.coherence and a committed tail
+        self.last_diverse = None                  # ops.DiverseSubset: select_action with self.diverse
         self._last_sampled = None
 
     def commit(self, row: int):
@@ -574,8 +576,32 @@ class PI0Policy:
         of the chunk committed last time, over min(n_action_steps, chunk_size - n_action_steps) steps). It is kept as
         self.last_coherence_prior, fp32 [rows] on the device; the caller combines priors with plain torch, for example
         candidate_prior = last_proposal_prior + c * last_coherence_prior (no c is recommended). A call that finds the queue filled, the
-        attribute None or no committed tail launches nothing and leaves last_coherence_prior as it is; reset() clears both."""
+        attribute None or no committed tail launches nothing and leaves last_coherence_prior as it is; reset() clears both.
+        self.diverse (a host.Diversity set on the policy; None, the default = nothing is launched): of every prompt's rows only
+        diverse.keep are queued, picked greedily by quality + weight * distance to the rows already picked
+        (ops.diverse_subset_actions on the same normalised [rows, n_action_steps, 7] view, after the augmentation and after the priors;
+        quality = last_proposal_prior when self.proposal_prior is set, else none). A prompt's rows are samples_per_prompt + n_augmented
+        with augment=, else proposal_prior.samples_per_prompt, else the whole batch (one prompt); keep beyond that is a CoverError before
+        the policy runs. The queue then holds G * keep rows per step (an unfilled slot repeats the prompt's first pick);
+        last_proposal_prior and last_coherence_prior are gathered alike, -inf on unfilled slots, so they stay the candidate_prior of the
+        queued rows. The result is kept as self.last_diverse (ops.DiverseSubset): .picked maps a queued row back to the row of the
+        sampled batch that commit(row) takes. A call that finds the queue filled, or the attribute None, leaves it; reset() clears it."""
         if len(self._action_queue) == 0:
+            diverse = self.diverse
+            if diverse is not None:                        # checked before the policy runs
+                from .host import Diversity
+                if not isinstance(diverse, Diversity):
+                    raise ops.L.CoverError(f"PI0Policy.diverse must be None or a host.Diversity (got {type(diverse).__name__})")
+                if self.config.action_dim != 7:
+                    raise ops.L.CoverError(f"PI0Policy.diverse: action_dim must be 7 (got {self.config.action_dim})")
+                if augment is not None:
+                    diverse_rows = augment.samples_per_prompt + augment.n_augmented
+                elif self.proposal_prior is not None and hasattr(self.proposal_prior, "samples_per_prompt"):
+                    diverse_rows = self.proposal_prior.samples_per_prompt
+                else:
+                    diverse_rows = int(batch["observation.state"].shape[0])
+                if diverse.keep > diverse_rows:
+                    raise ops.L.CoverError(f"PI0Policy.diverse: keep = {diverse.keep} exceeds the {diverse_rows} rows of a prompt")
             coherence = self.coherence if self.committed_tail is not None else None
             if self.coherence is not None:                 # checked before the policy runs
                 from .host import Coherence
@@ -618,6 +644,18 @@ class PI0Policy:
                 ones = torch.ones(1, dtype=torch.float32, device=actions.device)
                 self.last_coherence_prior = ops.coherence_prior_actions(
                     actions, S, self.committed_tail, ones, shift=0, **coherence.kwargs(actions.device, self.config.n_action_steps))
+            if diverse is not None:
+                sub = ops.diverse_subset_actions(actions, diverse_rows, diverse.keep,
+                                                 quality=self.last_proposal_prior if proposal_prior is not None else None,
+                                                 **diverse.kwargs(actions.device, self.config.n_action_steps))
+                kept, valid = sub.picked.reshape(-1).clamp(min=0).to(torch.int64), sub.valid.reshape(-1)
+                gather = lambda prior: torch.where(valid, prior[kept], torch.full_like(prior[kept], -math.inf))
+                if proposal_prior is not None:
+                    self.last_proposal_prior = gather(self.last_proposal_prior)
+                if coherence is not None:
+                    self.last_coherence_prior = gather(self.last_coherence_prior)
+                self.last_diverse = sub
+                actions = sub.rows
             actions = unnormalize_action(actions, self._norm.get("action", IDENTITY))
             self._action_queue.extend(actions.transpose(0, 1))
         return self._action_queue

@@ -1091,6 +1091,78 @@ typedef struct cover_coherence_args {
 int cover_coherence_prior_tokens(const cover_coherence_args* args, void* stream);
 int cover_coherence_prior_actions(const cover_coherence_args* args, void* stream);
 
+/* Diverse candidate subsets: per prompt group a greedy selection of at most m of its S rows by quality plus weight times the distance to
+ * the rows already chosen (maximal marginal relevance; with no quality, the farthest-point traversal), with an optional covering
+ * distance that leaves out rows already covered by a pick. A group is group_rows (S) contiguous rows (row i belongs to group i / S).
+ * The picks are sequential, so the whole loop is one launch: one 1024-thread block per group, thread tid owning rows tid + 1024 q. One
+ * launch, no workspace, no atomics, recordable; no result depends on the schedule. All arithmetic is fp32, one rounding per operation,
+ * never an fma.
+ * Pair distance D(i, j) of two rows of one group: cover_coherence_prior's D with T = h and shift = 0, x / y the rows' values:
+ *   D = 0.0f
+ *   for t = 0..h-1 in order:
+ *     e = 0.0f
+ *     for d = 0..5 with dim_scale[d] != 0:  diff = x - y;  s = diff * dim_scale[d];  sq = s * s;  e = e + sq
+ *       (a dim whose scale is 0 is not read into the sum: a NaN there is invisible)
+ *     if gripper_penalty != 0 and the classes (x_6 >= 0.5f) and (y_6 >= 0.5f) differ:  e = e + gripper_penalty
+ *     p = step_weight[t] * e;  D = D + p
+ * quality: fp32 [G * S], optional; NULL = every quality is 0.0f. weight: the factor of the distance term.
+ * Per group:
+ *   Row i is ELIGIBLE iff quality[i] is not NaN and D(i, i) is not NaN (so: every element the distance reads is finite; a NaN in dim 6
+ *   or in a dim of scale 0 is invisible). A dim_scale entry that is negative or not finite makes no row eligible; there is no trap.
+ *   mind[i] = +inf, assign[i] = -1 for every row.
+ *   Pick 0: the eligible row of the largest quality, the lowest index on a tie (-0 == +0). Its value v is its quality.
+ *   Pick k >= 1: row i is a CANDIDATE iff it is eligible, not picked yet and mind[i] > cover_dist. Its value is
+ *     weight == 0:  v = quality[i]          (no product is formed)
+ *     otherwise  :  prod = weight * mind[i];  v = quality[i] + prod
+ *     and a row whose v is NaN is no candidate at this step. The pick is the lexicographic (v descending with -0 == +0, index
+ *     ascending) maximum over the candidates. With no candidate the selection ends: count = k.
+ *   After every pick, slot k holding row p, EVERY row i of the group (picked, ineligible and row p itself included) is updated:
+ *     d = D(i, p);  if d < mind[i]: mind[i] = d, assign[i] = k     (strict: an equal distance keeps the earlier slot; a NaN d never
+ *     enters). The update after the last pick runs too, so assign and row_dist are final.
+ *   cover_dist < 0 switches the covering rule off (mind >= 0 > cover_dist for every row, +inf included); cover_dist == 0 leaves out
+ *   rows at distance 0 of a pick (exact duplicates in the dims that count); cover_dist = r > 0 ends the selection once every eligible row
+ *   lies within r of a pick, so count adapts to the group.
+ * Outputs (NULL = not written, except picked_rows_out; every cell of a given output is stored, unfilled slots k >= count included):
+ *   picked_rows_out int32 [G][m]   the global row g * S + p of slot k                       unfilled: -1
+ *   count_out       int32 [G]      the number of picks made
+ *   pick_value_out  fp32 [G][m]    v at pick time (the value's bits)                        unfilled: 0x7FC00000
+ *   pick_dist_out   fp32 [G][m]    mind[p] at pick time; +inf for slot 0                    unfilled: +inf
+ *   assign_out      int32 [G * S]  the slot of the nearest pick, -1 where there is none
+ *   row_dist_out    fp32 [G * S]   the final mind
+ *   out             int64 [G * m][7 h] (tokens) or fp32 [G * m][h][7] (actions): the picked rows verbatim, as cover_refine_* gathers its
+ *                   elites; an unfilled slot repeats the group's slot-0 row, a group with no pick stores its input row 0 in every slot.
+ * cover_diverse_subset_tokens: src = int64 tokens, element (row, t, d) at src[row * n_stride + t * 7 + d] (n_stride >= 7 h; t_stride
+ *   unused), x = centers[clamp(tok_vocab - token - 1, 0, n_centers - 1)] (cover_tokens_to_histories' rule).
+ * cover_diverse_subset_actions: src = fp32, element (row, t, d) at src[row * n_stride + t * t_stride + d] (strides in elements, unit last
+ *   stride: a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place); centers unused.
+ * Only the cells named above are read: nothing of src outside its [rows][h][7] view. step_weight fp32 [h] (the caller's, made on the
+ * host), dim_scale fp32 [6]; both device memory.
+ * The group's values stay in LDS (row stride 7 h | 1 floats) when 4 * ((S + 1) * (7 h | 1) + h + m) <= 160 KiB - 256 B, and are read
+ * from src again at every distance otherwise; the choice is a function of (S, m, h) alone and both paths run the same arithmetic.
+ * COVER_EINVAL, and nothing launched, unless G >= 1, 1 <= m <= group_rows <= 4096, 1 <= h <= 64, G * group_rows <= 2^20, weight finite
+ * and >= 0, cover_dist not NaN and < +inf, gripper_penalty finite and >= 0, src / step_weight / dim_scale / picked_rows_out non-null
+ * and, for tokens, n_stride >= 7 h, centers non-null, n_centers >= 1. */
+typedef struct cover_diverse_args {
+    const void* src;                /* int64 tokens or fp32 actions, see above */
+    long long n_stride, t_stride;   /* in elements */
+    const float* centers;           /* tokens: [n_centers] bin centres */
+    int n_centers, tok_vocab;
+    const float* quality;           /* [G * group_rows], optional */
+    const float* step_weight;       /* [h] */
+    const float* dim_scale;         /* [6] */
+    int G, group_rows, m, h;
+    float weight, cover_dist, gripper_penalty, _pad;
+    int* picked_rows_out;           /* int32 [G][m] */
+    int* count_out;                 /* int32 [G], optional */
+    float* pick_value_out;          /* [G][m], optional */
+    float* pick_dist_out;           /* [G][m], optional */
+    int* assign_out;                /* int32 [G * group_rows], optional */
+    float* row_dist_out;            /* [G * group_rows], optional */
+    void* out;                      /* int64 [G * m][7 h] or fp32 [G * m][h][7], optional */
+} cover_diverse_args;
+int cover_diverse_subset_tokens(const cover_diverse_args* args, void* stream);
+int cover_diverse_subset_actions(const cover_diverse_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
