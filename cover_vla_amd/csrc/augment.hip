@@ -4,7 +4,7 @@
 // operators with contraction off for the whole file, because hipcc would otherwise fuse d * d + ss and mean + s * z into one v_fma_f32.
 #include "common.h"
 #include "kernels.h"
-#include "augment_fit.h"   // aug_value, augment_group_stats: the fit, shared with proposal_prior.hip and refine.hip
+#include "augment_fit.h"   // augment_group_stats: the fit, shared with proposal_prior.hip and refine.hip; the rows are chunk_rows.h's chunk_src
 #include "augment_draw.h"  // aug_store, augment_draw_rows: the draw, shared with refine.hip
 
 #pragma clang fp contract(off)
@@ -16,28 +16,23 @@ __global__ __launch_bounds__(256) void augment_k(cover_augment_args a, long long
     __shared__ float s_mean[6 * 64], s_s[6 * 64];
     __shared__ int s_jwin[64];
     const int g = blockIdx.x, n = a.n, K = a.K, h = a.h, w = 7 * h;
-    const T* in = (const T*)a.src + (long long)g * n * a.n_stride;
     T* out = (T*)a.out + (size_t)g * (n + K) * w;
-    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, a.n, a.h, a.sigma, a.sd_floor, a.mean_out, a.sd_out, a.votes_out};
-    augment_group_stats<T>(f, in, t_stride, g, s_mean, s_s, s_jwin);
-    for (int i = threadIdx.x; i < n * w; i += blockDim.x) {
-        const int j = i / w, r = i - j * w, t = r / 7, d = r - t * 7;
-        out[i] = in[(long long)j * a.n_stride + (long long)t * t_stride + d];
-    }
+    const aug_fit<T> f = {chunk_src_of<T>(a, t_stride, (long long)g * n), a.n, a.h, a.sigma, a.sd_floor, a.mean_out, a.sd_out, a.votes_out};
+    augment_group_stats<T>(f, g, s_mean, s_s, s_jwin);
+    chunk_gather_rows(f.src, n, w, out, [](int r) { return r; });
     __syncthreads();
-    augment_draw_rows<T>(f, in, t_stride, out + (size_t)n * w, a.normals + (size_t)g * K * 6 * h, K, a.clip_lo, a.clip_hi, s_mean, s_s, s_jwin);
+    augment_draw_rows<T>(f, out + (size_t)n * w, a.normals + (size_t)g * K * 6 * h, K, a.clip_lo, a.clip_hi, s_mean, s_s, s_jwin);
 }
 
 static bool augment_args_ok(const cover_augment_args* a) {
-    const float flt_max = 3.402823466e+38f;
     if (a->G < 1 || a->n < 1 || a->n > 4096 || a->K < 0 || a->K > 4096 || a->h < 1 || a->h > 64) return false;
     if ((long long)a->G * (a->n + a->K) > (1ll << 20)) return false;
-    if (!(a->sigma >= 0.0f) || !(a->sigma <= flt_max) || !(a->sd_floor >= 0.0f) || !(a->sd_floor <= flt_max)) return false;   // a NaN fails both
+    if (!f32_ge(a->sigma, 0.0f) || !f32_ge(a->sd_floor, 0.0f)) return false;
     if (!(a->clip_lo <= a->clip_hi)) return false;
     return a->src && a->out && (a->K == 0 || a->normals);
 }
 hipError_t launch_augment_tokens(const cover_augment_args* a, hipStream_t st) {
-    if (!augment_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    if (!augment_args_ok(a) || !token_form_ok(a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(augment_k<int64_t>, dim3(a->G), dim3(256), 0, st, *a, 7ll);
     return hipGetLastError();
 }

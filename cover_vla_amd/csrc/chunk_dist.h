@@ -2,7 +2,8 @@
 // against each other) share: the step-weighted sum over the steps of the squared, per-dim scaled differences of the six translation /
 // rotation values, plus a penalty where the gripper classes differ. Stated once, so the two files cannot drift apart: both results are
 // compared with numpy restatements as bit patterns. Contraction is off from here to the end of the including file (hipcc would otherwise
-// fuse s * s + e into one v_fma_f32).
+// fuse s * s + e into one v_fma_f32). The values it is given come from chunk_rows.h's chunk_src (the row source and the token rule);
+// smooth.hip takes chunk_finite and chunk_load_scale from here and keeps a pair weight of its own.
 #pragma once
 #include "common.h"
 

@@ -3,11 +3,12 @@
 // unexecuted tail of the chunk committed last time) and forward contrast (strong rows with positive, weak rows with negative weights) in
 // one form. O(S * R * 6 T) per group: one wave per candidate row n, 16 rows per block, the lanes walk the references r in lane-strided
 // order over r-tiles staged in LDS; several blocks per group. A lane's chain order is a function of r alone, so no result depends on the
-// tiling. The candidate values come through augment_fit.h's aug_value, so the token form reads what cover_augment_* / cover_refine_* /
-// cover_smooth_scores_* read. The results are compared with a numpy restatement as bit patterns: contraction is off for the whole file.
+// tiling. The candidate rows are chunk_rows.h's chunk_src, staged through its aug_value, so the token form reads what cover_augment_* /
+// cover_refine_* / cover_smooth_scores_* read. The results are compared with a numpy restatement as bit patterns: contraction is off for
+// the whole file.
 #include "common.h"
 #include "kernels.h"
-#include "augment_fit.h"
+#include "chunk_rows.h"   // chunk_src, chunk_stage_rows: the rows and their way into LDS
 #include "chunk_dist.h"   // chunk_pair_dist: the pair distance, shared with diverse.hip
 
 #pragma clang fp contract(off)
@@ -41,16 +42,12 @@ __global__ __launch_bounds__(1024) void coherence_k(cover_coherence_args a, long
     const int g = blockIdx.x / tiles, n0 = (blockIdx.x - g * tiles) * COHERENCE_ROWS_PER_BLOCK;
     const int n = n0 + wv;
     const bool live = n < S;
-    const T* in = (const T*)a.src + (long long)g * S * a.n_stride;
+    const chunk_src<T> in = chunk_src_of<T>(a, t_stride, (long long)g * S);
     const float* ref = a.ref + (long long)g * a.ref_g_stride + 7 * a.shift;   // candidate step t meets reference step t + shift
     const float* wt = a.ref_weight + (long long)g * a.w_g_stride;
-    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, 0, a.h, 0.0f, 0.0f, nullptr, nullptr, nullptr};
     float sc[6];
     const bool usable = chunk_load_scale(a.dim_scale, sc);   // a negative or non-finite scale: every prior of the launch is NaN
-    for (int i = threadIdx.x; i < COHERENCE_ROWS_PER_BLOCK * w7; i += blockDim.x) {
-        const int r = i / w7, c = i - r * w7, t = c / 7, d = c - t * 7;
-        if (n0 + r < S) s_own[r * stride + c] = aug_value(f, in[(long long)(n0 + r) * a.n_stride + (long long)t * t_stride + d]);
-    }
+    chunk_stage_rows(in, n0, min(COHERENCE_ROWS_PER_BLOCK, S - n0), w7, s_own, stride);
     for (int i = threadIdx.x; i < To; i += blockDim.x) s_sw[i] = a.step_weight[i];
 
     const float* x = s_own + wv * stride;
@@ -95,7 +92,6 @@ __global__ __launch_bounds__(1024) void coherence_k(cover_coherence_args a, long
 }
 
 static bool coherence_args_ok(const cover_coherence_args* a) {
-    const float flt_max = 3.402823466e+38f;
     if (a->G < 1 || a->group_rows < 1 || a->group_rows > COHERENCE_MAX_ROWS || a->R < 1 || a->R > COHERENCE_MAX_REFS) return false;
     if (a->h < 1 || a->h > 64 || a->hr < 1 || a->hr > 64 || a->shift < 0 || a->shift >= a->hr) return false;
     if ((long long)a->G * a->group_rows > (1ll << 20)) return false;
@@ -105,26 +101,22 @@ static bool coherence_args_ok(const cover_coherence_args* a) {
         if (gap < 0 || (a->R > 1 && gap / (a->R - 1) < a->ref_r_stride)) return false;
     }
     if (a->w_g_stride != 0 && a->w_g_stride != a->R) return false;
-    if (!(a->gripper_penalty >= 0.0f) || !(a->gripper_penalty <= flt_max)) return false;   // a NaN fails both
+    if (!f32_ge(a->gripper_penalty, 0.0f)) return false;
     return a->src && a->ref && a->ref_weight && a->step_weight && a->dim_scale && a->prior_out;
 }
 template <typename T>
 static hipError_t coherence_launch(const cover_coherence_args* a, long long t_stride, hipStream_t st) {
     const int S = a->group_rows, R = a->R, To = a->h < a->hr - a->shift ? a->h : a->hr - a->shift, stride = (7 * To) | 1;
-    int TR = COHERENCE_TILE_FLOATS / stride / 64 * 64;
-    TR = TR < 64 ? 64 : (TR > COHERENCE_MAX_TILE ? COHERENCE_MAX_TILE : TR);
-    if (TR > (R + 63) / 64 * 64) TR = (R + 63) / 64 * 64;
+    const int TR = chunk_tile_rows(stride, R, COHERENCE_TILE_FLOATS, COHERENCE_MAX_TILE);
     const size_t lds = ((size_t)(COHERENCE_ROWS_PER_BLOCK + TR) * stride + To) * sizeof(float);   // <= (80 * 449 + 64) * 4 = 143,936 B at T = 64
-    if (lds > 64 * 1024) {
-        const hipError_t e = LDS_ATTR_160K(coherence_k<T>);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = LDS_ATTR_FOR(coherence_k<T>, lds);
+    if (e != hipSuccess) return e;
     const int tiles = (S + COHERENCE_ROWS_PER_BLOCK - 1) / COHERENCE_ROWS_PER_BLOCK;
     hipLaunchKernelGGL(coherence_k<T>, dim3(a->G * tiles), dim3(64 * COHERENCE_ROWS_PER_BLOCK), lds, st, *a, t_stride, TR, stride);
     return hipGetLastError();
 }
 hipError_t launch_coherence_prior_tokens(const cover_coherence_args* a, hipStream_t st) {
-    if (!coherence_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    if (!coherence_args_ok(a) || !token_form_ok(a)) return hipErrorInvalidValue;
     return coherence_launch<int64_t>(a, 7ll, st);
 }
 hipError_t launch_coherence_prior_actions(const cover_coherence_args* a, hipStream_t st) {

@@ -26,6 +26,13 @@ static inline hipError_t lds_attr_160k_cached(const void* fn, LdsAttrCache& c) {
     return e;
 }
 #define LDS_ATTR_160K(kfn) ([&]() -> hipError_t { static LdsAttrCache c_; return lds_attr_160k_cached((const void*)(kfn), c_); }())
+// The same for a launch of `lds` bytes of dynamic LDS: nothing to do up to 64 KiB. A failure is reported by the value, so the sticky error
+// is cleared: the next launch's hipGetLastError must not see it.
+static inline hipError_t lds_attr_reported(hipError_t e) {
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+#define LDS_ATTR_FOR(kfn, lds) ((lds) > 64 * 1024 ? lds_attr_reported(LDS_ATTR_160K(kfn)) : hipSuccess)
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
@@ -79,6 +86,11 @@ __device__ __forceinline__ float act_apply_bf16(float x, int act) {
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;

@@ -4,13 +4,15 @@
 // depend on each other, so one 1024-thread block owns a group for the whole loop: thread tid keeps mind / assign of rows tid + 1024 q
 // (q < 4) in registers, the newest pick's row is staged in LDS and read as a broadcast, and the block arg-max is a min over unique 64-bit
 // keys (desc_key(v) << 32 | row), so no result depends on the schedule. O(m * S * 6 h) per group, latency-bound by design: two barriers
-// per pick. The distance is chunk_dist.h's, shared with coherence.hip; the values come through augment_fit.h's aug_value, so the token
-// form reads what cover_augment_* / cover_refine_* / cover_coherence_prior_* read. The results are compared with a numpy restatement as
-// bit patterns: contraction is off for the whole file.
+// per pick. The distance is chunk_dist.h's, shared with coherence.hip; the rows are chunk_rows.h's chunk_src, read through its aug_value,
+// so the token form reads what cover_augment_* / cover_refine_* / cover_coherence_prior_* read. The results are compared with a numpy
+// restatement as bit patterns: contraction is off for the whole file. The staging and gather walks are written out here, with the
+// block's fixed step, and not taken from chunk_rows.h: with the shared walks the compiler laid the pick loop out differently and the
+// resident path measured 3 - 21 % slower (docs/OPTIMISATION_LOG.md); as written the kernels compile to the instructions they had.
 #include "common.h"
 #include "kernels.h"
 #include "keysort.h"       // desc_key
-#include "augment_fit.h"   // aug_value
+#include "chunk_rows.h"    // chunk_src, aug_value; token_form_ok, f32_ge
 #include "chunk_dist.h"
 
 #pragma clang fp contract(off)
@@ -45,7 +47,7 @@ __global__ __launch_bounds__(DIVERSE_THREADS) void diverse_k(cover_diverse_args 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = blockIdx.x, S = a.group_rows, m = a.m, h = a.h, w7 = 7 * h;
     const T* in = (const T*)a.src + (long long)g * S * a.n_stride;
-    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, 0, h, 0.0f, 0.0f, nullptr, nullptr, nullptr};
+    const chunk_src<T> f = {in, a.n_stride, t_stride, a.centers, a.n_centers, a.tok_vocab};
     float sc[6];
     const bool usable = chunk_load_scale(a.dim_scale, sc);   // a negative or non-finite scale: no row is eligible
     const float penalty = a.gripper_penalty, weight = a.weight, cover = a.cover_dist;
@@ -175,12 +177,10 @@ __global__ __launch_bounds__(DIVERSE_THREADS) void diverse_k(cover_diverse_args 
 }
 
 static bool diverse_args_ok(const cover_diverse_args* a) {
-    const float flt_max = 3.402823466e+38f;
     if (a->G < 1 || a->m < 1 || a->m > a->group_rows || a->group_rows > DIVERSE_MAX_ROWS || a->h < 1 || a->h > 64) return false;
     if ((long long)a->G * a->group_rows > (1ll << 20)) return false;
-    if (!(a->weight >= 0.0f) || !(a->weight <= flt_max)) return false;                     // a NaN fails both
-    if (!(a->cover_dist <= flt_max)) return false;                                          // NaN and +inf; -inf is "off"
-    if (!(a->gripper_penalty >= 0.0f) || !(a->gripper_penalty <= flt_max)) return false;
+    if (!f32_ge(a->weight, 0.0f) || !f32_ge(a->gripper_penalty, 0.0f)) return false;
+    if (!f32_ge(a->cover_dist, -INFINITY)) return false;                                    // NaN and +inf; -inf is "off"
     return a->src && a->step_weight && a->dim_scale && a->picked_rows_out;
 }
 template <typename T>
@@ -190,13 +190,8 @@ static hipError_t diverse_launch(const cover_diverse_args* a, long long t_stride
     const bool resident = fixed + rows <= DIVERSE_LDS_BUDGET;   // a function of (S, m, h) alone
     const size_t lds = DIVERSE_PART_BYTES + fixed + (resident ? rows : 0);
     if (resident) {
-        if (lds > 64 * 1024) {
-            const hipError_t e = LDS_ATTR_160K((diverse_k<T, true>));
-            if (e != hipSuccess) {
-                (void)hipGetLastError();   // reported here: the next launch's hipGetLastError must not see it
-                return e;
-            }
-        }
+        const hipError_t e = LDS_ATTR_FOR((diverse_k<T, true>), lds);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL((diverse_k<T, true>), dim3(a->G), dim3(DIVERSE_THREADS), lds, st, *a, t_stride, stride);
     } else {
         hipLaunchKernelGGL((diverse_k<T, false>), dim3(a->G), dim3(DIVERSE_THREADS), lds, st, *a, t_stride, stride);
@@ -204,7 +199,7 @@ static hipError_t diverse_launch(const cover_diverse_args* a, long long t_stride
     return hipGetLastError();
 }
 hipError_t launch_diverse_subset_tokens(const cover_diverse_args* a, hipStream_t st) {
-    if (!diverse_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    if (!diverse_args_ok(a) || !token_form_ok(a)) return hipErrorInvalidValue;
     return diverse_launch<int64_t>(a, 7ll, st);
 }
 hipError_t launch_diverse_subset_actions(const cover_diverse_args* a, hipStream_t st) {

@@ -2,8 +2,8 @@
 // group's rows are ranked by their scores, the n_elite best are gathered to the front of the output verbatim, the diagonal Gaussian of
 // augment.hip is fitted to those gathered rows and K new rows are drawn from it behind them. The fit is augment_fit.h's and the draw
 // augment_draw.h's, both shared with augment.hip, so the output is what cover_augment_* gives on the gathered rows, bit for bit; the
-// order is a sort of unique keys (keysort.h), so it does not depend on the schedule. The results are compared with a numpy restatement
-// as bit patterns: contraction is off for the whole file.
+// order is a sort of unique keys (keysort.h), so it does not depend on the schedule. The input rows and the gather are chunk_rows.h's
+// (chunk_src, chunk_gather_rows). The results are compared with a numpy restatement as bit patterns: contraction is off for the whole file.
 #include "common.h"
 #include "kernels.h"
 #include "keysort.h"
@@ -39,13 +39,8 @@ __global__ __launch_bounds__(256) void refine_k(cover_refine_args a, long long t
     __syncthreads();
     bitonic_sort_lds(s_key, n2);   // returns behind a barrier
     // 2. gather: output row r < m is the input row of rank r (m <= S, and the S live keys sort in front of the dead ones: j < S)
-    const T* in = (const T*)a.src + (long long)g * S * a.n_stride;
     T* out = (T*)a.out + (size_t)g * (m + K) * w;
-    for (int i = threadIdx.x; i < m * w; i += blockDim.x) {
-        const int r = i / w, c = i - r * w, t = c / 7, d = c - t * 7;
-        const int j = (int)(uint32_t)s_key[r];
-        out[i] = in[(long long)j * a.n_stride + (long long)t * t_stride + d];
-    }
+    chunk_gather_rows(chunk_src_of<T>(a, t_stride, (long long)g * S), m, w, out, [&](int r) { return (int)(uint32_t)s_key[r]; });
     for (int r = threadIdx.x; r < m; r += blockDim.x) {
         const int j = (int)(uint32_t)s_key[r];
         if (a.elite_rows_out) a.elite_rows_out[(size_t)g * m + r] = g * S + j;
@@ -54,24 +49,23 @@ __global__ __launch_bounds__(256) void refine_k(cover_refine_args a, long long t
     __syncthreads();   // the gathered rows, stored by this block, are what the fit reads
     // 3. fit and draw: cover_augment_*'s second half on the output's own first m rows (row stride 7 h, step stride 7), so the chains run
     // in rank order and a gripper tie goes to the best elite's class
-    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, (long long)w, m, h, a.sigma, a.sd_floor, a.mean_out, a.sd_out, a.votes_out};
-    augment_group_stats<T>(f, out, 7ll, g, s_mean, s_s, s_jwin);
+    const aug_fit<T> f = {{out, (long long)w, 7ll, a.centers, a.n_centers, a.tok_vocab}, m, h, a.sigma, a.sd_floor, a.mean_out, a.sd_out, a.votes_out};
+    augment_group_stats<T>(f, g, s_mean, s_s, s_jwin);
     __syncthreads();
-    augment_draw_rows<T>(f, out, 7ll, out + (size_t)m * w, a.normals + (size_t)g * K * 6 * h, K, a.clip_lo, a.clip_hi, s_mean, s_s, s_jwin);
+    augment_draw_rows<T>(f, out + (size_t)m * w, a.normals + (size_t)g * K * 6 * h, K, a.clip_lo, a.clip_hi, s_mean, s_s, s_jwin);
 }
 
 static bool refine_args_ok(const cover_refine_args* a) {
-    const float flt_max = 3.402823466e+38f;
     if (a->G < 1 || a->n_elite < 1 || a->n_elite > a->group_rows || a->group_rows > REFINE_MAX_ROWS || a->K < 0 || a->K > 4096 || a->h < 1 ||
         a->h > 64)
         return false;
     if ((long long)a->G * a->group_rows > (1ll << 20) || (long long)a->G * (a->n_elite + a->K) > (1ll << 20)) return false;
-    if (!(a->sigma >= 0.0f) || !(a->sigma <= flt_max) || !(a->sd_floor >= 0.0f) || !(a->sd_floor <= flt_max)) return false;   // a NaN fails both
+    if (!f32_ge(a->sigma, 0.0f) || !f32_ge(a->sd_floor, 0.0f)) return false;
     if (!(a->clip_lo <= a->clip_hi)) return false;
     return a->src && a->scores && a->out && (a->K == 0 || a->normals);
 }
 hipError_t launch_refine_tokens(const cover_refine_args* a, hipStream_t st) {
-    if (!refine_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    if (!refine_args_ok(a) || !token_form_ok(a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(refine_k<int64_t>, dim3(a->G), dim3(256), 0, st, *a, 7ll);
     return hipGetLastError();
 }

@@ -2,27 +2,23 @@
 // local mean (Nadaraya-Watson, Epanechnikov weights on a scaled squared distance in the 6-D action space) of one fp32 score per row,
 // shrunk towards the group mean. O(S^2 * 6 h) per group: one wave per row n, 16 rows per block, the lanes walk the group's rows j in
 // lane-strided order over j-tiles of de-tokenised values staged in LDS; several blocks per group, each block recomputing what it needs
-// of the group (its mean), so no thread's result depends on the tiling. The values come through augment_fit.h's aug_value, so the token
-// form reads what cover_augment_* / cover_refine_* read. The results are compared with a numpy restatement as bit patterns: contraction
-// is off for the whole file.
+// of the group (its mean), so no thread's result depends on the tiling. The rows are chunk_rows.h's chunk_src, staged through its
+// aug_value, so the token form reads what cover_augment_* / cover_refine_* read. The results are compared with a numpy restatement as
+// bit patterns: contraction is off for the whole file.
 #include "common.h"
 #include "kernels.h"
-#include "augment_fit.h"
+#include "chunk_rows.h"   // chunk_src, chunk_stage_rows: the rows and their way into LDS
+#include "chunk_dist.h"   // chunk_finite, chunk_load_scale
 
 #pragma clang fp contract(off)
 
 #define SMOOTH_MAX_ROWS 4096
 #define SMOOTH_ROWS_PER_BLOCK 16      // one wave each
 #define SMOOTH_TILE_FLOATS 12288      // the LDS budget of one j-tile (48 KiB) while more than 64 rows fit
+#define SMOOTH_MAX_TILE 1024          // rows per j-tile at the narrowest row
 
-__device__ __forceinline__ bool smooth_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the weight of one pair of different rows: xn / xj point at the rows' [h][7] values (step stride 7)
+// the weight of one pair of different rows: xn / xj point at the rows' [h][7] values (step stride 7). NOT chunk_dist.h's
+// chunk_pair_dist_of: d2 is one chain over (step, dim) with no per-step subtotal and no step weight, a different sequence of roundings.
 __device__ __forceinline__ float smooth_pair_weight(const float* xn, const float* xj, int h, const float* sc, bool split, float radius2) {
     bool same = true;
     float d2 = 0.0f;
@@ -59,27 +55,18 @@ __global__ __launch_bounds__(1024) void smooth_k(cover_smooth_args a, long long 
     const int g = blockIdx.x / tiles, n0 = (blockIdx.x - g * tiles) * SMOOTH_ROWS_PER_BLOCK;
     const int n = n0 + wv;
     const bool live = n < S;
-    const T* in = (const T*)a.src + (long long)g * S * a.n_stride;
+    const chunk_src<T> in = chunk_src_of<T>(a, t_stride, (long long)g * S);
     const float* score = a.scores + (size_t)g * S;
-    const aug_fit f = {a.centers, a.n_centers, a.tok_vocab, a.n_stride, 0, h, 0.0f, 0.0f, nullptr, nullptr, nullptr};
     float sc[6];
-    bool usable = true;            // a negative or non-finite scale: every pair weight is 0
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        sc[d] = a.dim_scale[d];
-        if (!(sc[d] >= 0.0f) || !smooth_finite(sc[d])) usable = false;
-    }
+    const bool usable = chunk_load_scale(a.dim_scale, sc);   // a negative or non-finite scale: every pair weight is 0
     const bool split = a.split_gripper != 0;
-    for (int i = threadIdx.x; i < SMOOTH_ROWS_PER_BLOCK * w7; i += blockDim.x) {
-        const int r = i / w7, c = i - r * w7, t = c / 7, d = c - t * 7;
-        if (n0 + r < S) s_own[r * stride + c] = aug_value(f, in[(long long)(n0 + r) * a.n_stride + (long long)t * t_stride + d]);
-    }
+    chunk_stage_rows(in, n0, min(SMOOTH_ROWS_PER_BLOCK, S - n0), w7, s_own, stride);
     // the group mean: a lane-strided chain over the finite scores, the butterfly, one divide
     float msum = 0.0f;
     int mcnt = 0;
     for (int j = lane; j < S; j += 64) {
         const float s = score[j];
-        if (smooth_finite(s)) {
+        if (chunk_finite(s)) {
             msum = msum + s;
             mcnt += 1;
         }
@@ -95,10 +82,7 @@ __global__ __launch_bounds__(1024) void smooth_k(cover_smooth_args a, long long 
     for (int j0 = 0; j0 < S; j0 += TJ) {
         __syncthreads();           // the previous tile has been read (first pass: nothing to wait for but the own rows' stores)
         const int rows = min(TJ, S - j0);
-        for (int i = threadIdx.x; i < rows * w7; i += blockDim.x) {
-            const int r = i / w7, c = i - r * w7, t = c / 7, d = c - t * 7;
-            s_x[r * stride + c] = aug_value(f, in[(long long)(j0 + r) * a.n_stride + (long long)t * t_stride + d]);
-        }
+        chunk_stage_rows(in, j0, rows, w7, s_x, stride);
         __syncthreads();
         if (live) {
             for (int jj = lane; jj < rows; jj += 64) {
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(1024) void smooth_k(cover_smooth_args a, long long 
                     dsum = dsum + w;
                     cnt += 1;
                     const float s = score[j];
-                    if (smooth_finite(s)) {
+                    if (chunk_finite(s)) {
                         den = den + w;
                         const float prod = w * s;
                         num = num + prod;
@@ -125,7 +109,7 @@ __global__ __launch_bounds__(1024) void smooth_k(cover_smooth_args a, long long 
     if (live && lane == 0) {
         const size_t o = (size_t)g * S + n;
         const float own = score[n];
-        if (!smooth_finite(own)) {
+        if (!chunk_finite(own)) {
             ((uint32_t*)a.smoothed_out)[o] = ((const uint32_t*)score)[n];   // bit for bit, a NaN keeps its payload
         } else if (a.shrink == 0.0f) {
             a.smoothed_out[o] = num / den;
@@ -141,29 +125,24 @@ __global__ __launch_bounds__(1024) void smooth_k(cover_smooth_args a, long long 
 }
 
 static bool smooth_args_ok(const cover_smooth_args* a) {
-    const float flt_max = 3.402823466e+38f;
     if (a->G < 1 || a->group_rows < 1 || a->group_rows > SMOOTH_MAX_ROWS || a->h < 1 || a->h > 64) return false;
     if ((long long)a->G * a->group_rows > (1ll << 20)) return false;
-    if (!(a->radius2 > 0.0f) || !(a->radius2 <= flt_max) || !(a->shrink >= 0.0f) || !(a->shrink <= flt_max)) return false;   // a NaN fails both
+    if (!f32_gt(a->radius2, 0.0f) || !f32_ge(a->shrink, 0.0f)) return false;
     return a->src && a->scores && a->dim_scale && a->smoothed_out;
 }
 template <typename T>
 static hipError_t smooth_launch(const cover_smooth_args* a, long long t_stride, hipStream_t st) {
     const int S = a->group_rows, stride = (7 * a->h) | 1;
-    int TJ = SMOOTH_TILE_FLOATS / stride / 64 * 64;
-    TJ = TJ < 64 ? 64 : (TJ > 1024 ? 1024 : TJ);
-    if (TJ > (S + 63) / 64 * 64) TJ = (S + 63) / 64 * 64;
+    const int TJ = chunk_tile_rows(stride, S, SMOOTH_TILE_FLOATS, SMOOTH_MAX_TILE);
     const size_t lds = (size_t)(SMOOTH_ROWS_PER_BLOCK + TJ) * stride * sizeof(float);   // <= 80 * 449 * 4 = 143,680 B at h = 64
-    if (lds > 64 * 1024) {
-        const hipError_t e = LDS_ATTR_160K(smooth_k<T>);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = LDS_ATTR_FOR(smooth_k<T>, lds);
+    if (e != hipSuccess) return e;
     const int tiles = (S + SMOOTH_ROWS_PER_BLOCK - 1) / SMOOTH_ROWS_PER_BLOCK;
     hipLaunchKernelGGL(smooth_k<T>, dim3(a->G * tiles), dim3(64 * SMOOTH_ROWS_PER_BLOCK), lds, st, *a, t_stride, TJ, stride);
     return hipGetLastError();
 }
 hipError_t launch_smooth_scores_tokens(const cover_smooth_args* a, hipStream_t st) {
-    if (!smooth_args_ok(a) || a->n_stride < 7 * a->h || !a->centers || a->n_centers < 1) return hipErrorInvalidValue;
+    if (!smooth_args_ok(a) || !token_form_ok(a)) return hipErrorInvalidValue;
     return smooth_launch<int64_t>(a, 7ll, st);
 }
 hipError_t launch_smooth_scores_actions(const cover_smooth_args* a, hipStream_t st) {

@@ -194,7 +194,34 @@ class _SmoothFields(NamedTuple):
     split_gripper: bool = True
 
 
-_SMOOTH_SCALES = {}      # (dim_scale, device) -> the fp32 [6] device tensor: one upload per device
+def _finite_f32(who, **named):
+    """Every value is a finite Python number (bools rejected) that is finite in fp32 as well, the value the launch receives."""
+    import ctypes
+    from ._lib import CoverError
+    for name, v in named.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(ctypes.c_float(v).value)):
+            raise CoverError(f"{who}: {name} must be a finite number (got {v!r})")
+
+
+_UPLOADS = {}            # ("scale", dim_scale, device) / ("steps", decay, h, device) -> the fp32 device tensor: one upload per device
+
+
+def _scale_on(dim_scale, device):
+    """A checked dim_scale tuple as the fp32 [6] tensor the launch reads, uploaded once per device."""
+    import torch
+    key = ("scale", dim_scale, str(torch.device(device)))
+    if key not in _UPLOADS:
+        _UPLOADS[key] = torch.tensor(dim_scale, dtype=torch.float32).to(device)
+    return _UPLOADS[key]
+
+
+def _steps_on(decay, h, device):
+    """coherence_step_weights(h, decay) as the fp32 [h] tensor the launch reads, uploaded once per device and h."""
+    import torch
+    key = ("steps", decay, int(h), str(torch.device(device)))
+    if key not in _UPLOADS:
+        _UPLOADS[key] = torch.from_numpy(coherence_step_weights(int(h), decay)).to(device)
+    return _UPLOADS[key]
 
 
 class Smooth(_SmoothFields):
@@ -212,9 +239,7 @@ class Smooth(_SmoothFields):
         from ._lib import CoverError
         from .ops import smooth_dim_scale
         f32 = lambda v: ctypes.c_float(v).value                     # the value the launch receives
-        for name, v in (("radius", radius), ("shrink", shrink)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(f32(v))):
-                raise CoverError(f"Smooth: {name} must be a finite number (got {v!r})")
+        _finite_f32("Smooth", radius=radius, shrink=shrink)
         if not (f32(radius) > 0 and math.isfinite(f32(f32(radius) * f32(radius))) and f32(f32(radius) * f32(radius)) > 0):
             raise CoverError(f"Smooth: radius must be > 0 with a finite fp32 square > 0 (got {radius!r})")
         if not shrink >= 0:
@@ -224,11 +249,7 @@ class Smooth(_SmoothFields):
 
     def scale_on(self, device):
         """dim_scale as the fp32 [6] tensor the launch reads, uploaded once per device."""
-        import torch
-        key = (self.dim_scale, str(torch.device(device)))
-        if key not in _SMOOTH_SCALES:
-            _SMOOTH_SCALES[key] = torch.tensor(self.dim_scale, dtype=torch.float32).to(device)
-        return _SMOOTH_SCALES[key]
+        return _scale_on(self.dim_scale, device)
 
     def kwargs(self, device) -> dict:
         """The keywords of ops.smooth_scores_tokens / ops.smooth_scores_actions."""
@@ -254,9 +275,6 @@ class _CoherenceFields(NamedTuple):
     gripper_penalty: float = 0.0
 
 
-_COHERENCE_UPLOADS = {}  # ("scale", dim_scale, device) / ("steps", decay, h, device) -> the fp32 device tensor: one upload per device
-
-
 class Coherence(_CoherenceFields):
     """What OpenVLA.coherence_prior takes and PI0Policy.coherence holds: every candidate gets the prior -sum_r w_r D(candidate, r) over
     a set of reference chunks, D the sum over the overlapping steps t of decay^t * (the squared distance of the translation / rotation
@@ -268,12 +286,9 @@ class Coherence(_CoherenceFields):
     __slots__ = ()
 
     def __new__(cls, dim_scale, decay, gripper_penalty=0.0):
-        import ctypes
         from ._lib import CoverError
         from .ops import smooth_dim_scale
-        for name, v in (("decay", decay), ("gripper_penalty", gripper_penalty)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(ctypes.c_float(v).value)):
-                raise CoverError(f"Coherence: {name} must be a finite number (got {v!r})")
+        _finite_f32("Coherence", decay=decay, gripper_penalty=gripper_penalty)
         if not 0 < decay <= 1:
             raise CoverError(f"Coherence: decay must be in (0, 1] (got {decay!r})")
         if not gripper_penalty >= 0:
@@ -283,19 +298,11 @@ class Coherence(_CoherenceFields):
 
     def scale_on(self, device):
         """dim_scale as the fp32 [6] tensor the launch reads, uploaded once per device."""
-        import torch
-        key = ("scale", self.dim_scale, str(torch.device(device)))
-        if key not in _COHERENCE_UPLOADS:
-            _COHERENCE_UPLOADS[key] = torch.tensor(self.dim_scale, dtype=torch.float32).to(device)
-        return _COHERENCE_UPLOADS[key]
+        return _scale_on(self.dim_scale, device)
 
     def steps_on(self, device, h):
         """coherence_step_weights(h, decay) as the fp32 [h] tensor the launch reads, uploaded once per device and h."""
-        import torch
-        key = ("steps", self.decay, int(h), str(torch.device(device)))
-        if key not in _COHERENCE_UPLOADS:
-            _COHERENCE_UPLOADS[key] = torch.from_numpy(coherence_step_weights(int(h), self.decay)).to(device)
-        return _COHERENCE_UPLOADS[key]
+        return _steps_on(self.decay, h, device)
 
     def kwargs(self, device, h) -> dict:
         """The keywords of ops.coherence_prior_tokens / ops.coherence_prior_actions for candidates of h steps."""
@@ -330,9 +337,7 @@ class Diversity(_DiversityFields):
         f32 = lambda v: ctypes.c_float(v).value                     # the value the launch receives
         if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or not 1 <= keep <= 4096:
             raise CoverError(f"Diversity: keep must be an integer in [1, 4096] (got {keep!r})")
-        for name, v in (("weight", weight), ("decay", decay), ("gripper_penalty", gripper_penalty)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and math.isfinite(f32(v))):
-                raise CoverError(f"Diversity: {name} must be a finite number (got {v!r})")
+        _finite_f32("Diversity", weight=weight, decay=decay, gripper_penalty=gripper_penalty)
         if not weight >= 0:
             raise CoverError(f"Diversity: weight must be >= 0 (got {weight!r})")
         if not 0 < decay <= 1:
@@ -346,10 +351,9 @@ class Diversity(_DiversityFields):
 
     def kwargs(self, device, h) -> dict:
         """The keywords of ops.diverse_subset_tokens / ops.diverse_subset_actions for rows of h steps (keep is positional there). The
-        step weights and the scale are Coherence's uploads: one per device."""
-        coh = Coherence(self.dim_scale, self.decay, self.gripper_penalty)
-        return dict(weight=self.weight, cover_dist=self.cover_dist, step_weight=coh.steps_on(device, h), dim_scale=coh.scale_on(device),
-                    gripper_penalty=self.gripper_penalty)
+        step weights and the scale are the uploads a Coherence of the same values has: one per device."""
+        return dict(weight=self.weight, cover_dist=self.cover_dist, step_weight=_steps_on(self.decay, h, device),
+                    dim_scale=_scale_on(self.dim_scale, device), gripper_penalty=self.gripper_penalty)
 
 
 def spread_scores(scores_kept, subset, group_rows):

@@ -1409,8 +1409,31 @@ def _augment_stats(G, steps, dev):
                         torch.empty(G, steps, 2, dtype=torch.int32, device=dev))
 
 
-def _token_rows(what, tokens, steps, centers):
-    """The input checks of the token forms (augment_tokens, proposal_prior_tokens) -> (steps, row stride in elements)."""
+class _Rows(NamedTuple):
+    """The candidate rows of one call, as _token_rows / _action_rows found them: what every kernel over candidate rows is told of them."""
+    what: str                           # the public function's name, for the messages
+    src: torch.Tensor
+    elem: torch.dtype                   # int64 (tokens) or fp32 (actions)
+    n_stride: int                       # row stride, in elements
+    t_stride: int                       # step stride, in elements
+    N: int
+    steps: int
+    centers: Optional[torch.Tensor]     # tokens: fp32 [n_centers]
+    tok_vocab: int
+
+    def out_shape(self, R):
+        """The shape of a gathered output of R rows."""
+        return (R, 7 * self.steps) if self.elem == torch.int64 else (R, self.steps, 7)
+
+    def fill(self, a):
+        """The row fields of any of the six argument structs."""
+        a.src, a.n_stride, a.t_stride = self.src.data_ptr(), self.n_stride, self.t_stride
+        if self.centers is not None:
+            a.centers, a.n_centers, a.tok_vocab = self.centers.data_ptr(), self.centers.numel(), int(self.tok_vocab)
+
+
+def _token_rows(what, tokens, steps, centers, tok_vocab):
+    """The input checks of the token forms -> their _Rows."""
     if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1):
         raise L.CoverError(f"{what}: tokens must be int64 [rows, >= 7 steps] with unit column stride")
     steps = int(steps)
@@ -1418,20 +1441,86 @@ def _token_rows(what, tokens, steps, centers):
         raise L.CoverError(f"{what}: steps >= 1 and 7 * steps <= columns are required (got steps={steps}, tokens {tuple(tokens.shape)})")
     if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 1 or centers.numel() < 1 or not centers.is_contiguous():
         raise L.CoverError(f"{what}: centers must be contiguous fp32 [n_centers >= 1]")
-    return steps, max(tokens.stride(0), 7 * steps)
+    return _Rows(what, tokens, torch.int64, max(tokens.stride(0), 7 * steps), 7, tokens.shape[0], steps, centers, tok_vocab)
 
 
 def _action_rows(what, actions):
-    """The input check of the float forms (augment_actions, proposal_prior_actions)."""
+    """The input check of the float forms -> their _Rows."""
     if not torch.is_tensor(actions) or actions.dtype != torch.float32 or actions.dim() != 3 or actions.shape[2] < 7 or actions.stride(2) != 1:
         raise L.CoverError(f"{what}: actions must be fp32 [rows, steps, >= 7] with unit last stride")
+    return _Rows(what, actions, torch.float32, actions.stride(0), actions.stride(1), actions.shape[0], actions.shape[1], None, 0)
+
+
+# The checks the families share, each stated once. A family's own conditions (n_fit <= group_rows, radius > 0, ...) stay in its helper.
+def _chk_ints(what, **named):
+    """Integers, bools rejected -> the ints, in the order given."""
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in named.values()):
+        raise L.CoverError(f"{what}: {', '.join(named)} must be integers (got {', '.join(repr(v) for v in named.values())})")
+    return tuple(int(v) for v in named.values())
+
+
+def _chk_groups(rows, group_rows):
+    """rows in prompt groups of group_rows -> (G, S)."""
+    what, N = rows.what, rows.N
+    S, = _chk_ints(what, group_rows=group_rows)
+    if not 1 <= S <= 4096 or N < 1 or N % S != 0:
+        raise L.CoverError(f"{what}: 1 <= group_rows <= 4096 and rows % group_rows == 0 are required (got rows={N}, group_rows={S})")
+    if not 1 <= rows.steps <= 64 or N > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={rows.steps}, rows={N})")
+    return N // S, S
+
+
+def _chk_f32(what, name, t, *shapes, hint=""):
+    """t: a contiguous fp32 tensor of one of the shapes."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous():
+        raise L.CoverError(f"{what}: {name} must be contiguous fp32 {' or '.join(str(list(s)) for s in shapes)}{hint} "
+                           f"(got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__})")
+
+
+def _f32_number(what, name, v, finite=True):
+    """A Python or numpy number, bools rejected, finite (finite=False: anything but a NaN) -> the fp32 value the launch receives, which
+    may be +-inf or 0 where v is not: the range conditions are the caller's."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or (not math.isfinite(v) if finite else math.isnan(v)):
+        raise L.CoverError(f"{what}: {name} must be a {'finite ' if finite else ''}number (got {v!r})")
+    return C.c_float(float(v)).value
+
+
+def _dim_scale_for(what, dim_scale, src):
+    """dim_scale as the fp32 [6] tensor the launch reads, on src's device: a device tensor (host.Smooth's, host.Coherence's,
+    host.Diversity's upload: validated there, once) as it is, anything else through smooth_dim_scale."""
+    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:
+        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
+            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
+    else:
+        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
+    return dim_scale.to(src.device)
+
+
+def _out_or_new(what, out, shape, dtype, src):
+    """out, checked, or a new tensor of that shape beside src."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=src.device)
+    if not torch.is_tensor(out) or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise L.CoverError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)}")
+    return out
+
+
+def _one_device(what, src, *others):
+    """Every tensor of the call (None = not given) is on src's device, which is a GPU -> that device."""
+    _chk_dev(src, *others)
+    if any(t is not None and t.device != src.device for t in others):
+        raise L.CoverError(f"{what}: every tensor must be on one device")
+    return src.device
+
+
+def _launch(rows, fn, a):
+    rows.fill(a)
+    L.check(getattr(L.lib(), fn)(C.byref(a), _stream()), rows.what)
 
 
 def _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip):
     """The checks of what a draw takes (augment_*, refine_*): the normals' layout and the values -> (sigma, sd_floor, clip lo, clip hi)."""
-    if not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != (G, K, steps, 6) or not normals.is_contiguous():
-        raise L.CoverError(f"{what}: normals must be contiguous fp32 [prompts, n_augmented, steps, 6] = [{G}, {K}, {steps}, 6] "
-                           f"(got {tuple(normals.shape) if torch.is_tensor(normals) else type(normals).__name__})")
+    _chk_f32(what, "normals", normals, (G, K, steps, 6), hint=" = [prompts, n_augmented, steps, 6]")
     sigma, sd_floor = float(sigma), float(sd_floor)
     for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
         if not (math.isfinite(v) and v >= 0.0 and math.isfinite(C.c_float(v).value)):
@@ -1445,9 +1534,9 @@ def _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip):
     return sigma, sd_floor, lo, hi
 
 
-def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, out_shape,
-             stats, centers=None, tok_vocab=0):
-    """The checks and the launch both augment wrappers share. src: the input tensor; elem: its dtype; out_shape(G, S) -> the output's shape."""
+def _augment(rows, fn, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, stats):
+    """The checks and the launch both augment wrappers share."""
+    what, N, steps = rows.what, rows.N, rows.steps
     n, K = int(n_samples), int(n_augmented)
     if not 1 <= n <= 4096 or not 0 <= K <= 4096 or N < 1 or N % n != 0:
         raise L.CoverError(f"{what}: 1 <= n_samples <= 4096, 0 <= n_augmented <= 4096 and rows % n_samples == 0 are required "
@@ -1457,26 +1546,17 @@ def _augment(what, fn, src, elem, n_stride, t_stride, N, steps, n_samples, n_aug
         raise L.CoverError(f"{what}: 1 <= steps <= 64 and prompts * (n_samples + n_augmented) <= 2^20 are required (got steps={steps}, "
                            f"prompts={G})")
     sigma, sd_floor, lo, hi = _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip)
-    shape = out_shape(G, S)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != elem or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise L.CoverError(f"{what}: out must be a contiguous {elem} tensor of shape {shape}")
-    _chk_dev(src, normals, centers, out)
-    dev = src.device
-    if any(t is not None and t.device != dev for t in (normals, centers, out)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
-    if out is None:
-        out = torch.empty(shape, dtype=elem, device=dev)
+    out = _out_or_new(what, out, rows.out_shape(G * S), rows.elem, rows.src)
+    dev = _one_device(what, rows.src, normals, rows.centers, out)
     st = _augment_stats(G, steps, dev) if stats else None
     a = L.AugmentArgs()
-    a.src, a.n_stride, a.t_stride, a.normals = src.data_ptr(), n_stride, t_stride, (normals.data_ptr() if K else None)
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.normals = normals.data_ptr() if K else None
     a.G, a.n, a.K, a.h = G, n, K, steps
     a.sigma, a.sd_floor, a.clip_lo, a.clip_hi = sigma, sd_floor, lo, hi
     a.out = out.data_ptr()
     if st is not None:
         a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     return (out, st) if stats else out
 
 
@@ -1492,10 +1572,8 @@ def augment_tokens(tokens, n_samples, n_augmented, normals, centers, tok_vocab, 
     [G, n_augmented, steps, 6] (host.augmentation_normals): the same normals give the same tokens. centers fp32 [n_centers].
     Downstream code takes the result as it takes sampled tokens, with group_size = S. stats=True -> (out, AugmentStats).
     One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("augment_tokens", tokens, steps, centers)
-    return _augment("augment_tokens", lambda h: h.cover_augment_tokens, tokens, torch.int64, n_stride, 7,
-                    tokens.shape[0], steps, n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, 7 * steps),
-                    stats, centers=centers, tok_vocab=tok_vocab)
+    rows = _token_rows("augment_tokens", tokens, steps, centers, tok_vocab)
+    return _augment(rows, "cover_augment_tokens", n_samples, n_augmented, normals, sigma, sd_floor, clip, out, stats)
 
 
 def augment_actions(actions, n_samples, n_augmented, normals, *, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0), out=None, stats=False):
@@ -1504,53 +1582,30 @@ def augment_actions(actions, n_samples, n_augmented, normals, *, sigma=1.0, sd_f
     The first n_samples rows per prompt are the input's first 7 dims bit for bit; augmented values are stored as they are (clipped to
     clip; +-inf = no clip), the gripper float is that of the lowest-index sample in the majority class (>= 0.5), a tie going to the class
     of sample 0. See augment_tokens for the arithmetic."""
-    _action_rows("augment_actions", actions)
-    N, steps = actions.shape[0], actions.shape[1]
-    return _augment("augment_actions", lambda h: h.cover_augment_actions, actions, torch.float32, actions.stride(0), actions.stride(1), N, steps,
-                    n_samples, n_augmented, normals, sigma, sd_floor, clip, out, lambda G, S: (G * S, steps, 7), stats)
+    rows = _action_rows("augment_actions", actions)
+    return _augment(rows, "cover_augment_actions", n_samples, n_augmented, normals, sigma, sd_floor, clip, out, stats)
 
 
 # ------------------------------------------------------------------------------------------------ proposal log-density prior
-def _proposal_prior(what, fn, src, n_stride, t_stride, N, steps, group_rows, n_fit, sigma, sd_floor, log_share, out, stats, centers=None,
-                    tok_vocab=0):
+def _proposal_prior(rows, fn, group_rows, n_fit, sigma, sd_floor, log_share, out, stats):
     """The checks and the launch both proposal-prior wrappers share."""
-    ints = (int, np.integer)
-    if isinstance(group_rows, bool) or isinstance(n_fit, bool) or not (isinstance(group_rows, ints) and isinstance(n_fit, ints)):
-        raise L.CoverError(f"{what}: group_rows and n_fit must be integers (got {group_rows!r}, {n_fit!r})")
-    S, n = int(group_rows), int(n_fit)
-    if not 1 <= n <= S <= 4096 or N < 1 or N % S != 0:
-        raise L.CoverError(f"{what}: 1 <= n_fit <= group_rows <= 4096 and rows % group_rows == 0 are required "
-                           f"(got rows={N}, group_rows={S}, n_fit={n})")
-    G = N // S
-    if not 1 <= steps <= 64 or N > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
-    vals = []
+    what, N, steps = rows.what, rows.N, rows.steps
+    n, = _chk_ints(what, n_fit=n_fit)
+    G, S = _chk_groups(rows, group_rows)
+    if not 1 <= n <= S:
+        raise L.CoverError(f"{what}: 1 <= n_fit <= group_rows is required (got group_rows={S}, n_fit={n})")
+    sigma, sd_floor = _f32_number(what, "sigma", sigma), _f32_number(what, "sd_floor", sd_floor)
     for name, v in (("sigma", sigma), ("sd_floor", sd_floor)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
-            raise L.CoverError(f"{what}: {name} must be a number (got {v!r})")
-        v = float(v)
-        if not (math.isfinite(v) and math.isfinite(C.c_float(v).value) and C.c_float(v).value > 0.0):
+        if not (math.isfinite(v) and v > 0.0):
             raise L.CoverError(f"{what}: {name} must be finite and > 0 in fp32 (got {v})")
-        vals.append(C.c_float(v).value)
-    sigma, sd_floor = vals
     if not C.c_float(sigma * sd_floor).value > 0.0:
         raise L.CoverError(f"{what}: the fp32 product sigma * sd_floor must be > 0 (got {sigma} * {sd_floor})")
-    if log_share is not None and (not torch.is_tensor(log_share) or log_share.dtype != torch.float32 or tuple(log_share.shape) != (n + 1,)
-                                  or not log_share.is_contiguous()):
-        raise L.CoverError(f"{what}: log_share must be contiguous fp32 [n_fit + 1] = [{n + 1}] (host.vote_log_shares)")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
-        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
-    _chk_dev(src, centers, log_share, out)
-    dev = src.device
-    if any(t is not None and t.device != dev for t in (centers, log_share, out)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
-    if out is None:
-        out = torch.empty(N, dtype=torch.float32, device=dev)
+    if log_share is not None:
+        _chk_f32(what, "log_share", log_share, (n + 1,), hint=" = [n_fit + 1] (host.vote_log_shares)")
+    out = _out_or_new(what, out, (N,), torch.float32, rows.src)
+    dev = _one_device(what, rows.src, rows.centers, log_share, out)
     st = _augment_stats(G, steps, dev) if stats else None
     a = L.ProposalPriorArgs()
-    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
     if log_share is not None:
         a.log_share = log_share.data_ptr()
     a.G, a.group_rows, a.n_fit, a.h = G, S, n, steps
@@ -1558,7 +1613,7 @@ def _proposal_prior(what, fn, src, n_stride, t_stride, N, steps, group_rows, n_f
     a.prior_out = out.data_ptr()
     if st is not None:
         a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     return (out, st) if stats else out
 
 
@@ -1575,18 +1630,16 @@ def proposal_prior_tokens(tokens, group_rows, n_fit, centers, tok_vocab, *, step
     augment_tokens group_rows = n_samples + n_augmented and n_fit = n_samples; group_rows == n_fit scores plain policy samples among
     their siblings. sigma and sd_floor must be > 0 (no default is chosen). A NaN appears only in the float form. stats=True ->
     (prior, AugmentStats) of the fit. One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("proposal_prior_tokens", tokens, steps, centers)
-    return _proposal_prior("proposal_prior_tokens", lambda h: h.cover_proposal_prior_tokens, tokens, n_stride, 7, tokens.shape[0], steps,
-                           group_rows, n_fit, sigma, sd_floor, log_share, out, stats, centers=centers, tok_vocab=tok_vocab)
+    rows = _token_rows("proposal_prior_tokens", tokens, steps, centers, tok_vocab)
+    return _proposal_prior(rows, "cover_proposal_prior_tokens", group_rows, n_fit, sigma, sd_floor, log_share, out, stats)
 
 
 def proposal_prior_actions(actions, group_rows, n_fit, *, sigma, sd_floor, log_share=None, out=None, stats=False):
     """The same for a flow-matching policy's chunks (cover_proposal_prior_actions): actions fp32 [G * group_rows, steps, >= 7] with unit
     last stride and any other strides -- a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place -> fp32 [G * group_rows]. A
     NaN element of a row that is not among the n_fit fitted ones gives a NaN prior for that row only. See proposal_prior_tokens."""
-    _action_rows("proposal_prior_actions", actions)
-    return _proposal_prior("proposal_prior_actions", lambda h: h.cover_proposal_prior_actions, actions, actions.stride(0), actions.stride(1),
-                           actions.shape[0], actions.shape[1], group_rows, n_fit, sigma, sd_floor, log_share, out, stats)
+    rows = _action_rows("proposal_prior_actions", actions)
+    return _proposal_prior(rows, "cover_proposal_prior_actions", group_rows, n_fit, sigma, sd_floor, log_share, out, stats)
 
 
 # ------------------------------------------------------------------------------------------------ verifier-guided refinement
@@ -1596,40 +1649,22 @@ class RefineElites(NamedTuple):
     scores: torch.Tensor   # fp32 [G, n_elite]: its score, bit for bit
 
 
-def _refine(what, fn, src, elem, n_stride, t_stride, N, steps, scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out,
-            out_shape, stats, elites, centers=None, tok_vocab=0):
-    """The checks and the launch both refine wrappers share. out_shape(G, rows per group) -> the output's shape."""
-    ints = (int, np.integer)
-    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, n_elite, n_new)):
-        raise L.CoverError(f"{what}: group_rows, n_elite and n_new must be integers (got {group_rows!r}, {n_elite!r}, {n_new!r})")
-    S, m, K = int(group_rows), int(n_elite), int(n_new)
-    if not 1 <= m <= S <= 4096 or not 0 <= K <= 4096 or N < 1 or N % S != 0:
-        raise L.CoverError(f"{what}: 1 <= n_elite <= group_rows <= 4096, 0 <= n_new <= 4096 and rows % group_rows == 0 are required "
-                           f"(got rows={N}, group_rows={S}, n_elite={m}, n_new={K})")
-    G = N // S
-    if not 1 <= steps <= 64 or N > 1 << 20 or G * (m + K) > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64, rows <= 2^20 and prompts * (n_elite + n_new) <= 2^20 are required (got steps={steps}, "
-                           f"rows={N}, prompts={G})")
-    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or not scores.is_contiguous():
-        raise L.CoverError(f"{what}: scores must be contiguous fp32 [rows] = [{N}] "
-                           f"(got {tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__})")
+def _refine(rows, fn, scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out, stats, elites):
+    """The checks and the launch both refine wrappers share."""
+    what, N, steps = rows.what, rows.N, rows.steps
+    m, K = _chk_ints(what, n_elite=n_elite, n_new=n_new)
+    G, S = _chk_groups(rows, group_rows)
+    if not 1 <= m <= S or not 0 <= K <= 4096 or G * (m + K) > 1 << 20:
+        raise L.CoverError(f"{what}: 1 <= n_elite <= group_rows, 0 <= n_new <= 4096 and prompts * (n_elite + n_new) <= 2^20 are required "
+                           f"(got group_rows={S}, n_elite={m}, n_new={K}, prompts={G})")
+    _chk_f32(what, "scores", scores, (N,), hint=" = [rows]")
     sigma, sd_floor, lo, hi = _draw_checks(what, normals, G, K, steps, sigma, sd_floor, clip)
-    shape = out_shape(G, m + K)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != elem or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise L.CoverError(f"{what}: out must be a contiguous {elem} tensor of shape {shape}")
-    _chk_dev(src, scores, normals, centers, out)
-    dev = src.device
-    if any(t is not None and t.device != dev for t in (scores, normals, centers, out)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
-    if out is None:
-        out = torch.empty(shape, dtype=elem, device=dev)
+    out = _out_or_new(what, out, rows.out_shape(G * (m + K)), rows.elem, rows.src)
+    dev = _one_device(what, rows.src, scores, normals, rows.centers, out)
     st = _augment_stats(G, steps, dev) if stats else None
     el = RefineElites(torch.empty(G, m, dtype=torch.int32, device=dev), torch.empty(G, m, dtype=torch.float32, device=dev)) if elites else None
     a = L.RefineArgs()
-    a.src, a.n_stride, a.t_stride, a.scores = src.data_ptr(), n_stride, t_stride, scores.data_ptr()
-    a.normals = normals.data_ptr() if K else None
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
+    a.scores, a.normals = scores.data_ptr(), (normals.data_ptr() if K else None)
     a.G, a.group_rows, a.n_elite, a.K, a.h = G, S, m, K, steps
     a.sigma, a.sd_floor, a.clip_lo, a.clip_hi = sigma, sd_floor, lo, hi
     a.out = out.data_ptr()
@@ -1637,7 +1672,7 @@ def _refine(what, fn, src, elem, n_stride, t_stride, N, steps, scores, group_row
         a.elite_rows_out, a.elite_scores_out = el.rows.data_ptr(), el.scores.data_ptr()
     if st is not None:
         a.mean_out, a.sd_out, a.votes_out = st.mean.data_ptr(), st.sd.data_ptr(), st.votes.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     res = (out,) + ((st,) if stats else ()) + ((el,) if elites else ())
     return res if len(res) > 1 else out
 
@@ -1655,10 +1690,8 @@ def refine_tokens(tokens, scores, group_rows, n_elite, n_new, normals, centers, 
     a pure top-n_elite gather. Downstream code takes the result as it takes augment_tokens' output, with group_size = n_elite + n_new and
     n_fit = n_elite. stats=True adds the AugmentStats of the fit, elites=True adds RefineElites (the gathered rows' input indices and
     scores): -> out, (out, stats), (out, elites) or (out, stats, elites). One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("refine_tokens", tokens, steps, centers)
-    return _refine("refine_tokens", lambda h: h.cover_refine_tokens, tokens, torch.int64, n_stride, 7, tokens.shape[0], steps, scores,
-                   group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out, lambda G, R: (G * R, 7 * steps), stats, elites,
-                   centers=centers, tok_vocab=tok_vocab)
+    rows = _token_rows("refine_tokens", tokens, steps, centers, tok_vocab)
+    return _refine(rows, "cover_refine_tokens", scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out, stats, elites)
 
 
 def refine_actions(actions, scores, group_rows, n_elite, n_new, normals, *, sigma=1.0, sd_floor=0.0, clip=(-1.0, 1.0), out=None,
@@ -1667,10 +1700,8 @@ def refine_actions(actions, scores, group_rows, n_elite, n_new, normals, *, sigm
     stride and any other strides -- a [B, steps, 7] view of a [B, chunk, 32] buffer is read in place -> contiguous fp32
     [G * (n_elite + n_new), steps, 7]. The elites are the input's first 7 dims bit for bit; the new rows are augment_actions' on them
     (a gripper tie goes to the class of the best elite). See refine_tokens for the ranking and the returns."""
-    _action_rows("refine_actions", actions)
-    return _refine("refine_actions", lambda h: h.cover_refine_actions, actions, torch.float32, actions.stride(0), actions.stride(1),
-                   actions.shape[0], actions.shape[1], scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out,
-                   lambda G, R: (G * R, actions.shape[1], 7), stats, elites)
+    rows = _action_rows("refine_actions", actions)
+    return _refine(rows, "cover_refine_actions", scores, group_rows, n_elite, n_new, normals, sigma, sd_floor, clip, out, stats, elites)
 
 
 # ------------------------------------------------------------------------------------------------ neighbourhood-smoothed scores
@@ -1696,56 +1727,30 @@ def smooth_dim_scale(dim_scale, what="smooth_dim_scale") -> np.ndarray:
     return f
 
 
-def _smooth(what, fn, src, n_stride, t_stride, N, steps, scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats,
-            centers=None, tok_vocab=0):
+def _smooth(rows, fn, scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats):
     """The checks and the launch both smoothing wrappers share."""
-    if isinstance(group_rows, bool) or not isinstance(group_rows, (int, np.integer)):
-        raise L.CoverError(f"{what}: group_rows must be an integer (got {group_rows!r})")
-    S = int(group_rows)
-    if not 1 <= S <= 4096 or N < 1 or N % S != 0:
-        raise L.CoverError(f"{what}: 1 <= group_rows <= 4096 and rows % group_rows == 0 are required (got rows={N}, group_rows={S})")
-    G = N // S
-    if not 1 <= steps <= 64 or N > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
-    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or not scores.is_contiguous():
-        raise L.CoverError(f"{what}: scores must be contiguous fp32 [rows] = [{N}] "
-                           f"(got {tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__})")
-    for name, v in (("radius", radius), ("shrink", shrink)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not math.isfinite(v):
-            raise L.CoverError(f"{what}: {name} must be a finite number (got {v!r})")
-    r = C.c_float(float(radius)).value
+    what, N = rows.what, rows.N
+    G, S = _chk_groups(rows, group_rows)
+    _chk_f32(what, "scores", scores, (N,), hint=" = [rows]")
+    r, shrink = _f32_number(what, "radius", radius), _f32_number(what, "shrink", shrink)
     radius2 = C.c_float(r * r).value            # squared once, in fp32 (the product of two fp32 values is exact in float64)
-    shrink = C.c_float(float(shrink)).value
     if not (r > 0.0 and math.isfinite(radius2) and radius2 > 0.0):
         raise L.CoverError(f"{what}: radius must be > 0 with a finite fp32 square > 0 (got {radius!r})")
     if not (math.isfinite(shrink) and shrink >= 0.0):
         raise L.CoverError(f"{what}: shrink must be finite and >= 0 (got {shrink!r})")
-    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Smooth's upload: validated there, once
-        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
-            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
-    else:
-        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
-    _chk_dev(src, scores, centers, out)
-    dev = src.device
-    dim_scale = dim_scale.to(dev)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
-        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
-    if any(t is not None and t.device != dev for t in (scores, dim_scale, centers, out)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
-    if out is None:
-        out = torch.empty(N, dtype=torch.float32, device=dev)
+    dim_scale = _dim_scale_for(what, dim_scale, rows.src)
+    out = _out_or_new(what, out, (N,), torch.float32, rows.src)
+    dev = _one_device(what, rows.src, scores, dim_scale, rows.centers, out)
     st = SmoothStats(torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
                      torch.empty(G, dtype=torch.float32, device=dev)) if stats else None
     a = L.SmoothArgs()
-    a.src, a.n_stride, a.t_stride, a.scores, a.dim_scale = src.data_ptr(), n_stride, t_stride, scores.data_ptr(), dim_scale.data_ptr()
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
-    a.G, a.group_rows, a.h, a.split_gripper = G, S, steps, 1 if split_gripper else 0
+    a.scores, a.dim_scale = scores.data_ptr(), dim_scale.data_ptr()
+    a.G, a.group_rows, a.h, a.split_gripper = G, S, rows.steps, 1 if split_gripper else 0
     a.radius2, a.shrink = radius2, shrink
     a.smoothed_out = out.data_ptr()
     if st is not None:
         a.density_out, a.neighbours_out, a.group_mean_out = st.density.data_ptr(), st.neighbours.data_ptr(), st.group_mean.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     return (out, st) if stats else out
 
 
@@ -1763,9 +1768,8 @@ def smooth_scores_tokens(tokens, scores, group_rows, centers, tok_vocab, *, step
     (host.Smooth's, validated there; on the device a negative or non-finite entry makes every pair weight 0). No radius, scale or shrink
     is chosen or recommended: there is no task-success data to choose them on. stats=True -> (smoothed, SmoothStats). Every rounding is
     specified in include/cover_hip.h. One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("smooth_scores_tokens", tokens, steps, centers)
-    return _smooth("smooth_scores_tokens", lambda h: h.cover_smooth_scores_tokens, tokens, n_stride, 7, tokens.shape[0], steps, scores,
-                   group_rows, radius, dim_scale, shrink, split_gripper, out, stats, centers=centers, tok_vocab=tok_vocab)
+    rows = _token_rows("smooth_scores_tokens", tokens, steps, centers, tok_vocab)
+    return _smooth(rows, "cover_smooth_scores_tokens", scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats)
 
 
 def smooth_scores_actions(actions, scores, group_rows, *, radius, dim_scale, shrink=0.0, split_gripper=True, out=None, stats=False):
@@ -1773,9 +1777,8 @@ def smooth_scores_actions(actions, scores, group_rows, *, radius, dim_scale, shr
     other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer, or the padded history tensor [N, 10, 7]
     score_histories holds (rows and pads that are equal within a group contribute exact zeros to the distance). A NaN element in a dim
     of non-zero scale isolates its row: every pair weight with it is 0. See smooth_scores_tokens."""
-    _action_rows("smooth_scores_actions", actions)
-    return _smooth("smooth_scores_actions", lambda h: h.cover_smooth_scores_actions, actions, actions.stride(0), actions.stride(1),
-                   actions.shape[0], actions.shape[1], scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats)
+    rows = _action_rows("smooth_scores_actions", actions)
+    return _smooth(rows, "cover_smooth_scores_actions", scores, group_rows, radius, dim_scale, shrink, split_gripper, out, stats)
 
 
 # ------------------------------------------------------------------------------------------------ chunk-coherence prior
@@ -1785,18 +1788,11 @@ class CoherenceStats(NamedTuple):
     nearest: torch.Tensor      # int32 [rows]: that reference's index, the lowest on a tie (-1 when there is none)
 
 
-def _coherence(what, fn, src, n_stride, t_stride, N, steps, group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty,
-               out, stats, centers=None, tok_vocab=0):
+def _coherence(rows, fn, group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out, stats):
     """The checks and the launch both coherence wrappers share."""
-    ints = (int, np.integer)
-    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, shift)):
-        raise L.CoverError(f"{what}: group_rows and shift must be integers (got {group_rows!r}, {shift!r})")
-    S, shift = int(group_rows), int(shift)
-    if not 1 <= S <= 4096 or N < 1 or N % S != 0:
-        raise L.CoverError(f"{what}: 1 <= group_rows <= 4096 and rows % group_rows == 0 are required (got rows={N}, group_rows={S})")
-    G = N // S
-    if not 1 <= steps <= 64 or N > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
+    what, N, steps = rows.what, rows.N, rows.steps
+    shift, = _chk_ints(what, shift=shift)
+    G, S = _chk_groups(rows, group_rows)
     if not torch.is_tensor(ref) or ref.dtype != torch.float32 or ref.dim() not in (3, 4) or ref.shape[-1] != 7 or not ref.is_contiguous():
         raise L.CoverError(f"{what}: ref must be contiguous fp32 [R, hr, 7] (shared) or [prompts, R, hr, 7] "
                            f"(got {tuple(ref.shape) if torch.is_tensor(ref) else type(ref).__name__})")
@@ -1805,38 +1801,16 @@ def _coherence(what, fn, src, n_stride, t_stride, N, steps, group_rows, ref, ref
         raise L.CoverError(f"{what}: a per-prompt ref must have one set per prompt: [{G}, R, hr, 7] (got {tuple(ref.shape)})")
     if not 1 <= R <= 4096 or not 1 <= hr <= 64 or not 0 <= shift < hr:
         raise L.CoverError(f"{what}: 1 <= R <= 4096, 1 <= hr <= 64 and 0 <= shift < hr are required (got R={R}, hr={hr}, shift={shift})")
-    if (not torch.is_tensor(ref_weight) or ref_weight.dtype != torch.float32 or tuple(ref_weight.shape) not in ((R,), (G, R))
-            or not ref_weight.is_contiguous()):
-        raise L.CoverError(f"{what}: ref_weight must be contiguous fp32 [R] = [{R}] (shared) or [prompts, R] = [{G}, {R}] "
-                           f"(got {tuple(ref_weight.shape) if torch.is_tensor(ref_weight) else type(ref_weight).__name__})")
-    if not torch.is_tensor(step_weight) or step_weight.dtype != torch.float32 or tuple(step_weight.shape) != (steps,) or not step_weight.is_contiguous():
-        raise L.CoverError(f"{what}: step_weight must be contiguous fp32 [steps] = [{steps}] (host.coherence_step_weights makes it) "
-                           f"(got {tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__})")
-    if (isinstance(gripper_penalty, bool) or not isinstance(gripper_penalty, (int, float, np.floating, np.integer))
-            or not math.isfinite(gripper_penalty)):
-        raise L.CoverError(f"{what}: gripper_penalty must be a finite number (got {gripper_penalty!r})")
-    penalty = C.c_float(float(gripper_penalty)).value
+    _chk_f32(what, "ref_weight", ref_weight, (R,), (G, R), hint=" = [R] (shared) or [prompts, R]")
+    _chk_f32(what, "step_weight", step_weight, (steps,), hint=" = [steps] (host.coherence_step_weights makes it)")
+    penalty = _f32_number(what, "gripper_penalty", gripper_penalty)
     if not (math.isfinite(penalty) and penalty >= 0.0):
         raise L.CoverError(f"{what}: gripper_penalty must be finite and >= 0 (got {gripper_penalty!r})")
-    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Coherence's upload: validated there, once
-        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
-            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
-    else:
-        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
-    _chk_dev(src, ref, ref_weight, step_weight, centers, out)
-    dev = src.device
-    dim_scale = dim_scale.to(dev)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N,) or not out.is_contiguous()):
-        raise L.CoverError(f"{what}: out must be a contiguous fp32 tensor of shape ({N},)")
-    if any(t is not None and t.device != dev for t in (ref, ref_weight, step_weight, dim_scale, centers, out)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
-    if out is None:
-        out = torch.empty(N, dtype=torch.float32, device=dev)
+    dim_scale = _dim_scale_for(what, dim_scale, rows.src)
+    out = _out_or_new(what, out, (N,), torch.float32, rows.src)
+    dev = _one_device(what, rows.src, ref, ref_weight, step_weight, dim_scale, rows.centers, out)
     st = CoherenceStats(torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)) if stats else None
     a = L.CoherenceArgs()
-    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
     a.ref, a.ref_g_stride, a.ref_r_stride = ref.data_ptr(), (R * hr * 7 if ref.dim() == 4 else 0), hr * 7
     a.ref_weight, a.w_g_stride = ref_weight.data_ptr(), (R if ref_weight.dim() == 2 else 0)
     a.step_weight, a.dim_scale = step_weight.data_ptr(), dim_scale.data_ptr()
@@ -1844,7 +1818,7 @@ def _coherence(what, fn, src, n_stride, t_stride, N, steps, group_rows, ref, ref
     a.prior_out = out.data_ptr()
     if st is not None:
         a.min_dist_out, a.nearest_out = st.min_dist.data_ptr(), st.nearest.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     return (out, st) if stats else out
 
 
@@ -1865,20 +1839,16 @@ def coherence_prior_tokens(tokens, group_rows, ref, ref_weight, centers, tok_voc
     validated there; on the device a negative or non-finite entry makes every prior NaN). A NaN candidate element gives its own row a NaN
     prior. No decay, scale, penalty or mixing weight is chosen or recommended: there is no task-success data to choose them on.
     stats=True -> (prior, CoherenceStats). Every rounding is specified in include/cover_hip.h. One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("coherence_prior_tokens", tokens, steps, centers)
-    return _coherence("coherence_prior_tokens", lambda h: h.cover_coherence_prior_tokens, tokens, n_stride, 7, tokens.shape[0], steps,
-                      group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out, stats, centers=centers,
-                      tok_vocab=tok_vocab)
+    rows = _token_rows("coherence_prior_tokens", tokens, steps, centers, tok_vocab)
+    return _coherence(rows, "cover_coherence_prior_tokens", group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out, stats)
 
 
 def coherence_prior_actions(actions, group_rows, ref, ref_weight, *, shift=0, step_weight, dim_scale, gripper_penalty=0.0, out=None,
                             stats=False):
     """The same for float rows (cover_coherence_prior_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last stride and any
     other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer. See coherence_prior_tokens."""
-    _action_rows("coherence_prior_actions", actions)
-    return _coherence("coherence_prior_actions", lambda h: h.cover_coherence_prior_actions, actions, actions.stride(0), actions.stride(1),
-                      actions.shape[0], actions.shape[1], group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out,
-                      stats)
+    rows = _action_rows("coherence_prior_actions", actions)
+    return _coherence(rows, "cover_coherence_prior_actions", group_rows, ref, ref_weight, shift, step_weight, dim_scale, gripper_penalty, out, stats)
 
 
 # ------------------------------------------------------------------------------------------------ diverse candidate subsets
@@ -1899,53 +1869,30 @@ class DiverseSubset(NamedTuple):
         return self.picked >= 0
 
 
-def _diverse(what, fn, src, elem, n_stride, t_stride, N, steps, group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale,
-             gripper_penalty, out_shape, centers=None, tok_vocab=0):
-    """The checks and the launch both diverse-subset wrappers share. out_shape(rows) -> the gathered output's shape."""
-    ints = (int, np.integer)
-    if any(isinstance(v, bool) or not isinstance(v, ints) for v in (group_rows, keep)):
-        raise L.CoverError(f"{what}: group_rows and keep must be integers (got {group_rows!r}, {keep!r})")
-    S, m = int(group_rows), int(keep)
-    if not 1 <= m <= S <= 4096 or N < 1 or N % S != 0:
-        raise L.CoverError(f"{what}: 1 <= keep <= group_rows <= 4096 and rows % group_rows == 0 are required "
-                           f"(got rows={N}, group_rows={S}, keep={m})")
-    G = N // S
-    if not 1 <= steps <= 64 or N > 1 << 20:
-        raise L.CoverError(f"{what}: 1 <= steps <= 64 and rows <= 2^20 are required (got steps={steps}, rows={N})")
-    if quality is not None and (not torch.is_tensor(quality) or quality.dtype != torch.float32 or tuple(quality.shape) != (N,)
-                                or not quality.is_contiguous()):
-        raise L.CoverError(f"{what}: quality must be None or contiguous fp32 [rows] = [{N}] "
-                           f"(got {tuple(quality.shape) if torch.is_tensor(quality) else type(quality).__name__})")
-    if not torch.is_tensor(step_weight) or step_weight.dtype != torch.float32 or tuple(step_weight.shape) != (steps,) or not step_weight.is_contiguous():
-        raise L.CoverError(f"{what}: step_weight must be contiguous fp32 [steps] = [{steps}] (host.coherence_step_weights makes it) "
-                           f"(got {tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__})")
-    for name, v in (("weight", weight), ("cover_dist", cover_dist), ("gripper_penalty", gripper_penalty)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or math.isnan(v):
-            raise L.CoverError(f"{what}: {name} must be a number (got {v!r})")
-    weight, cover, penalty = (C.c_float(float(v)).value for v in (weight, cover_dist, gripper_penalty))
+def _diverse(rows, fn, group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty):
+    """The checks and the launch both diverse-subset wrappers share."""
+    what, N, steps = rows.what, rows.N, rows.steps
+    m, = _chk_ints(what, keep=keep)
+    G, S = _chk_groups(rows, group_rows)
+    if not 1 <= m <= S:
+        raise L.CoverError(f"{what}: 1 <= keep <= group_rows is required (got group_rows={S}, keep={m})")
+    if quality is not None:
+        _chk_f32(what, "quality", quality, (N,), hint=" = [rows], or None")
+    _chk_f32(what, "step_weight", step_weight, (steps,), hint=" = [steps] (host.coherence_step_weights makes it)")
+    weight, penalty = _f32_number(what, "weight", weight), _f32_number(what, "gripper_penalty", gripper_penalty)
+    cover = _f32_number(what, "cover_dist", cover_dist, finite=False)
     if not (math.isfinite(weight) and weight >= 0.0):
         raise L.CoverError(f"{what}: weight must be finite and >= 0 (got {weight!r})")
     if not cover < math.inf:
         raise L.CoverError(f"{what}: cover_dist must be < +inf in fp32; a negative value switches the covering rule off (got {cover_dist!r})")
     if not (math.isfinite(penalty) and penalty >= 0.0):
         raise L.CoverError(f"{what}: gripper_penalty must be finite and >= 0 (got {gripper_penalty!r})")
-    if torch.is_tensor(dim_scale) and dim_scale.is_cuda:      # host.Diversity's upload: validated there, once
-        if dim_scale.dtype != torch.float32 or tuple(dim_scale.shape) != (6,) or not dim_scale.is_contiguous():
-            raise L.CoverError(f"{what}: a device dim_scale must be contiguous fp32 [6]")
-    else:
-        dim_scale = torch.from_numpy(smooth_dim_scale(dim_scale.detach().numpy() if torch.is_tensor(dim_scale) else dim_scale, what))
-    _chk_dev(src, quality, step_weight, centers)
-    dev = src.device
-    dim_scale = dim_scale.to(dev)
-    if any(t is not None and t.device != dev for t in (quality, step_weight, dim_scale, centers)):
-        raise L.CoverError(f"{what}: every tensor must be on one device")
+    dim_scale = _dim_scale_for(what, dim_scale, rows.src)
+    dev = _one_device(what, rows.src, quality, step_weight, dim_scale, rows.centers)
     i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
-    res = DiverseSubset(torch.empty(out_shape(G * m), dtype=elem, device=dev), torch.empty(G, m, **i32), torch.empty(G, **i32),
+    res = DiverseSubset(torch.empty(rows.out_shape(G * m), dtype=rows.elem, device=dev), torch.empty(G, m, **i32), torch.empty(G, **i32),
                         torch.empty(G, m, **f32), torch.empty(G, m, **f32), torch.empty(N, **i32), torch.empty(N, **f32))
     a = L.DiverseArgs()
-    a.src, a.n_stride, a.t_stride = src.data_ptr(), n_stride, t_stride
-    if centers is not None:
-        a.centers, a.n_centers, a.tok_vocab = centers.data_ptr(), centers.numel(), int(tok_vocab)
     a.quality = quality.data_ptr() if quality is not None else None
     a.step_weight, a.dim_scale = step_weight.data_ptr(), dim_scale.data_ptr()
     a.G, a.group_rows, a.m, a.h = G, S, m, steps
@@ -1953,7 +1900,7 @@ def _diverse(what, fn, src, elem, n_stride, t_stride, N, steps, group_rows, keep
     a.out, a.picked_rows_out, a.count_out = res.rows.data_ptr(), res.picked.data_ptr(), res.count.data_ptr()
     a.pick_value_out, a.pick_dist_out = res.value.data_ptr(), res.dist.data_ptr()
     a.assign_out, a.row_dist_out = res.assign.data_ptr(), res.row_dist.data_ptr()
-    L.check(fn(L.lib())(C.byref(a), _stream()), what)
+    _launch(rows, fn, a)
     return res
 
 
@@ -1977,20 +1924,16 @@ def diverse_subset_tokens(tokens, group_rows, keep, centers, tok_vocab, *, steps
     (host.Diversity's, validated there; on the device a negative or non-finite entry makes count 0). No keep, weight, scale or covering
     distance is chosen or recommended: there is no task-success data to choose them on. Every rounding is specified in
     include/cover_hip.h. One launch, no workspace, recordable."""
-    steps, n_stride = _token_rows("diverse_subset_tokens", tokens, steps, centers)
-    return _diverse("diverse_subset_tokens", lambda h: h.cover_diverse_subset_tokens, tokens, torch.int64, n_stride, 7, tokens.shape[0],
-                    steps, group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty,
-                    lambda R: (R, 7 * steps), centers=centers, tok_vocab=tok_vocab)
+    rows = _token_rows("diverse_subset_tokens", tokens, steps, centers, tok_vocab)
+    return _diverse(rows, "cover_diverse_subset_tokens", group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty)
 
 
 def diverse_subset_actions(actions, group_rows, keep, *, quality=None, weight, cover_dist=-1.0, step_weight, dim_scale, gripper_penalty=0.0):
     """The same for float rows (cover_diverse_subset_actions): actions fp32 [G * group_rows, steps, >= 7] with unit last stride and any
     other strides, read in place -- a [B, steps, 7] view of a [B, chunk, 32] buffer -> DiverseSubset whose .rows is contiguous fp32
     [G * keep, steps, 7], the picked rows' first 7 dims bit for bit. See diverse_subset_tokens."""
-    _action_rows("diverse_subset_actions", actions)
-    return _diverse("diverse_subset_actions", lambda h: h.cover_diverse_subset_actions, actions, torch.float32, actions.stride(0),
-                    actions.stride(1), actions.shape[0], actions.shape[1], group_rows, keep, quality, weight, cover_dist, step_weight,
-                    dim_scale, gripper_penalty, lambda R: (R, actions.shape[1], 7))
+    rows = _action_rows("diverse_subset_actions", actions)
+    return _diverse(rows, "cover_diverse_subset_actions", group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty)
 
 
 # ------------------------------------------------------------------------------------------------ beam search

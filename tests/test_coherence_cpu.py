@@ -229,7 +229,9 @@ def test_binding_mirrors_the_header():
 def test_kernel_file_shares_the_token_rule():
     csrc = os.path.join(ROOT, "cover_vla_amd", "csrc")
     text = open(os.path.join(csrc, "coherence.hip")).read()
-    assert '#include "augment_fit.h"' in text and "aug_value(" in text and "tok_vocab -" not in text
+    rows = open(os.path.join(csrc, "chunk_rows.h")).read()                 # the row source holds the token rule, once
+    assert '#include "chunk_rows.h"' in text and "chunk_stage_rows(" in text and "tok_vocab -" not in text and "centers[" not in text
+    assert rows.count("tok_vocab -") == 1 and "s.value(" in rows[rows.index("void chunk_stage_rows("):]
     assert "#pragma clang fp contract(off)" in text and "atomic" not in text.lower().replace("no atomics", "")
     assert "powf" not in text and "fmaf" not in text
     assert " coherence.hip " in open(os.path.join(csrc, "Makefile")).read()

@@ -356,9 +356,12 @@ def test_kernel_files_share_one_distance():
         assert '#include "chunk_dist.h"' in text and "chunk_pair_dist" in text and "diff * sc" not in text, name
         assert "#pragma clang fp contract(off)" in text and "powf" not in text and "fmaf" not in text
     text = open(os.path.join(csrc, "diverse.hip")).read()
-    assert "aug_value(" in text and "desc_key(" in text and "tok_vocab -" not in text and "atomic" not in text.lower()
+    rows = open(os.path.join(csrc, "chunk_rows.h")).read()                 # the row source holds the token rule, once
+    assert '#include "chunk_rows.h"' in text and "aug_value(f, " in text and "chunk_src<T> f = {" in text and "centers[" not in text
+    assert rows.count("tok_vocab -") == 1 and "aug_value(*this" in rows and shared.count("diff * sc") == 1
+    assert "desc_key(" in text and "tok_vocab -" not in text and "atomic" not in text.lower()
     make = open(os.path.join(csrc, "Makefile")).read()
-    assert " diverse.hip " in make and " chunk_dist.h " in make
+    assert " diverse.hip " in make and " chunk_dist.h " in make and " chunk_rows.h " in make
     capi = open(os.path.join(csrc, "capi.hip")).read()
     assert "DIVERSE_LIMITS" in capi and "SZ(cover_diverse_args)" in capi
 

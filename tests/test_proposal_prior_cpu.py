@@ -325,5 +325,9 @@ def test_the_fit_is_stated_once():
     assert "sqrtf(var)" in text["augment_fit.h"] and "#pragma clang fp contract(off)" in text["augment_fit.h"]
     for f in ("augment.hip", "proposal_prior.hip"):
         assert '#include "augment_fit.h"' in text[f] and "augment_group_stats<T>(" in text[f] and "sqrtf" not in text[f]
-        assert "#pragma clang fp contract(off)" in text[f]
-    assert "proposal_prior.hip" in open(os.path.join(csrc, "Makefile")).read()
+        assert "#pragma clang fp contract(off)" in text[f] and "tok_vocab -" not in text[f]
+    rows = open(os.path.join(csrc, "chunk_rows.h")).read()                 # the rows the fit reads: one token rule, in the row source
+    assert '#include "chunk_rows.h"' in text["augment_fit.h"] and "tok_vocab -" not in text["augment_fit.h"]
+    assert rows.count("tok_vocab -") == 1 and rows.count("float aug_value(") == 2 and "#pragma clang fp contract(off)" in rows
+    make = open(os.path.join(csrc, "Makefile")).read()
+    assert "proposal_prior.hip" in make and " chunk_rows.h " in make

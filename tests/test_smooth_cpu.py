@@ -179,9 +179,12 @@ def test_binding_mirrors_the_header():
 def test_kernel_file_shares_the_token_rule():
     csrc = os.path.join(ROOT, "cover_vla_amd", "csrc")
     text = open(os.path.join(csrc, "smooth.hip")).read()
-    assert '#include "augment_fit.h"' in text and "aug_value(" in text and "tok_vocab -" not in text
+    rows = open(os.path.join(csrc, "chunk_rows.h")).read()                 # the row source holds the token rule, once
+    assert '#include "chunk_rows.h"' in text and "chunk_stage_rows(" in text and "tok_vocab -" not in text and "centers[" not in text
+    assert rows.count("tok_vocab -") == 1 and "s.value(" in rows[rows.index("void chunk_stage_rows("):]
     assert "#pragma clang fp contract(off)" in text and "atomic" not in text.lower().replace("no atomics", "")
-    assert "smooth.hip" in open(os.path.join(csrc, "Makefile")).read()
+    make = open(os.path.join(csrc, "Makefile")).read()
+    assert "smooth.hip" in make and " chunk_rows.h " in make
 
 
 # ------------------------------------------------------------------------------------------------ host validation
