@@ -235,6 +235,14 @@ class DiverseArgs(C.Structure):
                 ("row_dist_out", c_p), ("out", c_p)]
 
 
+class FastDecodeArgs(C.Structure):
+    _fields_ = [("tokens", c_p), ("tok_row_stride", c_ll), ("tok_step_stride", c_ll), ("band_lo", c_ll), ("band_hi", c_ll),
+                ("stop_ids", c_ll * 4), ("skip_ids", c_ll * 8), ("n_stop", c_i), ("n_skip", c_i),
+                ("piece_off", c_p), ("piece_sym", c_p), ("basis", c_p),
+                ("B", c_i), ("L", c_i), ("n_pieces", c_i), ("min_token", c_i), ("H", c_i), ("D", c_i), ("relaxed", c_i), ("scale", c_f),
+                ("out", c_p), ("out_n_stride", c_ll), ("out_t_stride", c_ll), ("coeff_out", c_p), ("n_symbols", c_p), ("status", c_p)]
+
+
 class BeamMergeArgs(C.Structure):
     _fields_ = [("cum", c_p), ("cand_tok", c_p), ("ld_tok", c_ll), ("cand_lp", c_p), ("ld_lp", c_ll), ("feed_pad", c_ll),
                 ("groups", c_i), ("B", c_i), ("parent_out", c_p), ("token_out", c_p), ("feed_out", c_p), ("cum_out", c_p),
@@ -320,7 +328,7 @@ _STRUCTS = {
     "cover_score_select_args": ScoreSelectArgs, "cover_prior_select_args": PriorSelectArgs, "cover_augment_args": AugmentArgs,
     "cover_proposal_prior_args": ProposalPriorArgs, "cover_member_scores_args": MemberScoresArgs,
     "cover_refine_args": RefineArgs, "cover_smooth_args": SmoothArgs, "cover_coherence_args": CoherenceArgs,
-    "cover_diverse_args": DiverseArgs,
+    "cover_diverse_args": DiverseArgs, "cover_fast_decode_args": FastDecodeArgs,
     "cover_beam_merge_args": BeamMergeArgs,
     "cover_kv_gather_slots_args": KvGatherSlotsArgs, "cover_beam_backtrack_args": BeamBacktrackArgs,
     "cover_gumbel_topn_args": GumbelTopnArgs, "cover_beam_merge_gumbel_args": BeamMergeGumbelArgs, "cover_workspace": Workspace, "cover_vit_layer": VitLayer,
@@ -409,6 +417,7 @@ SYMBOLS = {
     "cover_coherence_prior_actions": (c_i, [_P(CoherenceArgs), c_p]),
     "cover_diverse_subset_tokens": (c_i, [_P(DiverseArgs), c_p]),
     "cover_diverse_subset_actions": (c_i, [_P(DiverseArgs), c_p]),
+    "cover_fast_decode": (c_i, [_P(FastDecodeArgs), c_p]),
     "cover_beam_merge": (c_i, [_P(BeamMergeArgs), c_p]),
     "cover_kv_gather_slots": (c_i, [_P(KvGatherSlotsArgs), c_p]),
     "cover_beam_backtrack": (c_i, [_P(BeamBacktrackArgs), c_p]),

@@ -477,6 +477,14 @@ int cover_diverse_subset_actions(const cover_diverse_args* a, void* stream) {
     HIPCHK(launch_diverse_subset_actions(a, ST(stream)), "diverse_subset_actions (" DIVERSE_LIMITS ")");
     return COVER_OK;
 }
+int cover_fast_decode(const cover_fast_decode_args* a, void* stream) {
+    if (!a) return fail(COVER_EINVAL, "cover_fast_decode: null args");
+    HIPCHK(launch_fast_decode(a, ST(stream)),
+           "fast_decode (1 <= B <= 2^20, 1 <= L <= 4096, 1 <= H <= 128, 1 <= D <= 32, n_pieces >= 1, 0 <= band_lo <= band_hi, 0 <= n_stop <= 4, "
+           "0 <= n_skip <= 8, |min_token| <= 2^30, scale finite and != 0, relaxed 0 or 1, token strides >= 0, out_t_stride >= D, "
+           "out_n_stride >= (H - 1) * out_t_stride + D, tokens / piece_off / piece_sym / basis / out required)");
+    return COVER_OK;
+}
 
 int cover_beam_merge(const cover_beam_merge_args* a, void* stream) {
     if (!a) return fail(COVER_EINVAL, "cover_beam_merge: null args");
@@ -603,7 +611,7 @@ size_t cover_sizeof(const char* n) {
     SZ(cover_beam_merge_args); SZ(cover_kv_gather_slots_args); SZ(cover_beam_backtrack_args);
     SZ(cover_gumbel_topn_args); SZ(cover_beam_merge_gumbel_args); SZ(cover_augment_args); SZ(cover_proposal_prior_args);
     SZ(cover_member_scores_args); SZ(cover_refine_args); SZ(cover_smooth_args); SZ(cover_coherence_args);
-    SZ(cover_diverse_args);
+    SZ(cover_diverse_args); SZ(cover_fast_decode_args);
 #undef SZ
     return 0;
 }

@@ -123,6 +123,8 @@ hipError_t launch_coherence_prior_actions(const cover_coherence_args* a, hipStre
 // ---- diverse.hip ---------------------------------------------------------------------------------
 hipError_t launch_diverse_subset_tokens(const cover_diverse_args* a, hipStream_t st);
 hipError_t launch_diverse_subset_actions(const cover_diverse_args* a, hipStream_t st);
+// ---- fast_decode.hip -----------------------------------------------------------------------------
+hipError_t launch_fast_decode(const cover_fast_decode_args* a, hipStream_t st);
 // ---- beam.hip ------------------------------------------------------------------------------------
 hipError_t launch_beam_merge(const cover_beam_merge_args* a, hipStream_t st);
 hipError_t launch_beam_merge_gumbel(const cover_beam_merge_gumbel_args* a, hipStream_t st);

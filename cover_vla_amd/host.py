@@ -269,6 +269,38 @@ def coherence_step_weights(h: int, decay: float) -> np.ndarray:
     return (np.float64(decay) ** np.arange(int(h), dtype=np.float64)).astype(np.float32)
 
 
+def fast_idct_basis(H: int) -> np.ndarray:
+    """The basis of the pi0-FAST de-tokeniser (ops.fast_decode, basis=): fp32 numpy [H, H], the orthonormal inverse DCT-II matrix
+    scipy.fft.idct(x, axis=0, norm="ortho") multiplies by -- B[t][0] = sqrt(1 / H), B[t][k] = sqrt(2 / H) * cos(pi * (2 t + 1) * k / (2 H))
+    -- computed in float64 and rounded to fp32 once. It is made on the host so that the device takes no cosine and the chunk stays a
+    fixed bit pattern; move it to the device once (torch.from_numpy(...).to(dev); PI0FASTPolicy does)."""
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= 128:
+        raise ValueError(f"fast_idct_basis: an integer 1 <= H <= 128 is required (got {H!r})")
+    H = int(H)
+    t, k = np.arange(H, dtype=np.float64)[:, None], np.arange(H, dtype=np.float64)[None, :]
+    basis = np.sqrt(2.0 / H) * np.cos(np.pi * (2.0 * t + 1.0) * k / (2.0 * H))
+    basis[:, 0] = np.sqrt(1.0 / H)
+    return basis.astype(np.float32)
+
+
+def fast_pieces_from_decoder(bpe_decode, n_pieces: int) -> list:
+    """The piece list ops.fast_piece_table takes, from a BPE decoder (the FAST processor's bpe_tokenizer.decode): entry f is the list of
+    code points of bpe_decode([f]), each FAST id decoded ON ITS OWN; an id whose decode raises becomes None (undecodable: a row that
+    holds it decodes to zeros, as the reference's decoder does when the sequence raises).
+    The assumption this rests on, which the caller owns: the BPE's decode of a sequence is the concatenation of its pieces' decodes.
+    That holds for the FAST processor's character-level BPE (a token is a string of symbols and decode joins them); it does not hold
+    for a decoder that cleans up spaces between tokens, merges byte fallbacks across tokens or strips at the sequence ends."""
+    if isinstance(n_pieces, bool) or not isinstance(n_pieces, (int, np.integer)) or n_pieces < 1:
+        raise ValueError(f"fast_pieces_from_decoder: an integer n_pieces >= 1 is required (got {n_pieces!r})")
+    pieces = []
+    for f in range(int(n_pieces)):
+        try:
+            pieces.append([ord(ch) for ch in bpe_decode([f])])
+        except Exception:
+            pieces.append(None)
+    return pieces
+
+
 class _CoherenceFields(NamedTuple):
     dim_scale: Any
     decay: float

@@ -1936,6 +1936,156 @@ def diverse_subset_actions(actions, group_rows, keep, *, quality=None, weight, c
     return _diverse(rows, "cover_diverse_subset_actions", group_rows, keep, quality, weight, cover_dist, step_weight, dim_scale, gripper_penalty)
 
 
+# ------------------------------------------------------------------------------------------------ pi0-FAST de-tokeniser
+FAST_TRUNCATED, FAST_PADDED, FAST_MISMATCH, FAST_STRAY, FAST_UNDECODABLE, FAST_NO_TERMINATOR = 1, 2, 4, 8, 16, 32
+FAST_MAX_SYMBOLS = 1 << 18          # of a whole piece table: 4096 positions of the longest piece stay below 2^31
+
+
+class FastPieces:
+    """The piece table of fast_decode (cover_fast_decode): piece_off int32 [n_pieces + 1], non-decreasing from 0, and piece_sym int32, the
+    code points FAST id f decodes to at piece_sym[piece_off[f] : piece_off[f + 1]]; a piece whose first symbol is negative marks an id
+    the BPE could not decode. Both contiguous and on one device (fast_piece_table builds them). The contents are validated here, once
+    (one read-back when the tensors are on the device): the kernel indexes piece_sym with them."""
+
+    def __init__(self, piece_off, piece_sym):
+        for name, t in (("piece_off", piece_off), ("piece_sym", piece_sym)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise L.CoverError(f"FastPieces: {name} must be a contiguous int32 tensor of one dim")
+        if piece_off.numel() < 2:
+            raise L.CoverError("FastPieces: an empty piece table (piece_off must have n_pieces + 1 >= 2 entries)")
+        if piece_off.device != piece_sym.device:
+            raise L.CoverError("FastPieces: piece_off and piece_sym must be on one device")
+        off, sym = piece_off.detach().cpu().numpy().astype(np.int64), piece_sym.detach().cpu().numpy()
+        if off[0] != 0 or np.any(np.diff(off) < 0):
+            raise L.CoverError("FastPieces: piece_off must start at 0 and never decrease")
+        if off[-1] > min(FAST_MAX_SYMBOLS, sym.shape[0]) or sym.shape[0] < 1:
+            raise L.CoverError(f"FastPieces: piece_off ends at {off[-1]}: beyond piece_sym's {sym.shape[0]} entries or the limit of "
+                               f"{FAST_MAX_SYMBOLS} symbols (piece_sym must hold at least one entry)")
+        used = sym[:off[-1]]
+        starts = off[:-1][np.diff(off) > 0]                        # where a non-empty piece begins: the one place a marker may stand
+        inner = np.ones(used.shape[0], dtype=bool)
+        inner[starts] = False
+        if np.any(used > 0x10FFFF) or np.any(used[inner] < 0):
+            raise L.CoverError("FastPieces: symbols are code points in [0, 0x10FFFF]; a negative one only as a piece's first (undecodable)")
+        self.piece_off, self.piece_sym = piece_off, piece_sym
+
+    @property
+    def n_pieces(self):
+        return self.piece_off.numel() - 1
+
+
+def fast_piece_table(pieces, device=None):
+    """Build a FastPieces on the host: pieces is a sequence over the FAST ids 0 .. n_pieces - 1, each entry the sequence of code points
+    the id decodes to (possibly empty) or None for an id that cannot be decoded (host.fast_pieces_from_decoder makes it from a BPE
+    decoder). Returns the FastPieces, on device if given. CoverError on an empty table, a code point outside [0, 0x10FFFF] or more than
+    2^18 symbols in all."""
+    if isinstance(pieces, (str, bytes)) or not hasattr(pieces, "__len__") or len(pieces) < 1:
+        raise L.CoverError("fast_piece_table: pieces must be a non-empty sequence of code-point sequences (None = undecodable)")
+    off, sym = [0], []
+    for f, p in enumerate(pieces):
+        if p is None:
+            sym.append(-1)
+        else:
+            vals = [ord(v) if isinstance(v, str) else v for v in p]
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0x10FFFF for v in vals):
+                raise L.CoverError(f"fast_piece_table: piece {f} must hold code points in [0, 0x10FFFF] (got {list(p)!r})")
+            sym.extend(int(v) for v in vals)
+        off.append(len(sym))
+        if len(sym) > FAST_MAX_SYMBOLS:
+            raise L.CoverError(f"fast_piece_table: more than {FAST_MAX_SYMBOLS} symbols in all")
+    sym = sym or [0]                                               # a table of empty pieces still hands the kernel a pointer
+    t_off, t_sym = torch.tensor(off, dtype=torch.int32), torch.tensor(sym, dtype=torch.int32)
+    return FastPieces(t_off, t_sym) if device is None else FastPieces(t_off.to(device), t_sym.to(device))
+
+
+class FastDecoded(NamedTuple):
+    """What fast_decode returns with stats=True."""
+    actions: torch.Tensor      # fp32 [B, horizon, action_dim] (or the caller's out)
+    coeff: torch.Tensor        # int32 [B, horizon * action_dim]: the quantised DCT coefficients, frequency-major; zeros on a fatal status
+    n_symbols: torch.Tensor    # int32 [B]: the symbols the row's tokens decode to, before truncation
+    status: torch.Tensor       # int32 [B]: FAST_* bits
+
+
+def _chk_id_list(what, name, ids, limit):
+    if isinstance(ids, (str, bytes)) or not hasattr(ids, "__len__") or len(ids) > limit:
+        raise L.CoverError(f"{what}: {name} must be a sequence of at most {limit} token ids (got {ids!r})")
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -(1 << 62) <= v < (1 << 62) for v in ids):
+        raise L.CoverError(f"{what}: {name} must hold integers (got {ids!r})")
+    return [int(v) for v in ids]
+
+
+def fast_decode(tokens, pieces, basis, *, band, stop_ids, skip_ids=(), min_token, scale, horizon, action_dim, relaxed=True, out=None,
+                stats=False):
+    """The pi0-FAST de-tokeniser on the device (cover_fast_decode): tokens int64 [B, L <= 4096] with ANY non-negative strides -- the
+    candidate-major tensor generate_tokens returns, or the transposed view of a step-major [L, B] buffer: strides are passed, nothing is
+    copied -> the fp32 action chunks [B, horizon, action_dim], the layout the *_actions calls read in place. Per row: the tokens before
+    the first of stop_ids (the terminator "|", EOS, pad; at most 4) are walked in order; a token t of the half-open band = (lo, hi)
+    (pi0fast.fast_action_token_range) is the FAST id hi - 1 - t and contributes the code points of its piece (pieces: a FastPieces); a
+    token of skip_ids (format tokens such as "Action", ":" and BOS; at most 8) contributes nothing; the symbols + min_token are the
+    quantised DCT coefficients, [horizon, action_dim] frequency-major; relaxed truncates or zero-pads to horizon * action_dim, otherwise
+    another count is an error; the chunk is the orthonormal inverse DCT of coefficients / scale along the horizon, with basis = fp32
+    [horizon, horizon] on the device (host.fast_idct_basis). A stray id, an undecodable piece or (not relaxed) a wrong count zeroes the
+    row, as the reference's decoder does on any exception. The semantics are defined on IDS: PI0FASTPolicy.extract_actions decodes to
+    text and encodes again, which prepends BOS and lets the tokenizer re-segment; those artefacts are deliberately not reproduced.
+    out: an fp32 [B, horizon, action_dim] tensor or VIEW with unit last stride whose rows do not overlap -- the first action_dim
+    columns of a [B, chunk, 32] buffer; only those cells are written. stats=True -> FastDecoded(actions, coeff, n_symbols, status), status
+    holding the FAST_* bits (1 truncated, 2 padded, 4 count mismatch, 8 stray id, 16 undecodable piece, 32 no terminator; 4 / 8 / 16 zero
+    the row). Every rounding is specified in include/cover_hip.h: the result is a fixed bit pattern. One launch, no workspace,
+    recordable."""
+    what = "fast_decode"
+    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2:
+        raise L.CoverError(f"{what}: tokens must be an int64 tensor [B, L]")
+    B, Lt = tokens.shape
+    if B < 1 or B > 1 << 20 or not 1 <= Lt <= 4096 or min(tokens.stride()) < 0:
+        raise L.CoverError(f"{what}: 1 <= B <= 2^20, 1 <= L <= 4096 and non-negative strides are required (got tokens {tuple(tokens.shape)})")
+    if not isinstance(pieces, FastPieces):
+        raise L.CoverError(f"{what}: pieces must be an ops.FastPieces (ops.fast_piece_table builds one)")
+    H, D, min_token = _chk_ints(what, horizon=horizon, action_dim=action_dim, min_token=min_token)
+    if not 1 <= H <= 128 or not 1 <= D <= 32:
+        raise L.CoverError(f"{what}: 1 <= horizon <= 128 and 1 <= action_dim <= 32 are required (got horizon={H}, action_dim={D})")
+    if abs(min_token) > 1 << 30:
+        raise L.CoverError(f"{what}: |min_token| <= 2^30 is required (got {min_token})")
+    _chk_f32(what, "basis", basis, (H, H), hint=" = [horizon, horizon] (host.fast_idct_basis makes it)")
+    if not isinstance(band, (tuple, list)) or len(band) != 2:
+        raise L.CoverError(f"{what}: band must be the half-open (lo, hi) of pi0fast.fast_action_token_range (got {band!r})")
+    lo, hi = _chk_ints(what, band_lo=band[0], band_hi=band[1])
+    if not 0 <= lo <= hi < 1 << 62:
+        raise L.CoverError(f"{what}: 0 <= band_lo <= band_hi is required (got {lo}, {hi})")
+    stop_ids, skip_ids = _chk_id_list(what, "stop_ids", stop_ids, 4), _chk_id_list(what, "skip_ids", skip_ids, 8)
+    s = _f32_number(what, "scale", scale)
+    if not math.isfinite(s) or s == 0.0:
+        raise L.CoverError(f"{what}: scale must be finite and non-zero as fp32 (got {scale!r})")
+    if not isinstance(relaxed, (bool, np.bool_)):
+        raise L.CoverError(f"{what}: relaxed must be a bool (got {relaxed!r})")
+    if out is None:
+        out = torch.empty(B, H, D, dtype=torch.float32, device=tokens.device)
+    elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, H, D) or (D > 1 and out.stride(2) != 1):
+        raise L.CoverError(f"{what}: out must be an fp32 tensor or view of shape {(B, H, D)} with unit last stride")
+    t_stride = out.stride(1) if H > 1 else D
+    n_stride = out.stride(0) if B > 1 else (H - 1) * t_stride + D
+    if t_stride < D or n_stride < (H - 1) * t_stride + D:
+        raise L.CoverError(f"{what}: out's steps and rows must not overlap (strides {tuple(out.stride())} for shape {(B, H, D)})")
+    dev = _one_device(what, tokens, pieces.piece_off, pieces.piece_sym, basis, out)
+    st = None
+    if stats:
+        st = (torch.empty(B, H * D, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+              torch.empty(B, dtype=torch.int32, device=dev))
+    a = L.FastDecodeArgs()
+    a.tokens, a.tok_row_stride, a.tok_step_stride = tokens.data_ptr(), tokens.stride(0), tokens.stride(1)
+    a.band_lo, a.band_hi, a.n_stop, a.n_skip = lo, hi, len(stop_ids), len(skip_ids)
+    for i, v in enumerate(stop_ids):
+        a.stop_ids[i] = v
+    for i, v in enumerate(skip_ids):
+        a.skip_ids[i] = v
+    a.piece_off, a.piece_sym, a.basis = pieces.piece_off.data_ptr(), pieces.piece_sym.data_ptr(), basis.data_ptr()
+    a.B, a.L, a.n_pieces, a.min_token, a.H, a.D, a.relaxed, a.scale = B, Lt, pieces.n_pieces, min_token, H, D, int(bool(relaxed)), s
+    a.out, a.out_n_stride, a.out_t_stride = out.data_ptr(), n_stride, t_stride
+    if st is not None:
+        a.coeff_out, a.n_symbols, a.status = (t.data_ptr() for t in st)
+    L.check(L.lib().cover_fast_decode(C.byref(a), _stream()), what)
+    return FastDecoded(out, *st) if stats else out
+
+
 # ------------------------------------------------------------------------------------------------ beam search
 def beam_merge(cum, cand_tok, cand_lp, n_beams, feed_pad, out_parent=None, out_token=None, out_feed=None, out_cum=None, out_step_lp=None):
     """One beam-search step over G = rows / n_beams prompt groups (cover_beam_merge; row g * n_beams + b is beam b of group g).

@@ -349,6 +349,23 @@ class PI0FASTConfig:
     # host.TokenGrammar (fast_chunk_grammar / host.length_grammar): a per-row automaton picks each step's allowed set
     # (generate_tokens(grammar=)); exclusive with allowed_token_ranges. None = no grammar
     token_grammar: Optional[object] = None
+    # de-tokenise on the device (PI0FASTPolicy.extract_actions_device: one ops.fast_decode launch on the generated ids, no host copy)
+    # instead of extract_actions' text round trip. Defined on ids, so not the reference's text artefacts: off by default. With it the
+    # caller supplies, as for allowed_token_ranges, the size of the FAST BPE vocabulary, the PaliGemma id of the terminator "|" and the
+    # ids of the format tokens ("Action", ":"; the tokenizer's BOS is always added) that carry no symbols
+    device_detokenize: bool = False
+    fast_vocab_size: Optional[int] = None
+    action_end_token_id: Optional[int] = None
+    action_format_token_ids: Sequence[int] = ()
+
+
+class _DeviceDetokenizer(NamedTuple):
+    """What PI0FASTPolicy builds once for extract_actions_device: the arguments of ops.fast_decode that do not change between calls."""
+    pieces: ops.FastPieces
+    basis: torch.Tensor                 # fp32 [chunk_size, chunk_size] on the device
+    band: Tuple[int, int]
+    stop_ids: Tuple[int, ...]
+    skip_ids: Tuple[int, ...]
 
 
 class PI0FASTPolicy:
@@ -374,7 +391,23 @@ class PI0FASTPolicy:
             self.allowed_tokens = ops.TokenAllow(bits)
         if config.token_grammar is not None and config.allowed_token_ranges is not None:
             raise ValueError("token_grammar and allowed_token_ranges are mutually exclusive: a grammar carries its own sets")
+        self.last_chunks = None                   # fp32 [B, chunk_size, action_dim] on the device, before un-normalisation (device_detokenize)
+        self.last_decode_status = None            # int32 [B] on the device: the ops.FAST_* bits of each row of last_chunks
+        self._detok = self._device_detokenizer() if config.device_detokenize else None
         self.reset()
+
+    def _device_detokenizer(self) -> _DeviceDetokenizer:
+        """The piece table (every FAST id decoded on its own by the injected BPE), the IDCT basis and the id sets, on the device, once."""
+        from .host import fast_idct_basis, fast_pieces_from_decoder
+        c, tok, ft = self.config, self.paligemma_tokenizer, self.fast_tokenizer
+        if c.fast_vocab_size is None or c.action_end_token_id is None:
+            raise ValueError("device_detokenize needs fast_vocab_size and action_end_token_id (the PaliGemma id of \"|\")")
+        band = fast_action_token_range(tok.vocab_size, c.fast_vocab_size, c.fast_skip_tokens)
+        stop = dict.fromkeys(int(t) for t in (c.action_end_token_id, tok.eos_token_id, self.pad_token_id))
+        skip = dict.fromkeys([int(t) for t in c.action_format_token_ids] + [int(t) for t in [getattr(tok, "bos_token_id", None)] if t is not None])
+        pieces = ops.fast_piece_table(fast_pieces_from_decoder(ft.bpe_tokenizer.decode, c.fast_vocab_size), self.model.dev)
+        basis = torch.from_numpy(fast_idct_basis(c.chunk_size)).to(self.model.dev)
+        return _DeviceDetokenizer(pieces, basis, band, tuple(stop), tuple(skip))
 
     def reset(self):
         self._action_queue = deque([], maxlen=self.config.n_action_steps)
@@ -409,6 +442,24 @@ class PI0FASTPolicy:
                                                 relaxed_decoding=self.config.relaxed_action_decoding)
             outs.append(torch.tensor(acts, device=tokens.device).squeeze(0))
         return torch.stack(outs, dim=0)
+
+    def extract_actions_device(self, tokens: torch.Tensor) -> torch.Tensor:
+        """extract_actions on the device (config.device_detokenize): ONE ops.fast_decode launch on the generated ids int64 [B, L], where they
+        are -> fp32 [B, chunk_size, action_dim] on the device; each row's ops.FAST_* bits are kept in last_decode_status.
+        Defined on ids, not on text: the tokens before the first of ("|", EOS, pad) are walked in order, an id of the FAST band
+        contributes its piece's code points (each FAST id decoded on its own by the injected BPE: host.fast_pieces_from_decoder states the
+        assumption), the format ids and BOS contribute nothing, and any other id zeroes the row. extract_actions' text round trip --
+        batch_decode, string clean-up, encode (which prepends BOS and lets sentencepiece re-segment), the id mirror -- has artefacts that
+        are deliberately NOT reproduced, so the two agree where the generated ids are a clean "Action: <band ids>|" and can differ
+        elsewhere; that is why the option is off by default."""
+        if self._detok is None:
+            raise ops.L.CoverError("extract_actions_device needs a policy built with PI0FASTConfig(device_detokenize=True)")
+        d, ft = self._detok, self.fast_tokenizer
+        dec = ops.fast_decode(tokens, d.pieces, d.basis, band=d.band, stop_ids=d.stop_ids, skip_ids=d.skip_ids, min_token=int(ft.min_token),
+                              scale=float(ft.scale), horizon=self.config.chunk_size, action_dim=self.config.action_dim,
+                              relaxed=bool(self.config.relaxed_action_decoding), stats=True)
+        self.last_decode_status = dec.status
+        return dec.actions
 
     @torch.no_grad()
     def select_action(self, batch: dict) -> torch.Tensor:
@@ -456,7 +507,10 @@ class PI0FASTPolicy:
                 from .host import sequence_logprob
                 toks, lps = toks
                 self.last_sequence_logprobs = sequence_logprob(lps)
-            actions = self.extract_actions(toks.cpu(), self.config.chunk_size, self.config.action_dim)
+            if self._detok is not None:
+                actions = self.last_chunks = self.extract_actions_device(toks)
+            else:
+                actions = self.extract_actions(toks.cpu(), self.config.chunk_size, self.config.action_dim)
             actions = actions[:, : self.config.n_action_steps, : self.config.action_dim]
             actions = unnormalize_action(actions.to(torch.float32), self.normalization["action"])
             self._action_queue.extend(actions.transpose(0, 1))

@@ -1163,6 +1163,67 @@ typedef struct cover_diverse_args {
 int cover_diverse_subset_tokens(const cover_diverse_args* args, void* stream);
 int cover_diverse_subset_actions(const cover_diverse_args* args, void* stream);
 
+/* pi0-FAST de-tokeniser: generated PaliGemma ids -> FAST ids -> the pieces' code points -> quantised DCT coefficients -> an fp32 action
+ * chunk [H][D] per row, the layout the *_actions entries above read in place. The semantics are defined on ids (no text round trip): a
+ * FAST id decodes to a fixed piece of code points, and a row's symbol string is the concatenation of its pieces in position order.
+ * One launch, one 256-thread block per row, no workspace, no atomics, no host read-back: recordable. The expansion is integer-exact, the
+ * IDCT all fp32, one rounding per operation, never an fma; no result depends on the schedule.
+ * tokens: int64, element (b, p) at tokens[b * tok_row_stride + p * tok_step_stride] (strides in elements, >= 0): a candidate-major
+ *   [B][L] tensor and a step-major [L][B] buffer are read in place, as cover_prior_select reads them.
+ * The piece table (device memory): piece_off int32 [n_pieces + 1], non-decreasing from 0; piece_sym int32 [piece_off[n_pieces]], the
+ *   code points FAST id f decodes to at piece_sym[piece_off[f] .. piece_off[f + 1]). A piece whose FIRST symbol is negative marks an id
+ *   the caller's BPE could not decode. L * (the longest piece) < 2^31 is the caller's to keep (ops.fast_piece_table: at most 2^18
+ *   symbols in all).
+ * Per row b:
+ *   1. stop = the first position p whose token is one of stop_ids[0 .. n_stop), or L when there is none; then status bit 32.
+ *   2. Every position p < stop, token t:
+ *        band_lo <= t < band_hi and f = band_hi - 1 - t < n_pieces:  the piece of f. Undecodable: status bit 16, no symbols.
+ *                                                                      Otherwise len_p = piece_off[f + 1] - piece_off[f] symbols (0 is fine).
+ *        else t one of skip_ids[0 .. n_skip):                        nothing
+ *        else:                                                        status bit 8 (an id outside the band, f >= n_pieces, a negative id)
+ *   3. n = the integer sum of len_p; a piece's symbols start at the exclusive prefix sum of len_p over the positions before it.
+ *   4. q[s] = sym + min_token for symbol s < H * D of the concatenation, q[s] = 0 for n <= s < H * D. relaxed: n > H * D sets bit 1
+ *      (truncated, possibly inside a piece), n < H * D bit 2 (padded). Not relaxed: n != H * D sets bit 4.
+ *   5. If any of the bits 4, 8, 16 is set, every q is 0.
+ *   6. coeff_out[b][s] = q[s], n_symbols[b] = n (before truncation), status[b] = the bits.
+ *   7. The coefficient matrix is q as [H][D], frequency-major: k = s / D, d = s % D.
+ *   8. c[k][d] = (float)q[k][d] / scale;  acc = 0.0f;  for k = 0 .. H-1 in order: prod = basis[t][k] * c[k][d];  acc = acc + prod;
+ *      out(b, t, d) = acc at out[b * out_n_stride + t * out_t_stride + d]. The chain always runs, so a zeroed row stores +0.0f.
+ *   9. Every (t, d) of every row is stored, and no other cell of out: the first D columns of a [B][chunk][32] buffer can be the target.
+ * basis: fp32 [H][H], basis[t][k] = the orthonormal inverse DCT-II (DCT-III) matrix, made on the host (host.fast_idct_basis): the device
+ *   takes no cosine. It is staged in LDS next to c when 4 * (H * D + H * H) <= 64 KiB and read from memory otherwise; both run the same
+ *   arithmetic.
+ * Optional outputs (NULL = not written): coeff_out int32 [B][H * D], n_symbols int32 [B], status int32 [B].
+ * COVER_EINVAL, and nothing launched, unless 1 <= B <= 2^20, 1 <= L <= 4096, 1 <= H <= 128, 1 <= D <= 32, n_pieces >= 1,
+ * 0 <= band_lo <= band_hi, 0 <= n_stop <= 4, 0 <= n_skip <= 8, |min_token| <= 2^30, scale finite and != 0, relaxed 0 or 1, token strides
+ * >= 0, out_t_stride >= D, out_n_stride >= (H - 1) * out_t_stride + D (when B > 1), tokens / piece_off / piece_sym / basis / out non-null. */
+#define COVER_FAST_TRUNCATED 1
+#define COVER_FAST_PADDED 2
+#define COVER_FAST_MISMATCH 4
+#define COVER_FAST_STRAY 8
+#define COVER_FAST_UNDECODABLE 16
+#define COVER_FAST_NO_TERMINATOR 32
+typedef struct cover_fast_decode_args {
+    const int64_t* tokens;          /* element (b, p) at tokens[b * tok_row_stride + p * tok_step_stride] */
+    long long tok_row_stride, tok_step_stride;
+    long long band_lo, band_hi;     /* the half-open band of PaliGemma ids that carry FAST ids */
+    long long stop_ids[4];
+    long long skip_ids[8];
+    int n_stop, n_skip;
+    const int* piece_off;           /* int32 [n_pieces + 1] */
+    const int* piece_sym;           /* int32 [piece_off[n_pieces]] */
+    const float* basis;             /* fp32 [H][H] */
+    int B, L, n_pieces, min_token;
+    int H, D, relaxed;
+    float scale;
+    float* out;                     /* element (b, t, d) at out[b * out_n_stride + t * out_t_stride + d] */
+    long long out_n_stride, out_t_stride;
+    int* coeff_out;                 /* int32 [B][H * D], optional */
+    int* n_symbols;                 /* int32 [B], optional */
+    int* status;                    /* int32 [B], optional */
+} cover_fast_decode_args;
+int cover_fast_decode(const cover_fast_decode_args* args, void* stream);
+
 /* Beam search: the three launches a step-synchronous beam search adds to top-n lists (cover_token_topn) and a decode pass. No
  * workspace, nothing data-dependent in a launch (recordable), every result a fixed function of the inputs.
  *
